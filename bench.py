@@ -3,7 +3,9 @@
 
 A "step" is one denoising step of the whole local batch: timestep select -> NCHW->NHWC ->
 AF-UNet forward (a few hundred HIP kernels from libafldm_hip.so) -> DDIM update, replayed as one
-captured HIP graph.  Reported: the MEDIAN of --regions (5) timed regions of --steps steps each.  Workload = BASELINE.json configs[1] (batch 64 per GPU, bf16 storage /
+captured HIP graph.  Exactly --steps steps are timed, split over at most --regions (5) timed regions; reported: the MEDIAN
+over the regions of their time per step.  --dump-outputs DIR writes the latents of the last timed step (what a caller of
+the sampler receives) as DIR/latents.npy.  Workload = BASELINE.json configs[1] (batch 64 per GPU, bf16 storage /
 MFMA with fp32 accumulation), synthetic: seeded random weights of the FFHQ architecture
 (conv_out x0.1), CPU-seeded noise, inputs resident in HBM before the timed region.
 N > 1: launched by torch.distributed.run, one rank per GPU, batch-sharded (weak scaling: 64 per
@@ -303,12 +305,43 @@ def cpu_baseline(budget_s=14.0):
                        f"50 DDIM steps ({sec * steps:.1f} s) on {cores} threads after 1 warm-up step; single-thread: {steps1} steps")
 
 
-def timed_regions(run_steps, k, regions, world, dev):
-    """`regions` timed regions of exactly k steps each, every one bracketed by barrier + synchronize on both sides,
-    MAX over ranks per region; returns the per-region seconds."""
+def region_steps(steps, regions, steps_per_graph):
+    """Split `steps` timed steps over at most `regions` regions, none shorter than one multi-step graph replay (so the
+    split does not change which captured graph a step replays); sizes differ by at most one."""
+    n = max(1, min(regions, steps // max(1, steps_per_graph)))
+    return [steps // n + (i < steps % n) for i in range(n)]
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_BYTES, seed=0):
+    """Write each array as out_dir/<name>.npy in float32.  If together they exceed `max_bytes`, every array keeps a fixed,
+    seeded sample of its rows (dim 0, in order) in proportion to its size.  Returns {name: record} for the JSON line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().contiguous() for k, v in arrays.items()}
+    total = sum(v.numel() * 4 for v in arrays.values())
+    rec = {}
+    for name, v in arrays.items():
+        rows = None
+        if total > max_bytes:
+            row_bytes = max(1, v[0].numel() * 4)
+            keep = max(1, (v.numel() * 4 * max_bytes // total) // row_bytes)
+            rows = torch.randperm(v.shape[0], generator=torch.Generator().manual_seed(seed))[:keep].sort().values
+            v = v[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), v.numpy())
+        rec[name] = {"shape": list(v.shape), "dtype": "float32",
+                     "sampled_rows": None if rows is None else f"{len(rows)} rows, torch.randperm seed {seed}, sorted"}
+    return rec
+
+
+def timed_regions(run_steps, sizes, world, dev):
+    """One timed region per entry of `sizes` (that many steps), every one bracketed by barrier + synchronize on both
+    sides, MAX over ranks per region; returns the per-region seconds."""
     from afldm_amd import parallel
     out = []
-    for _ in range(regions):
+    for k in sizes:
         torch.cuda.synchronize()
         parallel.barrier()
         torch.cuda.synchronize()
@@ -565,13 +598,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64, help="samples per GPU")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--regions", type=int, default=5, help="timed regions of --steps steps each; the median is reported")
+    ap.add_argument("--regions", type=int, default=5,
+                    help="the --steps timed steps are split over at most this many regions; the median is reported")
     ap.add_argument("--workload", default="unet", choices=["unet", "vae", "harness"])
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the batch 1 / 8 / fp32 / AF-VAE side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the latents of the last timed step as DIR/latents.npy (float32; unet workload)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "unet":
+        ap.error("--dump-outputs is implemented for the unet workload only")
 
     from afldm_amd import parallel
     from afldm_amd.engine import DenoiseEngine
@@ -629,9 +669,13 @@ def main():
         # that one-off set-up belongs to the warm-up, not to the timed steps
         parallel.all_gather_into(final, eng.lat)
     pos[0] = 0
-    regions = timed_regions(run_steps, args.steps, max(1, args.regions), world, dev)
-    dt = median(regions)
+    sizes = region_steps(args.steps, max(1, args.regions), 1 if args.no_graph else eng.steps_per_graph)
+    regions = timed_regions(run_steps, sizes, world, dev)
+    step_s = median([r / k for r, k in zip(regions, sizes)])
     finite = bool(torch.isfinite(eng.lat).all().item())
+    # the output of the last timed step, as a caller of the sampler receives it (N > 1: the all-gathered latents)
+    dumped = dump_outputs(args.dump_outputs, {"latents": final if world > 1 else eng.lat}) \
+        if args.dump_outputs and rank == 0 else None
     # the process group as it actually ran (every rank takes part): world size, backend, each rank's device, and the
     # sampler's one collective timed on its own + verified block by block
     rccl = parallel.rccl_record(dev, local, payload=eng.lat) if world > 1 else None
@@ -639,12 +683,12 @@ def main():
     if rank == 0:
         out = {
             "metric": "denoise-steps/sec + ms/step, FFHQ-256 AF-UNet, batch 64 @1/2/4/8 GPU",     # BASELINE.json "metric", verbatim
-            "value": round(total * args.steps / dt, 2),
+            "value": round(total / step_s, 2),
             "unit": "denoise-steps/s",
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": round(1e3 * dt / args.steps, 4),
+            "ms_per_step": round(1e3 * step_s, 4),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -657,18 +701,21 @@ def main():
                                                   "the timestep only and are tabulated once per 50-step schedule in DenoiseEngine.__init__ "
                                                   "(outside the timed region; < 0.1 % of the step's flops, 6 launches): a timed step copies "
                                                   "its table row instead of recomputing them as the reference does per step",
-                       "timing": f"median of {len(regions)} timed regions of {args.steps} steps, each bracketed by barrier + "
-                                 "synchronize, MAX over ranks",
-                       "regions_ms_per_step": [round(1e3 * r / args.steps, 4) for r in regions]},
+                       "timing": f"{args.steps} timed steps in {len(regions)} regions of {sizes} steps, each bracketed by "
+                                 "barrier + synchronize, MAX over ranks; median over the regions of their time per step",
+                       "region_steps": sizes,
+                       "regions_ms_per_step": [round(1e3 * r / k, 4) for r, k in zip(regions, sizes)]},
         }
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         out["rccl"] = rccl if rccl is not None else {"world_size": 1, "backend": None,
                                                      "note": "single process: no process group, no collective"}
         out["box"] = box_record(dev)
         if not args.no_roofline:
             roof, fam = roofline_pass(unet, B, dtype)
             peak = PEAK_BF16_TFLOPS if dtype == torch.bfloat16 else PEAK_F32_TFLOPS
-            rate = roof.pop("step_dense_tflop") / (dt / args.steps)
-            out["step_dense"] = {"tflop_per_step": round(rate * dt / args.steps, 4), "tflops": round(rate, 1), "peak": peak,
+            rate = roof.pop("step_dense_tflop") / step_s
+            out["step_dense"] = {"tflop_per_step": round(rate * step_s, 4), "tflops": round(rate, 1), "peak": peak,
                                  "frac": round(rate / peak, 4), "af_filter_tflop_per_step": roof.pop("step_af_filter_tflop"),
                                  "note": "algorithmic flops of the step's convolutions + linear layers + attention over the timed step"}
             if roof.get("bound") == "mfma" and dtype == torch.bfloat16 and out["box"].get("mfma_tflops_random_operands"):
@@ -681,7 +728,7 @@ def main():
             out["kernel_families"] = fam
             fam_sum = sum(f["ms_per_step"] for f in fam.values())
             out["kernel_families_note"] = (f"every family is timed as a back-to-back HIP-graph replay of its own launches of one step: the families "
-                                           f"sum to {fam_sum:.3f} ms against the {1e3 * dt / args.steps:.3f} ms timed step (MFMA-heavy launches replayed "
+                                           f"sum to {fam_sum:.3f} ms against the {1e3 * step_s:.3f} ms timed step (MFMA-heavy launches replayed "
                                            "back to back run slower than interleaved with the step's other kernels), so per-family ms / tflops and "
                                            "roofline.frac are slightly pessimistic, never optimistic")
         del eng

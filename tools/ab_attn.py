@@ -1,6 +1,6 @@
 # same-box A/B: bench step with / without the fused attention front end + standalone kernel timings
 import os, sys, time, json, subprocess
-root = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def run(env_extra, tag):
     env = dict(os.environ, **env_extra)
     r = subprocess.run([sys.executable, "bench.py", "--steps", "40", "--warmup", "10", "--no-cpu-baseline", "--no-roofline", "--no-extras"],

@@ -1,6 +1,6 @@
 # generic same-box in-step A/B: python tools/ab_env.py "label=ENV=V,ENV2=V" "label2=" ...
 import os, sys, json, subprocess
-root = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def run(env_extra, tag):
     env = dict(os.environ, **env_extra)
     extra = os.environ.get("AB_ARGS", "").split()          # e.g. AB_ARGS="--batch 8"

@@ -1,6 +1,6 @@
 # same-box A/B of the AF-VAE workload (BASELINE configs[3]) across conv3h sub-plane variants
 import os, sys, json, subprocess
-root = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def run(env_extra, tag):
     env = dict(os.environ, **env_extra)
     r = subprocess.run([sys.executable, "bench.py", "--workload", "vae", "--no-cpu-baseline"], capture_output=True, text=True, env=env, cwd=root)

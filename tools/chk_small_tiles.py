@@ -1,5 +1,5 @@
-import ctypes, sys, torch
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tools")
+import ctypes, os, sys, torch
+_tools = os.path.dirname(os.path.abspath(__file__)); sys.path.insert(0, os.path.dirname(_tools)); sys.path.insert(0, _tools)
 from afldm_amd import _lib, ops
 from bench_kernels import timeit_graph
 for (B, H, Cin, Cout, va, vb) in ((8, 32, 192, 192, 55, 65), (8, 16, 384, 384, 54, 66), (1, 32, 192, 192, 55, 65), (1, 16, 384, 384, 54, 66), (8, 32, 576, 192, 55, 65), (4, 16, 768, 384, 54, 66)):
