@@ -100,6 +100,11 @@ def _load():
         "afldm_conv2d_variant": ([POINTER(ConvArgs)], c_int),
         "afldm_conv2d_c8_ok": ([POINTER(ConvArgs)], c_int),
         "afldm_conv2d_norm_ok": ([POINTER(ConvArgs)], c_int),
+        "afldm_conv2d_s2": ([POINTER(ConvArgs), ip, ip, vp], c_int),
+        "afldm_conv2d_up2": ([POINTER(ConvArgs), vp], c_int),
+        "afldm_conv2d_s2_stats_splits": ([POINTER(ConvArgs)], c_int),
+        "afldm_conv2d_up2_stats_splits": ([POINTER(ConvArgs)], c_int),
+        "afldm_pack_weight_up2": ([vp, vp, ip, ip, ip, vp], c_int),
         "afldm_attention": ([vp, ip, vp, ip, vp, vp, ip, ip, ip, ip, ip, ip, ip, fp, ip, vp], c_int),
         "afldm_attn_block_fused_supported": ([ip, ip, ip, ip], c_int),
         "afldm_attn_block_fused_trace": ([vp], c_int),

@@ -8,10 +8,11 @@ ResnetBlock2D.nonlinearity is wrapped in WarpedNonlinearity.  NOT touched, as in
 reference: unet.conv_act, time_embedding.act, attention.  No parameter is added, so
 state-dict keys stay vanilla diffusers.
 """
+from ..models.blocks import Downsample2D, NearestUpsample2D, StridedDownsample2D, Upsample2D
 from .af_blocks import AliasFreeDownsample2D, AliasFreeUpsample2D, WarpedNonlinearity
 
 __all__ = ["wrap_nonlinearity", "replace_upsampler", "replace_downsampler", "wrap_resblock_nonlinearity",
-           "make_af_unet", "make_af_vae", "make_af_vae_from_config", "make_af_controlnet"]
+           "make_af_unet", "make_af_vae", "make_af_vae_from_config", "make_af_controlnet", "enable_vanilla_resampling"]
 
 
 def wrap_nonlinearity(nonlinearity):
@@ -74,3 +75,18 @@ def make_af_vae_from_config(vae):
     cfg = vae.config
     make_af_vae(vae, mod_mid_act=cfg.mid_act, mod_down_filtered_act=cfg.down_filtered_act,
                 mod_up_filtered_act=cfg.up_filtered_act, mod_resampling_layer=cfg.up_rescale)
+
+
+def enable_vanilla_resampling(model):
+    """Opt in to the vanilla resamplers on HIP (not part of the reference's API): every remaining plain Downsample2D /
+    Upsample2D with use_conv in `model` (UNet2DModel, AutoencoderKL, any module tree) becomes StridedDownsample2D /
+    NearestUpsample2D, sharing the original conv's parameters.  Alias-free resamplers, and the use_conv=False forms, are
+    left alone; calling it again changes nothing.  Vanilla LDM: enable_vanilla_resampling(unet) without make_af_unet; partly
+    alias-free VAE: make_af_vae_from_config(vae) and then enable_vanilla_resampling(vae).  Returns `model`."""
+    swaps = {Downsample2D: StridedDownsample2D, Upsample2D: NearestUpsample2D}
+    for parent in list(model.modules()):
+        for key, child in list(parent._modules.items()):
+            cls = swaps.get(type(child))
+            if cls is not None and child.use_conv and not getattr(child, "use_conv_transpose", False):
+                parent._modules[key] = cls.from_vanilla(child)
+    return model

@@ -252,8 +252,9 @@ class Downsample2D(nn.Module):
 
     def forward(self, hidden_states, *args, **kwargs):
         raise NotImplementedError(
-            "afldm_amd executes the alias-free model only: call make_af_unet(unet) "
-            "(afldm.af_modules.af_api) before running; the strided Downsample2D has no HIP path")
+            "afldm_amd executes the alias-free model by default: call make_af_unet(unet) "
+            "(afldm.af_modules.af_api) before running, or opt in to the vanilla resamplers with "
+            "enable_vanilla_resampling(model) (same module); this Downsample2D has not been swapped")
 
 
 class Upsample2D(nn.Module):
@@ -283,8 +284,78 @@ class Upsample2D(nn.Module):
 
     def forward(self, hidden_states, output_size=None, *args, **kwargs):
         raise NotImplementedError(
-            "afldm_amd executes the alias-free model only: call make_af_unet(unet) first; the "
-            "nearest-neighbour Upsample2D has no HIP path")
+            "afldm_amd executes the alias-free model by default: call make_af_unet(unet) first, or opt in to the "
+            "vanilla resamplers with enable_vanilla_resampling(model) (afldm.af_modules.af_api); this Upsample2D "
+            "has not been swapped")
+
+
+def _adopt(new, old):
+    """Hand every registered submodule (the conv, under each of its names) of `old` to `new`: parameters are shared."""
+    for key, m in old._modules.items():
+        new._modules[key] = m
+    return new
+
+
+class StridedDownsample2D(Downsample2D):
+    """Downsample2D with use_conv on HIP: the stride-2 3x3 convolution (afldm_conv2d_s2).  Same constructor, attributes and
+    state-dict keys as Downsample2D; af_api.enable_vanilla_resampling installs it.  padding=1 pads every side by one,
+    padding=0 is diffusers' F.pad(x, (0, 1, 0, 1)) in front of an unpadded conv (the VAE encoder)."""
+
+    @classmethod
+    def from_vanilla(cls, d):
+        conv = d.conv
+        new = cls(d.channels, d.use_conv, out_channels=d.out_channels, padding=d.padding, name=d.name,
+                  kernel_size=conv.kernel_size[0], bias=conv.bias is not None)
+        return _adopt(new, d)
+
+    def forward(self, hidden_states, *args, **kwargs):
+        if not self.use_conv:
+            raise NotImplementedError("afldm_amd: Downsample2D(use_conv=False) (AvgPool2d) has no HIP path")
+        x = hidden_states
+        assert x.ndim == 4 and x.shape[-1] == self.channels and not ops.is_c8(x)          # NHWC
+        conv = self.conv
+        if tuple(conv.kernel_size) != (3, 3) or tuple(conv.stride) != (2, 2) or self.padding not in (0, 1):
+            raise NotImplementedError(f"afldm_amd: Downsample2D kernel {conv.kernel_size} / stride {conv.stride} / "
+                                      f"padding {self.padding} has no HIP path (3x3, stride 2, padding 0 or 1)")
+        w, b = packed_conv(conv, x.dtype)
+        return ops.conv2d_s2(x, w, b, pad=(1, 1) if self.padding == 1 else (0, 1), want_stats=True)
+
+
+class NearestUpsample2D(Upsample2D):
+    """Upsample2D with use_conv on HIP: nearest x2 fused into the 3x3 convolution in phase-decomposed form
+    (afldm_conv2d_up2, weights folded once per dtype by afldm_pack_weight_up2).  Same constructor, attributes and
+    state-dict keys as Upsample2D; af_api.enable_vanilla_resampling installs it."""
+
+    @classmethod
+    def from_vanilla(cls, u):
+        conv = u.conv if u.name == "conv" else u.Conv2d_0
+        new = cls(u.channels, u.use_conv, u.use_conv_transpose, out_channels=u.out_channels, name=u.name,
+                  kernel_size=None if conv is None else conv.kernel_size[0],
+                  padding=1 if conv is None else conv.padding[0], bias=conv is not None and conv.bias is not None,
+                  interpolate=u.interpolate)
+        return _adopt(new, u)
+
+    def forward(self, hidden_states, output_size=None, *args, **kwargs):
+        x = hidden_states
+        assert x.ndim == 4 and x.shape[-1] == self.channels and not ops.is_c8(x)          # NHWC
+        if not self.use_conv:
+            raise NotImplementedError("afldm_amd: Upsample2D(use_conv=False) has no HIP path")
+        conv = self.conv if self.name == "conv" else self.Conv2d_0
+        if tuple(conv.kernel_size) != (3, 3) or tuple(conv.padding) != (1, 1) or tuple(conv.stride) != (1, 1):
+            raise NotImplementedError(f"afldm_amd: Upsample2D conv kernel {conv.kernel_size} / padding {conv.padding} "
+                                      "has no HIP path (3x3, padding 1)")
+        H, W = x.shape[1], x.shape[2]
+        if not self.interpolate:
+            return conv_forward(conv, x, want_stats=True)
+        if output_size is not None and tuple(output_size) != (2 * H, 2 * W):
+            raise ValueError(f"NearestUpsample2D: output_size {tuple(output_size)} is not 2x the input {(H, W)}")
+        cache = conv.__dict__.setdefault("_afldm_cache", {})
+        key = ("up2", x.dtype)
+        if key not in cache:
+            cache[key] = (ops.pack_weight_up2(conv.weight, x.dtype),
+                          None if conv.bias is None else conv.bias.detach().to(torch.float32).contiguous())
+        w, b = cache[key]
+        return ops.conv2d_up2(x, w, b, want_stats=True)
 
 
 def _bias_f32(conv):

@@ -1089,6 +1089,110 @@ def conv2d_launch(a):
     check(lib.afldm_conv2d(ctypes.byref(a), stream_ptr()), "conv2d")
 
 
+# ----------------------------------------------------------------------------- vanilla resamplers (csrc/resconv.hip)
+def fold_up2_weight(w):
+    """conv3x3(nearest2x(x)) as four 2x2 convolutions of x: OIHW [Cout, Cin, 3, 3] -> [4, Cout, Cin, 2, 2] fp32, phase
+    p = 2 a + c computes output pixel (2i + a, 2j + c) from input rows {i - 1 + a, i + a} and columns {j - 1 + c, j + c}.
+    Per axis, phase 0 takes taps {w0, w1 + w2} and phase 1 {w0 + w1, w2}; rows are folded first, then columns (the order
+    afldm_pack_weight_up2 sums in, so the two agree bit for bit)."""
+    w = w.detach().to(torch.float32)
+    rows = [torch.stack([w[:, :, 0], w[:, :, 1] + w[:, :, 2]], 2),          # [Cout, Cin, 2, 3] per row phase
+            torch.stack([w[:, :, 0] + w[:, :, 1], w[:, :, 2]], 2)]
+    out = []
+    for a in (0, 1):
+        r = rows[a]
+        for cols in ((r[..., 0], r[..., 1] + r[..., 2]), (r[..., 0] + r[..., 1], r[..., 2])):
+            out.append(torch.stack(cols, 3))
+    return torch.stack(out, 0).contiguous()
+
+
+def pack_weight_up2(w, dtype):
+    """OIHW fp32 [Cout, Cin, 3, 3] -> the folded weight [4, Cout, 2, 2, Cin] of conv2d_up2 in `dtype` (one rounding)."""
+    _dev(w, "weight")
+    w = w.detach().to(torch.float32).contiguous()
+    Cout, Cin, KH, KW = w.shape
+    assert (KH, KW) == (3, 3), "the nearest-x2 fold is defined for 3x3 kernels"
+    out = torch.empty((4, Cout, 2, 2, Cin), dtype=dtype, device=w.device)
+    check(lib.afldm_pack_weight_up2(ptr(w), ptr(out), Cout, Cin, _code(out), stream_ptr()), "pack_weight_up2")
+    return out
+
+
+def _resconv_args(x, w, bias, out, Cout):
+    _dev(x, "x")
+    _dev(w, "w")
+    if bias is not None:
+        _dev(bias, "bias")
+    a = ConvArgs()
+    a.x1, a.w, a.bias, a.y = ptr(x), ptr(w), ptr(bias), ptr(out)
+    a.B, a.H, a.W = x.shape[:3]
+    a.C1, a.Cout, a.KS = x.shape[-1], Cout, 3
+    a.y_ld = a.res_ld = Cout
+    a.dtype = _code(x)
+    a.keep = (x, w, bias, out)
+    return a
+
+
+def _resconv_stats(out, a, S):
+    st = torch.empty((a.B, S, a.Cout, 2), dtype=torch.float32, device=out.device)
+    a.stats_out = ptr(st)
+    a.keep = a.keep + (st,)
+    return st
+
+
+def _fold_stats(st, B, Cout, device):
+    if st.shape[1] > _MAX_SPLITS and st.shape[1] % _MAX_SPLITS == 0:
+        folded = torch.empty((B, _MAX_SPLITS, Cout, 2), dtype=torch.float32, device=device)
+        check(lib.afldm_gn_fold(ptr(st), st.shape[1], ptr(folded), _MAX_SPLITS, B, Cout, stream_ptr()), "gn_fold")
+        return folded
+    return st
+
+
+def conv2d_s2(x, w, bias=None, pad=(1, 1), want_stats=False, out=None):
+    """F.conv2d(x, w, bias, stride=2) of x zero-padded by pad = (pad_lo, pad_hi) rows / columns, NHWC [B, H, W, Cin] ->
+    [B, H/2, W/2, Cout] (afldm_conv2d_s2).  w: the packed OHWI weight (pack_weight).  Downsample2D uses pad (1, 1), the VAE
+    encoder's F.pad(x, (0, 1, 0, 1)) + padding=0 is (0, 1).  want_stats: the output carries its GroupNorm partial sums
+    (.gn_partial) from the epilogue."""
+    B, H, W_, _ = x.shape
+    Cout = w.shape[0]
+    assert tuple(w.shape[1:3]) == (3, 3) and w.shape[3] == x.shape[-1], f"weight {tuple(w.shape)} vs input {tuple(x.shape)}"
+    if out is None:
+        out = torch.empty((B, H // 2, W_ // 2, Cout), dtype=x.dtype, device=x.device)
+    a = _resconv_args(x, w, bias, out, Cout)
+    st = _resconv_stats(out, a, lib.afldm_conv2d_s2_stats_splits(ctypes.byref(a))) if want_stats else None
+    lo, hi = int(pad[0]), int(pad[1])
+    tok = _begin()
+    check(lib.afldm_conv2d_s2(ctypes.byref(a), lo, hi, stream_ptr()), "conv2d_s2")
+    if st is not None:
+        out.gn_partial = _fold_stats(st, B, Cout, x.device)
+    if tok is not None:
+        M, Cin = B * (H // 2) * (W_ // 2), x.shape[-1]
+        _end(tok, "conv_s2", 2.0 * M * Cout * 9 * Cin, (B * H * W_ * Cin + Cout * 9 * Cin + M * Cout) * x.element_size(),
+             replay=lambda a=a: check(lib.afldm_conv2d_s2(ctypes.byref(a), lo, hi, stream_ptr()), "conv2d_s2"))
+    return out
+
+
+def conv2d_up2(x, w_up2, bias=None, want_stats=False, out=None):
+    """F.conv2d(F.interpolate(x, scale_factor=2, mode='nearest'), w, bias, padding=1) on NHWC [B, H, W, Cin] ->
+    [B, 2H, 2W, Cout] without forming the x2 tensor (afldm_conv2d_up2).  w_up2: pack_weight_up2(w).  Profiled FLOPs are
+    the folded ones (16 taps per 2x2 output block); the literal convolution does 36."""
+    B, H, W_, Cin = x.shape
+    assert w_up2.ndim == 5 and w_up2.shape[0] == 4 and w_up2.shape[4] == Cin, f"weight {tuple(w_up2.shape)} vs {tuple(x.shape)}"
+    Cout = w_up2.shape[1]
+    if out is None:
+        out = torch.empty((B, 2 * H, 2 * W_, Cout), dtype=x.dtype, device=x.device)
+    a = _resconv_args(x, w_up2, bias, out, Cout)
+    st = _resconv_stats(out, a, lib.afldm_conv2d_up2_stats_splits(ctypes.byref(a))) if want_stats else None
+    tok = _begin()
+    check(lib.afldm_conv2d_up2(ctypes.byref(a), stream_ptr()), "conv2d_up2")
+    if st is not None:
+        out.gn_partial = _fold_stats(st, B, Cout, x.device)
+    if tok is not None:
+        M = B * H * W_
+        _end(tok, "conv_up2", 2.0 * M * 4 * Cout * 4 * Cin, (M * Cin + 16 * Cout * Cin + 4 * M * Cout) * x.element_size(),
+             replay=lambda a=a: check(lib.afldm_conv2d_up2(ctypes.byref(a), stream_ptr()), "conv2d_up2"))
+    return out
+
+
 # ----------------------------------------------------------------------------- attention
 def attention(q, k, vt, heads, scale=None, out=None):
     """q [B,Tq,C], k [Bk,Tk,C] token-major (may be column slices of wider buffers: the leading

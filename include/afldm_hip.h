@@ -334,6 +334,25 @@ size_t afldm_conv2d_workspace(const afldm_conv_args* args);
 /* split count S of the statistics afldm_conv2d writes to stats_out for this problem (> 0). */
 int afldm_conv2d_stats_splits(const afldm_conv_args* args);
 
+/* ---- vanilla resamplers (diffusers Downsample2D / Upsample2D with use_conv; csrc/resconv.hip) ---------------------------
+ * Read from afldm_conv_args: x1, w, bias (fp32, may be NULL), y, B, H, W (the INPUT plane), C1 (= Cin), Cout, dtype and
+ * stats_out (may be NULL: then [B][S][Cout][2] per-channel partial sums of the stored output, S = the matching _stats_splits);
+ * every other field is ignored.  Cin and Cout multiples of 8; inputs of 2 GiB or more run as launches over whole samples.
+ * afldm_conv2d_s2: F.conv2d(x, w, bias, stride=2) of the zero-padded x (pad_lo rows / columns in front, pad_hi behind; the
+ *   UNet's padding=1 is (1, 1), the VAE encoder's F.pad(x, (0, 1, 0, 1)) + padding=0 is (0, 1)); w OHWI [Cout][3][3][Cin]
+ *   (afldm_pack_weight); H, W even; y [B, H/2, W/2, Cout].
+ * afldm_conv2d_up2: F.conv2d(F.interpolate(x, scale_factor=2, mode='nearest'), w, bias, padding=1) without the x2 tensor:
+ *   output pixel (2i + a, 2j + c) is a 2x2 convolution of x around (i, j) with phase-folded weights, w = the
+ *   afldm_pack_weight_up2 form; Cout a multiple of 64; y [B, 2H, 2W, Cout]. */
+int afldm_conv2d_s2(const afldm_conv_args* args, int pad_lo, int pad_hi, afldm_stream_t stream);
+int afldm_conv2d_up2(const afldm_conv_args* args, afldm_stream_t stream);
+int afldm_conv2d_s2_stats_splits(const afldm_conv_args* args);
+int afldm_conv2d_up2_stats_splits(const afldm_conv_args* args);
+/* OIHW fp32 [Cout][Cin][3][3] -> the folded up2 weight [4][Cout][2][2][Cin] in `dtype`, phase = 2 a + c.  Per axis, phase 0
+ * takes taps {i-1: w0, i: w1 + w2} and phase 1 {i: w0 + w1, i+1: w2}; rows are folded first, then columns, in fp32, and the
+ * sum is rounded once. */
+int afldm_pack_weight_up2(const float* src, void* dst, int Cout, int Cin, int dtype, afldm_stream_t stream);
+
 /* ---- attention ---------------------------------------------------------------------------
  * F.scaled_dot_product_attention as called by AttnProcessor2_0 / CrossFrameAttnProcessor
  * (cross_frame_attn.py:125,128): o = softmax(q k^T * scale) v per (batch, head).

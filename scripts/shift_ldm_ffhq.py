@@ -32,6 +32,9 @@ def parse_args():
     p.add_argument("--fixed_resize", action="store_true",
                    help="opt OUT of the reference-exact flow: resize --input_path to sample_size x VAE ratio (256) before the VAE "
                         "(the reference resizes to sample_size = 32 and inverts a 4 x 4 latent) and draw the noise on the CPU")
+    p.add_argument("--vanilla", action="store_true",
+                   help="run the vanilla LDM baseline: skip make_af_unet / make_af_vae_from_config and run the plain strided / "
+                        "nearest-neighbour resamplers on HIP (af_api.enable_vanilla_resampling) on both models")
     p.add_argument("--reference_exact", action="store_true", help="accepted for compatibility: this is the default now")
     return p.parse_args()
 
@@ -40,7 +43,7 @@ def main():
     args = parse_args()
     from afldm_amd import compat, parallel
     compat.install()
-    from afldm.af_modules.af_api import make_af_unet, make_af_vae_from_config
+    from afldm.af_modules.af_api import enable_vanilla_resampling, make_af_unet, make_af_vae_from_config
     from afldm.pipelines.ldm_pipeline import MyLDMPipeline
     from afldm_amd.harness import shift_ldm
     rank, world, local = parallel.init_distributed()
@@ -68,8 +71,12 @@ def main():
         raise SystemExit("pass --ckpt DIR (or AFLDM_CKPT) or --random-init; checkpoints cannot be downloaded here")
     pipe = pipe.to(f"cuda:{local}").to(dtype)
     pipe.set_progress_bar_config(disable=True)
-    make_af_unet(pipe.unet)
-    make_af_vae_from_config(pipe.vae)
+    if args.vanilla:
+        enable_vanilla_resampling(pipe.unet)
+        enable_vanilla_resampling(pipe.vae)
+    else:
+        make_af_unet(pipe.unet)
+        make_af_vae_from_config(pipe.vae)
     frames, errs = shift_ldm(pipe, args.num_inference_steps, args.shift_steps, args.output_path, args.input_path,
                              generator=torch.Generator().manual_seed(args.seed), rank=rank, world=world, batch_offsets=not args.sequential,
                              reference_exact=not args.fixed_resize, use_graph=not args.eager)
