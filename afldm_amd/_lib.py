@@ -115,6 +115,8 @@ def _load():
                                         vp], c_int),
         "afldm_ddim_step": ([vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, vp], c_int),
         "afldm_ddim_step_flat": ([vp, vp, vp, fp, fp, fp, fp, c_size_t, vp], c_int),
+        "afldm_dpm_step": ([vp, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, vp], c_int),
+        "afldm_dpm_step_flat": ([vp, vp, vp, vp, fp, fp, fp, fp, fp, fp, c_size_t, vp], c_int),
         "afldm_select_timestep": ([vp, vp, vp, ip, vp], c_int),
         "afldm_select_step_row": ([vp, vp, vp, ip, vp, vp, c_size_t, vp], c_int),
         "afldm_probe_mfma": ([vp, ip, ip, vp], c_int),

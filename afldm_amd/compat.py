@@ -14,6 +14,7 @@ def install_diffusers_shim(force=False):
     from .models.unet_2d import UNet2DModel, UNet2DOutput
     from .pipelines.pipeline_utils import DiffusionPipeline, ImagePipelineOutput
     from .schedulers.ddim import DDIMScheduler, DDIMSchedulerOutput
+    from .schedulers.dpmsolver import DPMSolverMultistepScheduler, DPMSolverMultistepSchedulerOutput
     from .utils import randn_tensor
 
     def mod(name, **attrs):
@@ -25,7 +26,8 @@ def install_diffusers_shim(force=False):
 
     from .models.vae import AutoencoderKL
 
-    root = mod("diffusers", UNet2DModel=UNet2DModel, DDIMScheduler=DDIMScheduler, AutoencoderKL=AutoencoderKL,
+    root = mod("diffusers", UNet2DModel=UNet2DModel, DDIMScheduler=DDIMScheduler,
+               DPMSolverMultistepScheduler=DPMSolverMultistepScheduler, AutoencoderKL=AutoencoderKL,
                DiffusionPipeline=DiffusionPipeline, __version__="0.32.1+afldm_amd_shim", __path__=[])
     root.models = mod("diffusers.models", UNet2DModel=UNet2DModel, AutoencoderKL=AutoencoderKL, __path__=[])
     root.models.unets = mod("diffusers.models.unets", __path__=[])
@@ -34,8 +36,11 @@ def install_diffusers_shim(force=False):
     mod("diffusers.models.downsampling", Downsample2D=blocks.Downsample2D)
     mod("diffusers.models.upsampling", Upsample2D=blocks.Upsample2D)
     mod("diffusers.models.resnet", ResnetBlock2D=blocks.ResnetBlock2D)
-    root.schedulers = mod("diffusers.schedulers", DDIMScheduler=DDIMScheduler, __path__=[])
+    root.schedulers = mod("diffusers.schedulers", DDIMScheduler=DDIMScheduler,
+                          DPMSolverMultistepScheduler=DPMSolverMultistepScheduler, __path__=[])
     mod("diffusers.schedulers.scheduling_ddim", DDIMScheduler=DDIMScheduler, DDIMSchedulerOutput=DDIMSchedulerOutput)
+    mod("diffusers.schedulers.scheduling_dpmsolver_multistep", DPMSolverMultistepScheduler=DPMSolverMultistepScheduler,
+        SchedulerOutput=DPMSolverMultistepSchedulerOutput)
     root.utils = mod("diffusers.utils", __path__=[])
     mod("diffusers.utils.torch_utils", randn_tensor=randn_tensor)
     root.pipelines = mod("diffusers.pipelines", DiffusionPipeline=DiffusionPipeline, __path__=[])

@@ -1,0 +1,156 @@
+// dpm.hip — DPM-Solver(++) multistep update (DPMSolverMultistepScheduler, afldm_amd/schedulers/dpmsolver.py).
+// For epsilon / v / sample prediction every step of order 1..3 is a linear combination of the latent, the model
+// output and at most two earlier converted outputs, so a step is one coefficient row (p, q, a, b0, b1, b2, 0, 0):
+//   m0 = p x + q eps;  x_out = a x + b0 m0 + b1 h1 + b2 h2;  h2 <- h1, h1 <- m0
+// HBM-bound elementwise: every thread owns 4 consecutive pixels of one (b, c) plane (16-byte loads of x / h1 / h2 /
+// x_out), grid capped at 2048 blocks and grid-stride beyond (guide G11).  Each thread reads and writes its own
+// indices only, so x and x_out may alias and the history shifts in place.
+#include "common.hpp"
+
+namespace afldm {
+
+namespace {
+
+template <int V>
+struct vecf {
+  float v[V];
+};
+
+template <int V>
+__device__ __forceinline__ vecf<V> ld(const float* p) {
+  vecf<V> r;
+  if constexpr (V == 4) {
+    f32x4 q = *reinterpret_cast<const f32x4*>(p);
+    r.v[0] = q[0]; r.v[1] = q[1]; r.v[2] = q[2]; r.v[3] = q[3];
+  } else {
+#pragma unroll
+    for (int k = 0; k < V; ++k) r.v[k] = p[k];
+  }
+  return r;
+}
+
+template <int V>
+__device__ __forceinline__ void st(float* p, const vecf<V>& r) {
+  if constexpr (V == 4) {
+    f32x4 q = {r.v[0], r.v[1], r.v[2], r.v[3]};
+    *reinterpret_cast<f32x4*>(p) = q;
+  } else {
+#pragma unroll
+    for (int k = 0; k < V; ++k) p[k] = r.v[k];
+  }
+}
+
+struct dpm_row {
+  float p, q, a, b0, b1, b2;
+};
+
+// one group of V elements: x, h1, h2 at `i` (same layout), eps values already in registers
+template <int V>
+__device__ __forceinline__ void dpm_update(const float* x, float* x_out, float* h1, float* h2, size_t i,
+                                           const float (&e)[V], const dpm_row& c) {
+  vecf<V> xv = ld<V>(x + i), a1 = ld<V>(h1 + i), a2 = ld<V>(h2 + i), out, m;
+#pragma unroll
+  for (int k = 0; k < V; ++k) {
+    m.v[k] = c.p * xv.v[k] + c.q * e[k];
+    out.v[k] = c.a * xv.v[k] + c.b0 * m.v[k] + c.b1 * a1.v[k] + c.b2 * a2.v[k];
+  }
+  st<V>(x_out + i, out);
+  st<V>(h2 + i, a1);
+  st<V>(h1 + i, m);
+}
+
+}  // namespace
+
+// x, x_out NCHW fp32; eps NHWC T; hist [2][B][C][HW].  V = 4 needs HW % 4 == 0 and 16-byte aligned fp32 tensors.
+template <typename T, int V>
+__global__ void __launch_bounds__(256) k_dpm_step(const float* x, const T* __restrict__ eps, float* x_out, float* hist,
+                                                  const float* __restrict__ coef, const int* __restrict__ step_idx, int B,
+                                                  int C, int HW) {
+  const int s = *step_idx;
+  const float* r = coef + 8 * (size_t)s;
+  const dpm_row c{r[0], r[1], r[2], r[3], r[4], r[5]};
+  const size_t n = (size_t)B * C * HW;
+  float* h1 = hist;
+  float* h2 = hist + n;
+  const size_t groups = n / V;
+  for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (size_t)gridDim.x * blockDim.x) {
+    const size_t i = g * V;
+    const int pix = (int)(i % HW);
+    const size_t plane = i / HW;
+    const int ch = (int)(plane % C);
+    const size_t b = plane / C;
+    const T* ep = eps + ((size_t)b * HW + pix) * C + ch;
+    float e[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) e[k] = to_f32(ep[(size_t)k * C]);
+    dpm_update<V>(x, x_out, h1, h2, i, e, c);
+  }
+}
+
+// flat same-layout fp32 tensors, coefficients by value; hist [2][n].  16-byte groups, then a scalar tail.
+template <int V>
+__global__ void __launch_bounds__(256) k_dpm_step_flat(const float* x, const float* __restrict__ eps, float* x_out,
+                                                       float* hist, dpm_row c, size_t n) {
+  float* h1 = hist;
+  float* h2 = hist + n;
+  const size_t groups = n / V;
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t g = tid; g < groups; g += stride) {
+    const size_t i = g * V;
+    vecf<V> ev = ld<V>(eps + i);
+    float e[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) e[k] = ev.v[k];
+    dpm_update<V>(x, x_out, h1, h2, i, e, c);
+  }
+  for (size_t i = groups * V + tid; i < n; i += stride) {
+    const float e[1] = {eps[i]};
+    dpm_update<1>(x, x_out, h1, h2, i, e, c);
+  }
+}
+
+__global__ void k_dpm_advance(int* step_idx) { *step_idx += 1; }
+
+static inline int dpm_grid(size_t work) {
+  size_t g = (work + 255) / 256;
+  return (int)(g < 2048 ? (g ? g : 1) : 2048);
+}
+
+}  // namespace afldm
+
+using namespace afldm;
+
+extern "C" int afldm_dpm_step(const float* x, const void* eps, float* x_out, float* hist, const float* coef, int* step_idx,
+                              int advance, int B, int C, int H, int W, int dtype, afldm_stream_t stream) {
+  AFLDM_REQUIRE(x && eps && x_out && hist && coef && step_idx, AFLDM_ENULL, "afldm_dpm_step: NULL pointer");
+  AFLDM_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, AFLDM_ESHAPE, "afldm_dpm_step: bad shape");
+  hipStream_t st = (hipStream_t)stream;
+  const int HW = H * W;
+  const size_t n = (size_t)B * C * HW;
+  const bool v4 = HW % 4 == 0 && aligned16(x) && aligned16(x_out) && aligned16(hist);
+  if (v4) {
+    DISPATCH_T(dtype, (k_dpm_step<float, 4><<<dpm_grid(n / 4), 256, 0, st>>>(x, (const float*)eps, x_out, hist, coef, step_idx, B, C, HW)),
+               (k_dpm_step<bf16, 4><<<dpm_grid(n / 4), 256, 0, st>>>(x, (const bf16*)eps, x_out, hist, coef, step_idx, B, C, HW)),
+               "afldm_dpm_step");
+  } else {
+    DISPATCH_T(dtype, (k_dpm_step<float, 1><<<dpm_grid(n), 256, 0, st>>>(x, (const float*)eps, x_out, hist, coef, step_idx, B, C, HW)),
+               (k_dpm_step<bf16, 1><<<dpm_grid(n), 256, 0, st>>>(x, (const bf16*)eps, x_out, hist, coef, step_idx, B, C, HW)),
+               "afldm_dpm_step");
+  }
+  if (advance) k_dpm_advance<<<1, 1, 0, st>>>(step_idx);
+  return check_launch("afldm_dpm_step");
+}
+
+extern "C" int afldm_dpm_step_flat(const float* x, const float* eps, float* x_out, float* hist, float p, float q, float a,
+                                   float b0, float b1, float b2, size_t n, afldm_stream_t stream) {
+  AFLDM_REQUIRE(x && eps && x_out && hist, AFLDM_ENULL, "afldm_dpm_step_flat: NULL pointer");
+  if (n == 0) return AFLDM_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const dpm_row c{p, q, a, b0, b1, b2};
+  // the second history plane starts n floats in: 16-byte groups need n % 4 == 0 as well as aligned bases
+  if (n % 4 == 0 && aligned16(x) && aligned16(eps) && aligned16(x_out) && aligned16(hist))
+    k_dpm_step_flat<4><<<dpm_grid(n / 4), 256, 0, st>>>(x, eps, x_out, hist, c, n);
+  else
+    k_dpm_step_flat<1><<<dpm_grid(n), 256, 0, st>>>(x, eps, x_out, hist, c, n);
+  return check_launch("afldm_dpm_step_flat");
+}

@@ -12,6 +12,9 @@ increments itself — so a replay needs no host value and no synchronisation:
     x_nhwc <- NCHW fp32 latents                   (afldm_nchw_to_nhwc)
     eps    <- UNet(x_nhwc, t)                     (~250 HIP kernels at batch 64, all from libafldm_hip.so)
     lat    <- DDIM(lat, eps, coef[step])          (afldm_ddim_step, in place)
+
+A scheduler with `update_kind = "dpm"` (DPMSolverMultistepScheduler) has [steps, 8] rows instead and the last line
+is afldm_dpm_step, which also keeps the solver's two previous converted outputs in an fp32 history buffer.
 """
 import os
 
@@ -52,6 +55,10 @@ class DenoiseEngine:
         self.t_cur = torch.zeros(1, dtype=torch.float32, device=dev)
         self.lat = torch.zeros(batch_size, c, s, s, dtype=torch.float32, device=dev)
         self.x_nhwc = torch.empty(batch_size, s, s, c, dtype=unet.dtype, device=dev)
+        # the update: DDIM's linear form (also the I2SB ODE and inversion rows) unless the scheduler says otherwise
+        self.update_kind = getattr(scheduler, "update_kind", "ddim")
+        if self.update_kind not in ("ddim", "dpm"):
+            raise NotImplementedError(f"DenoiseEngine: update_kind {self.update_kind!r}")
         self.graph = None
         self.graph_multi = None
         # a replay boundary costs ~9 us of idle GPU (host launch + graph start): besides the one-step graph a
@@ -74,6 +81,10 @@ class DenoiseEngine:
         # counters of in-kernel reductions / cluster hand-overs: private to this engine (one per branch), so that its
         # captured graphs can replay next to another engine's on a different stream
         self._sync = [ops.new_sync_buffer(dev) for _ in range(self.branches)]
+        # DPM-Solver history (the two previous converted outputs), one contiguous [2, B / branches, C, H, W] per branch
+        self.hist = None
+        if self.update_kind == "dpm":
+            self.hist = torch.zeros(self.branches, 2, batch_size // self.branches, c, s, s, dtype=torch.float32, device=dev)
 
     # one denoise step, entirely stream-ordered
     def _step(self):
@@ -101,10 +112,14 @@ class DenoiseEngine:
         with ops.sync_scope(self._sync[branch]):
             ops.to_nhwc(lat, self.unet.dtype, out=x_nhwc)
             eps = self.unet.forward_nhwc(x_nhwc, self.t_cur, temb_slices=self.temb_slices)
-            ops.ddim_step(lat, eps, self.coef, self.step_idx, advance=False, out=lat)
+            if self.hist is None:
+                ops.ddim_step(lat, eps, self.coef, self.step_idx, advance=False, out=lat)
+            else:
+                ops.dpm_step(lat, eps, self.hist[branch], self.coef, self.step_idx, advance=False, out=lat)
 
     def _capture(self):
         keep = self.lat.clone()
+        keep_hist = None if self.hist is None else self.hist.clone()     # the warm-up step shifts the history too
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                 # warm-up: packs weights, fills caches, sizes workspaces
@@ -128,6 +143,8 @@ class DenoiseEngine:
             self.graph_multi = gm
         self.step_idx.fill_(-1)
         self.lat.copy_(keep)
+        if keep_hist is not None:
+            self.hist.copy_(keep_hist)
 
     def check_errors(self):
         """Read (and clear) the error words of this engine's sync buffers.  The attention block's in-launch hand-over
@@ -172,6 +189,8 @@ class DenoiseEngine:
         self.refresh_if_stale()
         self.lat.copy_(latents.to(device=self.lat.device, dtype=torch.float32) * self.scheduler.init_noise_sigma)
         self.step_idx.fill_(-1)
+        if self.hist is not None:
+            self.hist.zero_()        # the first rows weigh it by 0, but stale memory may hold NaN
 
     def step(self, k=1):
         if self.use_graph and self.graph is None:

@@ -189,6 +189,10 @@ def shift_ldm(pipeline, num_inference_steps=50, num_shift_steps=16, output_path=
       sample_size; the reference resizes to (sample_size, sample_size) = 32 x 32 BEFORE the VAE
       (shift_ldm_ffhq.py:110-113), i.e. inverts a 4 x 4 latent.
     * the initial noise is drawn on the CPU (device independent) instead of on the GPU (:118-122)."""
+    from .schedulers.dpmsolver import DPMSolverMultistepScheduler
+    if isinstance(pipeline.scheduler, DPMSolverMultistepScheduler):
+        raise NotImplementedError("shift_ldm samples with DDIM (cross-frame STORE / LOAD passes): a pipeline whose scheduler is "
+                                  "a DPMSolverMultistepScheduler is not supported")
     device = pipeline.device
     vae, unet, scheduler = pipeline.vae, pipeline.unet, pipeline.scheduler
     pipeline.set_progress_bar_config(disable=True)

@@ -1373,6 +1373,33 @@ def ddim_step_flat(x, eps, coefs, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- DPM-Solver(++)
+def dpm_step(x, eps_nhwc, hist, coef, step_idx, advance=False, out=None):
+    """x NCHW fp32, eps NHWC dtype, hist fp32 [2, B, C, H, W] (updated in place); coef float[8*nsteps] and step_idx
+    int32[1] on device."""
+    _dev(x, "x"); _dev(eps_nhwc, "eps"); _dev(hist, "hist")
+    B, C, H, W = x.shape
+    assert hist.dtype == torch.float32 and hist.is_contiguous() and tuple(hist.shape) == (2, B, C, H, W)
+    if out is None:
+        out = torch.empty_like(x)
+    check(lib.afldm_dpm_step(ptr(x), ptr(eps_nhwc), ptr(out), ptr(hist), ptr(coef), ptr(step_idx), int(advance), B, C, H, W,
+                             _code(eps_nhwc), stream_ptr()), "dpm_step")
+    return out
+
+
+def dpm_step_flat(x, eps, hist, row, out=None):
+    """x, eps: same-shape contiguous fp32 CUDA tensors; hist fp32 [2, *x.shape] (updated in place); row = the six
+    floats (p, q, a, b0, b1, b2)."""
+    _dev(x, "x"); _dev(eps, "eps"); _dev(hist, "hist")
+    assert x.dtype == eps.dtype == hist.dtype == torch.float32 and x.shape == eps.shape and hist.is_contiguous()
+    assert hist.numel() == 2 * x.numel()
+    if out is None:
+        out = torch.empty_like(x)
+    check(lib.afldm_dpm_step_flat(ptr(x), ptr(eps), ptr(out), ptr(hist), *[float(c) for c in row[:6]], x.numel(),
+                                  stream_ptr()), "dpm_step_flat")
+    return out
+
+
 def select_timestep(tvals, step_idx, t_out, pre_advance=False):
     check(lib.afldm_select_timestep(ptr(tvals), ptr(step_idx), ptr(t_out), int(pre_advance), stream_ptr()),
           "select_timestep")

@@ -12,6 +12,7 @@ import torch
 from ..engine import DenoiseEngine
 from ..models.unet_2d import UNet2DModel
 from ..schedulers.ddim import DDIMScheduler
+from ..schedulers.dpmsolver import DPMSolverMultistepScheduler
 from ..utils import randn_tensor
 from .pipeline_utils import DiffusionPipeline, ImagePipelineOutput
 
@@ -42,7 +43,7 @@ class MyLDMPipeline(DiffusionPipeline):
         # scheduler object: __call__ re-creates the scheduler every time (like the reference, ldm_pipeline.py:80),
         # and an identity key made every call rebuild the engine and re-capture its HIP graphs
         cfg_key = tuple(sorted((k, repr(v)) for k, v in dict(self.scheduler.config).items()))
-        key = (batch, steps, use_graph, self.unet.dtype, str(self.unet.device), cfg_key)
+        key = (batch, steps, use_graph, self.unet.dtype, str(self.unet.device), type(self.scheduler), cfg_key)
         if key not in self._engines:
             self._engines = {key: DenoiseEngine(self.unet, self.scheduler, batch, steps, use_graph)}
         return self._engines[key]
@@ -50,11 +51,15 @@ class MyLDMPipeline(DiffusionPipeline):
     @torch.no_grad()
     def __call__(self, batch_size=1, generator=None, eta=0.0, num_inference_steps=50, latents=None,
                  output_type="pil", return_dict=True, use_graph=True, **kwargs):
-        self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
+        # DDIM, as the reference forces (ldm_pipeline.py:80), unless the caller opted into DPM-Solver(++): that one is
+        # re-created from its own config, and `eta` does not apply to it (diffusers' accepts_eta)
+        dpm = isinstance(self.scheduler, DPMSolverMultistepScheduler)
+        sched_cls = DPMSolverMultistepScheduler if dpm else DDIMScheduler
+        self.scheduler = sched_cls.from_config(self.scheduler.config)
         if latents is None:
             latents = randn_tensor((batch_size, self.unet.config.in_channels, self.unet.config.sample_size,
                                     self.unet.config.sample_size), generator=generator)
-        if eta != 0.0:
+        if eta != 0.0 and not dpm:
             # stochastic DDIM (reference ldm_pipeline.py:96-109 forwards eta to scheduler.step): the per-step noise comes
             # from the caller's generator on the host, so this is the eager loop, not the captured graph
             self.scheduler.set_timesteps(num_inference_steps)
@@ -102,6 +107,8 @@ class MyLDMPipeline(DiffusionPipeline):
         otherwise - bf16 latents, which the reference carries in their own dtype between steps, or a UNet with cross-frame
         processors installed - the eager loop below."""
         from .. import ops
+        if isinstance(self.scheduler, DPMSolverMultistepScheduler):
+            raise NotImplementedError("ddim_inversion needs a DDIMScheduler: DPM-Solver inversion is not implemented")
         rows = self._inversion_rows()
         if (use_graph and latent.is_cuda and latent.dtype == torch.float32 and len(rows) >= 1
                 and tuple(latent.shape[1:]) == (self.unet.config.in_channels, self.unet.config.sample_size, self.unet.config.sample_size)

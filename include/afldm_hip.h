@@ -413,6 +413,20 @@ int afldm_ddim_step(const float* x, const void* eps, float* x_prev, const float*
 int afldm_ddim_step_flat(const float* x, const float* eps, float* x_prev, float sqrt_a_t,
                          float sqrt_1m_a_t, float sqrt_a_prev, float sqrt_1m_a_prev, size_t n,
                          afldm_stream_t stream);
+/* ---- DPM-Solver(++) multistep update ---------------------------------------------------------
+ * DPMSolverMultistepScheduler.step, orders 1-3, epsilon / v / sample prediction, no thresholding: each step is
+ * the coefficient row (p, q, a, b0, b1, b2, 0, 0) applied elementwise,
+ *   m0 = p x + q eps;  x_out = a x + b0 m0 + b1 h1 + b2 h2;  then h2 <- h1, h1 <- m0
+ * (m0: the converted model output - x0 for dpmsolver++, eps for dpmsolver; h1, h2: the two before it).
+ * coef: device float[8*nsteps]; step_idx / advance as afldm_ddim_step (capturable).
+ * x, x_out: NCHW fp32 [B,C,H,W], may alias; eps: NHWC dtype; hist: fp32 [2][B][C][H][W], h1 then h2,
+ * zeroed before the first step (its coefficients are 0 there, but 0 * NaN is not). */
+int afldm_dpm_step(const float* x, const void* eps, float* x_out, float* hist, const float* coef, int* step_idx,
+                   int advance, int B, int C, int H, int W, int dtype, afldm_stream_t stream);
+/* Same update on flat same-layout fp32 tensors of n elements, hist [2][n], the row by value: the
+ * DPMSolverMultistepScheduler.step(model_output, timestep, sample) API. */
+int afldm_dpm_step_flat(const float* x, const float* eps, float* x_out, float* hist, float p, float q, float a,
+                        float b0, float b1, float b2, size_t n, afldm_stream_t stream);
 /* tvals[step] -> t_out[0] (device->device), so the timestep also follows step_idx.  pre_advance != 0:
  * step_idx is incremented first (a sampler loop then starts from step_idx = -1 and needs no `advance`
  * launch behind afldm_ddim_step). */
