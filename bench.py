@@ -10,11 +10,15 @@ MFMA with fp32 accumulation), synthetic: seeded random weights of the FFHQ archi
 (conv_out x0.1), CPU-seeded noise, inputs resident in HBM before the timed region.
 N > 1: launched by torch.distributed.run, one rank per GPU, batch-sharded (weak scaling: 64 per
 GPU), no per-step communication, ONE RCCL all-gather of the final latents inside the timed
-region.  Rank 0 prints one JSON line.  At N = 1 the same line also carries, timed inside this run: the other
-single-GPU configurations of north_star (batch 1 / 8 bf16, batch 64 / 1 fp32: `other_configs`), BASELINE configs[3]
-(the AF-VAE at 256^2 x 128 with its shift-equivariance check: `vae_c4`; also `--workload vae` on its own), the north-star
-harness procedure of BASELINE configs[0] on the graph-replayed path (`harness_c1`; `--workload harness`), the
-roofline of the dominant kernel family and the CPU baseline on BASELINE configs[0].
+region.  Rank 0 prints one JSON line.  A plain run does only that: set up, warm up, time the steps, dump (if asked) and
+print.  With --full the same line also carries the box fingerprint (`box`), the roofline of the dominant kernel family
+(`roofline`, `kernel_families`, `step_dense`), at N > 1 the process-group record with the all-gather timed and verified
+on its own (`rccl`), and at N = 1, timed inside this run: the other single-GPU configurations of north_star (batch 1 / 8
+bf16, batch 64 / 1 fp32: `other_configs`; `concurrent_jobs`), BASELINE configs[3] (the AF-VAE at 256^2 x 128 with its
+shift-equivariance check: `vae_c4`; also `--workload vae` on its own), the north-star harness procedure of BASELINE
+configs[0] on the graph-replayed path (`harness_c1`; `--workload harness`), the I2SB bridge of BASELINE configs[4]
+(`i2sb_c5`) and the CPU baseline on BASELINE configs[0] (`cpu_baseline`).  --no-roofline / --no-extras /
+--no-cpu-baseline leave single parts of that out.
 """
 import argparse
 import json
@@ -602,9 +606,13 @@ def main():
                     help="the --steps timed steps are split over at most this many regions; the median is reported")
     ap.add_argument("--workload", default="unet", choices=["unet", "vae", "harness"])
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the batch 1 / 8 / fp32 / AF-VAE side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also measure and check everything else: box fingerprint, roofline and "
+                         "kernel families, process-group record (N > 1), side configurations and workloads, CPU baseline (N = 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline and kernel families")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the batch 1 / 8 / fp32 / concurrent-job / AF-VAE / harness / I2SB side measurements")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the latents of the last timed step as DIR/latents.npy (float32; unet workload)")
     args = ap.parse_args()
@@ -676,9 +684,9 @@ def main():
     # the output of the last timed step, as a caller of the sampler receives it (N > 1: the all-gathered latents)
     dumped = dump_outputs(args.dump_outputs, {"latents": final if world > 1 else eng.lat}) \
         if args.dump_outputs and rank == 0 else None
-    # the process group as it actually ran (every rank takes part): world size, backend, each rank's device, and the
-    # sampler's one collective timed on its own + verified block by block
-    rccl = parallel.rccl_record(dev, local, payload=eng.lat) if world > 1 else None
+    # --full: the process group as it actually ran (every rank takes part): world size, backend, each rank's device, and
+    # the sampler's one collective timed on its own + verified block by block
+    rccl = parallel.rccl_record(dev, local, payload=eng.lat) if world > 1 and args.full else None
 
     if rank == 0:
         out = {
@@ -708,6 +716,8 @@ def main():
         }
         if dumped is not None:
             out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+    if rank == 0 and args.full:
+        # everything besides the headline figure: measured after it, by rank 0 of the same process
         out["rccl"] = rccl if rccl is not None else {"world_size": 1, "backend": None,
                                                      "note": "single process: no process group, no collective"}
         out["box"] = box_record(dev)
@@ -744,6 +754,7 @@ def main():
             out["i2sb_c5"] = i2sb_c5()
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline()
+    if rank == 0:
         print(json.dumps(out), flush=True)
     parallel.barrier()
 

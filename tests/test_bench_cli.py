@@ -72,3 +72,20 @@ def test_bench_dump_outputs_are_the_latents_of_the_last_timed_step(tmp_path):
     rel = lambda a, b: float((a - b).pow(2).mean().sqrt() / b.pow(2).mean().sqrt())
     print(f"[bench dump] vs engine step 12: {rel(got, ref):.3e}; step 11 vs 12: {rel(prev, ref):.3e}")
     assert rel(got, ref) <= 1e-3 and rel(prev, ref) > 10 * max(rel(got, ref), 1e-6)
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_prints_the_headline_line_only():
+    """A plain run (no --full) sets up, warms up, times its steps and prints the result line; the records that take runs
+    of their own (box fingerprint, roofline, side configurations and workloads, CPU baseline) come only with --full."""
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "5", "--warmup", "1"]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert r.returncode == 0 and len(lines) == 1, r.stdout[-2000:] + r.stderr[-3000:]
+    d = json.loads(lines[0])
+    assert d["unit"] == "denoise-steps/s" and d["higher_is_better"] is True and d["dtype"] == "bf16" and d["n_gpus"] == 1
+    assert d["steps"] == 5 and sum(d["config"]["region_steps"]) == 5 and d["config"]["latents_finite"]
+    assert d["value"] > 0 and abs(d["value"] - 64e3 / d["ms_per_step"]) <= 1e-3 * d["value"]
+    full_only = {"rccl", "box", "roofline", "kernel_families", "step_dense", "other_configs", "concurrent_jobs", "vae_c4",
+                 "harness_c1", "i2sb_c5", "cpu_baseline"}
+    assert not full_only & set(d), sorted(full_only & set(d))

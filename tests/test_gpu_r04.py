@@ -479,7 +479,7 @@ def test_bench_two_ranks_on_one_gpu_runs_the_multi_rank_path():
     GPU of the test box: AFLDM_SAME_GPU=1 puts both ranks on device 0 and the backend is gloo (RCCL refuses two ranks on
     one device).  Not a scaling point - it executes everything the N > 1 line needs besides RCCL itself: per-rank noise
     shards and graph capture, barrier + MAX-over-ranks timing, the all-gather of the final latents inside the timed
-    region, the process-group record; and it checks the record's honesty (2 ranks, ONE distinct device)."""
+    region, the process-group record (--full); and it checks the record's honesty (2 ranks, ONE distinct device)."""
     import json, os, socket, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     with socket.socket() as s:
@@ -488,7 +488,7 @@ def test_bench_two_ranks_on_one_gpu_runs_the_multi_rank_path():
     env = dict(os.environ, AFLDM_SAME_GPU="1", AFLDM_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--regions", "1",
-           "--no-cpu-baseline", "--no-extras", "--no-roofline"]
+           "--full", "--no-cpu-baseline", "--no-extras", "--no-roofline"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, r.stdout[-2000:] + r.stderr[-3000:]
