@@ -117,6 +117,7 @@ def _load():
         "afldm_ddim_step_flat": ([vp, vp, vp, fp, fp, fp, fp, c_size_t, vp], c_int),
         "afldm_dpm_step": ([vp, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, vp], c_int),
         "afldm_dpm_step_flat": ([vp, vp, vp, vp, fp, fp, fp, fp, fp, fp, c_size_t, vp], c_int),
+        "afldm_sde_step": ([vp, vp, vp, c_size_t, vp, vp, vp, ip, ip, ip, ip, ip, ip, vp], c_int),
         "afldm_select_timestep": ([vp, vp, vp, ip, vp], c_int),
         "afldm_select_step_row": ([vp, vp, vp, ip, vp, vp, c_size_t, vp], c_int),
         "afldm_probe_mfma": ([vp, ip, ip, vp], c_int),

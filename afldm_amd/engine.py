@@ -15,6 +15,12 @@ increments itself — so a replay needs no host value and no synchronisation:
 
 A scheduler with `update_kind = "dpm"` (DPMSolverMultistepScheduler) has [steps, 8] rows instead and the last line
 is afldm_dpm_step, which also keeps the solver's two previous converted outputs in an fp32 history buffer.
+
+A schedule with `update_kind = "sde"` (schedulers/sde.py: DDIM with eta != 0, the stochastic / clipped I2SB bridge) has
+[steps, 8] rows (p, q, lo, hi, a, b, d, c) and the last line is afldm_sde_step, which also reads that step's row of an fp32
+noise buffer [steps, B, C, H, W].  The noise is drawn per run by the caller's generator - run(latents, draw=...), the same
+randn calls the eager loop makes, in the same order - never inside a capture.  Draws on the CPU (a CPU generator) go through
+pinned staging: the next replay group's noise is drawn while the GPU runs the current group.
 """
 import os
 
@@ -57,7 +63,7 @@ class DenoiseEngine:
         self.x_nhwc = torch.empty(batch_size, s, s, c, dtype=unet.dtype, device=dev)
         # the update: DDIM's linear form (also the I2SB ODE and inversion rows) unless the scheduler says otherwise
         self.update_kind = getattr(scheduler, "update_kind", "ddim")
-        if self.update_kind not in ("ddim", "dpm"):
+        if self.update_kind not in ("ddim", "dpm", "sde"):
             raise NotImplementedError(f"DenoiseEngine: update_kind {self.update_kind!r}")
         self.graph = None
         self.graph_multi = None
@@ -85,6 +91,14 @@ class DenoiseEngine:
         self.hist = None
         if self.update_kind == "dpm":
             self.hist = torch.zeros(self.branches, 2, batch_size // self.branches, c, s, s, dtype=torch.float32, device=dev)
+        # stochastic update: one noise row per step, filled per run; the steps that draw none keep zeros (c = 0 there, and
+        # 0 * NaN of stale memory is not 0).  Pinned staging for CPU draws, one buffer per replay group in flight.
+        self.noise = None
+        if self.update_kind == "sde":
+            self.draws = tuple(scheduler.draws)
+            assert len(self.draws) == num_inference_steps
+            self.noise = torch.zeros(num_inference_steps, batch_size, c, s, s, dtype=torch.float32, device=dev)
+            self._stage = []
 
     # one denoise step, entirely stream-ordered
     def _step(self):
@@ -112,7 +126,11 @@ class DenoiseEngine:
         with ops.sync_scope(self._sync[branch]):
             ops.to_nhwc(lat, self.unet.dtype, out=x_nhwc)
             eps = self.unet.forward_nhwc(x_nhwc, self.t_cur, temb_slices=self.temb_slices)
-            if self.hist is None:
+            if self.noise is not None:
+                per = self.B // self.branches
+                ops.sde_step(lat, eps, self.noise[:, branch * per:(branch + 1) * per], self.coef, self.step_idx, advance=False,
+                             out=lat)
+            elif self.hist is None:
                 ops.ddim_step(lat, eps, self.coef, self.step_idx, advance=False, out=lat)
             else:
                 ops.dpm_step(lat, eps, self.hist[branch], self.coef, self.step_idx, advance=False, out=lat)
@@ -205,10 +223,55 @@ class DenoiseEngine:
         for _ in range(k):
             self.graph.replay()
 
+    def _fill(self, k0, k1, draw):
+        """Noise rows k0 .. k1 - 1: one draw() per step that draws, in step order.  A CPU draw is copied into pinned staging and
+        on to the device with non_blocking (stream-ordered before the replays that read it); the staging buffer is reused only
+        after the event behind its previous copy has passed.  A device draw is copied on the stream."""
+        ks = [k for k in range(k0, k1) if self.draws[k]]
+        if not ks:
+            return
+        stage = None
+        for i, k in enumerate(ks):
+            z = draw()
+            if tuple(z.shape) != tuple(self.noise.shape[1:]):
+                raise ValueError(f"DenoiseEngine: draw() gave {tuple(z.shape)}, want {tuple(self.noise.shape[1:])}")
+            if z.device.type != "cpu":
+                self.noise[k].copy_(z)
+                continue
+            if stage is None:
+                if len(self._stage) < 2:
+                    self._stage.append((torch.empty((self.steps_per_graph,) + tuple(self.noise.shape[1:]), dtype=torch.float32,
+                                                    pin_memory=True), torch.cuda.Event()))
+                    stage = self._stage[-1]
+                else:
+                    self._stage.append(self._stage.pop(0))          # the older of the two
+                    stage = self._stage[-1]
+                    stage[1].synchronize()
+            stage[0][i].copy_(z)
+            self.noise[k].copy_(stage[0][i], non_blocking=True)
+        if stage is not None:
+            stage[1].record()
+
     @torch.no_grad()
-    def run(self, latents):
+    def run(self, latents, draw=None):
+        """latents -> the sampled latents (fp32).  An "sde" schedule needs `draw`: a callable returning the next noise tensor
+        [B, C, H, W] (on the CPU or on the engine's device, any float dtype), called once per drawing step in step order -
+        for a seeded run, the scheduler's own randn_tensor call with the caller's generator (SdeSchedule.draw_noise)."""
         self.reset(latents)
-        self.step(self.n)
+        if self.noise is None:
+            self.step(self.n)
+        else:
+            if draw is None:
+                raise ValueError("DenoiseEngine: a stochastic ('sde') schedule needs run(latents, draw=...)")
+            # group by replay: while the GPU runs one group, the host draws the next one's noise
+            g = self.steps_per_graph if self.use_graph else 1
+            self._fill(0, min(g, self.n), draw)
+            k = 0
+            while k < self.n:
+                m = min(g, self.n - k)
+                self.step(m)
+                k += m
+                self._fill(k, min(k + g, self.n), draw)
         out = self.lat.clone()
         self.check_errors()                           # one 8-byte read per run: a run whose hand-over failed must not return latents
         return out

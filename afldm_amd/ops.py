@@ -1400,6 +1400,24 @@ def dpm_step_flat(x, eps, hist, row, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- stochastic update (DDIM eta != 0, I2SB bridge)
+def sde_step(x, eps_nhwc, noise, coef, step_idx, advance=False, out=None):
+    """x NCHW fp32 [B, C, H, W], eps NHWC dtype; noise: fp32 view [steps, B, C, H, W] whose last four dimensions are contiguous
+    (a batch slice of a larger buffer is fine: the row stride is noise.stride(0)); coef float[8*nsteps] rows
+    (p, q, lo, hi, a, b, d, c) and step_idx int32[1] on device."""
+    _dev(x, "x"); _dev(eps_nhwc, "eps")
+    if not noise.is_cuda:
+        raise RuntimeError("afldm_amd: noise must live on an MI355X (cuda) device; there is no CPU path")
+    B, C, H, W = x.shape
+    assert noise.dtype == torch.float32 and noise.dim() == 5 and tuple(noise.shape[1:]) == (B, C, H, W)
+    assert noise[0].is_contiguous() and noise.stride(0) >= B * C * H * W
+    if out is None:
+        out = torch.empty_like(x)
+    check(lib.afldm_sde_step(ptr(x), ptr(eps_nhwc), ptr(noise), noise.stride(0), ptr(out), ptr(coef), ptr(step_idx),
+                             int(advance), B, C, H, W, _code(eps_nhwc), stream_ptr()), "sde_step")
+    return out
+
+
 def select_timestep(tvals, step_idx, t_out, pre_advance=False):
     check(lib.afldm_select_timestep(ptr(tvals), ptr(step_idx), ptr(t_out), int(pre_advance), stream_ptr()),
           "select_timestep")

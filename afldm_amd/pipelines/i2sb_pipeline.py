@@ -45,15 +45,33 @@ class I2SBLDMPipeline(MyLDMPipeline):
             cache[key] = DenoiseEngine(self.unet, ode, batch, ode.evaluations, use_graph=True)
         return cache[key]
 
+    def _sde_engine(self, batch, steps, is_ode):
+        """DenoiseEngine over the stochastic and / or clipped bridge (scheduler.bridge_schedule, afldm_sde_step), cached apart from
+        the unclipped ODE's engines."""
+        from ..engine import DenoiseEngine
+        sde = self.scheduler.bridge_schedule(steps, is_ode)
+        cfg_key = tuple(sorted((k, repr(v)) for k, v in dict(sde.config).items()))
+        key = (batch, steps, self.unet.dtype, str(self.unet.device), cfg_key)
+        cache = self.__dict__.setdefault("_sde_engines", {})
+        if key not in cache:
+            cache.clear()
+            cache[key] = DenoiseEngine(self.unet, sde, batch, len(sde.rows), use_graph=True)
+        return cache[key]
+
     def _bridge(self, latents, steps, is_ode, generator, latent_dtype=torch.float32, use_graph=True):
         """steps - 1 UNet evaluations from the encoded degraded image towards the clean latent: the reference loop
-        leaves before its last timestep (i2sb_pipeline.py:48-50).  The deterministic, unclipped bridge with the latent carried
-        in fp32 (is_ode, clip_sample off - what scripts/shift_ldm_sr.py runs) replays captured HIP graphs (use_graph); the
-        stochastic / clipped forms and latent_dtype=None run the eager loop below."""
+        leaves before its last timestep (i2sb_pipeline.py:48-50).  With the latent carried in fp32 every form replays captured
+        HIP graphs (use_graph): the deterministic, unclipped bridge (is_ode, clip_sample off - what scripts/shift_ldm_sr.py
+        runs) on the DDIM kernel's linear form, the stochastic and / or clipped forms on afldm_sde_step, whose noise the engine
+        draws with `generator` exactly as the loop below does (same randn_tensor calls, same order).  use_graph=False and
+        latent_dtype=None run the eager loop below."""
         sched, unet = self.scheduler, self.unet
-        if (use_graph and is_ode and not sched.config.clip_sample and latent_dtype == torch.float32 and latents.is_cuda
-                and steps >= 2):
-            return self._ode_engine(latents.shape[0], steps).run(latents).to(latents.dtype)
+        if use_graph and latent_dtype == torch.float32 and latents.is_cuda and steps >= 2:
+            if is_ode and not sched.config.clip_sample:
+                return self._ode_engine(latents.shape[0], steps).run(latents).to(latents.dtype)
+            eng = self._sde_engine(latents.shape[0], steps, is_ode)
+            draw = eng.scheduler.drawer(generator, tuple(latents.shape), latents.device, torch.float32)
+            return eng.run(latents, draw=draw).to(latents.dtype)
         sched.set_timesteps(steps)
         # The latent is carried in fp32 BETWEEN evaluations whatever the UNet's dtype (as DenoiseEngine does for DDIM): a
         # step of the 100-step bridge moves the latent by about one bf16 ulp, and a latent stored in bf16 - what the

@@ -38,14 +38,16 @@ class MyLDMPipeline(DiffusionPipeline):
             vae = AutoencoderKL.from_pretrained(path, subfolder="vae")
         return cls(vae, unet, scheduler)
 
-    def _engine(self, batch, steps, use_graph):
+    def _engine(self, batch, steps, use_graph, schedule=None):
         # keyed on the scheduler's CONFIG (the coefficient / timestep tables are a function of it), not on the
         # scheduler object: __call__ re-creates the scheduler every time (like the reference, ldm_pipeline.py:80),
-        # and an identity key made every call rebuild the engine and re-capture its HIP graphs
-        cfg_key = tuple(sorted((k, repr(v)) for k, v in dict(self.scheduler.config).items()))
-        key = (batch, steps, use_graph, self.unet.dtype, str(self.unet.device), type(self.scheduler), cfg_key)
+        # and an identity key made every call rebuild the engine and re-capture its HIP graphs.  `schedule`: a view of the
+        # scheduler to replay instead (the stochastic DDIM rows, whose config carries eta)
+        sched = self.scheduler if schedule is None else schedule
+        cfg_key = tuple(sorted((k, repr(v)) for k, v in dict(sched.config).items()))
+        key = (batch, steps, use_graph, self.unet.dtype, str(self.unet.device), type(sched), cfg_key)
         if key not in self._engines:
-            self._engines = {key: DenoiseEngine(self.unet, self.scheduler, batch, steps, use_graph)}
+            self._engines = {key: DenoiseEngine(self.unet, sched, batch, steps, use_graph)}
         return self._engines[key]
 
     @torch.no_grad()
@@ -59,9 +61,18 @@ class MyLDMPipeline(DiffusionPipeline):
         if latents is None:
             latents = randn_tensor((batch_size, self.unet.config.in_channels, self.unet.config.sample_size,
                                     self.unet.config.sample_size), generator=generator)
+        if eta != 0.0 and not dpm and use_graph:
+            # stochastic DDIM (reference ldm_pipeline.py:96-109 forwards eta to scheduler.step) on the captured graphs: the
+            # engine draws every step's noise with the caller's generator - the randn_tensor calls of the loop below, in its
+            # order - before the replays that read it.  The latent is carried in fp32 between steps, as for eta = 0; with a
+            # bf16 UNet the loop below stores it in bf16 (the reference's storage), so the two differ by that rounding.
+            sde = self.scheduler.stochastic_schedule(num_inference_steps, eta)
+            eng = self._engine(latents.shape[0], num_inference_steps, use_graph, schedule=sde)
+            draw = eng.scheduler.drawer(generator, tuple(latents.shape), self.unet.device, self.unet.dtype)
+            latents = eng.run(latents, draw=draw).to(self.unet.dtype)
+            return self._deliver(latents, output_type, return_dict)
         if eta != 0.0 and not dpm:
-            # stochastic DDIM (reference ldm_pipeline.py:96-109 forwards eta to scheduler.step): the per-step noise comes
-            # from the caller's generator on the host, so this is the eager loop, not the captured graph
+            # stochastic DDIM, use_graph=False: the eager loop, one scheduler.step per UNet evaluation
             self.scheduler.set_timesteps(num_inference_steps)
             latents = latents.to(device=self.unet.device, dtype=self.unet.dtype)
             for t in self.progress_bar(self.scheduler._timesteps_host):

@@ -4,7 +4,9 @@ step, alphas_cumprod, final_alpha_cumprod, init_noise_sigma, config.
 
 The schedule tables are a few hundred host floats; `step` on CUDA tensors launches the HIP
 update kernel (afldm_ddim_step_flat).  eta = 0 / epsilon prediction / no clipping — the
-reference's configuration (configs/ldm/noise_scheduler.json:1-14); other settings raise."""
+reference's configuration (configs/ldm/noise_scheduler.json:1-14); other settings raise.  `stochastic_schedule`
+tabulates the eta != 0 update for the graph-replayed engine (afldm_sde_step)."""
+import math
 from dataclasses import dataclass
 
 import numpy as np
@@ -13,6 +15,7 @@ import torch
 from .. import ops
 from ..utils import randn_tensor
 from ..configs import FFHQ_DDIM_CONFIG, FrozenConfig
+from .sde import SdeSchedule
 
 
 @dataclass
@@ -98,6 +101,30 @@ class DDIMScheduler:
         """float32 [nsteps, 4] device table for the graph-replayed loop (afldm_ddim_step)."""
         rows = [self.coefficients(t) for t in self._timesteps_host]
         return torch.tensor(rows, dtype=torch.float32).to(device)
+
+    def sde_coefficients(self, timestep, eta):
+        """(p, q, lo, hi, a, b, d, c) of the stochastic step (diffusers DDIMScheduler.step with eta, epsilon prediction, no clip)
+        in float64 from the fp32 alphas_cumprod, for afldm_sde_step: x0 = (x - sqrt(1-a_t) eps) / sqrt(a_t) unclipped,
+        x_prev = sqrt(a_prev) x0 + sqrt(max(1 - a_prev - sigma^2, 0)) eps + sigma z, sigma = eta sqrt(_variance(t))."""
+        t = int(timestep)
+        prev_t = t - self.config.num_train_timesteps // self.num_inference_steps
+        a_t = float(self.alphas_cumprod[t])
+        a_prev = float(self.alphas_cumprod[prev_t]) if prev_t >= 0 else float(self.final_alpha_cumprod)
+        sigma = float(eta) * math.sqrt((1 - a_prev) / (1 - a_t) * (1 - a_t / a_prev))
+        return (1 / math.sqrt(a_t), -math.sqrt(1 - a_t) / math.sqrt(a_t), -math.inf, math.inf,
+                0.0, math.sqrt(a_prev), math.sqrt(max(1 - a_prev - sigma * sigma, 0.0)), sigma)
+
+    def stochastic_schedule(self, num_inference_steps, eta):
+        """The eta != 0 sampler of `num_inference_steps` as the schedule DenoiseEngine replays with afldm_sde_step.  Every step
+        draws, the last one included (its sigma is 0 with set_alpha_to_one, but step() still draws): randn_tensor in the
+        model's dtype, as step() draws with the model output's."""
+        if self.config.clip_sample or self.config.prediction_type != "epsilon":
+            raise NotImplementedError("afldm_amd.DDIMScheduler implements the reference's setting: "
+                                      "epsilon prediction, clip_sample=False")
+        self.set_timesteps(num_inference_steps)
+        ts = list(self._timesteps_host)
+        return SdeSchedule(dict(self.config, _ddim_eta=float(eta)), ts, [self.sde_coefficients(t, eta) for t in ts],
+                           [True] * len(ts), noise_dtype=None)
 
     def step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None,
              variance_noise=None, return_dict=True):

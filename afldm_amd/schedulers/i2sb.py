@@ -2,7 +2,9 @@
 pipeline (tables :188-197, set_timesteps :224-300, step :382-459, add_noise :461-485,
 compute_label :507-513, previous_timestep :518-531).  The schedule tables are host floats; `step`
 on CUDA tensors runs the same flat update kernel as DDIM (afldm_ddim_step_flat):
-  x0 = x - s_t eps;  x_prev = mu_x0 x0 + mu_xt x = (mu_x0 + mu_xt) x0 + mu_xt s_t eps."""
+  x0 = x - s_t eps;  x_prev = mu_x0 x0 + mu_xt x = (mu_x0 + mu_xt) x0 + mu_xt s_t eps.
+The graph-replayed engine takes the unclipped ODE as DDIM rows (ode_schedule) and every other form as afldm_sde_step rows
+(bridge_schedule)."""
 from dataclasses import dataclass
 
 import numpy as np
@@ -11,6 +13,7 @@ import torch
 from .. import ops
 from ..configs import FrozenConfig
 from ..utils import randn_tensor
+from .sde import SdeSchedule
 
 
 def compute_gaussian_product_coef(sigma1, sigma2):
@@ -141,6 +144,32 @@ class I2SBScheduler:
         its last timestep, i2sb_pipeline.py:48-50) as the (timesteps, coefficient table) object DenoiseEngine / the harness's
         CrossFrameSampler replay as HIP graphs; None when the configuration clips x0 (the clamp breaks the linear form)."""
         return None if self.config.clip_sample else _OdeSchedule(self, int(num_inference_steps))
+
+    def sde_coefficients(self, timestep, is_ode):
+        """(p, q, lo, hi, a, b, d, c) of step() in any (is_ode, clip_sample) form, in float64 from the fp32 std_fwd table, for
+        afldm_sde_step: x0 = clamp(x - std_fwd eps, -range, range) (unclipped: lo / hi = -inf / inf),
+        x_prev = mu_xt x + mu_x0 x0 + sqrt(var) z, the noise term only when t > 0 and not is_ode (reference
+        i2sb_scheduler.py:382-459)."""
+        t, prev_t = int(timestep), self.previous_timestep(timestep)
+        std_fwd, std_prev = np.float64(self.std_fwd[t]), np.float64(self.std_fwd[prev_t])
+        with np.errstate(invalid="ignore"):          # t = 0: prev_t < 0 wraps as in step(), and its noise term is off
+            std_delta = np.sqrt(std_fwd ** 2 - std_prev ** 2)
+            mu_x0, mu_xt, var = compute_gaussian_product_coef(std_prev, std_delta)
+            c = float(np.sqrt(var)) if t > 0 and not is_ode else 0.0
+        r = float(self.config.clip_sample_range) if self.config.clip_sample else float("inf")
+        return (1.0, -float(std_fwd), -r, r, float(mu_xt), float(mu_x0), 0.0, c)
+
+    def bridge_schedule(self, num_inference_steps, is_ode=False):
+        """The bridge of `num_inference_steps` (num_inference_steps - 1 UNet evaluations, as ode_schedule) in any form - the
+        stochastic one (is_ode=False, the pipeline's default) and / or with clip_sample (the scheduler's default) - as the
+        schedule DenoiseEngine replays with afldm_sde_step.  A step draws exactly when step() does (t > 0 and not is_ode),
+        in fp32 (step() draws with the fp32 model output's dtype)."""
+        steps = int(num_inference_steps)
+        self.set_timesteps(steps)
+        ts = list(self._timesteps_host[:steps - 1])
+        return SdeSchedule(dict(self.config, _i2sb_bridge_steps=steps, _i2sb_is_ode=bool(is_ode)), ts,
+                           [self.sde_coefficients(t, is_ode) for t in ts], [t > 0 and not is_ode for t in ts],
+                           noise_dtype=torch.float32)
 
     def step(self, model_output, timestep, sample, is_ode=False, generator=None, return_dict=True):
         if not sample.is_cuda:

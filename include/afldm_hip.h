@@ -427,6 +427,17 @@ int afldm_dpm_step(const float* x, const void* eps, float* x_out, float* hist, c
  * DPMSolverMultistepScheduler.step(model_output, timestep, sample) API. */
 int afldm_dpm_step_flat(const float* x, const float* eps, float* x_out, float* hist, float p, float q, float a,
                         float b0, float b1, float b2, size_t n, afldm_stream_t stream);
+/* ---- Stochastic sampler update (DDIM eta != 0, the I2SB bridge) ---------------------------------------------
+ * diffusers DDIMScheduler.step with eta != 0 (epsilon prediction, no clip) and I2SBScheduler.step in every
+ * (is_ode, clip_sample) form: step s = *step_idx applies the row coef[8 s .. 8 s + 8) = (p, q, lo, hi, a, b, d, c),
+ *   x0 = clamp(p x + q eps, lo, hi);  x_out = a x + b x0 + d eps + c z,  z = noise[s * noise_step_stride + i]
+ * lo = -inf, hi = +inf: no clip; the clamp passes a NaN through as torch.clamp does.  The noise rows are drawn by the
+ * caller's generator before the step (outside any captured graph): the same randn calls as the eager loop.
+ * x, x_out: NCHW fp32 [B,C,H,W], may alias; noise: fp32 rows of [B,C,H,W] NCHW, noise_step_stride floats apart
+ * (>= B*C*H*W: a branch passes its batch slice of a larger buffer); eps: NHWC dtype; advance as afldm_ddim_step. */
+int afldm_sde_step(const float* x, const void* eps, const float* noise, size_t noise_step_stride, float* x_out,
+                   const float* coef, int* step_idx, int advance, int B, int C, int H, int W, int dtype,
+                   afldm_stream_t stream);
 /* tvals[step] -> t_out[0] (device->device), so the timestep also follows step_idx.  pre_advance != 0:
  * step_idx is incremented first (a sampler loop then starts from step_idx = -1 and needs no `advance`
  * launch behind afldm_ddim_step). */
