@@ -27,6 +27,7 @@ class ConvArgs(Structure):
         ("defer_reduce", c_int), ("w_batch_stride", ctypes.c_longlong),
         ("y_norm", c_void_p), ("norm_gamma", c_void_p), ("norm_beta", c_void_p), ("norm_groups", c_int), ("norm_eps", c_float),
         ("x_layout", c_int), ("y_layout", c_int),
+        ("sc_x1", c_void_p), ("sc_x2", c_void_p), ("sc_w", c_void_p), ("sc_C1", c_int), ("sc_C2", c_int),
     ]
 
 
@@ -100,6 +101,7 @@ def _load():
         "afldm_conv2d_variant": ([POINTER(ConvArgs)], c_int),
         "afldm_conv2d_c8_ok": ([POINTER(ConvArgs)], c_int),
         "afldm_conv2d_norm_ok": ([POINTER(ConvArgs)], c_int),
+        "afldm_conv2d_shortcut_ok": ([POINTER(ConvArgs)], c_int),
         "afldm_conv2d_s2": ([POINTER(ConvArgs), ip, ip, vp], c_int),
         "afldm_conv2d_up2": ([POINTER(ConvArgs), vp], c_int),
         "afldm_conv2d_s2_stats_splits": ([POINTER(ConvArgs)], c_int),

@@ -2098,6 +2098,25 @@ static void fill_convp(const afldm_conv_args* a, ConvP& p) {
   p.x_c8 = a->x_layout == 1 ? 1 : 0;
   p.y_c8 = a->y_layout == 1 ? 1 : 0;
   p.w_nt = 0;       // set per plan (conv_dispatch: a single row tile)
+  p.sc_x1 = a->sc_x1; p.sc_x2 = a->sc_x2; p.sc_w = a->sc_w;
+  p.sc_C1 = a->sc_x1 ? a->sc_C1 : 0; p.sc_C2 = a->sc_x1 ? a->sc_C2 : 0;
+}
+
+// the 1x1 conv_shortcut folded into this 3x3 convolution (afldm_conv_args.sc_*): one k_conv3h launch with one tap per K step and
+// the whole K per workgroup; the shortcut's channel blocks must lie inside one of the two inputs, and no residual
+template <typename T>
+static bool shortcut_ok(const afldm_conv_args* a) {
+  const int kstep = KCH_DEFAULT * epr<T>();
+  const long long M = (long long)a->B * a->H * a->W, Csc = (long long)a->sc_C1 + a->sc_C2;
+  if (!a->sc_x1 || !a->sc_w || a->sc_C1 <= 0 || a->sc_C2 < 0 || a->sc_C1 % kstep || a->sc_C2 % kstep || (a->sc_C2 > 0) != (a->sc_x2 != nullptr))
+    return false;
+  if (!aligned16(a->sc_x1) || !aligned16(a->sc_x2) || !aligned16(a->sc_w)) return false;
+  if (a->KS != 3 || a->residual || a->defer_reduce || a->w_batch_stride || a->y_norm || a->y2 || a->out_mode != 0) return false;
+  const long long cmax = a->sc_C1 > a->sc_C2 ? a->sc_C1 : a->sc_C2;
+  if (M >= (1ll << 28) || M * cmax * (long long)sizeof(T) >= (1ll << 31) || (long long)a->Cout * Csc * (long long)sizeof(T) >= (1ll << 31)) return false;
+  if (lin_wreg_bm(a) || skinny_stats_splits(a)) return false;
+  const Exec ex = resolve_exec<T>(a);
+  return ex.pl.kind == 0 && kVariants[ex.vid].ver == 6 && ex.splitk == 1 && !ex.fused && conv3h_shortcut_ok(ex.vid);
 }
 
 // 8-channel-block operands (afldm_conv_args.x_layout / y_layout = 1): only where afldm_conv2d is ONE halo-patch launch with the
@@ -2121,6 +2140,8 @@ template <typename T>
 static int conv_dispatch(const afldm_conv_args* a, hipStream_t st) {
   AFLDM_REQUIRE((a->x_layout == 0 && a->y_layout == 0) || c8_ok<T>(a), AFLDM_ESHAPE,
                 "afldm_conv2d: x_layout / y_layout = 1 (8-channel blocks) is not available for this problem (afldm_conv2d_c8_ok)");
+  AFLDM_REQUIRE(!a->sc_x1 || shortcut_ok<T>(a), AFLDM_ESHAPE,
+                "afldm_conv2d: the folded shortcut (sc_x1 / sc_w) is not available for this problem (afldm_conv2d_shortcut_ok)");
   ConvP p;
   fill_convp<T>(a, p);
   const Exec ex = resolve_exec<T>(a);
@@ -2288,7 +2309,7 @@ static afldm_conv_args conv_chunk_args(const afldm_conv_args* a, int c) {
 // takes and *variant its id.  The merged launches of actconv.hip run that tile as their last phase.
 template <typename T>
 static bool plan_h3(const afldm_conv_args* a, ConvP& p, int& vid) {
-  if (conv_batch_chunk(a) != a->B || a->w_batch_stride || a->defer_reduce || a->KS != 3) return false;
+  if (conv_batch_chunk(a) != a->B || a->w_batch_stride || a->defer_reduce || a->KS != 3 || a->sc_x1) return false;
   if (lin_wreg_bm(a) || skinny_stats_splits(a)) return false;
   fill_convp<T>(a, p);
   const Exec ex = resolve_exec<T>(a);
@@ -2340,6 +2361,13 @@ extern "C" int afldm_conv2d_norm_ok(const afldm_conv_args* a) {
   return norm_fusable<bf16>(a, e, smode) ? 1 : 0;
 }
 
+extern "C" int afldm_conv2d_shortcut_ok(const afldm_conv_args* a) {
+  if (!a || conv_validate(a) || conv_batch_chunk(a) != a->B) return 0;
+  if (a->dtype == AFLDM_BF16) return shortcut_ok<bf16>(a) ? 1 : 0;
+  if (a->dtype == AFLDM_F32) return shortcut_ok<float>(a) ? 1 : 0;
+  return 0;
+}
+
 extern "C" int afldm_conv2d_stats_splits(const afldm_conv_args* a0) {
   if (!a0 || (a0->dtype != AFLDM_F32 && a0->dtype != AFLDM_BF16)) return 0;
   const afldm_conv_args ac = conv_chunk_args(a0, conv_batch_chunk(a0));
@@ -2369,6 +2397,7 @@ extern "C" int afldm_conv2d(const afldm_conv_args* a, afldm_stream_t stream) {
     return AFLDM_EDTYPE;
   }
   const int c = conv_batch_chunk(a);
+  AFLDM_REQUIRE(!a->sc_x1 || c == a->B, AFLDM_ESHAPE, "afldm_conv2d: the folded shortcut needs the whole batch in one launch");
   if (c == a->B) return a->dtype == AFLDM_F32 ? conv_dispatch<float>(a, st) : conv_dispatch<bf16>(a, st);
   // whole-sample chunks (see conv_batch_chunk): every per-sample operand advances by its own stride
   const size_t esz = a->dtype == AFLDM_F32 ? 4 : 2;

@@ -55,7 +55,13 @@
   const int ncb = Ct / KSTEP;
   const int ks = H3_BZ;
   const int cb_lo = (ncb * ks) / p.splitk, cb_hi = (ncb * (ks + 1)) / p.splitk;   // this slice's channel blocks
-  const int G = (cb_hi - cb_lo) * SPC;
+  // folded 1x1 shortcut (TPS == 1, whole K: conv3h_shortcut_ok): its nsc channel blocks follow the 3x3 ones as blocks cb_hi ..
+  // cb_end - 1 of ONE K step each - the centre tap of a patch whose halo is left zero (never read: no bytes fetched for it)
+  // (not on the 256-pixel tiles of whole 16x16 samples, variants 44 / 49: the extra loop spills there, and no shortcut site runs them)
+  constexpr bool HAS_SC = TPS == 1 && !SUB && !(BM == 256 && W_ == 16);
+  const int nsc = (HAS_SC && p.sc_x1) ? (p.sc_C1 + p.sc_C2) / KSTEP : 0;
+  const int cb_end = cb_hi + nsc;
+  const int Gm = (cb_hi - cb_lo) * SPC, G = Gm + nsc;
   int m0, b_tile, oh0, ow0 = 0, sp_tile;                         // first pixel, sample, tile origin, tile index inside the sample
   if constexpr (SUB) {
     const int tw = p.W / W_, tps = (p.H / ROWS) * tw;
@@ -119,16 +125,31 @@
       const int c = h_chunk_at<MF>(lane & 7, h_sw_rows<MF>(r));
       woff[i] = (((unsigned)(n0 + r) * 9u + (unsigned)tis) * (unsigned)Ct + (unsigned)(c * EPC)) * ESZ;
     }
+    const int Csc = p.sc_C1 + p.sc_C2;
+    __amdgpu_buffer_rsrc_t rws = __builtin_amdgcn_make_buffer_rsrc((void*)p.sc_w, 0, (int)((long long)p.Cout * Csc * ESZ), 0x00020000);
     // cursor of the next weight step to issue
     int is_g = 0, is_st = 0, is_cb = cb_lo, is_slot = 0;
     auto issue_weights = [&]() {
       char* sbase = smem + 2 * PATCH + is_slot * W_STAGE;
-      const unsigned so = is_g < G ? (unsigned)((is_st * TPS * Ct + is_cb * KSTEP) * ESZ) : OOB;
+      if (HAS_SC && is_g >= Gm && is_g < G) {
+        // shortcut step: the 1x1 weight rows [n0, n0 + BN) x channel block is_g - Gm, laid out as one tap of the 3x3 stream
+        const unsigned so = (unsigned)((is_g - Gm) * KSTEP * ESZ);
 #pragma unroll
-      for (int i = 0; i < WPW; ++i) {
-        lds_ptr_t dst = (lds_ptr_t)(sbase + (wave + NPROD * i) * 1024);
-        if (p.w_nt) __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, dst, 16, (int)woff[i], (int)so, 0, 2);
-        else __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, dst, 16, (int)woff[i], (int)so, 0, 0);
+        for (int i = 0; i < WPW; ++i) {
+          const int r = 8 * (wave + NPROD * i) + (lane >> 3);
+          const unsigned wo = ((unsigned)(n0 + r) * (unsigned)Csc + (unsigned)(h_chunk_at<MF>(lane & 7, h_sw_rows<MF>(r)) * EPC)) * ESZ;
+          lds_ptr_t dst = (lds_ptr_t)(sbase + (wave + NPROD * i) * 1024);
+          if (p.w_nt) __builtin_amdgcn_raw_ptr_buffer_load_lds(rws, dst, 16, (int)wo, (int)so, 0, 2);
+          else __builtin_amdgcn_raw_ptr_buffer_load_lds(rws, dst, 16, (int)wo, (int)so, 0, 0);
+        }
+      } else {
+        const unsigned so = is_g < Gm ? (unsigned)((is_st * TPS * Ct + is_cb * KSTEP) * ESZ) : OOB;
+#pragma unroll
+        for (int i = 0; i < WPW; ++i) {
+          lds_ptr_t dst = (lds_ptr_t)(sbase + (wave + NPROD * i) * 1024);
+          if (p.w_nt) __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, dst, 16, (int)woff[i], (int)so, 0, 2);
+          else __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, dst, 16, (int)woff[i], (int)so, 0, 0);
+        }
       }
       ++is_g;
       if (++is_st == SPC) {
@@ -139,6 +160,30 @@
     };
     auto issue_patch = [&](int cb) {
       char* sbase = smem + ((cb - cb_lo) & 1) * PATCH;
+      if (HAS_SC && cb >= cb_hi) {
+        // shortcut block j: channels [j KSTEP, (j + 1) KSTEP) of the virtual concat sc_x1 | sc_x2 (NHWC); only the tile's own
+        // pixels are fetched (the centre tap never reads the halo), addresses recomputed here - nine times a tile - rather
+        // than kept in registers
+        const int c0 = (cb - cb_hi) * KSTEP;
+        const bool in1 = c0 < p.sc_C1;
+        const int Cs = in1 ? p.sc_C1 : p.sc_C2;
+        __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(in1 ? p.sc_x1 : p.sc_x2), 0,
+                                                                     (int)((long long)p.M * Cs * ESZ), 0x00020000);
+        const unsigned so = (unsigned)((in1 ? c0 : c0 - p.sc_C1) * ESZ);
+#pragma unroll
+        for (int i = 0; i < PPW; ++i) {
+          const int q = 8 * pj[i] + (lane >> 3);
+          const int c = h_chunk_at<MF>(lane & 7, h_sw_patch<MF, W_>(q));
+          const int pr = q / PW, pc = q - pr * PW;
+          const int sg = pr / (SEG + 2), jj = pr - sg * (SEG + 2);
+          const bool in = q < NPQ && pc >= 1 && pc <= W_ && jj >= 1 && jj <= SEG;
+          const int pixel = m0 + (sg * SEG + jj - 1) * W_ + (pc - 1);
+          const unsigned off = in ? ((unsigned)pixel * (unsigned)Cs + (unsigned)(c * EPC)) * ESZ : OOB;
+          lds_ptr_t dst = (lds_ptr_t)(sbase + pj[i] * 1024);
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, dst, 16, (int)off, (int)so, 0, 0);
+        }
+        return;
+      }
       const unsigned so = p.x_c8 ? (unsigned)cb * (unsigned)(KSTEP * ESZ) * (unsigned)HW : (unsigned)(cb * KSTEP * ESZ);
 #pragma unroll
       for (int i = 0; i < PPW; ++i) {
@@ -150,21 +195,34 @@
 #pragma unroll
     for (int s = 0; s < STAGES - 1; ++s) issue_weights();
     int st = 0, cb = cb_lo, since = STAGES;                      // K steps since the last patch issue (in the loop)
+    bool fresh = false;                                          // this step's patch was issued one step ago (shortcut blocks)
     for (int g = 0; g < G; ++g) {
       // in flight behind the weights of step g: the weights of steps g+1 .. g+STAGES-2, and - for the STAGES-1 steps
-      // after a patch issue - that patch (issued behind step g+STAGES-1's weights of its iteration)
-      if (since <= STAGES - 1) wait_vmcnt<(STAGES - 2) * WPW + PPW>();
+      // after a patch issue - that patch (issued behind step g+STAGES-1's weights of its iteration).  A shortcut block is
+      // one step long, so the next one's patch goes out IN FRONT of that step's weights and only those may stay in flight.
+      if (fresh) wait_vmcnt<(STAGES >= 3 ? WPW : 0)>();
+      else if (since <= STAGES - 1) wait_vmcnt<(STAGES - 2) * WPW + PPW>();
       else wait_vmcnt<(STAGES - 2) * WPW>();
       __builtin_amdgcn_s_barrier();
       ++since;
+      fresh = false;
       if (!(p.dbg & 1)) {
-        issue_weights();
-        if (st == 0 && cb + 1 < cb_hi) {
-          issue_patch(cb + 1);
-          since = 1;
+        if (HAS_SC && cb >= cb_hi) {
+          if (cb + 1 < cb_end) {
+            issue_patch(cb + 1);
+            fresh = true;
+            since = STAGES;
+          }
+          issue_weights();
+        } else {
+          issue_weights();
+          if (st == 0 && cb + 1 < cb_end) {
+            issue_patch(cb + 1);
+            since = 1;
+          }
         }
       }
-      if (++st == SPC) {
+      if ((HAS_SC && cb >= cb_hi) || ++st == SPC) {
         st = 0;
         ++cb;
       }
@@ -405,9 +463,16 @@
         k_step(std::integral_constant<int, 2>{});
       }
     } else {
-      for (; g < G; ++g) {
+      for (; g < Gm; ++g) {
         __builtin_amdgcn_s_barrier();
         k_step(RT{});
+      }
+      for (; HAS_SC && g < G; ++g) {                     // folded shortcut: one centre-tap step per channel block
+        __builtin_amdgcn_s_barrier();
+        st = 4;
+        k_step(RT{});
+        st = 0;
+        pbuf ^= 1;
       }
     }
   }

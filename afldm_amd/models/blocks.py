@@ -30,6 +30,10 @@ _SC_ORDER = int(os.environ.get("AFLDM_SHORTCUT_ORDER", "0"))
 # them; a convolution writing blocks loses more in its epilogue (16-byte pieces to 24 planes per row) than the activation
 # behind it gains: 4.804 (0) / 4.785 (7) / 4.827 (2) / 4.754 (5) ms/step, same box (profiles/r05/c8_layout_ab.txt).
 _C8_EDGES = int(os.environ.get("AFLDM_C8_EDGES", "5"))
+# A ResnetBlock2D's 1x1 conv_shortcut runs inside its conv2 - extra centre-tap K steps of the halo-patch kernel over the block input,
+# one bias b2 + b_sc - where afldm_conv2d_shortcut_ok allows it, instead of a launch of its own whose output conv2 re-reads as its
+# residual.  AFLDM_NO_SHORTCUT_FOLD=1: the two launches (A/B).
+_SC_FOLD = os.environ.get("AFLDM_NO_SHORTCUT_FOLD", "0") != "1"
 
 
 def _pair(x):
@@ -428,6 +432,55 @@ class ResnetBlock2D(nn.Module):
                           ops.conv2d_c8_ok(h_in, w2, b2, residual=h_in))
         return cache[key]
 
+    def _sc_bias(self):
+        """conv2.bias + conv_shortcut.bias, summed in fp64 and rounded once to fp32: the bias of conv2 with the shortcut folded in."""
+        cache = self.__dict__.setdefault("_afldm_cache", {})
+        if "sc_bias" not in cache:
+            b = torch.zeros(self.out_channels, dtype=torch.float64, device=self.conv2.weight.device)
+            for conv in (self.conv2, self.conv_shortcut):
+                if conv.bias is not None:
+                    b += conv.bias.detach().double()
+            cache["sc_bias"] = b.float().contiguous()
+        return cache["sc_bias"]
+
+    def _sc_fold_plan(self, input_tensor, c8):
+        """True when conv2 takes the 1x1 conv_shortcut as extra K steps (afldm_conv2d_shortcut_ok: one halo-patch launch with one
+        filter tap per step - the 32^2 / 16^2 levels at the larger batches) instead of its output as the residual.  c8: conv2 reads
+        8-channel blocks.  Only booleans are cached here (the packed weights live in the modules' `_afldm_cache`)."""
+        if (not _SC_FOLD or self.conv_shortcut is None or tuple(self.conv_shortcut.kernel_size) != (1, 1)
+                or tuple(self.conv2.kernel_size) != (3, 3)):
+            return False
+        x1, x2 = _pair(input_tensor)
+        if x1.ndim != 4 or x1.shape[1] != x1.shape[2]:
+            return False
+        B, N = x1.shape[0], x1.shape[1]
+        key = (B, N, x1.shape[-1], None if x2 is None else x2.shape[-1], x1.dtype, x1.device, bool(c8))
+        cache = self.__dict__.setdefault("_afldm_sc_fold", {})
+        if key not in cache:
+            w2, _ = packed_conv(self.conv2, x1.dtype)
+            wsc, _ = packed_conv(self.conv_shortcut, x1.dtype)
+            h_in = torch.empty((B, N, N, self.out_channels), dtype=x1.dtype, device=x1.device)
+            if c8:
+                h_in.c8 = True
+            cache[key] = ops.conv2d_shortcut_ok(h_in, w2, self._sc_bias(), (x1, x2, wsc))
+        return cache[key]
+
+    def _conv2_sc_folded(self, h, input_tensor, next_gn):
+        """conv2(h) + conv_shortcut(input_tensor) as ONE launch (see _sc_fold_plan); with next_gn, the attention block's GroupNorm
+        rides along where the epilogue can apply it (as the unfolded path does)."""
+        x1, x2 = _pair(input_tensor)
+        w2, _ = packed_conv(self.conv2, h.dtype)
+        wsc, _ = packed_conv(self.conv_shortcut, h.dtype)
+        kw = {}
+        if next_gn is not None:
+            gamma, beta = packed_norm(next_gn)
+            kw["norm_out"] = (gamma, beta, next_gn.num_groups, next_gn.eps)
+        out = ops.conv2d(h, w2, self._sc_bias(), want_stats=True, shortcut=(x1, x2, wsc), **kw)
+        hn = getattr(out, "norm_applied", None)
+        if hn is not None:
+            out.gn_applied = (hn, next_gn)
+        return out
+
     def _norm_act(self, norm, x, out_c8=False, out_const=False):
         """norm -> self.nonlinearity fused: GroupNorm statistics, then either the fused
         GN + WarpedNonlinearity kernel (alias-free model) or GN + SiLU."""
@@ -591,16 +644,17 @@ class ResnetBlock2D(nn.Module):
         e1, e2, e3 = c8_1 and bool(_C8_EDGES & 1), c8_1 and bool(_C8_EDGES & 2), c8_2 and bool(_C8_EDGES & 4)
         res = None
         merged1 = bool(ops._ACTCONV_SITES) and x1.ndim == 4 and (x1.shape[1], x1.shape[-1] + (0 if x2 is None else x2.shape[-1])) in ops._ACTCONV_SITES
+        fold = not merged1 and self._sc_fold_plan(input_tensor, e3)
         if merged1:
             h = None
-        elif self.conv_shortcut is not None and _SC_ORDER == 2:
+        elif self.conv_shortcut is not None and _SC_ORDER == 2 and not fold:
             # shortcut first, the activation beside it (AQL policy: afldm_amd/aql.py; tools/aql_shortcut_ab.py)
             res = conv_forward(self.conv_shortcut, input_tensor)
             with aql.independent("act1"):
                 h = self._norm_act(self.norm1, input_tensor, out_c8=e1)
         else:
             h = self._norm_act(self.norm1, input_tensor, out_c8=e1)
-        if self.conv_shortcut is not None and _SC_ORDER == 1:
+        if self.conv_shortcut is not None and _SC_ORDER == 1 and not fold:
             with aql.independent("shortcut"):
                 res = conv_forward(self.conv_shortcut, input_tensor)
         fused = self._conv1_norm2_act_fused(h, temb_proj, temb_stride) if h is not None else None
@@ -614,6 +668,8 @@ class ResnetBlock2D(nn.Module):
             # (the convs whose outputs feed a GroupNorm emit its statistics from their epilogue)
             h = conv_forward(self.conv1, h, temb=temb_proj, temb_stride=temb_stride, want_stats=True, out_c8=e2)
             h = self._norm_act(self.norm2, h, out_c8=e3)
+        if fold:
+            return self._conv2_sc_folded(h, input_tensor, next_gn)
         if res is not None:
             pass
         elif self.conv_shortcut is not None:

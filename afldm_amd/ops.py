@@ -776,9 +776,42 @@ def conv2d_c8_ok(x1, w, bias=None, temb=None, temb_stride=0, residual=None, want
 _C8_OK = {}
 
 
+def _set_shortcut(a, shortcut):
+    sx1, sx2, sw = shortcut
+    _dev(sx1, "shortcut x1")
+    assert not is_c8(sx1) and not is_c8(sx2), "the folded shortcut reads NHWC tensors"
+    a.sc_x1, a.sc_x2, a.sc_w = ptr(sx1), ptr(sx2), ptr(sw)
+    a.sc_C1, a.sc_C2 = sx1.shape[-1], 0 if sx2 is None else sx2.shape[-1]
+    a.keep = a.keep + (sx1, sx2, sw)
+
+
+def conv2d_shortcut_ok(x1, w, bias, shortcut, temb=None, temb_stride=0, want_stats=True):
+    """True when conv2d(x1, w, bias, shortcut=(sx1, sx2, sw)) runs the 1x1 shortcut inside the 3x3 convolution itself
+    (afldm_conv2d_shortcut_ok): one halo-patch launch, whole K per workgroup.  The probe carries what the real launch carries."""
+    sx1, sx2, sw = shortcut
+    if x1.ndim != 4 or sx1.ndim != 4 or w.shape[1] != 3 or sw.shape[1] != 1:
+        return False
+    key = (tuple(x1.shape), is_c8(x1), x1.dtype, tuple(w.shape), tuple(sx1.shape), None if sx2 is None else tuple(sx2.shape),
+           temb is not None, int(temb_stride), bool(want_stats), str(x1.device))
+    if key not in _SC_OK:
+        a = conv_args(x1, w, bias, None, temb, temb_stride, None, None)
+        a.y = ptr(sx1)                 # (a non-NULL, aligned placeholder: the queries do not dereference it)
+        if want_stats and w.shape[0] % 4 == 0:
+            a.stats_out = ptr(sx1)
+        _set_shortcut(a, shortcut)
+        # (a plan that would split K given the room is not the one-launch halo kernel)
+        _SC_OK[key] = (not lib.afldm_conv2d_workspace(ctypes.byref(a))) and bool(lib.afldm_conv2d_shortcut_ok(ctypes.byref(a)))
+    return _SC_OK[key]
+
+
+_SC_OK = {}
+
+
 def conv2d(x1, w, bias=None, x2=None, temb=None, temb_stride=0, residual=None, out=None, out_mode=0,
-           workspace=None, want_stats=False, temb_mod=0, w_batch_stride=0, norm_out=None, out_c8=False):
+           workspace=None, want_stats=False, temb_mod=0, w_batch_stride=0, norm_out=None, out_c8=False, shortcut=None):
     """stride-1 'same' conv (KS in {1,3}) / linear on NHWC input with packed OHWI weights.
+    shortcut = (sx1, sx2, sw): a 1x1 convolution of the virtual concat sx1 | sx2 with the packed weight sw, added inside this 3x3
+    convolution (bias = the sum of both biases; only where conv2d_shortcut_ok says so).
     out_mode 1 returns the channel-major [B, Cout, H*W] tensor (V^T for attention).
     want_stats: also emit the per-channel GroupNorm partial sums of the output (from the GEMM
     epilogue where possible) and attach them to the returned tensor as `.gn_partial`."""
@@ -794,6 +827,8 @@ def conv2d(x1, w, bias=None, x2=None, temb=None, temb_stride=0, residual=None, o
         a.y_layout = 1
         out.c8 = True
     a.w_batch_stride = int(w_batch_stride)   # per-sample weights (elements between samples' weight tensors; `w` = sample 0's)
+    if shortcut is not None:
+        _set_shortcut(a, shortcut)
     if out_mode == 1 and x1.ndim == 3:      # [B, T, C] tokens: treat T as the pixel axis
         a.B, a.H, a.W = x1.shape[0], x1.shape[1], 1
     if workspace is None:
@@ -832,10 +867,12 @@ def conv2d(x1, w, bias=None, x2=None, temb=None, temb_stride=0, residual=None, o
         M, Ct = a.B * a.H * a.W, a.C1 + a.C2
         es = x1.element_size()
         kind = "conv3x3" if a.KS == 3 else ("conv1x1" if a.H * a.W > 1 and x1.ndim == 4 else "linear")
-        # algorithmic bytes: input + weights + output (+ the residual read), as tools/replay_conv3x3.py counts them
+        Csc = a.sc_C1 + a.sc_C2 if shortcut is not None else 0
+        # algorithmic bytes: input + weights + output (+ the residual read; + the folded shortcut's input and weights), as
+        # tools/replay_conv3x3.py counts them
         keep = (a, st, out, workspace)
-        _end(tok, kind, 2.0 * M * a.Cout * a.KS * a.KS * Ct,
-             (M * Ct + a.Cout * a.KS * a.KS * Ct + M * a.Cout * (2 if residual is not None else 1)) * es,
+        _end(tok, kind, 2.0 * M * a.Cout * (a.KS * a.KS * Ct + Csc),
+             (M * (Ct + Csc) + a.Cout * (a.KS * a.KS * Ct + Csc) + M * a.Cout * (2 if residual is not None else 1)) * es,
              replay=lambda keep=keep: conv2d_launch(keep[0]))
     return out
 

@@ -314,12 +314,25 @@ typedef struct {
    * contiguous run instead of H*W 16-byte pieces.  Same values, same arithmetic. */
   int x_layout;
   int y_layout;
+  /* optional: the 1x1 conv_shortcut of diffusers ResnetBlock2D (in_channels != out_channels) folded into its conv2, the call being
+   * conv2 itself: y = conv3x3(x1) + conv1x1(sc_x1 | sc_x2, sc_w) + bias, where `bias` is conv2.bias + conv_shortcut.bias and there
+   * is no `residual`.  sc_x1 [B*H*W][sc_C1] and sc_x2 [B*H*W][sc_C2] (NHWC, dtype T; sc_x2 NULL when sc_C2 = 0) are the block input
+   * (a virtual concat on the up path), sc_w [Cout][sc_C1 + sc_C2] the 1x1 weight in the afldm_pack_weight (OHWI) form.  The
+   * shortcut's channels run as extra centre-tap K steps of the halo-patch kernel; only honoured where afldm_conv2d_shortcut_ok(args)
+   * == 1 (sc_x1 = NULL otherwise, and run the 1x1 convolution as its own call feeding `residual`). */
+  const void* sc_x1;
+  const void* sc_x2;
+  const void* sc_w;
+  int sc_C1, sc_C2;
 } afldm_conv_args;
 int afldm_conv2d(const afldm_conv_args* args, afldm_stream_t stream);
 /* 1: afldm_conv2d(args) accepts x_layout = 1 and / or y_layout = 1 (asked with both at 0 or 1: the answer does not depend on them). */
 int afldm_conv2d_c8_ok(const afldm_conv_args* args);
 /* 1: afldm_conv2d(args) will apply the GroupNorm described by norm_gamma / norm_beta / norm_groups / norm_eps into y_norm itself. */
 int afldm_conv2d_norm_ok(const afldm_conv_args* args);
+/* 1: afldm_conv2d(args) accepts the folded shortcut described by sc_x1 / sc_x2 / sc_w / sc_C1 / sc_C2 (one halo-patch launch with one
+ * filter tap per K step, whole K per workgroup, no residual; the 32^2 / 16^2 levels at the larger batches). */
+int afldm_conv2d_shortcut_ok(const afldm_conv_args* args);
 /* Tuning hook (benchmarks only): force tile/pipeline variant `variant` (>= 0) and/or a split-K
  * factor (>= 1) for subsequent afldm_conv2d calls; -1 restores the automatic choice. */
 int afldm_conv2d_tune(int variant, int splitk);
