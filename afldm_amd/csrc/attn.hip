@@ -23,7 +23,16 @@
 //    ones appended to V^T.  A score costs max + exp2 + cvt on the VALU;
 //  * V arrives channel-major (vt[b][c][t], written by afldm_conv2d out_mode 1), so V^T rows are
 //    contiguous key runs and O^T leaves 4 consecutive head channels of one query per lane.
+//
+// INTERP (afldm_attention_interp): two K / V^T sources blended per sample,
+//   o = (1 - alpha[b]) softmax(q k0^T scale) v0 + alpha[b] softmax(q k1^T scale) v1.
+// The staging pipeline runs ONE stream of 2 * nchunks chunks (source 1's first chunks are prefetched under source 0's
+// last); at the source boundary the normalised O of source 0, weighted by 1 - alpha, moves to a second set of
+// accumulators and the running max / row sums restart exactly as at chunk 0 (source 1 alone is then the same
+// arithmetic as a single-source launch on it); the epilogue adds alpha times source 1's normalised O in fp32 and rounds once.
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include "common.hpp"
 
@@ -41,6 +50,16 @@ struct AttnP {
   int qblocks;  // query blocks (of 32 * waves) per (b, head)
 };
 
+template <typename T>
+struct AttnIP : AttnP<T> {
+  const T* k1;           // the second source, same layout / leading dimension as k, vt
+  const T* vt1;
+  const float* alpha;    // [B] blend weights, read when the kernel runs (a replayed graph sees the values of its replay)
+};
+
+template <typename T, bool INTERP>
+using AttnArg = typename std::conditional<INTERP, AttnIP<T>, AttnP<T>>::type;
+
 __device__ __forceinline__ int aswz(int row) { return (4 - ((row >> 2) & 3)) & 3; }
 
 constexpr int KC = 64;              // keys per chunk
@@ -50,8 +69,9 @@ template <typename T, int ND /* 16-row tiles of V^T: head_dim rows + the row of 
           int NKF /* chunk pairs covering head_dim + the -m_run channel in QK^T */, int NW /* waves */,
           bool RAGGED /* Tk % 64 != 0: clamped / element-wise staging and key masking */,
           int DBG = 0 /* timing decomposition (AFLDM_ATTN_DBG): 1 no exp2, 2 no P V MFMA, 4 no S MFMA, 8 no max,
-                         16 no per-chunk staging, 32 no per-chunk barrier; results are garbage */>
-__global__ void __launch_bounds__(NW * 64) k_attn(AttnP<T> p) {
+                         16 no per-chunk staging, 32 no per-chunk barrier; results are garbage */,
+          bool INTERP = false /* two sources blended by alpha[b] (afldm_attention_interp) */>
+__global__ void __launch_bounds__(NW * 64) k_attn(AttnArg<T, INTERP> p) {
   typedef Mma<T> MM;
   typedef typename MM::Chunk Chunk;
   constexpr int EPC = MM::EPC, KPF = MM::KPF;
@@ -151,6 +171,7 @@ __global__ void __launch_bounds__(NW * 64) k_attn(AttnP<T> p) {
 #pragma unroll
   for (int i = 0; i < VPT; ++i) vp[i] = vbase + (vact[i] ? vsrc[i] : vkey[i]);
 
+  // (load_chunk2 below is the INTERP twin of this loader: a change to the ragged clamps or the tiny-V staging goes into both)
   auto load_chunk = [&](int key0, bool advance, Chunk (&rk)[KPT], Chunk (&rv)[VPT]) {
     if constexpr (!RAGGED) {
       const int kstep = advance ? KC * p.ldk : 0, vstep = advance ? KC : 0;   // past the end: reload the last chunk
@@ -325,8 +346,65 @@ __global__ void __launch_bounds__(NW * 64) k_attn(AttnP<T> p) {
   // in flight from global memory.
   Chunk rkA[KPT], rvA[VPT], rkB[KPT], rvB[VPT];
   const int nchunks = (p.Tk + KC - 1) / KC;
-  load_chunk(0, 1 < nchunks, rkA, rvA);     // pointers now at chunk 1 (if there is one)
-  load_chunk(KC, 2 < nchunks, rkB, rvB);    // chunk 1 (or chunk 0 again when there is only one)
+  // INTERP: source 1's bases (the same offsets as kbase / vbase) and this sample's blend weight; load_chunk2 loads chunk c
+  // of the 2 * nchunks stream, source c / nchunks (the pieces and clamps of load_chunk addressed from the source's base; past
+  // the end a chunk-aligned level reloads the last chunk, a ragged one loads nothing)
+  const T* kbase1 = kbase;
+  const T* vbase1 = vbase;
+  float blend = 0.f;
+  if constexpr (INTERP) {
+    kbase1 = p.k1 + (size_t)kb * p.Tk * p.ldk + h * p.d;
+    vbase1 = p.vt1 + ((size_t)kb * C + h * p.d) * p.Tk;
+    blend = p.alpha[b];
+  }
+  auto load_chunk2 = [&](int c, Chunk (&rk)[KPT], Chunk (&rv)[VPT]) {
+    if (c >= 2 * nchunks) {
+      if constexpr (RAGGED) return;
+      c = 2 * nchunks - 1;
+    }
+    const bool s1 = c >= nchunks;
+    const int key0 = (s1 ? c - nchunks : c) * KC;
+    const T* kbs = s1 ? kbase1 : kbase;
+    const T* vbs = s1 ? vbase1 : vbase;
+    if constexpr (!RAGGED) {
+      const T* kc = kbs + (size_t)key0 * p.ldk;
+#pragma unroll
+      for (int i = 0; i < KPT; ++i) rk[i] = ld16<Chunk>(kc + (kact[i] ? ksrc[i] : krow[i] * p.ldk));
+#pragma unroll
+      for (int i = 0; i < VPT; ++i) rv[i] = ld16<Chunk>(vbs + key0 + (vact[i] ? vsrc[i] : vkey[i]));
+      return;
+    }
+#pragma unroll
+    for (int i = 0; i < KPT; ++i) {
+      if (kact[i]) {
+        int off = key0 * p.ldk + ksrc[i];
+        if (key0 + krow[i] >= p.Tk) off = (p.Tk - 1) * p.ldk + ksrc[i] - krow[i] * p.ldk;
+        rk[i] = ld16<Chunk>(kbs + off);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < VPT; ++i) {
+      if (vact[i]) {
+        if (tiny) {
+          rv[i] = MM::zero();
+#pragma unroll
+          for (int e = 0; e < EPC; ++e)
+            if (key0 + vkey[i] + e < p.Tk) rv[i][e] = vbs[vsrc[i] + key0 + e];
+        } else {
+          int off = vsrc[i] + key0;
+          if (key0 + vkey[i] + EPC > p.Tk) off = vsrc[i] - vkey[i] + p.Tk - EPC;
+          rv[i] = ld16<Chunk>(vbs + off);
+        }
+      }
+    }
+  };
+  if constexpr (INTERP) {
+    load_chunk2(0, rkA, rvA);
+    load_chunk2(1, rkB, rvB);
+  } else {
+    load_chunk(0, 1 < nchunks, rkA, rvA);     // pointers now at chunk 1 (if there is one)
+    load_chunk(KC, 2 < nchunks, rkB, rvB);    // chunk 1 (or chunk 0 again when there is only one)
+  }
   // ---- LDS padding is written ONCE: K pieces beyond head_dim and V^T rows beyond head_dim stay
   // zero in both buffers, V^T row `d` is all ones (-> row d of O^T accumulates the softmax
   // denominator on the MFMA pipe, no VALU adds), K channel slot `d` is a constant 1 (Q carries
@@ -358,22 +436,64 @@ __global__ void __launch_bounds__(NW * 64) k_attn(AttnP<T> p) {
   __syncthreads();       // zero fill / constant rows complete before the live pieces land
   store_chunk(0, rkA, rvA);
   __syncthreads();
-  for (int c = 0; c < nchunks; c += 2) {
-    // even step: B holds chunk c+1, A receives chunk c+2
-    if (!(DBG & 16)) load_chunk((c + 2) * KC, c + 3 < nchunks, rkA, rvA);
-    compute(c * KC, 0);
-    if (!(DBG & 16) && c + 1 < nchunks) store_chunk(1, rkB, rvB);
-    if (!(DBG & 32)) __syncthreads();
-    if (c + 1 >= nchunks) break;
-    // odd step: A holds chunk c+2, B receives chunk c+3
-    if (!(DBG & 16)) load_chunk((c + 3) * KC, c + 4 < nchunks, rkB, rvB);
-    compute((c + 1) * KC, 1);
-    if (!(DBG & 16) && c + 2 < nchunks) store_chunk(0, rkA, rvA);
-    if (!(DBG & 32)) __syncthreads();
+  [[maybe_unused]] f32x4 ob[2][ND];    // INTERP: (1 - alpha) x the normalised O of source 0
+  if constexpr (INTERP) {
+    // the same two-stage pipeline over both sources' chunks; at the boundary (chunk nchunks, wave-uniform) source 0's O is
+    // normalised, weighted by 1 - alpha and parked in ob, and the accumulators, m_run and Q's -m_run channel restart as at
+    // chunk 0 (`first` in compute() holds again: key0 is the chunk's offset within its source)
+    const int ltile = p.d >> 4, lsrc = li + 16 * ((p.d & 15) >> 2);
+    auto step = [&](int c, int buf) {
+      if (c == nchunks) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          float lsel = 0.f;
+#pragma unroll
+          for (int td = 0; td < ND; ++td)
+            if (td == ltile) lsel = oacc[u][td][0];
+          const float w = (1.0f - blend) / __shfl(lsel, lsrc, 64);
+#pragma unroll
+          for (int td = 0; td < ND; ++td) {
+            ob[u][td] = oacc[u][td] * w;
+            oacc[u][td] = f32x4{0.f, 0.f, 0.f, 0.f};
+          }
+          m_run[u] = 0.f;
+#pragma unroll
+          for (int kf = 0; kf < NKF; ++kf)
+            if (kf == kf_pad && lg == lg_pad) qf[u][kf][0] = from_f32<T>(0.f);
+        }
+      }
+      compute((c < nchunks ? c : c - nchunks) * KC, buf);
+    };
+    const int nall = 2 * nchunks;        // even: every pair of steps is whole
+    for (int c = 0; c < nall; c += 2) {
+      load_chunk2(c + 2, rkA, rvA);
+      step(c, 0);
+      store_chunk(1, rkB, rvB);
+      __syncthreads();
+      load_chunk2(c + 3, rkB, rvB);
+      step(c + 1, 1);
+      if (c + 2 < nall) store_chunk(0, rkA, rvA);
+      __syncthreads();
+    }
+  } else {
+    for (int c = 0; c < nchunks; c += 2) {
+      // even step: B holds chunk c+1, A receives chunk c+2
+      if (!(DBG & 16)) load_chunk((c + 2) * KC, c + 3 < nchunks, rkA, rvA);
+      compute(c * KC, 0);
+      if (!(DBG & 16) && c + 1 < nchunks) store_chunk(1, rkB, rvB);
+      if (!(DBG & 32)) __syncthreads();
+      if (c + 1 >= nchunks) break;
+      // odd step: A holds chunk c+2, B receives chunk c+3
+      if (!(DBG & 16)) load_chunk((c + 3) * KC, c + 4 < nchunks, rkB, rvB);
+      compute((c + 1) * KC, 1);
+      if (!(DBG & 16) && c + 2 < nchunks) store_chunk(0, rkA, rvA);
+      if (!(DBG & 32)) __syncthreads();
+    }
   }
 
   // ---- finish: the denominator sits in O^T row d = tile d/16, lane group (d%16)/4, element 0
-  // (head_dim is a multiple of 8); normalise, store 4 consecutive channels per lane
+  // (head_dim is a multiple of 8); normalise, store 4 consecutive channels per lane (INTERP: ob + alpha x source 1's
+  // normalised O in fp32, rounded once by a plain vector store)
   const int ltile = p.d >> 4, lsrc = li + 16 * ((p.d & 15) >> 2);
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
@@ -382,15 +502,20 @@ __global__ void __launch_bounds__(NW * 64) k_attn(AttnP<T> p) {
     for (int td = 0; td < ND; ++td)
       if (td == ltile) lsel = oacc[u][td][0];
     const float l = __shfl(lsel, lsrc, 64);
-    const float inv = 1.0f / l;
+    const float inv = (INTERP ? blend : 1.0f) / l;
     const int qrow = q0 + 16 * u + li;
     if (qrow < p.Tq) {
       T* op = p.o + ((size_t)b * p.Tq + qrow) * p.ldo + h * p.d;
 #pragma unroll
       for (int td = 0; td < ND; ++td) {
         const int dch = 16 * td + 4 * lg;
-        if (dch + 3 < p.d)
-          store4_out<T>(op + dch, oacc[u][td][0] * inv, oacc[u][td][1] * inv, oacc[u][td][2] * inv, oacc[u][td][3] * inv);
+        if (dch + 3 < p.d) {
+          if constexpr (INTERP)
+            store4<T>(op + dch, ob[u][td][0] + oacc[u][td][0] * inv, ob[u][td][1] + oacc[u][td][1] * inv,
+                      ob[u][td][2] + oacc[u][td][2] * inv, ob[u][td][3] + oacc[u][td][3] * inv);
+          else
+            store4_out<T>(op + dch, oacc[u][td][0] * inv, oacc[u][td][1] * inv, oacc[u][td][2] * inv, oacc[u][td][3] * inv);
+        }
       }
     }
   }
@@ -423,14 +548,28 @@ static bool attn_launch_nw(const AttnP<T>& p, int nd, int nkf, int grid, hipStre
   return true;
 }
 
+// afldm_attention_interp's kernels (no timing-decomposition variants; the K-fragment count follows from nd and the dtype:
+// fp32 (1,1) (2,2) (3,3), bf16 (1,1) (2,1) (3,2))
+template <typename T, int NW, bool RAGGED>
+static bool attn_interp_launch_nw(const AttnIP<T>& p, int nd, int grid, hipStream_t st) {
+  constexpr bool BF = sizeof(T) == 2;
+  if (nd == 1) k_attn<T, 1, 1, NW, RAGGED, 0, true><<<grid, NW * 64, 0, st>>>(p);
+  else if (nd == 2) k_attn<T, 2, BF ? 1 : 2, NW, RAGGED, 0, true><<<grid, NW * 64, 0, st>>>(p);
+  else if (nd == 3) k_attn<T, 3, BF ? 2 : 3, NW, RAGGED, 0, true><<<grid, NW * 64, 0, st>>>(p);
+  else return false;
+  return true;
+}
+
 template <typename T>
-static int attn_launch(const void* q, int ldq, const void* k, int ldk, const void* vt, void* o, int ldo, int B, int Bk,
-                       int heads, int Tq, int Tk, int d, float scale, hipStream_t st) {
-  AttnP<T> p;
+static void attn_params(AttnP<T>& p, const void* q, int ldq, const void* k, int ldk, const void* vt, void* o, int ldo, int B,
+                        int Bk, int heads, int Tq, int Tk, int d, float scale) {
   p.q = (const T*)q; p.k = (const T*)k; p.vt = (const T*)vt; p.o = (T*)o;
   p.ldq = ldq; p.ldk = ldk; p.ldo = ldo;
   p.B = B; p.Bk = Bk; p.heads = heads; p.Tq = Tq; p.Tk = Tk; p.d = d;
   p.scale_log2e = scale * 1.4426950408889634f;
+}
+
+static int attn_waves(int B, int heads, int Tq) {
   // 8 waves (256 queries share every staged chunk) once a (batch, head) has that many queries,
   // 4 waves below; a wave always owns 32 queries
   // (and 2 / 1 waves for the 8x8 / 4x4 planes: a 4-wave workgroup of the 4x4 level was one wave of 16 queries and
@@ -439,7 +578,38 @@ static int attn_launch(const void* q, int ldq, const void* k, int ldk, const voi
   // only with >= 1024 workgroups: with few of them (small batch) four waves stage the K / V chunks faster
   // (same box, ms/step: batch 64 5.499 -> 5.473; batch 8 2.543 -> 2.562, batch 1 2.295 -> 2.308 without this limit)
   const bool many = (long long)B * heads >= 1024;
-  const int waves = Tq >= 256 ? 8 : (Tq > 64 || !small_ok || !many) ? 4 : Tq > 32 ? 2 : 1;
+  return Tq >= 256 ? 8 : (Tq > 64 || !small_ok || !many) ? 4 : Tq > 32 ? 2 : 1;
+}
+
+template <typename T>
+static int attn_interp_launch(const void* q, int ldq, const void* k0, const void* k1, int ldk, const void* vt0, const void* vt1,
+                              const float* alpha, void* o, int ldo, int B, int Bk, int heads, int Tq, int Tk, int d, float scale,
+                              hipStream_t st) {
+  AttnIP<T> p;
+  attn_params<T>(p, q, ldq, k0, ldk, vt0, o, ldo, B, Bk, heads, Tq, Tk, d, scale);
+  p.k1 = (const T*)k1; p.vt1 = (const T*)vt1; p.alpha = alpha;
+  const int waves = attn_waves(B, heads, Tq);
+  p.qblocks = (Tq + 32 * waves - 1) / (32 * waves);
+  const int grid = B * heads * p.qblocks;
+  const int nd = d / 16 + 1;
+  const bool ragged = Tk % KC != 0;
+  const bool ok = waves == 8 ? (ragged ? attn_interp_launch_nw<T, 8, true>(p, nd, grid, st) : attn_interp_launch_nw<T, 8, false>(p, nd, grid, st))
+                  : waves == 4 ? (ragged ? attn_interp_launch_nw<T, 4, true>(p, nd, grid, st) : attn_interp_launch_nw<T, 4, false>(p, nd, grid, st))
+                  : waves == 2 ? (ragged ? attn_interp_launch_nw<T, 2, true>(p, nd, grid, st) : attn_interp_launch_nw<T, 2, false>(p, nd, grid, st))
+                               : (ragged ? attn_interp_launch_nw<T, 1, true>(p, nd, grid, st) : attn_interp_launch_nw<T, 1, false>(p, nd, grid, st));
+  if (!ok) {
+    set_error("afldm_attention_interp: unsupported head_dim %d", d);
+    return AFLDM_ESHAPE;
+  }
+  return check_launch("afldm_attention_interp");
+}
+
+template <typename T>
+static int attn_launch(const void* q, int ldq, const void* k, int ldk, const void* vt, void* o, int ldo, int B, int Bk,
+                       int heads, int Tq, int Tk, int d, float scale, hipStream_t st) {
+  AttnP<T> p;
+  attn_params<T>(p, q, ldq, k, ldk, vt, o, ldo, B, Bk, heads, Tq, Tk, d, scale);
+  const int waves = attn_waves(B, heads, Tq);
   p.qblocks = (Tq + 32 * waves - 1) / (32 * waves);
   const int grid = B * heads * p.qblocks;
   constexpr int KPF = Mma<T>::KPF;
@@ -460,19 +630,44 @@ static int attn_launch(const void* q, int ldq, const void* k, int ldk, const voi
 
 using namespace afldm;
 
+// the operand limits both entry points share
+static int attn_check(const char* name, const void* q, int ldq, const void* k, int ldk, const void* vt, void* o, int ldo, int B,
+                      int Bk, int heads, int Tq, int Tk, int d, int dtype) {
+  AFLDM_REQUIRE(q && k && vt && o, AFLDM_ENULL, "%s: NULL pointer", name);
+  AFLDM_REQUIRE(B > 0 && Bk > 0 && B % Bk == 0 && heads > 0 && Tq > 0 && Tk > 0, AFLDM_ESHAPE,
+                "%s: bad shape B=%d Bk=%d heads=%d Tq=%d Tk=%d", name, B, Bk, heads, Tq, Tk);
+  AFLDM_REQUIRE(d >= 8 && d <= 32 && d % 8 == 0, AFLDM_ESHAPE, "%s: head_dim %d must be 8, 16, 24 or 32", name, d);
+  AFLDM_REQUIRE(Tk % 4 == 0 && (Tk % 8 == 0 || dtype == AFLDM_F32 || Tk < 8), AFLDM_ESHAPE,
+                "%s: Tk=%d must be a multiple of 4 (fp32) / 8 (bf16), or < 8", name, Tk);
+  AFLDM_REQUIRE(ldq >= heads * d && ldk >= heads * d && ldo >= heads * d && ldq % 8 == 0 && ldk % 8 == 0 && ldo % 8 == 0,
+                AFLDM_ESHAPE, "%s: leading dims (%d,%d,%d) must be >= heads*d and multiples of 8", name, ldq, ldk, ldo);
+  AFLDM_REQUIRE(aligned16(q) && aligned16(k) && aligned16(vt) && aligned16(o), AFLDM_EALIGN,
+                "%s: pointers must be 16-byte aligned", name);
+  return AFLDM_OK;
+}
+
+extern "C" int afldm_attention_interp(const void* q, int ldq, const void* k0, const void* k1, int ldk, const void* vt0,
+                                      const void* vt1, const float* alpha, void* o, int ldo, int B, int Bk, int heads, int Tq,
+                                      int Tk, int d, float scale, int dtype, afldm_stream_t stream) {
+  const char* name = "afldm_attention_interp";
+  int rc = attn_check(name, q, ldq, k0, ldk, vt0, o, ldo, B, Bk, heads, Tq, Tk, d, dtype);
+  if (rc == AFLDM_OK) rc = attn_check(name, q, ldq, k1, ldk, vt1, o, ldo, B, Bk, heads, Tq, Tk, d, dtype);
+  if (rc != AFLDM_OK) return rc;
+  AFLDM_REQUIRE(alpha, AFLDM_ENULL, "%s: NULL alpha", name);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == AFLDM_F32)
+    return attn_interp_launch<float>(q, ldq, k0, k1, ldk, vt0, vt1, alpha, o, ldo, B, Bk, heads, Tq, Tk, d, scale, st);
+  if (dtype == AFLDM_BF16)
+    return attn_interp_launch<bf16>(q, ldq, k0, k1, ldk, vt0, vt1, alpha, o, ldo, B, Bk, heads, Tq, Tk, d, scale, st);
+  set_error("%s: unknown dtype %d", name, dtype);
+  return AFLDM_EDTYPE;
+}
+
 extern "C" int afldm_attention(const void* q, int ldq, const void* k, int ldk, const void* vt, void* o, int ldo, int B,
                                int Bk, int heads, int Tq, int Tk, int d, float scale, int dtype,
                                afldm_stream_t stream) {
-  AFLDM_REQUIRE(q && k && vt && o, AFLDM_ENULL, "afldm_attention: NULL pointer");
-  AFLDM_REQUIRE(B > 0 && Bk > 0 && B % Bk == 0 && heads > 0 && Tq > 0 && Tk > 0, AFLDM_ESHAPE,
-                "afldm_attention: bad shape B=%d Bk=%d heads=%d Tq=%d Tk=%d", B, Bk, heads, Tq, Tk);
-  AFLDM_REQUIRE(d >= 8 && d <= 32 && d % 8 == 0, AFLDM_ESHAPE, "afldm_attention: head_dim %d must be 8, 16, 24 or 32", d);
-  AFLDM_REQUIRE(Tk % 4 == 0 && (Tk % 8 == 0 || dtype == AFLDM_F32 || Tk < 8), AFLDM_ESHAPE,
-                "afldm_attention: Tk=%d must be a multiple of 4 (fp32) / 8 (bf16), or < 8", Tk);
-  AFLDM_REQUIRE(ldq >= heads * d && ldk >= heads * d && ldo >= heads * d && ldq % 8 == 0 && ldk % 8 == 0 && ldo % 8 == 0,
-                AFLDM_ESHAPE, "afldm_attention: leading dims (%d,%d,%d) must be >= heads*d and multiples of 8", ldq, ldk, ldo);
-  AFLDM_REQUIRE(aligned16(q) && aligned16(k) && aligned16(vt) && aligned16(o), AFLDM_EALIGN,
-                "afldm_attention: pointers must be 16-byte aligned");
+  const int rc = attn_check("afldm_attention", q, ldq, k, ldk, vt, o, ldo, B, Bk, heads, Tq, Tk, d, dtype);
+  if (rc != AFLDM_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (dtype == AFLDM_F32) return attn_launch<float>(q, ldq, k, ldk, vt, o, ldo, B, Bk, heads, Tq, Tk, d, scale, st);
   if (dtype == AFLDM_BF16) return attn_launch<bf16>(q, ldq, k, ldk, vt, o, ldo, B, Bk, heads, Tq, Tk, d, scale, st);

@@ -22,11 +22,28 @@ noise buffer [steps, B, C, H, W].  The noise is drawn per run by the caller's ge
 randn calls the eager loop makes, in the same order - never inside a capture.  Draws on the CPU (a CPU generator) go through
 pinned staging: the next replay group's noise is drawn while the GPU runs the current group.
 """
+import contextlib
+import gc
 import os
 
 import torch
 
 from . import ops
+
+
+@contextlib.contextmanager
+def capture_guard():
+    """Keep Python's cyclic garbage collector out of a stream capture.  A collection inside the capture can free an unreachable
+    CUDAGraph (another engine's, dropped inside a reference cycle), and destroying a graph is not permitted while a stream
+    captures: the process aborts.  Collect first, then keep the collector off until the capture ends."""
+    gc.collect()
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
 
 
 def model_state_key(model):
@@ -148,14 +165,14 @@ class DenoiseEngine:
         self.step_idx.fill_(-1)
         self.lat.copy_(keep)
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
+        with capture_guard(), torch.cuda.graph(g):
             self._step()
         self.graph = g
         if self.steps_per_graph > 1:
             self.step_idx.fill_(-1)
             self.lat.copy_(keep)
             gm = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gm):
+            with capture_guard(), torch.cuda.graph(gm):
                 for _ in range(self.steps_per_graph):
                     self._step()
             self.graph_multi = gm
@@ -189,15 +206,17 @@ class DenoiseEngine:
         key = model_state_key(self.unet)
         if key == self._model_key:
             return False
-        from .models.blocks import invalidate_packed
+        from .models.blocks import invalidate_stale_packed
         torch.cuda.synchronize()
         if self.unet.dtype != self.x_nhwc.dtype or self.unet.device != self.x_nhwc.device:
             # .to(dtype / device): every dtype-typed static buffer of the engine is stale, not just the table
-            invalidate_packed(self.unet)
+            invalidate_stale_packed(self.unet)
             self.__init__(self.unet, self.scheduler, self.B, self.n, self.use_graph, self.steps_per_graph, self.branches)
             return True
         self.graph = self.graph_multi = None
-        invalidate_packed(self.unet)       # in-place parameter edits do not pass through the modules' own hooks
+        # in-place parameter edits do not pass through the modules' own hooks; another engine of this model may have repacked
+        # (and captured on the new copies) already
+        invalidate_stale_packed(self.unet)
         self.temb_table.copy_(torch.cat([self.unet.temb_projection(t) for t in self.timesteps], 0))
         self._model_key = key
         return True

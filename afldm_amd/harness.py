@@ -17,7 +17,7 @@ import time
 import torch
 
 from . import parallel
-from .engine import DenoiseEngine, model_state_key
+from .engine import DenoiseEngine, capture_guard, model_state_key
 from .io_utils import image_to_tensor, save_gif_from_tensors
 from .pipelines.cross_frame_attn import (AttnState, CrossFrameAttnProcessor, get_unet_attn_processors,
                                          set_unet_attn_processor)
@@ -54,7 +54,7 @@ class _UnrolledEngine(DenoiseEngine):
         self.step_idx.fill_(-1)
         self.lat.copy_(keep)
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
+        with capture_guard(), torch.cuda.graph(g):
             for i in range(self.n):
                 self._host_step = i
                 self._step()
@@ -78,40 +78,65 @@ class CrossFrameSampler:
     attention and one unrolled engine per (pass kind, batch): the STORE graph writes every attention's K / V^T of every step
     into tensors of its own pool, the LOAD graphs read them in place - a new STORE replay (next seed / image) refreshes what
     the LOAD graphs see.  Cached on the pipeline: the first call captures (about the cost of two eager passes), later calls
-    replay."""
+    replay.
 
-    def __init__(self, unet, scheduler, steps):
-        self.unet, self.scheduler, self.steps = unet, scheduler, steps
+    interp=True (image interpolation, LDMInterpolationPipeline): the processors blend two stored passes (enable_interp); the
+    STORE pass is ONE batch-2 graph of both endpoints (AttnState.PAIR: sample s fills slot s), and a LOAD engine owns a
+    persistent [B] blend-weight buffer that its captured graph reads by address - run(..., alpha=...) fills it before the
+    replay.  Its engines are keyed ('interp', load, batch)."""
+
+    def __init__(self, unet, scheduler, steps, interp=False):
+        self.unet, self.scheduler, self.steps, self.interp = unet, scheduler, steps, bool(interp)
         self.attn_state = AttnState()
         self.names = list(get_unet_attn_processors(unet))
-        self.procs = {k: CrossFrameAttnProcessor(self.attn_state, cache_kv=True) for k in self.names}
+        self.procs = {k: CrossFrameAttnProcessor(self.attn_state, enable_interp=self.interp, cache_kv=True) for k in self.names}
         self.engines = {}
+        self.alphas = {}                              # interp: LOAD batch -> the blend-weight buffer its graph reads
         self.model_key, self.stored = None, False
-        self.key = (unet.dtype, str(unet.device), steps, tuple(sorted((k, repr(v)) for k, v in dict(scheduler.config).items())))
+        self.key = (unet.dtype, str(unet.device), steps, tuple(sorted((k, repr(v)) for k, v in dict(scheduler.config).items())),
+                    self.interp)
 
     def install(self):
         previous = get_unet_attn_processors(self.unet)
         set_unet_attn_processor(self.unet, dict(self.procs))
         return previous
 
-    def run(self, latents, load):
-        """One pass over the schedule (processors installed by the caller): STORE (load=False; attn_state is reset) or LOAD."""
-        from .models.blocks import invalidate_packed
+    def run(self, latents, load, alpha=None):
+        """One pass over the schedule (processors installed by the caller): STORE (load=False; attn_state is reset) or LOAD.
+        interp: a STORE pass takes the two endpoints as one batch of 2; a LOAD pass needs `alpha`, one blend weight per sample."""
+        from .models.blocks import invalidate_stale_packed
+        B = latents.shape[0]
         fp = model_state_key(self.unet)
-        if fp != self.model_key:                  # load_state_dict / .to() / surgery since the capture: every graph is stale
+        if self.model_key is None:
+            # first run: record the fingerprint.  Invalidating here (as a model change) freed the packed weights that other
+            # cached graphs of the same UNet - a captured ddim_inversion engine - still point at (ADVICE r06 item 1)
+            self.model_key = fp
+        elif fp != self.model_key:                # load_state_dict / .to() / surgery since the capture: every graph is stale
             torch.cuda.synchronize()
             self.engines.clear()
             for p in self.procs.values():
                 p.maps, p.kv = [dict(), dict()], [dict(), dict()]
-            invalidate_packed(self.unet)
+            invalidate_stale_packed(self.unet)        # (not the copies another engine repacked for these weights)
             self.model_key, self.stored = fp, False
         if load:
             if not self.stored:
                 raise RuntimeError("CrossFrameSampler: a LOAD pass needs a STORE pass first")
             self.attn_state.to_load()
+            if self.interp:
+                if alpha is None or len(alpha) != B:
+                    raise ValueError(f"CrossFrameSampler(interp): a LOAD pass of {B} samples needs {B} blend weights")
+                buf = self.alphas.get(B)
+                if buf is None:
+                    buf = self.alphas[B] = torch.zeros(B, dtype=torch.float32, device=self.unet.device)
+                buf.copy_(torch.as_tensor(alpha, dtype=torch.float32))        # stream-ordered before the replay that reads it
+                self.attn_state.set_alpha(buf)
         else:
             self.attn_state.reset()
-        key = (bool(load), latents.shape[0])
+            if self.interp:
+                if B != 2:
+                    raise ValueError(f"CrossFrameSampler(interp): the STORE pass is one batch of the two endpoints, got {B}")
+                self.attn_state.set_store_id(AttnState.PAIR)
+        key = ("interp", bool(load), B) if self.interp else (bool(load), B)
         if key not in self.engines:
             if not load:                          # a new STORE capture moves the stored tensors: the LOAD graphs read the old ones
                 self.engines.clear()
@@ -121,18 +146,19 @@ class CrossFrameSampler:
         return out
 
 
-def _sampler(pipeline, steps, sched=None):
+def _sampler(pipeline, steps, sched=None, interp=False):
     """The pipeline's cached CrossFrameSampler for `steps` evaluations of `sched` (default: a fresh DDIMScheduler of the pipeline's
-    configuration; the SR harness passes its I2SB ODE schedule)."""
+    configuration; the SR harness passes its I2SB ODE schedule).  interp: the interpolation sampler, cached apart."""
     from .schedulers.ddim import DDIMScheduler
     unet = pipeline.unet
     if sched is None:
         sched = DDIMScheduler.from_config(pipeline.scheduler.config)
-    smp = getattr(pipeline, "_xframe_sampler", None)
-    probe = (unet.dtype, str(unet.device), steps, tuple(sorted((k, repr(v)) for k, v in dict(sched.config).items())))
+    attr = "_xframe_interp_sampler" if interp else "_xframe_sampler"
+    smp = getattr(pipeline, attr, None)
+    probe = (unet.dtype, str(unet.device), steps, tuple(sorted((k, repr(v)) for k, v in dict(sched.config).items())), bool(interp))
     if smp is None or smp.unet is not unet or smp.key != probe or smp.names != list(get_unet_attn_processors(unet)):
-        smp = CrossFrameSampler(unet, sched, steps)
-        pipeline._xframe_sampler = smp
+        smp = CrossFrameSampler(unet, sched, steps, interp=interp)
+        setattr(pipeline, attr, smp)
     return smp
 
 

@@ -59,6 +59,30 @@ def invalidate_packed(module: nn.Module):
         m.__dict__.pop("_afldm_cache", None)
 
 
+def _weights_key(module: nn.Module):
+    """What the packed copies are made from: every parameter's and buffer's storage, in-place version counter, dtype and device
+    (tensors created under torch.inference_mode() have no version counter: -1)."""
+    def ver(t):
+        try:
+            return t._version
+        except RuntimeError:
+            return -1
+    return hash(tuple((t.data_ptr(), ver(t), t.dtype, str(t.device)) for t in (*module.parameters(), *module.buffers())))
+
+
+def invalidate_stale_packed(module: nn.Module):
+    """invalidate_packed, unless the packed copies were already dropped for the module's current weights.  Several cached graphs
+    of one model (a ddim_inversion engine, a cross-frame sampler's engines) notice a weight change one after the other; a
+    later one must not drop the copies that an earlier one has packed and captured since, or that graph replays freed memory.
+    Returns True when it dropped them."""
+    key = _weights_key(module)
+    if module.__dict__.get("_afldm_packed_for") == key:
+        return False
+    invalidate_packed(module)
+    module.__dict__["_afldm_packed_for"] = key
+    return True
+
+
 def packed_conv(mod, dtype):
     """(OHWI weight in `dtype`, fp32 bias) for an nn.Conv2d / nn.Linear, cached on the module."""
     cache = mod.__dict__.setdefault("_afldm_cache", {})
@@ -709,12 +733,17 @@ class AttnProcessor2_0:
     encoder_hidden_states, when given, is the already group-normed K/V source [Bk, HW, C]
     (the protocol CrossFrameAttnProcessor uses, reference cross_frame_attn.py:125)."""
 
-    def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None, kv=None, kv_sink=None):
+    def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None, kv=None, kv_sink=None,
+                 kv1=None, alpha=None):
         """kv / kv_sink (CrossFrameAttnProcessor with cache_kv): `kv_sink(k, vt)` receives this call's projected keys
         [B, T, C] (a view) and channel-major values [B, C, T] - the self-attention then runs on the three-launch path, where
         they exist in memory; `kv = (k, vt)` runs the attention against such a stored pair (Bk divides B) instead of projecting
-        an encoder_hidden_states map: K / V of the stored pass are the same numbers whichever pass projects them."""
+        an encoder_hidden_states map: K / V of the stored pass are the same numbers whichever pass projects them.
+        kv1 + alpha (the interpolating processor): a second stored pair, and the output is
+        to_out((1 - alpha) attn(q, kv) + alpha attn(q, kv1)) + residual with alpha [B] fp32 on the device - one
+        afldm_attention_interp launch and one to_out GEMM (to_out is affine and the residual is common to both terms)."""
         assert attention_mask is None
+        assert kv1 is None or (kv is not None and alpha is not None)
         B, H, W, C = hidden_states.shape
         gamma, beta = packed_norm(attn.group_norm)
         gn = attn.group_norm
@@ -770,7 +799,10 @@ class AttnProcessor2_0:
             q = linear_forward(attn.to_q, tokens)
             w, b = packed_qkv(attn, tokens.dtype, ("k", "v"))
             k, vt = ops.linear_split(encoder_hidden_states, w, b, C)
-        o = ops.attention(q, k, vt, attn.heads, scale=attn.scale)
+        if kv1 is not None:
+            o = ops.attention_interp(q, k, vt, kv1[0], kv1[1], alpha, attn.heads, scale=attn.scale)
+        else:
+            o = ops.attention(q, k, vt, attn.heads, scale=attn.scale)
         return linear_forward(attn.to_out[0], o.view(B, H, W, C), residual=hidden_states, want_stats=True)
 
 

@@ -1253,6 +1253,37 @@ def attention(q, k, vt, heads, scale=None, out=None):
     return out
 
 
+def attention_interp(q, k0, vt0, k1, vt1, alpha, heads, scale=None, out=None):
+    """(1 - alpha[b]) * attention(q, k0, vt0) + alpha[b] * attention(q, k1, vt1) for every sample b, each softmax normalised on
+    its own, blended in fp32 and rounded once (afldm_attention_interp: one launch).  Layouts as attention(); the two sources
+    have the same shape and the same leading dimension (k0 / k1 may be column slices of wider buffers).  alpha: fp32 device
+    tensor [B], read when the kernel runs - a captured graph picks up the values it holds at each replay."""
+    _dev(vt0, "vt0")
+    _dev(vt1, "vt1")
+    _dev(alpha, "alpha")
+    if not (q.is_cuda and k0.is_cuda and k1.is_cuda):
+        raise RuntimeError("afldm_amd: attention inputs must live on an MI355X (cuda) device; there is no CPU path")
+    B, Tq, C = q.shape
+    Bk, Tk, _ = k0.shape
+    if k1.shape != k0.shape or k1.stride() != k0.stride() or vt1.shape != vt0.shape or k0.dtype != k1.dtype:
+        raise ValueError(f"attention_interp: the two sources differ: k {tuple(k0.shape)} / {tuple(k1.shape)} (strides "
+                         f"{k0.stride()} / {k1.stride()}), vt {tuple(vt0.shape)} / {tuple(vt1.shape)}")
+    if alpha.dtype != torch.float32 or tuple(alpha.shape) != (B,):
+        raise ValueError(f"attention_interp: alpha must be fp32 [{B}], got {alpha.dtype} {tuple(alpha.shape)}")
+    ldq, ldk = q.stride(1), k0.stride(1)
+    assert q.stride(2) == 1 and k0.stride(2) == 1 and q.stride(0) == Tq * ldq and k0.stride(0) == Tk * ldk
+    d = C // heads
+    if scale is None:
+        scale = d ** -0.5
+    if out is None:
+        out = torch.empty((B, Tq, C), dtype=q.dtype, device=q.device)
+    tok = _begin()
+    check(lib.afldm_attention_interp(ptr(q), ldq, ptr(k0), ptr(k1), ldk, ptr(vt0), ptr(vt1), ptr(alpha), ptr(out), C, B, Bk,
+                                     heads, Tq, Tk, d, float(scale), _code(q), stream_ptr()), "attention_interp")
+    _end(tok, "attention_interp", 8.0 * B * heads * Tq * Tk * d, (2 * B * Tq * C + 4 * Bk * Tk * C) * q.element_size())
+    return out
+
+
 _FUSED_ATTN = os.environ.get("AFLDM_NO_FUSED_ATTN", "0") != "1"
 # below this many (sample, head) workgroups the chip is too empty with one workgroup per pair: the three-launch path wins.
 # In-step A/B (profiles/r04/small_batch_tiles_ab.txt): 128 against 256: batch 8 2.385 -> 2.362 (the 16^2 level fuses), batch 12

@@ -16,8 +16,13 @@ class AttnState:
     the mode - STORE the attention inputs of this pass / LOAD the stored ones as K, V / IDLE - plus the timestep that keys
     the stored maps, the slot a STORE pass writes (`store_id`, two slots for the interpolating processor) and the blend
     weight `alpha` of a LOAD pass.  `state`, `timestep`, `store_id` and `alpha` are read-only views; they change through
-    the set_* / to_* methods only, exactly as in the reference."""
+    the set_* / to_* methods only, exactly as in the reference.
+
+    Beyond the reference: `set_store_id(AttnState.PAIR)` makes ONE batch-2 STORE pass fill both slots (sample 0 -> slot 0, sample
+    1 -> slot 1: the samples are independent, so this is the reference's two batch-1 passes at half the launches), and
+    `set_alpha` also takes a 1-D fp32 device tensor, one blend weight per sample of the LOAD batch."""
     STORE, LOAD, IDLE = 0, 1, 2
+    PAIR = -1
     _FIELDS = ("state", "timestep", "store_id", "alpha")
 
     def __init__(self):
@@ -41,6 +46,12 @@ class AttnState:
         self._v["timestep"] = t.item() if torch.is_tensor(t) else t
 
     def set_alpha(self, alpha):
+        """A float (the reference: one weight for the whole LOAD batch) or a 1-D fp32 tensor of one weight per sample, on the
+        device for the cached path (afldm_attention_interp reads it when the kernel runs: a captured graph sees the values the
+        tensor holds at each replay)."""
+        if torch.is_tensor(alpha) and (alpha.ndim != 1 or alpha.dtype != torch.float32):
+            raise ValueError(f"AttnState.set_alpha: a tensor alpha must be 1-D fp32 (one weight per sample), got "
+                             f"{alpha.dtype} {tuple(alpha.shape)}")
         self._v["alpha"] = alpha
 
     def set_store_id(self, store_id):
@@ -57,7 +68,9 @@ class CrossFrameAttnProcessor(AttnProcessor2_0):
     """cache_kv (not in the reference; the graph-replayed harness sets it): a STORE pass also keeps the keys / values it
     projects from its own hidden states, and a LOAD pass attends to them directly instead of group-norming and projecting the
     stored map again every step (reference cross_frame_attn.py:88-125 recomputes them: same layer, same input, same numbers).
-    Without interpolation only; `maps` is still filled as the reference does."""
+    `maps` is still filled as the reference does.  With enable_interp, a LOAD pass that finds both slots cached runs
+    to_q -> ONE afldm_attention_interp launch over both stored pairs (per-sample alpha) -> ONE to_out + residual, instead of
+    two GroupNorms, two K / V projections, two attentions, two to_out GEMMs and a torch blend."""
 
     def __init__(self, attn_state: AttnState, enable_interp=False, cache_kv=False):
         super().__init__()
@@ -65,7 +78,17 @@ class CrossFrameAttnProcessor(AttnProcessor2_0):
         self.maps = [dict(), dict()]
         self.kv = [dict(), dict()]
         self.enable_interp = enable_interp
-        self.cache_kv = bool(cache_kv) and not enable_interp
+        self.cache_kv = bool(cache_kv)
+
+    def _alpha_vector(self, batch, device):
+        """The LOAD pass's blend weights as the fp32 device vector [batch] the interpolating kernel reads."""
+        alpha = self.attn_state.alpha
+        if torch.is_tensor(alpha):
+            if tuple(alpha.shape) != (batch,) or alpha.device != device:
+                raise ValueError(f"per-sample alpha {tuple(alpha.shape)} on {alpha.device} does not match the LOAD batch "
+                                 f"{batch} on {device}")
+            return alpha
+        return torch.full((batch,), float(alpha), dtype=torch.float32, device=device)
 
     def _kv_source(self, attn, stored, batch):
         """group-normed [Bk, HW, C] tokens of a stored NHWC map; Bk must divide the batch (the
@@ -91,13 +114,20 @@ class CrossFrameAttnProcessor(AttnProcessor2_0):
             # (under graph capture the tensor lives in the graph's pool for as long as this dict holds it and nobody writes it
             #  in place: no copy launch; eager passes keep the reference's clone)
             capturing = torch.cuda.is_current_stream_capturing()
+            if sid == AttnState.PAIR:
+                return self._store_pair(attn, hidden_states, attention_mask, temb, t, capturing)
             self.maps[sid][t] = hidden_states.detach() if capturing else hidden_states.detach().clone()
             if not self.cache_kv:
                 return super().__call__(attn, hidden_states, None, attention_mask, temb)
             return super().__call__(attn, hidden_states, None, attention_mask, temb,
                                     kv_sink=lambda k, vt: self.kv[sid].__setitem__(t, (k, vt)))
-        if self.cache_kv and t in self.kv[0] and hidden_states.shape[0] % self.kv[0][t][0].shape[0] == 0:
-            return super().__call__(attn, hidden_states, None, attention_mask, temb, kv=self.kv[0][t])
+        B = hidden_states.shape[0]
+        if self.cache_kv and t in self.kv[0] and B % self.kv[0][t][0].shape[0] == 0:
+            if not self.enable_interp:
+                return super().__call__(attn, hidden_states, None, attention_mask, temb, kv=self.kv[0][t])
+            if t in self.kv[1] and self.kv[1][t][0].shape == self.kv[0][t][0].shape:
+                return super().__call__(attn, hidden_states, None, attention_mask, temb, kv=self.kv[0][t], kv1=self.kv[1][t],
+                                        alpha=self._alpha_vector(B, hidden_states.device))
         map0 = self._kv_source(attn, self.maps[0][t], hidden_states.shape[0])
         if not self.enable_interp:
             return super().__call__(attn, hidden_states, map0, attention_mask, temb)
@@ -105,7 +135,25 @@ class CrossFrameAttnProcessor(AttnProcessor2_0):
         map1 = self._kv_source(attn, self.maps[1][t], hidden_states.shape[0])
         r1 = super().__call__(attn, hidden_states, map0, attention_mask, temb)
         r2 = super().__call__(attn, hidden_states, map1, attention_mask, temb)
+        if torch.is_tensor(alpha):                  # one weight per sample (NHWC: broadcast over H, W, C)
+            alpha = alpha.to(device=r1.device, dtype=r1.dtype).view(-1, 1, 1, 1)
         return (1 - alpha) * r1 + alpha * r2
+
+    def _store_pair(self, attn, hidden_states, attention_mask, temb, t, capturing):
+        """STORE with store_id PAIR: one batch-2 pass fills both slots, sample s -> slot s, as [s:s+1] views of the same maps /
+        K / V^T buffers."""
+        if hidden_states.shape[0] != 2:
+            raise ValueError(f"a two-slot STORE pass (store_id PAIR) runs at batch 2, got {hidden_states.shape[0]}")
+        for s in (0, 1):
+            m = hidden_states[s:s + 1].detach()
+            self.maps[s][t] = m if capturing else m.clone()
+        if not self.cache_kv:
+            return super().__call__(attn, hidden_states, None, attention_mask, temb)
+
+        def sink(k, vt):
+            for s in (0, 1):
+                self.kv[s][t] = (k[s:s + 1], vt[s:s + 1])
+        return super().__call__(attn, hidden_states, None, attention_mask, temb, kv_sink=sink)
 
 
 def get_unet_attn_processors(unet):

@@ -1,0 +1,209 @@
+"""LDMInterpolationPipeline — image interpolation of reference afldm/pipelines/image_interpolation_pipeline.py:284-766 on the
+unconditional UNet this project serves (the text-prompt and classifier-free-guidance parts drop out):
+
+  1. both images -> sample_size * vae_scale_factor, [-1, 1];
+  2. image2latent (:270-282): the MEAN of the VAE posterior times scaling_factor;
+  3. DDIM inversion of each latent (:232-268; the reference's processors store nothing it reads: plain processors here);
+  4. frame 0 / n-1 = the inverted latents, frame i = slerp(frame 0, frame n-1, linspace(0, 1, n)[i]) (warp_method 3);
+  5. two STORE passes of the full schedule, endpoint 0 into slot 0, endpoint 1 into slot 1 (:604-652);
+  6. the LOAD pass (:668-735): at every step each frame f attends to both stored passes, blended by alpha = f / (n - 1),
+     then one DDIM step (eta 0) advances all frames;
+  7. decode every frame.
+
+use_graph=True (default) runs 3 as one batch-2 graph run, 5 as ONE batch-2 graph (AttnState.PAIR), 6 as one graph over all
+n frames with a per-sample alpha buffer (each attention = one afldm_attention_interp launch over both cached K / V^T pairs)
+and 7 as one batched decode; the captures are cached on the pipeline, later calls replay.  use_graph=False follows the
+reference statement by statement: batch-1 passes, a per-frame LOAD with a host alpha, the non-cached processors.
+DESIGN.md section 12 lists the deviations from the reference script."""
+import os
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from ..schedulers.ddim import DDIMScheduler
+from .cross_frame_attn import AttnState, CrossFrameAttnProcessor, get_unet_attn_processors, set_unet_attn_processor
+from .ldm_pipeline import MyLDMPipeline
+
+
+def _arc_weights(cos_omega, t):
+    """Weights (w0, w1) of spherical interpolation at fraction t for the angle whose cosine is `cos_omega` (float64 0-d
+    tensors): w0 = sin((1 - t) omega) / sin omega, w1 = sin(t omega) / sin omega, with (1 - t) omega evaluated as
+    omega - t omega."""
+    omega = torch.arccos(cos_omega)
+    t_omega = omega * t
+    sin_omega = torch.sin(omega)
+    return torch.sin(omega - t_omega) / sin_omega, torch.sin(t_omega) / sin_omega
+
+
+@torch.no_grad()
+def slerp(a, b, t):
+    """Spherical interpolation between the tensors a and b at fraction t, the arithmetic of the reference's helper
+    (image_interpolation_pipeline.py:68-108): everything in float64, the cosine of the angle between the flattened tensors
+    clamped to [-1 + 1e-7, 1 - 1e-7] (parallel / antiparallel inputs stay finite), the result returned in fp16 for fp16
+    inputs and in fp32 for every other dtype."""
+    out_dtype = torch.float16 if a.dtype == torch.float16 else torch.float32
+    a64, b64 = a.double(), b.double()
+    cos_omega = torch.sum(a64 * b64) / (torch.linalg.norm(a64) * torch.linalg.norm(b64))
+    w0, w1 = _arc_weights(cos_omega.clamp(-1 + 1e-7, 1 - 1e-7), t)
+    return (a64 * w0 + b64 * w1).to(out_dtype)
+
+
+def interp_alphas(num_frames):
+    """(slerp fractions, LOAD blend weights) of an n-frame call.  They differ, as in the reference: the slerp takes
+    torch.linspace(0, 1, n) in fp32 (:536), the blend the Python float f / (n - 1) (:680)."""
+    return [float(a) for a in torch.linspace(0, 1, num_frames)], [f / (num_frames - 1) for f in range(num_frames)]
+
+
+def check_interp_args(scheduler, num_frames, warp_method):
+    """The calls LDMInterpolationPipeline refuses (before any work)."""
+    if warp_method != 3:
+        raise NotImplementedError(f"warp_method={warp_method} warps the inverted noise along optical flow, which needs the GMFlow "
+                                  "model: it is not available here; warp_method=3 (slerp of the inverted endpoints) is")
+    if not isinstance(num_frames, (int, np.integer)) or num_frames < 2:
+        raise ValueError(f"num_frames must be an integer >= 2 (the two endpoints are frames), got {num_frames!r}")
+    if not isinstance(scheduler, DDIMScheduler):
+        raise NotImplementedError(f"image interpolation samples with DDIM (inversion + cross-frame STORE / LOAD passes): a "
+                                  f"pipeline whose scheduler is a {type(scheduler).__name__} is not supported")
+
+
+class LDMInterpolationPipeline(MyLDMPipeline):
+    """Two-image interpolation with the interpolating cross-frame attention.  Build it with from_pretrained(dir) (as
+    MyLDMPipeline) or from another pipeline's modules: LDMInterpolationPipeline(**ldm_pipeline.components)."""
+
+    @property
+    def vae_scale_factor(self):
+        return 2 ** (len(self.vae.config.block_out_channels) - 1)
+
+    def _image(self, image, size):
+        """PIL image / path -> [1, 3, size, size] in [-1, 1] (Lanczos resize, diffusers VaeImageProcessor's default); a [-1, 1]
+        tensor [1, 3, H, W] is resized (bilinear, antialiased) only when it is not size x size already."""
+        from PIL import Image
+        if isinstance(image, (str, os.PathLike)):
+            image = Image.open(image)
+        if isinstance(image, Image.Image):
+            img = image.convert("RGB")
+            if img.size != (size, size):
+                img = img.resize((size, size), Image.LANCZOS)
+            return torch.from_numpy(np.asarray(img, dtype=np.float32) / 127.5 - 1.0).permute(2, 0, 1)[None]
+        if torch.is_tensor(image):
+            if image.ndim != 4 or tuple(image.shape[:2]) != (1, 3):
+                raise ValueError(f"an image tensor must be [1, 3, H, W] in [-1, 1], got {tuple(image.shape)}")
+            x = image.detach().float().cpu()
+            if tuple(x.shape[-2:]) != (size, size):
+                x = F.interpolate(x, size=(size, size), mode="bilinear", align_corners=False, antialias=True)
+            return x
+        raise TypeError(f"an image is a PIL image, a path or a [1, 3, H, W] tensor, got {type(image).__name__}")
+
+    @torch.no_grad()
+    def image2latent(self, image):
+        """Reference :270-282: the posterior MEAN (not a sample) times scaling_factor."""
+        return self.vae.encode(image.to(device=self.vae.device, dtype=self.vae.dtype)).latent_dist.mean * self.vae.config.scaling_factor
+
+    @torch.no_grad()
+    def __call__(self, image1, image2, num_frames=17, num_inference_steps=50, warp_method=3, enable_interp=True,
+                 output_type="pil", return_dict=True, use_graph=True, timings=None):
+        """Returns the num_frames frames (output_type 'latent' / 'pt' / 'np' / 'pil', as MyLDMPipeline).  enable_interp=False
+        keeps the reference's other branch: intermediate frames start from endpoint 0 and every frame attends to pass 0 only.
+        timings: a dict that receives the wall time of the VAE ('vae_s'), the UNet passes ('unet_s'), the rest ('other_s') and
+        'total_s' (synchronises at the phase boundaries; off when None)."""
+        from ..harness import _Clock
+        check_interp_args(self.scheduler, num_frames, warp_method)
+        if self.vae is None:
+            raise NotImplementedError("image interpolation encodes its two images: this pipeline was built without a VAE")
+        clock = _Clock(timings)
+        unet, n = self.unet, int(num_frames)
+        self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
+        size = unet.config.sample_size * self.vae_scale_factor
+        images = [self._image(im, size) for im in (image1, image2)]
+        fracs, weights = interp_alphas(n)
+        if not enable_interp:
+            weights = [0.0] * n           # pass 0 only: alpha 0 is exactly the single-source attention
+        clock.lap("other_s")
+        if use_graph:
+            latents = self._graph_frames(images, n, num_inference_steps, fracs, weights, enable_interp, clock)
+        else:
+            latents = self._eager_frames(images, n, num_inference_steps, fracs, weights, enable_interp, clock)
+        out = self._deliver(latents, output_type, return_dict)
+        clock.lap("vae_s")
+        clock.done()
+        return out
+
+    def _frames(self, z0, z1, n, fracs, enable_interp):
+        """Step 4: [n, C, H, W] initial latents from the two inverted ones (reference :551-599, warp_method 3)."""
+        latents = torch.empty((n,) + tuple(z0.shape[1:]), dtype=z0.dtype, device=z0.device)
+        latents[0], latents[-1] = z0[0], z1[0]
+        for i in range(1, n - 1):
+            latents[i] = slerp(latents[0], latents[-1], fracs[i]) if enable_interp else latents[0]
+        return latents
+
+    def _graph_frames(self, images, n, steps, fracs, weights, enable_interp, clock):
+        unet = self.unet
+        lat = self.image2latent(torch.cat(images, 0)).float()
+        clock.lap("vae_s")
+        self.scheduler.set_timesteps(steps, device=unet.device)
+        inv = self.ddim_inversion(lat, bar=False)            # both endpoints: one batch-2 run of the captured inversion graph
+        latents = self._frames(inv[0:1], inv[1:2], n, fracs, enable_interp)
+        clock.lap("unet_s")
+        out = self._graph_passes(inv, latents, steps, weights)
+        clock.lap("unet_s")
+        return out.to(unet.dtype)
+
+    def _graph_passes(self, ends, latents, steps, weights):
+        """Steps 5-6 on replayed graphs: the STORE pass of both endpoints `ends` [2, C, H, W] as one batch-2 graph (endpoint s ->
+        slot s), then the LOAD pass of all frames `latents` [n, C, H, W] with blend weights `weights` (n floats).  Returns the
+        fp32 latents; the caller's attention processors are restored."""
+        from ..harness import _sampler
+        smp = _sampler(self, steps, interp=True)
+        previous = smp.install()
+        try:
+            smp.run(ends, load=False)
+            return smp.run(latents, load=True, alpha=weights)
+        finally:
+            set_unet_attn_processor(self.unet, dict(previous))
+
+    def _eager_frames(self, images, n, steps, fracs, weights, enable_interp, clock):
+        unet, sched = self.unet, self.scheduler
+        lats = [self.image2latent(x) for x in images]
+        clock.lap("vae_s")
+        sched.set_timesteps(steps, device=unet.device)
+        inv = [self.ddim_inversion(z.to(unet.dtype), bar=False, use_graph=False) for z in lats]
+        latents = self._frames(inv[0], inv[1], n, fracs, enable_interp)
+        out = self._eager_passes(latents, steps, weights, enable_interp)
+        clock.lap("unet_s")
+        return out
+
+    def _eager_passes(self, latents, steps, weights, enable_interp=True):
+        """Steps 5-6 as the reference runs them (:604-735): batch-1 STORE passes of frame 0 (slot 0) and frame n-1 (slot 1) on the
+        non-cached processors, then at every step one batch-1 UNet call per frame with its host alpha and one DDIM step for all
+        frames.  Latents stay in their own dtype between steps; the caller's attention processors are restored."""
+        unet, sched = self.unet, self.scheduler
+        dev = unet.device
+        state = AttnState()
+        previous = get_unet_attn_processors(unet)
+        set_unet_attn_processor(unet, {k: CrossFrameAttnProcessor(state, enable_interp=enable_interp) for k in previous})
+
+        def store(z, sid):
+            state.set_store_id(sid)
+            sched.set_timesteps(steps, device=dev)
+            for t in sched._timesteps_host:
+                state.set_timestep(t)
+                eps = unet(sched.scale_model_input(z, t), t, return_dict=False)[0]
+                z = sched.step(eps, t, z, eta=0.0, return_dict=False)[0]
+
+        try:
+            state.reset()
+            store(latents[0:1], 0)
+            store(latents[-1:], 1)
+            state.to_load()
+            sched.set_timesteps(steps, device=dev)
+            for t in sched._timesteps_host:
+                state.set_timestep(t)
+                eps = []
+                for f in range(latents.shape[0]):
+                    state.set_alpha(weights[f])
+                    eps.append(unet(sched.scale_model_input(latents[f:f + 1], t), t, return_dict=False)[0])
+                latents = sched.step(torch.cat(eps), t, latents, eta=0.0, return_dict=False)[0]
+        finally:
+            set_unet_attn_processor(unet, dict(previous))
+        return latents

@@ -376,6 +376,16 @@ int afldm_pack_weight_up2(const float* src, void* dst, int Cout, int Cin, int dt
 int afldm_attention(const void* q, int ldq, const void* k, int ldk, const void* vt, void* o, int ldo,
                     int B, int Bk, int heads, int Tq, int Tk, int d, float scale, int dtype,
                     afldm_stream_t stream);
+/* The interpolating cross-frame attention (reference cross_frame_attn.py:100-122, enable_interp) with the two
+ * stored passes' K / V^T as two sources, blended per sample: for sample b, kb = b / (B/Bk),
+ *   o[b] = (1 - alpha[b]) softmax(q_b k0_kb^T scale) v0_kb + alpha[b] softmax(q_b k1_kb^T scale) v1_kb
+ * Each source's softmax is normalised on its own; the blend is fp32 and o is rounded once.  alpha [B] is fp32
+ * DEVICE memory read when the kernel runs (a captured graph picks up new values at every replay).  Operand
+ * layouts and limits are those of afldm_attention; the two sources share ldk and shape.  One launch replaces two
+ * attentions: to_out is affine and the residual common to both terms, so the blend may sit before to_out. */
+int afldm_attention_interp(const void* q, int ldq, const void* k0, const void* k1, int ldk, const void* vt0,
+                           const void* vt1, const float* alpha, void* o, int ldo, int B, int Bk, int heads, int Tq,
+                           int Tk, int d, float scale, int dtype, afldm_stream_t stream);
 
 /* ---- attention block front end, fused ------------------------------------------------------
  * group_norm -> to_q | to_k | to_v -> scaled_dot_product_attention of diffusers' AttnProcessor2_0 on the deprecated
