@@ -1499,3 +1499,77 @@ def select_step_row(tvals, step_idx, t_out, table, row_out, pre_advance=False):
     check(lib.afldm_select_step_row(ptr(tvals), ptr(step_idx), ptr(t_out), int(pre_advance), ptr(table), ptr(row_out),
                                     nbytes, stream_ptr()), "select_step_row")
     return t_out
+
+
+FLOW_PICK, FLOW_POOL = 0, 1
+
+
+def flow_splat_workspace(B, C, H, W, ds, mode):
+    """fp32 elements of afldm_flow_splat's accumulation workspace."""
+    n = lib.afldm_flow_splat_workspace(B, C, H, W, ds, mode)
+    if n == 0:
+        raise ValueError(f"flow_splat: bad arguments (B {B}, C {C}, H {H}, W {W}, ds {ds}, mode {mode}): H and W must be multiples of ds")
+    return n // 4
+
+
+def flow_splat(x, flow, scale, ds=1, mode=FLOW_PICK, fill=None, fill_pix_stride=1, out=None, occ=None, workspace=None):
+    """afldm_flow_splat: forward bilinear splat of x [Bs, C, H, W] along scale[b] * flow [Bs, 2, H, W] (fp32, channel 0 = row
+    displacement) for B = scale.numel() samples (sample b reads source b // (B // Bs)), then the finishing pass.
+      FLOW_PICK: (res [B, C, H/ds, W/ds], occ [B, 1, H/ds, W/ds]): the warp at every ds-th pixel; fill: [1 | B, C, H/ds * fps,
+        W/ds * fps] with fps = fill_pix_stride, applied as res * (1 - occ) + occ * fill[..., ::fps, ::fps].
+      FLOW_POOL: (pooled [B, C, H/ds, W/ds], occ [B, 1, H, W]): sum over ds x ds blocks of (fill * occ + res * (1 - occ)) / ds;
+        fill: [1 | B, C, H, W] or None (0).
+    scale is read when the kernels run (a captured call replays new values).  workspace: fp32 device tensor of at least
+    flow_splat_workspace(...) elements (allocated when None); the call zeroes it."""
+    _dev(x, "x"); _dev(flow, "flow"); _dev(scale, "scale")
+    Bs, C, H, W = x.shape
+    B = scale.numel()
+    if flow.dtype != torch.float32 or tuple(flow.shape) != (Bs, 2, H, W):
+        raise ValueError(f"flow_splat: flow must be fp32 [{Bs}, 2, {H}, {W}], got {flow.dtype} {tuple(flow.shape)}")
+    if scale.dtype != torch.float32 or scale.dim() != 1 or B % Bs:
+        raise ValueError(f"flow_splat: scale must be fp32 [B] with B a multiple of {Bs}, got {scale.dtype} {tuple(scale.shape)}")
+    if mode not in (FLOW_PICK, FLOW_POOL):
+        raise ValueError(f"flow_splat: unknown mode {mode!r}")
+    nws = flow_splat_workspace(B, C, H, W, ds, mode)
+    Ho, Wo = H // ds, W // ds
+    fbs = 0
+    if fill is not None:
+        _dev(fill, "fill")
+        fps = 1 if mode == FLOW_POOL else int(fill_pix_stride)
+        want = (C, H, W) if mode == FLOW_POOL else (C, Ho * fps, Wo * fps)
+        if fill.dtype != x.dtype or fill.dim() != 4 or fill.shape[0] not in (1, B) or tuple(fill.shape[1:]) != want:
+            raise ValueError(f"flow_splat: fill must be {x.dtype} [1 or {B}, {want[0]}, {want[1]}, {want[2]}], got {fill.dtype} "
+                             f"{tuple(fill.shape)}")
+        fbs = 0 if fill.shape[0] == 1 else fill.stride(0)
+    if workspace is None:
+        workspace = torch.empty(nws, dtype=torch.float32, device=x.device)
+    _dev(workspace, "workspace")
+    if workspace.dtype != torch.float32 or workspace.numel() < nws:
+        raise ValueError(f"flow_splat: workspace must be fp32 with at least {nws} elements")
+    occ_shape = (B, 1, H, W) if mode == FLOW_POOL else (B, 1, Ho, Wo)
+    if out is None:
+        out = torch.empty((B, C, Ho, Wo), dtype=x.dtype, device=x.device)
+    if occ is None:
+        occ = torch.empty(occ_shape, dtype=x.dtype, device=x.device)
+    _dev(out, "out"); _dev(occ, "occ")
+    assert tuple(out.shape) == (B, C, Ho, Wo) and tuple(occ.shape) == occ_shape and out.dtype == occ.dtype == x.dtype
+    check(lib.afldm_flow_splat(ptr(x), ptr(flow), ptr(scale), ptr(fill), fbs, int(fill_pix_stride), ptr(out), ptr(occ),
+                               ptr(workspace), workspace.numel() * 4, B, Bs, C, H, W, int(ds), mode, _code(x), stream_ptr()),
+          "flow_splat")
+    return out, occ
+
+
+def flow_warp(x, flow, add_grid=True, nearest=False, mask=False):
+    """afldm_flow_warp: grid_sample(align_corners=True, zeros) of x [B, C, Hin, Win] at coords_grid + flip(flow) (add_grid; flow
+    fp32 [B, 2, Hout, Wout], channel 0 = row displacement) or at the coordinates `flow` itself holds (channel 0 = x).  Returns
+    y [B, C, Hout, Wout], and with mask=True also the reference's in-bounds mask (bool [B, Hout, Wout])."""
+    _dev(x, "x"); _dev(flow, "flow")
+    B, C, Hi, Wi = x.shape
+    if flow.dtype != torch.float32 or flow.dim() != 4 or flow.shape[0] != B or flow.shape[1] != 2:
+        raise ValueError(f"flow_warp: flow / coordinates must be fp32 [{B}, 2, H, W], got {flow.dtype} {tuple(flow.shape)}")
+    Ho, Wo = flow.shape[-2:]
+    y = torch.empty((B, C, Ho, Wo), dtype=x.dtype, device=x.device)
+    m = torch.empty((B, Ho, Wo), dtype=torch.bool, device=x.device) if mask else None
+    check(lib.afldm_flow_warp(ptr(x), ptr(flow), ptr(y), ptr(m), B, C, Hi, Wi, Ho, Wo, int(bool(add_grid)), int(bool(nearest)),
+                              _code(x), stream_ptr()), "flow_warp")
+    return (y, m) if mask else y

@@ -480,6 +480,42 @@ int afldm_select_step_row(const float* tvals, int* step_idx, float* t_out, int p
 int afldm_masked_metrics(const void* a, const void* b, const float* mask, float* out, int B, size_t n,
                          int dtype, afldm_stream_t stream);
 
+/* ---- warping along an optical-flow field (afldm/shift_utils/flow_utils.py, flow_utils_np.py) ---------------
+ * afldm_flow_splat: the forward bilinear splat of `_forward_flow_warp` (flow_utils_np.py:116-152) and what the callers do
+ * behind it, for B samples in one call.  x [Bs][C][H][W] dtype and flow [Bs][2][H][W] fp32 (channel 0 = ROW displacement)
+ * are shared by groups of B / Bs samples (sample b reads source b / (B / Bs)); scale [B] fp32 on the DEVICE is the factor the
+ * reference multiplies the flow by before the warp (`f_flow * alpha`, image_interpolation_pipeline.py:571-577).  Source
+ * (i, j) lands at ci = i + scale * flow0, cj = j + scale * flow1 (fp32, product rounded before the add), i1 = int(ci)
+ * truncated towards zero, and each of the targets (i1 | i1 + 1, j1 | j1 + 1) inside the plane receives
+ * coef = (1 - |ci - gi|)(1 - |cj - gj|) (negative for some targets when ci or cj < 0): res += x * coef, cnt += coef, in fp32
+ * (return-less vector atomics: sums agree between runs to summation order, not bit for bit).  bwd_occ = 1 where cnt > 0 is
+ * false; no division by cnt.
+ *   mode AFLDM_FLOW_PICK: only targets with gi % ds == 0 and gj % ds == 0 are accumulated: out [B][C][H/ds][W/ds], occ
+ *     [B][1][H/ds][W/ds] (NULL: not written) are the reference's `[:, :, ::ds, ::ds]` of the warp (flow_utils.py:333-341).
+ *     fill != NULL applies `res * (1 - occ) + occ * fill` (image_interpolation_pipeline.py:574); fill is read at
+ *     [b * fill_batch_stride + c * (H/ds * W/ds * fps^2) + (ho * fps) * (W/ds * fps) + wo * fps] with fps = fill_pix_stride
+ *     (a full-resolution draw is read in place at the kept pixels with fps = ds; fill_batch_stride = 0 shares one draw).
+ *   mode AFLDM_FLOW_POOL: accumulated at full resolution, out [B][C][H/ds][W/ds] = sum over each ds x ds block of
+ *     (fill * occ + res * (1 - occ)) / ds (`collect_noise_pixel`, flow_utils.py:214-221; fill [.][C][H][W], NULL = 0),
+ *     occ [B][1][H][W] (NULL: not written).
+ * workspace: afldm_flow_splat_workspace(...) bytes (0 = bad arguments), zeroed by the call itself (a kernel: a
+ * captured call replays kernel nodes only).  x, fill, out, occ share `dtype`. */
+enum { AFLDM_FLOW_PICK = 0, AFLDM_FLOW_POOL = 1 };
+size_t afldm_flow_splat_workspace(int B, int C, int H, int W, int ds, int mode);
+int afldm_flow_splat(const void* x, const float* flow, const float* scale, const void* fill, long long fill_batch_stride,
+                     int fill_pix_stride, void* out, void* occ, float* workspace, size_t workspace_bytes, int B, int Bs, int C,
+                     int H, int W, int ds, int mode, int dtype, afldm_stream_t stream);
+/* afldm_flow_warp: `flow_warp` / `bilinear_sample` (flow_utils.py:53-86): F.grid_sample(align_corners=True,
+ * padding_mode='zeros'), bilinear (nearest = 0) or nearest (round half to even), of x [B][C][Hin][Win] dtype at
+ * add_grid != 0: x = j + flow[1], y = i + flow[0] (coords_grid + flip(flow): flow [B][2][Hout][Wout] fp32, channel 0 = row
+ * displacement); add_grid == 0: flow holds the sample coordinates themselves (channel 0 = x).  y [B][C][Hout][Wout];
+ * mask (NULL: not written) [B][Hout][Wout] bytes = the reference's in-bounds mask, formed from the coordinate normalised to
+ * [-1, 1] with its fp32 operations (2 c / (n - 1) - 1), so exact at the borders.  With Hin == Hout (Win == Wout) the pixel
+ * coordinate is used as it is instead of the normalised one un-normalised again (the same to 4 (n - 1) 2^-24 pixels).
+ * Coordinates are fp32 for both dtypes. */
+int afldm_flow_warp(const void* x, const float* flow, void* y, unsigned char* mask, int B, int C, int Hin, int Win, int Hout,
+                    int Wout, int add_grid, int nearest, int dtype, afldm_stream_t stream);
+
 /* ---- upfirdn2d ---------------------------------------------------------------------------
  * Zero-stuffing up-sample (upx, upy) -> pad (negative = crop) -> 2-D FIR -> decimate (downx, downy) on
  * NCHW planes: torch_utils/ops/upfirdn2d.py:140-194 (`_upfirdn2d_ref`; the reference's fast path is the

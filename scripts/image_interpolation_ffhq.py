@@ -25,11 +25,21 @@ def parse_args(argv=None):
     p.add_argument("--random-init", action="store_true",
                    help="seeded random weights of the FFHQ architecture and two seeded synthetic images (no checkpoint needed)")
     p.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"])
-    p.add_argument("--seed", type=int, default=1234, help="seeds the synthetic images of --random-init")
+    p.add_argument("--seed", type=int, default=1234,
+                   help="seeds the synthetic images of --random-init and the random draws of --warp-method 0-2")
     p.add_argument("--eager", action="store_true",
                    help="run the passes as the eager loop that follows the reference statement by statement instead of replayed "
                         "HIP graphs")
+    p.add_argument("--warp-method", type=int, default=3, choices=[0, 1, 2, 3],
+                   help="how intermediate frames start (reference image_interpolation_pipeline.py:556-599): 0 = up-sampled noise "
+                        "forward-warped along the flow (the reference script's choice), 1 = conditional noise up-sampling + warp, "
+                        "2 = the latents warped, 3 = slerp only; 0-2 need --flow")
+    p.add_argument("--flow", type=str, default=None, metavar="FILE.npz",
+                   help="optical flow between the two images from any estimator: arrays `fwd` and `bwd`, each [2, S, S] or "
+                        "[1, 2, S, S] at the image size, channel 0 = x displacement (GMFlow's output convention)")
     args = p.parse_args(argv)
+    if args.warp_method != 3 and not args.flow:
+        p.error("--warp-method 0, 1 and 2 warp along optical flow: pass --flow FILE.npz (arrays fwd, bwd)")
     if args.n_frames < 2:
         p.error("--n_frames must be >= 2")
     if not args.random_init and not (args.input_path_1 and args.input_path_2):
@@ -45,6 +55,20 @@ def synthetic_images(seed, size=256):
         x = torch.rand(1, 3, 8, 8, generator=g) * 2 - 1
         out.append(torch.nn.functional.interpolate(x, size=(size, size), mode="bicubic", align_corners=False).clamp(-1, 1))
     return out
+
+
+def load_flows(path):
+    """(fwd_flow, bwd_flow) fp32 [1, 2, S, S] from the arrays `fwd` and `bwd` of an .npz file."""
+    import numpy as np
+    with np.load(path) as z:
+        missing = [k for k in ("fwd", "bwd") if k not in z.files]
+        if missing:
+            raise SystemExit(f"{path}: array(s) {missing} missing (found {z.files})")
+        out = []
+        for k in ("fwd", "bwd"):
+            f = torch.from_numpy(np.asarray(z[k], dtype=np.float32))
+            out.append(f[None] if f.dim() == 3 else f)
+    return tuple(out)
 
 
 def build_pipeline(args):
@@ -81,8 +105,10 @@ def main(argv=None):
         image1, image2 = synthetic_images(args.seed)
     else:
         image1, image2 = args.input_path_1, args.input_path_2
+    flows = load_flows(args.flow) if args.flow else None
     frames = pipe(image1, image2, num_frames=args.n_frames, num_inference_steps=args.n_steps, output_type="pt",
-                  use_graph=not args.eager)
+                  use_graph=not args.eager, warp_method=args.warp_method, flows=flows,
+                  generator=torch.Generator().manual_seed(args.seed))
     save_gif_from_tensors(list(frames.float().cpu()), args.output_path, denorm=True)
     print(f"wrote {args.output_path}: {frames.shape[0]} frames of {tuple(frames.shape[1:])}")
     return frames
