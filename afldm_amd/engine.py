@@ -13,14 +13,17 @@ increments itself — so a replay needs no host value and no synchronisation:
     eps    <- UNet(x_nhwc, t)                     (~250 HIP kernels at batch 64, all from libafldm_hip.so)
     lat    <- DDIM(lat, eps, coef[step])          (afldm_ddim_step, in place)
 
-A scheduler with `update_kind = "dpm"` (DPMSolverMultistepScheduler) has [steps, 8] rows instead and the last line
-is afldm_dpm_step, which also keeps the solver's two previous converted outputs in an fp32 history buffer.
+The engine replays a Schedule (schedulers/schedule.py): the timesteps, the coefficient rows and the `kind` of update that
+reads them.  A scheduler passed instead is asked for its `.schedule(num_inference_steps)`.  Kind "ddim" (DDIM, the unclipped
+I2SB ODE, DDIM inversion) is the last line above.  Kind "dpm" (DPMSolverMultistepScheduler) has [steps, 8] rows and the last
+line is afldm_dpm_step, which also keeps the solver's two previous converted outputs in an fp32 history buffer.  Kind "sde"
+(DDIM with eta != 0, the stochastic / clipped I2SB bridge) has [steps, 8] rows (p, q, lo, hi, a, b, d, c) and the last line
+is afldm_sde_step, which also reads that step's row of an fp32 noise buffer [steps, B, C, H, W].  The noise is drawn per run by
+the caller's generator - run(latents, draw=...), the same randn calls the eager loop makes, in the same order - never inside a
+capture.  Draws on the CPU (a CPU generator) go through pinned staging: the next replay group's noise is drawn while the GPU
+runs the current group.
 
-A schedule with `update_kind = "sde"` (schedulers/sde.py: DDIM with eta != 0, the stochastic / clipped I2SB bridge) has
-[steps, 8] rows (p, q, lo, hi, a, b, d, c) and the last line is afldm_sde_step, which also reads that step's row of an fp32
-noise buffer [steps, B, C, H, W].  The noise is drawn per run by the caller's generator - run(latents, draw=...), the same
-randn calls the eager loop makes, in the same order - never inside a capture.  Draws on the CPU (a CPU generator) go through
-pinned staging: the next replay group's noise is drawn while the GPU runs the current group.
+cached_engine keeps the engines (and the harness's samplers) a pipeline has built: one resident entry per slot.
 """
 import contextlib
 import gc
@@ -29,6 +32,7 @@ import os
 import torch
 
 from . import ops
+from .schedulers.schedule import Schedule
 
 
 @contextlib.contextmanager
@@ -62,26 +66,39 @@ def model_state_key(model):
     return hash((mods, params, bufs))
 
 
+def cached_engine(owner, slot, schedule, batch, use_graph, unet, build=None, extra=()):
+    """The engine `owner` (a pipeline) keeps in its attribute `slot` for this schedule, batch, use_graph and the UNet's dtype and
+    device, built on a miss: DenoiseEngine(unet, schedule, batch, steps, use_graph), or build() for a slot that holds something
+    else (the harness's samplers; `extra`: what else identifies it).  A slot is a one-entry dict {key: engine}: a miss replaces
+    it, and with it the captured graphs and static buffers of the previous one.  Every field a graph bakes in must be in the key:
+    a missed one replays a stale graph."""
+    key = (batch, len(schedule.timesteps), use_graph, unet.dtype, str(unet.device)) + schedule.key + tuple(extra)
+    if key not in owner.__dict__.get(slot, ()):
+        made = build() if build is not None else DenoiseEngine(unet, schedule, batch, len(schedule.timesteps), use_graph)
+        owner.__dict__[slot] = {key: made}
+    return owner.__dict__[slot][key]
+
+
 class DenoiseEngine:
     def __init__(self, unet, scheduler, batch_size, num_inference_steps=50, use_graph=True, steps_per_graph=5, branches=1):
         if unet.device.type != "cuda":
             raise RuntimeError("DenoiseEngine needs the UNet on an MI355X ('cuda') device; there is no CPU path")
         self.unet, self.scheduler = unet, scheduler
+        self.schedule = scheduler if isinstance(scheduler, Schedule) else scheduler.schedule(num_inference_steps)
+        if len(self.schedule.timesteps) != num_inference_steps:
+            raise ValueError(f"DenoiseEngine: a schedule of {len(self.schedule.timesteps)} steps for {num_inference_steps}")
+        if self.schedule.kind not in self.UPDATES:
+            raise NotImplementedError(f"DenoiseEngine: update_kind {self.schedule.kind!r}")
         self.B, self.n = batch_size, num_inference_steps
         dev = unet.device
         c, s = unet.config.in_channels, unet.config.sample_size
-        scheduler.set_timesteps(num_inference_steps)
-        self.timesteps = list(scheduler._timesteps_host)
+        self.timesteps = list(self.schedule.timesteps)
         self.t_table = torch.tensor(self.timesteps, dtype=torch.float32).to(dev)
-        self.coef = scheduler.coefficient_table(dev).reshape(-1).contiguous()
+        self.coef = self.schedule.table(dev).reshape(-1).contiguous()
         self.step_idx = torch.full((1,), -1, dtype=torch.int32, device=dev)
         self.t_cur = torch.zeros(1, dtype=torch.float32, device=dev)
         self.lat = torch.zeros(batch_size, c, s, s, dtype=torch.float32, device=dev)
         self.x_nhwc = torch.empty(batch_size, s, s, c, dtype=unet.dtype, device=dev)
-        # the update: DDIM's linear form (also the I2SB ODE and inversion rows) unless the scheduler says otherwise
-        self.update_kind = getattr(scheduler, "update_kind", "ddim")
-        if self.update_kind not in ("ddim", "dpm", "sde"):
-            raise NotImplementedError(f"DenoiseEngine: update_kind {self.update_kind!r}")
         self.graph = None
         self.graph_multi = None
         # a replay boundary costs ~9 us of idle GPU (host launch + graph start): besides the one-step graph a
@@ -104,18 +121,30 @@ class DenoiseEngine:
         # counters of in-kernel reductions / cluster hand-overs: private to this engine (one per branch), so that its
         # captured graphs can replay next to another engine's on a different stream
         self._sync = [ops.new_sync_buffer(dev) for _ in range(self.branches)]
-        # DPM-Solver history (the two previous converted outputs), one contiguous [2, B / branches, C, H, W] per branch
-        self.hist = None
-        if self.update_kind == "dpm":
-            self.hist = torch.zeros(self.branches, 2, batch_size // self.branches, c, s, s, dtype=torch.float32, device=dev)
-        # stochastic update: one noise row per step, filled per run; the steps that draw none keep zeros (c = 0 there, and
-        # 0 * NaN of stale memory is not 0).  Pinned staging for CPU draws, one buffer per replay group in flight.
-        self.noise = None
-        if self.update_kind == "sde":
-            self.draws = tuple(scheduler.draws)
-            assert len(self.draws) == num_inference_steps
-            self.noise = torch.zeros(num_inference_steps, batch_size, c, s, s, dtype=torch.float32, device=dev)
-            self._stage = []
+        self.hist = self.noise = None
+        self._update, state = self.UPDATES[self.schedule.kind]
+        self._state = state(self)
+
+    def _no_state(self):
+        return [()] * self.branches
+
+    def _dpm_state(self):
+        """DPM-Solver history (the two previous converted outputs), one contiguous [2, B / branches, C, H, W] per branch."""
+        self.hist = torch.zeros((self.branches, 2, self.B // self.branches) + tuple(self.lat.shape[1:]), dtype=torch.float32,
+                                device=self.lat.device)
+        return [(self.hist[b],) for b in range(self.branches)]
+
+    def _sde_state(self):
+        """One noise row per step, filled per run; the steps that draw none keep zeros (c = 0 there, and 0 * NaN of stale memory
+        is not 0).  Pinned staging for CPU draws, one buffer per replay group in flight."""
+        self.noise = torch.zeros((self.n,) + tuple(self.lat.shape), dtype=torch.float32, device=self.lat.device)
+        self._stage = []
+        per = self.B // self.branches
+        return [(self.noise[:, b * per:(b + 1) * per],) for b in range(self.branches)]
+
+    # Schedule.kind -> the update of ops that ends a step, and what allocates the buffers it keeps between steps (one argument
+    # tuple per branch, passed between eps and the coefficient table)
+    UPDATES = {"ddim": (ops.ddim_step, _no_state), "dpm": (ops.dpm_step, _dpm_state), "sde": (ops.sde_step, _sde_state)}
 
     # one denoise step, entirely stream-ordered
     def _step(self):
@@ -143,43 +172,43 @@ class DenoiseEngine:
         with ops.sync_scope(self._sync[branch]):
             ops.to_nhwc(lat, self.unet.dtype, out=x_nhwc)
             eps = self.unet.forward_nhwc(x_nhwc, self.t_cur, temb_slices=self.temb_slices)
-            if self.noise is not None:
-                per = self.B // self.branches
-                ops.sde_step(lat, eps, self.noise[:, branch * per:(branch + 1) * per], self.coef, self.step_idx, advance=False,
-                             out=lat)
-            elif self.hist is None:
-                ops.ddim_step(lat, eps, self.coef, self.step_idx, advance=False, out=lat)
-            else:
-                ops.dpm_step(lat, eps, self.hist[branch], self.coef, self.step_idx, advance=False, out=lat)
+            self._update(lat, eps, *self._state[branch], self.coef, self.step_idx, advance=False, out=lat)
 
-    def _capture(self):
+    def _capture(self, counts, before_step=None):
+        """One captured graph per entry of `counts`, each holding that many steps from the start of the schedule, after ONE
+        warm-up step on a side stream.  before_step(i): called on the host before step i is launched or recorded (the harness
+        tells its attention processors the timestep).  The engine's state is as before on return."""
         keep = self.lat.clone()
         keep_hist = None if self.hist is None else self.hist.clone()     # the warm-up step shifts the history too
+
+        def rewind():
+            self.step_idx.fill_(-1)
+            self.lat.copy_(keep)
+            if keep_hist is not None:
+                self.hist.copy_(keep_hist)
+
+        def steps(k):
+            for i in range(k):
+                if before_step is not None:
+                    before_step(i)
+                self._step()
+
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                 # warm-up: packs weights, fills caches, sizes workspaces
-            self._step()
+            steps(1)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.check_errors()                           # (the warm-up step ran every hand-over once: free to look, we just synchronised)
-        self.step_idx.fill_(-1)
-        self.lat.copy_(keep)
-        g = torch.cuda.CUDAGraph()
-        with capture_guard(), torch.cuda.graph(g):
-            self._step()
-        self.graph = g
-        if self.steps_per_graph > 1:
-            self.step_idx.fill_(-1)
-            self.lat.copy_(keep)
-            gm = torch.cuda.CUDAGraph()
-            with capture_guard(), torch.cuda.graph(gm):
-                for _ in range(self.steps_per_graph):
-                    self._step()
-            self.graph_multi = gm
-        self.step_idx.fill_(-1)
-        self.lat.copy_(keep)
-        if keep_hist is not None:
-            self.hist.copy_(keep_hist)
+        graphs = []
+        for k in counts:
+            rewind()
+            g = torch.cuda.CUDAGraph()
+            with capture_guard(), torch.cuda.graph(g):
+                steps(k)
+            graphs.append(g)
+        rewind()
+        return graphs
 
     def check_errors(self):
         """Read (and clear) the error words of this engine's sync buffers.  The attention block's in-launch hand-over
@@ -211,7 +240,9 @@ class DenoiseEngine:
         if self.unet.dtype != self.x_nhwc.dtype or self.unet.device != self.x_nhwc.device:
             # .to(dtype / device): every dtype-typed static buffer of the engine is stale, not just the table
             invalidate_stale_packed(self.unet)
-            self.__init__(self.unet, self.scheduler, self.B, self.n, self.use_graph, self.steps_per_graph, self.branches)
+            scheduler = self.scheduler
+            self.__init__(self.unet, self.schedule, self.B, self.n, self.use_graph, self.steps_per_graph, self.branches)
+            self.scheduler = scheduler
             return True
         self.graph = self.graph_multi = None
         # in-place parameter edits do not pass through the modules' own hooks; another engine of this model may have repacked
@@ -224,14 +255,17 @@ class DenoiseEngine:
     def reset(self, latents):
         """latents: [B, C, H, W] (any device / float dtype); scaled by init_noise_sigma like the reference."""
         self.refresh_if_stale()
-        self.lat.copy_(latents.to(device=self.lat.device, dtype=torch.float32) * self.scheduler.init_noise_sigma)
+        self.lat.copy_(latents.to(device=self.lat.device, dtype=torch.float32) * self.schedule.init_noise_sigma)
         self.step_idx.fill_(-1)
         if self.hist is not None:
             self.hist.zero_()        # the first rows weigh it by 0, but stale memory may hold NaN
 
     def step(self, k=1):
         if self.use_graph and self.graph is None:
-            self._capture()
+            if self.steps_per_graph > 1:
+                self.graph, self.graph_multi = self._capture([1, self.steps_per_graph])
+            else:
+                self.graph, = self._capture([1])
         if not self.use_graph:
             for _ in range(k):
                 self._step()
@@ -246,7 +280,7 @@ class DenoiseEngine:
         """Noise rows k0 .. k1 - 1: one draw() per step that draws, in step order.  A CPU draw is copied into pinned staging and
         on to the device with non_blocking (stream-ordered before the replays that read it); the staging buffer is reused only
         after the event behind its previous copy has passed.  A device draw is copied on the stream."""
-        ks = [k for k in range(k0, k1) if self.draws[k]]
+        ks = [k for k in range(k0, k1) if self.schedule.draws[k]]
         if not ks:
             return
         stage = None
@@ -275,7 +309,7 @@ class DenoiseEngine:
     def run(self, latents, draw=None):
         """latents -> the sampled latents (fp32).  An "sde" schedule needs `draw`: a callable returning the next noise tensor
         [B, C, H, W] (on the CPU or on the engine's device, any float dtype), called once per drawing step in step order -
-        for a seeded run, the scheduler's own randn_tensor call with the caller's generator (SdeSchedule.draw_noise)."""
+        for a seeded run, the scheduler's own randn_tensor call with the caller's generator (Schedule.drawer)."""
         self.reset(latents)
         if self.noise is None:
             self.step(self.n)

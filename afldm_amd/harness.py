@@ -17,9 +17,9 @@ import time
 import torch
 
 from . import parallel
-from .engine import DenoiseEngine, capture_guard, model_state_key
+from .engine import DenoiseEngine, cached_engine, model_state_key
 from .io_utils import image_to_tensor, save_gif_from_tensors
-from .pipelines.cross_frame_attn import (AttnState, CrossFrameAttnProcessor, get_unet_attn_processors,
+from .pipelines.cross_frame_attn import (AttnState, CrossFrameAttnProcessor, eager_pass, get_unet_attn_processors,
                                          set_unet_attn_processor)
 from .shift_utils.metrics import mask_mse
 from .shift_utils.shifters import ImageShifter
@@ -34,42 +34,15 @@ class _UnrolledEngine(DenoiseEngine):
     def __init__(self, unet, scheduler, batch_size, num_inference_steps, attn_state):
         super().__init__(unet, scheduler, batch_size, num_inference_steps, use_graph=True, steps_per_graph=1, branches=1)
         self.attn_state = attn_state
-        self.graph_full = None
-        self._host_step = 0
-
-    def _step(self):
-        self.attn_state.set_timestep(self.timesteps[self._host_step])
-        super()._step()
-
-    def _capture(self):
-        keep = self.lat.clone()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                 # warm-up: packs weights, sizes workspaces (what it stores is overwritten below)
-            self._host_step = 0
-            self._step()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.check_errors()
-        self.step_idx.fill_(-1)
-        self.lat.copy_(keep)
-        g = torch.cuda.CUDAGraph()
-        with capture_guard(), torch.cuda.graph(g):
-            for i in range(self.n):
-                self._host_step = i
-                self._step()
-        self.graph_full = g
-        self.step_idx.fill_(-1)
-        self.lat.copy_(keep)
 
     def refresh_if_stale(self):
         return False            # CrossFrameSampler.run compares the model's fingerprint itself and drops every engine together
 
     def step(self, k=None):
         assert k in (None, self.n), "the unrolled graph runs the whole schedule"
-        if self.graph_full is None:
-            self._capture()
-        self.graph_full.replay()
+        if self.graph is None:        # (what the warm-up step stores is overwritten by the first replay)
+            self.graph, = self._capture([self.n], lambda i: self.attn_state.set_timestep(self.timesteps[i]))
+        self.graph.replay()
 
 
 class CrossFrameSampler:
@@ -86,6 +59,7 @@ class CrossFrameSampler:
     replay.  Its engines are keyed ('interp', load, batch)."""
 
     def __init__(self, unet, scheduler, steps, interp=False):
+        """scheduler: a Schedule of `steps` evaluations, or a scheduler with .schedule(steps) (as DenoiseEngine takes)."""
         self.unet, self.scheduler, self.steps, self.interp = unet, scheduler, steps, bool(interp)
         self.attn_state = AttnState()
         self.names = list(get_unet_attn_processors(unet))
@@ -93,8 +67,6 @@ class CrossFrameSampler:
         self.engines = {}
         self.alphas = {}                              # interp: LOAD batch -> the blend-weight buffer its graph reads
         self.model_key, self.stored = None, False
-        self.key = (unet.dtype, str(unet.device), steps, tuple(sorted((k, repr(v)) for k, v in dict(scheduler.config).items())),
-                    self.interp)
 
     def install(self):
         previous = get_unet_attn_processors(self.unet)
@@ -140,26 +112,20 @@ class CrossFrameSampler:
         if key not in self.engines:
             if not load:                          # a new STORE capture moves the stored tensors: the LOAD graphs read the old ones
                 self.engines.clear()
-            self.engines[key] = _UnrolledEngine(self.unet, self.scheduler, latents.shape[0], self.steps, self.attn_state)
+            self.engines[key] = _UnrolledEngine(self.unet, self.scheduler, B, self.steps, self.attn_state)
         out = self.engines[key].run(latents)
         self.stored = self.stored or not load
         return out
 
 
-def _sampler(pipeline, steps, sched=None, interp=False):
-    """The pipeline's cached CrossFrameSampler for `steps` evaluations of `sched` (default: a fresh DDIMScheduler of the pipeline's
-    configuration; the SR harness passes its I2SB ODE schedule).  interp: the interpolation sampler, cached apart."""
-    from .schedulers.ddim import DDIMScheduler
+def _sampler(pipeline, schedule, interp=False):
+    """The pipeline's cached CrossFrameSampler over `schedule` (a "ddim"-kind Schedule: DDIM, or the SR harness's I2SB ODE
+    bridge).  interp: the interpolation sampler, cached apart.  A sampler is bound to the UNet object and to the attention
+    modules it found there, so both are part of its key."""
     unet = pipeline.unet
-    if sched is None:
-        sched = DDIMScheduler.from_config(pipeline.scheduler.config)
-    attr = "_xframe_interp_sampler" if interp else "_xframe_sampler"
-    smp = getattr(pipeline, attr, None)
-    probe = (unet.dtype, str(unet.device), steps, tuple(sorted((k, repr(v)) for k, v in dict(sched.config).items())), bool(interp))
-    if smp is None or smp.unet is not unet or smp.key != probe or smp.names != list(get_unet_attn_processors(unet)):
-        smp = CrossFrameSampler(unet, sched, steps, interp=interp)
-        setattr(pipeline, attr, smp)
-    return smp
+    return cached_engine(pipeline, "_xframe_interp_sampler" if interp else "_xframe_sampler", schedule, None, True, unet,
+                         build=lambda: CrossFrameSampler(unet, schedule, len(schedule.timesteps), interp=interp),
+                         extra=(unet, tuple(get_unet_attn_processors(unet))))
 
 
 def vae_encode(vae, x):
@@ -168,6 +134,39 @@ def vae_encode(vae, x):
 
 def vae_decode(vae, x):
     return vae.decode(x / vae.config.scaling_factor, return_dict=False)[0]
+
+
+def _cross_frame_passes(pipeline, schedule, eager_steps):
+    """Installs the cross-frame processors and returns (denoise, the processors to restore afterwards); denoise(latents, load)
+    is one STORE (load=False) or LOAD pass.  schedule: the Schedule the passes replay as HIP graphs (the pipeline's cached
+    CrossFrameSampler); None: the eager loop over the non-cached processors, where eager_steps() -> (timesteps, step_fn) sets
+    the pipeline's scheduler up for one pass (step_fn(eps, t, latents) -> latents)."""
+    unet = pipeline.unet
+    if schedule is not None:
+        sampler = _sampler(pipeline, schedule)
+        return (lambda latents, load: sampler.run(latents, load).to(latents.dtype)), sampler.install()
+    attn_state = AttnState()
+    previous = get_unet_attn_processors(unet)
+    set_unet_attn_processor(unet, {k: CrossFrameAttnProcessor(attn_state) for k in previous})
+
+    def denoise(latents, load):
+        if load:
+            attn_state.to_load()
+        else:
+            attn_state.reset()
+        timesteps, step_fn = eager_steps()
+        return eager_pass(lambda x, t: unet(x, t, return_dict=False)[0], pipeline.scheduler, attn_state, timesteps,
+                          latents.to(pipeline.device), step_fn)
+    return denoise, previous
+
+
+def _load_passes(denoise, shifted, mine, batch_offsets):
+    """The LOAD passes of this rank's offsets `mine` over shifted[i] = (latent, mask): ONE batch (samples are independent; the
+    cross-frame K/V of the stored pass is shared by the whole batch) or one B = 1 pass per offset.  -> {i: denoised [1, ...]}"""
+    if batch_offsets and len(mine) > 1:
+        den_all = denoise(torch.cat([shifted[i][0] for i in mine], 0), load=True)
+        return {i: den_all[k:k + 1] for k, i in enumerate(mine)}
+    return {i: denoise(shifted[i][0], load=True) for i in mine}
 
 
 class _Clock:
@@ -215,6 +214,7 @@ def shift_ldm(pipeline, num_inference_steps=50, num_shift_steps=16, output_path=
       sample_size; the reference resizes to (sample_size, sample_size) = 32 x 32 BEFORE the VAE
       (shift_ldm_ffhq.py:110-113), i.e. inverts a 4 x 4 latent.
     * the initial noise is drawn on the CPU (device independent) instead of on the GPU (:118-122)."""
+    from .schedulers.ddim import DDIMScheduler
     from .schedulers.dpmsolver import DPMSolverMultistepScheduler
     if isinstance(pipeline.scheduler, DPMSolverMultistepScheduler):
         raise NotImplementedError("shift_ldm samples with DDIM (cross-frame STORE / LOAD passes): a pipeline whose scheduler is "
@@ -227,53 +227,30 @@ def shift_ldm(pipeline, num_inference_steps=50, num_shift_steps=16, output_path=
     image_shifter = ImageShifter()
     clock = _Clock(timings)
 
-    init_latent = None
-    if use_graph:
-        if input_path is not None:
-            # The reference inverts with its processors installed in their initial STORE state (shift_ldm_ffhq.py:110-116); what
-            # that stores is overwritten by the STORE pass, so the inversion runs here, on the plain processors and the captured-graph
-            # loop (MyLDMPipeline.ddim_inversion, latent carried in fp32): same procedure, no side effects to undo
-            size = unet.config.sample_size * (1 if reference_exact else ratio)
-            tensor = vae_encode(vae, image_to_tensor(input_path, (size, size)).to(device))
-            clock.lap("vae_s")
-            scheduler.set_timesteps(num_inference_steps, device=device)
-            init_latent = pipeline.ddim_inversion(tensor.float(), bar=False)
-            clock.lap("unet_s")
-        sampler = _sampler(pipeline, num_inference_steps)
-        attn_state = sampler.attn_state
-        previous = sampler.install()
+    def invert():
+        size = unet.config.sample_size * (1 if reference_exact else ratio)
+        tensor = vae_encode(vae, image_to_tensor(input_path, (size, size)).to(device))
+        clock.lap("vae_s")
+        scheduler.set_timesteps(num_inference_steps, device=device)
+        latent = pipeline.ddim_inversion(tensor.float() if use_graph else tensor, bar=False)
+        clock.lap("unet_s")
+        return latent
 
-        def denoise(latents, load):
-            return sampler.run(latents, load).to(latents.dtype)
-    else:
-        attn_state = AttnState()
-        previous = get_unet_attn_processors(unet)
-        set_unet_attn_processor(unet, {k: CrossFrameAttnProcessor(attn_state) for k in previous})
+    def eager_steps():
+        scheduler.set_timesteps(num_inference_steps, device=device)
+        return scheduler.timesteps, lambda eps, t, x: scheduler.step(eps, t, x, eta=0, return_dict=False)[0]
 
-        def denoise(latents, load):
-            if load:
-                attn_state.to_load()
-            else:
-                attn_state.reset()
-            latents = latents.to(device)
-            scheduler.set_timesteps(num_inference_steps, device=device)
-            for t in scheduler.timesteps:
-                attn_state.set_timestep(t)
-                eps = unet(scheduler.scale_model_input(latents, t), t, return_dict=False)[0]
-                latents = scheduler.step(eps, t, latents, eta=0, return_dict=False)[0]
-            return latents
-
+    # The reference inverts with its processors installed in their initial STORE state (shift_ldm_ffhq.py:110-116), as the eager
+    # path does below; what that stores is overwritten by the STORE pass, so the graph path inverts first, on the plain
+    # processors and the captured-graph loop (MyLDMPipeline.ddim_inversion, latent carried in fp32): same procedure, no side
+    # effects to undo
+    init_latent = invert() if use_graph and input_path is not None else None
+    schedule = DDIMScheduler.from_config(scheduler.config).schedule(num_inference_steps) if use_graph else None
+    denoise, previous = _cross_frame_passes(pipeline, schedule, eager_steps)
     try:
-        if init_latent is not None:
-            pass
-        elif input_path is not None:
-            size = unet.config.sample_size * (1 if reference_exact else ratio)
-            tensor = vae_encode(vae, image_to_tensor(input_path, (size, size)).to(device))
-            clock.lap("vae_s")
-            scheduler.set_timesteps(num_inference_steps, device=device)
-            init_latent = pipeline.ddim_inversion(tensor, bar=False)
-            clock.lap("unet_s")
-        else:
+        if init_latent is None and input_path is not None:
+            init_latent = invert()
+        elif init_latent is None:
             # CPU-side draw (seedable, device independent) — the reference draws on the GPU
             # (shift_ldm_ffhq.py:118-122), which is not reproducible across devices
             shape = (1, unet.config.in_channels, unet.config.sample_size, unet.config.sample_size)
@@ -292,11 +269,7 @@ def shift_ldm(pipeline, num_inference_steps=50, num_shift_steps=16, output_path=
         frames, errors = {}, {}
         shifted = {i: latent_shifter.shift(init_latent, 0, float(offsets[i])) for i in mine}
         clock.lap("shift_s")
-        if batch_offsets and len(mine) > 1:
-            den_all = denoise(torch.cat([shifted[i][0] for i in mine], 0), load=True)
-            dens = {i: den_all[k:k + 1] for k, i in enumerate(mine)}
-        else:
-            dens = {i: denoise(shifted[i][0], load=True) for i in mine}
+        dens = _load_passes(denoise, shifted, mine, batch_offsets)
         clock.lap("unet_s")
         for i in mine:
             tj = float(offsets[i])
@@ -349,35 +322,13 @@ def shift_ldm_sr(pipeline, num_inference_steps=50, num_shift_steps=16, output_pa
     latent_shifter = ImageShifter("ideal_crop", ratio)
     image_shifter = ImageShifter()
 
+    def eager_steps():
+        scheduler.set_timesteps(num_inference_steps, device=device)
+        return (scheduler.timesteps[:num_inference_steps - 1],
+                lambda eps, t, x: scheduler.step(eps, t, x, is_ode=True, generator=None).prev_sample)
+
     ode = scheduler.ode_schedule(num_inference_steps) if (use_graph and num_inference_steps >= 2) else None
-    if ode is not None:
-        sampler = _sampler(pipeline, ode.evaluations, ode)
-        attn_state = sampler.attn_state
-        previous = sampler.install()
-
-        def denoise(latents, load):
-            return sampler.run(latents, load).to(latents.dtype)
-    else:
-        attn_state = AttnState()
-        previous = get_unet_attn_processors(unet)
-        set_unet_attn_processor(unet, {k: CrossFrameAttnProcessor(attn_state) for k in previous})
-
-        def denoise(latents, load):
-            if load:
-                attn_state.to_load()
-            else:
-                attn_state.reset()
-            latents = latents.to(device)
-            scheduler.set_timesteps(num_inference_steps, device=device)
-            ts = scheduler.timesteps
-            for i, t in enumerate(ts):
-                if i == num_inference_steps - 1:
-                    break
-                attn_state.set_timestep(t)
-                eps = unet(scheduler.scale_model_input(latents, t), t, return_dict=False)[0]
-                latents = scheduler.step(eps, t, latents, is_ode=True, generator=None).prev_sample
-            return latents
-
+    denoise, previous = _cross_frame_passes(pipeline, ode, eager_steps)
     try:
         if image is None:
             image = image_to_tensor(input_path, (size, size))
@@ -389,11 +340,7 @@ def shift_ldm_sr(pipeline, num_inference_steps=50, num_shift_steps=16, output_pa
         frames, errors = {}, {}
         mine = parallel.interleaved(num_shift_steps, rank, world)
         shifts = {i: latent_shifter.shift(init_latent, 0, float(offsets[i])) for i in mine}
-        if batch_offsets and len(mine) > 1:      # one batched LOAD pass for this rank's offsets (see shift_ldm)
-            den_all = denoise(torch.cat([shifts[i][0] for i in mine], 0), load=True)
-            dens = {i: den_all[k:k + 1] for k, i in enumerate(mine)}
-        else:
-            dens = {i: denoise(shifts[i][0], load=True) for i in mine}
+        dens = _load_passes(denoise, shifts, mine, batch_offsets)
         for i in mine:
             tj = float(offsets[i])
             (shifted, mask), den = shifts[i], dens[i]

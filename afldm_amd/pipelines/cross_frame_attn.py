@@ -186,3 +186,12 @@ def set_unet_attn_processor(unet, processor):
 
     for name, module in unet.named_children():
         walk(name, module)
+
+
+def eager_pass(model, scheduler, attn_state, timesteps, latents, step_fn):
+    """`timesteps` eagerly, as the reference's loops run a STORE or LOAD pass: attn_state.set_timestep(t), eps = model(x, t)
+    - the UNet, or whatever evaluates it on the (scaled) latents - then latents = step_fn(eps, t, latents)."""
+    for t in timesteps:
+        attn_state.set_timestep(t)
+        latents = step_fn(model(scheduler.scale_model_input(latents, t), t), t, latents)
+    return latents

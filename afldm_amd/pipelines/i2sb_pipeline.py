@@ -32,32 +32,6 @@ class I2SBLDMPipeline(MyLDMPipeline):
                                latent_dtype=latent_dtype, use_graph=use_graph)
         return self._deliver(latents, output_type, return_dict)
 
-    def _ode_engine(self, batch, steps):
-        """DenoiseEngine over the deterministic bridge (scheduler.ode_schedule): the same captured-graph loop the DDIM sampler
-        uses - the unclipped ODE update is the DDIM kernel's linear form with another coefficient row per evaluation."""
-        from ..engine import DenoiseEngine
-        ode = self.scheduler.ode_schedule(steps)
-        cfg_key = tuple(sorted((k, repr(v)) for k, v in dict(ode.config).items()))
-        key = (batch, steps, self.unet.dtype, str(self.unet.device), cfg_key)
-        cache = self.__dict__.setdefault("_ode_engines", {})
-        if key not in cache:
-            cache.clear()
-            cache[key] = DenoiseEngine(self.unet, ode, batch, ode.evaluations, use_graph=True)
-        return cache[key]
-
-    def _sde_engine(self, batch, steps, is_ode):
-        """DenoiseEngine over the stochastic and / or clipped bridge (scheduler.bridge_schedule, afldm_sde_step), cached apart from
-        the unclipped ODE's engines."""
-        from ..engine import DenoiseEngine
-        sde = self.scheduler.bridge_schedule(steps, is_ode)
-        cfg_key = tuple(sorted((k, repr(v)) for k, v in dict(sde.config).items()))
-        key = (batch, steps, self.unet.dtype, str(self.unet.device), cfg_key)
-        cache = self.__dict__.setdefault("_sde_engines", {})
-        if key not in cache:
-            cache.clear()
-            cache[key] = DenoiseEngine(self.unet, sde, batch, len(sde.rows), use_graph=True)
-        return cache[key]
-
     def _bridge(self, latents, steps, is_ode, generator, latent_dtype=torch.float32, use_graph=True):
         """steps - 1 UNet evaluations from the encoded degraded image towards the clean latent: the reference loop
         leaves before its last timestep (i2sb_pipeline.py:48-50).  With the latent carried in fp32 every form replays captured
@@ -67,10 +41,14 @@ class I2SBLDMPipeline(MyLDMPipeline):
         latent_dtype=None run the eager loop below."""
         sched, unet = self.scheduler, self.unet
         if use_graph and latent_dtype == torch.float32 and latents.is_cuda and steps >= 2:
-            if is_ode and not sched.config.clip_sample:
-                return self._ode_engine(latents.shape[0], steps).run(latents).to(latents.dtype)
-            eng = self._sde_engine(latents.shape[0], steps, is_ode)
-            draw = eng.scheduler.drawer(generator, tuple(latents.shape), latents.device, torch.float32)
+            from ..engine import cached_engine
+            ode = sched.ode_schedule(steps) if is_ode else None
+            if ode is not None:
+                # the same captured-graph loop the DDIM sampler uses: the unclipped ODE update is the DDIM kernel's linear form
+                return cached_engine(self, "_ode_engines", ode, latents.shape[0], True, unet).run(latents).to(latents.dtype)
+            sde = sched.bridge_schedule(steps, is_ode)          # (engines cached apart from the unclipped ODE's)
+            eng = cached_engine(self, "_sde_engines", sde, latents.shape[0], True, unet)
+            draw = sde.drawer(generator, tuple(latents.shape), latents.device, torch.float32)
             return eng.run(latents, draw=draw).to(latents.dtype)
         sched.set_timesteps(steps)
         # The latent is carried in fp32 BETWEEN evaluations whatever the UNet's dtype (as DenoiseEngine does for DDIM): a

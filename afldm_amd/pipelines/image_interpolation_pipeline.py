@@ -25,7 +25,8 @@ import torch
 import torch.nn.functional as F
 
 from ..schedulers.ddim import DDIMScheduler
-from .cross_frame_attn import AttnState, CrossFrameAttnProcessor, get_unet_attn_processors, set_unet_attn_processor
+from .cross_frame_attn import (AttnState, CrossFrameAttnProcessor, eager_pass, get_unet_attn_processors,
+                               set_unet_attn_processor)
 from .ldm_pipeline import MyLDMPipeline
 
 
@@ -245,7 +246,7 @@ class LDMInterpolationPipeline(MyLDMPipeline):
         slot s), then the LOAD pass of all frames `latents` [n, C, H, W] with blend weights `weights` (n floats).  Returns the
         fp32 latents; the caller's attention processors are restored."""
         from ..harness import _sampler
-        smp = _sampler(self, steps, interp=True)
+        smp = _sampler(self, DDIMScheduler.from_config(self.scheduler.config).schedule(steps), interp=True)
         previous = smp.install()
         try:
             smp.run(ends, load=False)
@@ -279,27 +280,28 @@ class LDMInterpolationPipeline(MyLDMPipeline):
         previous = get_unet_attn_processors(unet)
         set_unet_attn_processor(unet, {k: CrossFrameAttnProcessor(state, enable_interp=enable_interp) for k in previous})
 
-        def store(z, sid):
-            state.set_store_id(sid)
+        def unet1(x, t):
+            return unet(x, t, return_dict=False)[0]
+
+        def frame_by_frame(x, t):
+            eps = []
+            for f in range(x.shape[0]):
+                state.set_alpha(weights[f])
+                eps.append(unet1(x[f:f + 1], t))
+            return torch.cat(eps)
+
+        def one_pass(model, z):
             sched.set_timesteps(steps, device=dev)
-            for t in sched._timesteps_host:
-                state.set_timestep(t)
-                eps = unet(sched.scale_model_input(z, t), t, return_dict=False)[0]
-                z = sched.step(eps, t, z, eta=0.0, return_dict=False)[0]
+            return eager_pass(model, sched, state, sched._timesteps_host, z,
+                              lambda eps, t, x: sched.step(eps, t, x, eta=0.0, return_dict=False)[0])
 
         try:
             state.reset()
-            store(latents[0:1], 0)
-            store(latents[-1:], 1)
+            for sid, z in ((0, latents[0:1]), (1, latents[-1:])):
+                state.set_store_id(sid)
+                one_pass(unet1, z)
             state.to_load()
-            sched.set_timesteps(steps, device=dev)
-            for t in sched._timesteps_host:
-                state.set_timestep(t)
-                eps = []
-                for f in range(latents.shape[0]):
-                    state.set_alpha(weights[f])
-                    eps.append(unet(sched.scale_model_input(latents[f:f + 1], t), t, return_dict=False)[0])
-                latents = sched.step(torch.cat(eps), t, latents, eta=0.0, return_dict=False)[0]
+            latents = one_pass(frame_by_frame, latents)
         finally:
             set_unet_attn_processor(unet, dict(previous))
         return latents

@@ -9,10 +9,11 @@ import os
 
 import torch
 
-from ..engine import DenoiseEngine
+from ..engine import cached_engine
 from ..models.unet_2d import UNet2DModel
 from ..schedulers.ddim import DDIMScheduler
 from ..schedulers.dpmsolver import DPMSolverMultistepScheduler
+from ..schedulers.schedule import Schedule
 from ..utils import randn_tensor
 from .pipeline_utils import DiffusionPipeline, ImagePipelineOutput
 
@@ -21,7 +22,6 @@ class MyLDMPipeline(DiffusionPipeline):
     def __init__(self, vae, unet: UNet2DModel, scheduler: DDIMScheduler):
         super().__init__()
         self.register_modules(vae=vae, unet=unet, scheduler=scheduler)
-        self._engines = {}
 
     @classmethod
     def from_pretrained(cls, path, **kw):
@@ -37,18 +37,6 @@ class MyLDMPipeline(DiffusionPipeline):
             from ..models.vae import AutoencoderKL
             vae = AutoencoderKL.from_pretrained(path, subfolder="vae")
         return cls(vae, unet, scheduler)
-
-    def _engine(self, batch, steps, use_graph, schedule=None):
-        # keyed on the scheduler's CONFIG (the coefficient / timestep tables are a function of it), not on the
-        # scheduler object: __call__ re-creates the scheduler every time (like the reference, ldm_pipeline.py:80),
-        # and an identity key made every call rebuild the engine and re-capture its HIP graphs.  `schedule`: a view of the
-        # scheduler to replay instead (the stochastic DDIM rows, whose config carries eta)
-        sched = self.scheduler if schedule is None else schedule
-        cfg_key = tuple(sorted((k, repr(v)) for k, v in dict(sched.config).items()))
-        key = (batch, steps, use_graph, self.unet.dtype, str(self.unet.device), type(sched), cfg_key)
-        if key not in self._engines:
-            self._engines = {key: DenoiseEngine(self.unet, sched, batch, steps, use_graph)}
-        return self._engines[key]
 
     @torch.no_grad()
     def __call__(self, batch_size=1, generator=None, eta=0.0, num_inference_steps=50, latents=None,
@@ -67,8 +55,8 @@ class MyLDMPipeline(DiffusionPipeline):
             # order - before the replays that read it.  The latent is carried in fp32 between steps, as for eta = 0; with a
             # bf16 UNet the loop below stores it in bf16 (the reference's storage), so the two differ by that rounding.
             sde = self.scheduler.stochastic_schedule(num_inference_steps, eta)
-            eng = self._engine(latents.shape[0], num_inference_steps, use_graph, schedule=sde)
-            draw = eng.scheduler.drawer(generator, tuple(latents.shape), self.unet.device, self.unet.dtype)
+            eng = cached_engine(self, "_engines", sde, latents.shape[0], use_graph, self.unet)
+            draw = sde.drawer(generator, tuple(latents.shape), self.unet.device, self.unet.dtype)
             latents = eng.run(latents, draw=draw).to(self.unet.dtype)
             return self._deliver(latents, output_type, return_dict)
         if eta != 0.0 and not dpm:
@@ -79,7 +67,9 @@ class MyLDMPipeline(DiffusionPipeline):
                 eps = self.unet(latents, t).sample
                 latents = self.scheduler.step(eps, t, latents, eta=eta, generator=generator).prev_sample
             return self._deliver(latents, output_type, return_dict)
-        eng = self._engine(latents.shape[0], num_inference_steps, use_graph)
+        # the engine is keyed on the schedule's key - the scheduler's class, CONFIG and step count - not on the scheduler
+        # object, which is re-created on every call (like the reference, ldm_pipeline.py:80); it shows the current one
+        eng = cached_engine(self, "_engines", self.scheduler.schedule(num_inference_steps), latents.shape[0], use_graph, self.unet)
         eng.scheduler = self.scheduler
         latents = eng.run(latents).to(self.unet.dtype)
         return self._deliver(latents, output_type, return_dict)
@@ -111,6 +101,12 @@ class MyLDMPipeline(DiffusionPipeline):
             rows.append((t, (float(a_prev ** 0.5), float((1 - a_prev) ** 0.5), float(a_t ** 0.5), float((1 - a_t) ** 0.5))))
         return rows
 
+    def inversion_schedule(self):
+        """_inversion_rows as the Schedule DenoiseEngine replays with afldm_ddim_step (timesteps ascending)."""
+        rows = self._inversion_rows()
+        ts = [t for t, _ in rows]
+        return Schedule.of(self.scheduler, "ddim", ts, [c for _, c in rows], _inversion_timesteps=tuple(ts))
+
     @torch.no_grad()
     def ddim_inversion(self, latent, bar=True, use_graph=True):
         """Deterministic DDIM inversion over reversed timesteps (reference ldm_pipeline.py:133-160).  use_graph (fp32 latents on the
@@ -120,36 +116,14 @@ class MyLDMPipeline(DiffusionPipeline):
         from .. import ops
         if isinstance(self.scheduler, DPMSolverMultistepScheduler):
             raise NotImplementedError("ddim_inversion needs a DDIMScheduler: DPM-Solver inversion is not implemented")
-        rows = self._inversion_rows()
-        if (use_graph and latent.is_cuda and latent.dtype == torch.float32 and len(rows) >= 1
+        sched = self.inversion_schedule()
+        if (use_graph and latent.is_cuda and latent.dtype == torch.float32 and len(sched.rows) >= 1
                 and tuple(latent.shape[1:]) == (self.unet.config.in_channels, self.unet.config.sample_size, self.unet.config.sample_size)
                 and all(type(m.processor).__name__ == "AttnProcessor2_0" for m in self.unet.modules() if hasattr(m, "processor"))):
-            sched = _InversionSchedule(self.scheduler, rows)
-            cfg_key = tuple(sorted((k, repr(v)) for k, v in dict(sched.config).items()))
-            key = (latent.shape[0], len(rows), self.unet.dtype, str(self.unet.device), cfg_key)
-            cache = self.__dict__.setdefault("_inv_engines", {})
-            if key not in cache:
-                cache.clear()
-                cache[key] = DenoiseEngine(self.unet, sched, latent.shape[0], len(rows), use_graph=True)
-            return cache[key].run(latent).to(latent.dtype)
+            return cached_engine(self, "_inv_engines", sched, latent.shape[0], True, self.unet).run(latent).to(latent.dtype)
+        rows = list(zip(sched.timesteps, sched.rows))
         it = self.progress_bar(rows) if bar else rows
         for t, coef in it:
             eps = self.unet(latent, t).sample
             latent = ops.ddim_step_flat(latent.float().contiguous(), eps.float().contiguous(), coef).to(latent.dtype)
         return latent
-
-
-class _InversionSchedule:
-    """Scheduler-shaped view of a DDIM inversion for DenoiseEngine: its timesteps (ascending) and one coefficient row per step."""
-
-    def __init__(self, scheduler, rows):
-        self.rows = rows
-        self.init_noise_sigma = 1.0
-        self.config = dict(scheduler.config, _inversion_timesteps=tuple(t for t, _ in rows))
-        self._timesteps_host = [t for t, _ in rows]
-
-    def set_timesteps(self, n=None, device=None):
-        assert n in (None, len(self.rows))
-
-    def coefficient_table(self, device):
-        return torch.tensor([c for _, c in self.rows], dtype=torch.float32).to(device)

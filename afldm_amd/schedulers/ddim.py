@@ -15,7 +15,7 @@ import torch
 from .. import ops
 from ..utils import randn_tensor
 from ..configs import FFHQ_DDIM_CONFIG, FrozenConfig
-from .sde import SdeSchedule
+from .schedule import Schedule
 
 
 @dataclass
@@ -97,10 +97,14 @@ class DDIMScheduler:
         a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
         return float((1 - a_prev) / (1 - a_t) * (1 - a_t / a_prev))
 
+    def schedule(self, num_inference_steps):
+        """The eta = 0 sampler of `num_inference_steps` as the Schedule DenoiseEngine replays with afldm_ddim_step."""
+        self.set_timesteps(num_inference_steps)
+        return Schedule.of(self, "ddim", self._timesteps_host, self.coefficients, _ddim_steps=int(num_inference_steps))
+
     def coefficient_table(self, device):
-        """float32 [nsteps, 4] device table for the graph-replayed loop (afldm_ddim_step)."""
-        rows = [self.coefficients(t) for t in self._timesteps_host]
-        return torch.tensor(rows, dtype=torch.float32).to(device)
+        """float32 [nsteps, 4] device table of the current timesteps (afldm_ddim_step)."""
+        return self.schedule(self.num_inference_steps).table(device)
 
     def sde_coefficients(self, timestep, eta):
         """(p, q, lo, hi, a, b, d, c) of the stochastic step (diffusers DDIMScheduler.step with eta, epsilon prediction, no clip)
@@ -115,16 +119,16 @@ class DDIMScheduler:
                 0.0, math.sqrt(a_prev), math.sqrt(max(1 - a_prev - sigma * sigma, 0.0)), sigma)
 
     def stochastic_schedule(self, num_inference_steps, eta):
-        """The eta != 0 sampler of `num_inference_steps` as the schedule DenoiseEngine replays with afldm_sde_step.  Every step
+        """The eta != 0 sampler of `num_inference_steps` as the Schedule DenoiseEngine replays with afldm_sde_step.  Every step
         draws, the last one included (its sigma is 0 with set_alpha_to_one, but step() still draws): randn_tensor in the
         model's dtype, as step() draws with the model output's."""
         if self.config.clip_sample or self.config.prediction_type != "epsilon":
             raise NotImplementedError("afldm_amd.DDIMScheduler implements the reference's setting: "
                                       "epsilon prediction, clip_sample=False")
         self.set_timesteps(num_inference_steps)
-        ts = list(self._timesteps_host)
-        return SdeSchedule(dict(self.config, _ddim_eta=float(eta)), ts, [self.sde_coefficients(t, eta) for t in ts],
-                           [True] * len(ts), noise_dtype=None)
+        ts = self._timesteps_host
+        return Schedule.of(self, "sde", ts, lambda t: self.sde_coefficients(t, eta), [True] * len(ts),
+                           _ddim_steps=int(num_inference_steps), _ddim_eta=float(eta))
 
     def step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None,
              variance_noise=None, return_dict=True):

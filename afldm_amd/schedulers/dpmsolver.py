@@ -9,7 +9,7 @@ two previous converted outputs, so a step is one coefficient row (afldm_dpm_step
 
 The rows, warm-up steps of lowered order and lower-order final steps included, are a function of the step index
 alone; they are computed in float64 from the schedule and rounded once to fp32.  `step` on CUDA tensors launches
-afldm_dpm_step_flat; DenoiseEngine replays afldm_dpm_step over `coefficient_table` (update_kind = "dpm").
+afldm_dpm_step_flat; DenoiseEngine replays afldm_dpm_step over `schedule(n)` (a Schedule of kind "dpm").
 Thresholding, the stochastic SDE variants and the Karras / exponential / beta sigma schedules are not linear in this
 sense (or not deterministic) and raise NotImplementedError."""
 import math
@@ -20,6 +20,7 @@ import torch
 
 from .. import ops
 from ..configs import FrozenConfig
+from .schedule import Schedule
 
 _DEFAULTS = dict(
     num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
@@ -43,7 +44,6 @@ class DPMSolverMultistepSchedulerOutput:
 
 class DPMSolverMultistepScheduler:
     order = 1
-    update_kind = "dpm"          # DenoiseEngine: afldm_dpm_step over [nsteps, 8] rows (default "ddim": afldm_ddim_step)
 
     def __init__(self, **kw):
         cfg = dict(_DEFAULTS)
@@ -218,11 +218,18 @@ class DPMSolverMultistepScheduler:
                 b += d1 * D1 + d2 * D2
         return (p, q, a, float(b[0]), float(b[1]), float(b[2]), 0.0, 0.0)
 
+    def schedule(self, num_inference_steps=None):
+        """The sampler of `num_inference_steps` (None: of the current timesteps, solver state untouched) as the Schedule
+        DenoiseEngine replays with afldm_dpm_step."""
+        if num_inference_steps is not None:
+            self.set_timesteps(num_inference_steps)
+        elif self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' first")
+        return Schedule.of(self, "dpm", self._timesteps_host, self._rows, _dpm_steps=self.num_inference_steps)
+
     def coefficient_table(self, device):
         """float32 [nsteps, 8] rows (p, q, a, b0, b1, b2, 0, 0) for afldm_dpm_step, rounded once from float64."""
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' first")
-        return torch.tensor(self._rows, dtype=torch.float64).to(torch.float32).to(device)
+        return self.schedule().table(device)
 
     # ------------------------------------------------------------------ diffusers step API
     def index_for_timestep(self, timestep):

@@ -13,7 +13,7 @@ import torch
 from .. import ops
 from ..configs import FrozenConfig
 from ..utils import randn_tensor
-from .sde import SdeSchedule
+from .schedule import Schedule
 
 
 def compute_gaussian_product_coef(sigma1, sigma2):
@@ -25,26 +25,6 @@ def compute_gaussian_product_coef(sigma1, sigma2):
 class I2SBSchedulerOutput:
     prev_sample: torch.Tensor
     pred_original_sample: torch.Tensor = None
-
-
-class _OdeSchedule:
-    """Scheduler-shaped view of an I2SBScheduler's deterministic bridge for the graph-replayed engines (afldm_amd/engine.py): the
-    timesteps of its evaluations and one (c0, c1, c2, c3) row per evaluation for afldm_ddim_step."""
-
-    def __init__(self, sched, steps):
-        self.sched, self.steps = sched, steps
-        self.evaluations = steps - 1
-        self.init_noise_sigma = 1.0
-        self.config = FrozenConfig(dict(sched.config, _i2sb_ode_steps=steps))
-        self._timesteps_host = []
-
-    def set_timesteps(self, num_evaluations=None, device=None):
-        assert num_evaluations in (None, self.evaluations), "the schedule is fixed by ode_schedule(num_inference_steps)"
-        self.sched.set_timesteps(self.steps)
-        self._timesteps_host = list(self.sched._timesteps_host[:self.evaluations])
-
-    def coefficient_table(self, device):
-        return torch.tensor([self.sched.ode_coefficients(t) for t in self._timesteps_host], dtype=torch.float32).to(device)
 
 
 class I2SBScheduler:
@@ -141,9 +121,14 @@ class I2SBScheduler:
 
     def ode_schedule(self, num_inference_steps):
         """The ODE bridge of `num_inference_steps` (num_inference_steps - 1 UNet evaluations: the reference loop leaves before
-        its last timestep, i2sb_pipeline.py:48-50) as the (timesteps, coefficient table) object DenoiseEngine / the harness's
-        CrossFrameSampler replay as HIP graphs; None when the configuration clips x0 (the clamp breaks the linear form)."""
-        return None if self.config.clip_sample else _OdeSchedule(self, int(num_inference_steps))
+        its last timestep, i2sb_pipeline.py:48-50) as the Schedule DenoiseEngine / the harness's CrossFrameSampler replay
+        with afldm_ddim_step; None when the configuration clips x0 (the clamp breaks the linear form)."""
+        if self.config.clip_sample:
+            return None
+        steps = int(num_inference_steps)
+        self.set_timesteps(steps)
+        ts = self._timesteps_host[:steps - 1]
+        return Schedule.of(self, "ddim", ts, self.ode_coefficients, _i2sb_ode_steps=steps)
 
     def sde_coefficients(self, timestep, is_ode):
         """(p, q, lo, hi, a, b, d, c) of step() in any (is_ode, clip_sample) form, in float64 from the fp32 std_fwd table, for
@@ -162,14 +147,13 @@ class I2SBScheduler:
     def bridge_schedule(self, num_inference_steps, is_ode=False):
         """The bridge of `num_inference_steps` (num_inference_steps - 1 UNet evaluations, as ode_schedule) in any form - the
         stochastic one (is_ode=False, the pipeline's default) and / or with clip_sample (the scheduler's default) - as the
-        schedule DenoiseEngine replays with afldm_sde_step.  A step draws exactly when step() does (t > 0 and not is_ode),
+        Schedule DenoiseEngine replays with afldm_sde_step.  A step draws exactly when step() does (t > 0 and not is_ode),
         in fp32 (step() draws with the fp32 model output's dtype)."""
         steps = int(num_inference_steps)
         self.set_timesteps(steps)
-        ts = list(self._timesteps_host[:steps - 1])
-        return SdeSchedule(dict(self.config, _i2sb_bridge_steps=steps, _i2sb_is_ode=bool(is_ode)), ts,
-                           [self.sde_coefficients(t, is_ode) for t in ts], [t > 0 and not is_ode for t in ts],
-                           noise_dtype=torch.float32)
+        ts = self._timesteps_host[:steps - 1]
+        return Schedule.of(self, "sde", ts, lambda t: self.sde_coefficients(t, is_ode), [t > 0 and not is_ode for t in ts],
+                           noise_dtype=torch.float32, _i2sb_bridge_steps=steps, _i2sb_is_ode=bool(is_ode))
 
     def step(self, model_output, timestep, sample, is_ode=False, generator=None, return_dict=True):
         if not sample.is_cuda:

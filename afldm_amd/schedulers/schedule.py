@@ -1,0 +1,78 @@
+"""Schedule — what a sampler hands the graph-replayed engine (afldm_amd/engine.py): one timestep and one coefficient row per
+UNet evaluation, fixed when it is made.  `kind` names the update kernel that reads the rows:
+
+    "ddim"  (c0, c1, c2, c3):            x0 = (x - c1 eps) / c0;  x_out = c2 x0 + c3 eps                  afldm_ddim_step
+    "dpm"   (p, q, a, b0, b1, b2, 0, 0): m0 = p x + q eps;  x_out = a x + b0 m0 + b1 m1 + b2 m2           afldm_dpm_step
+    "sde"   (p, q, lo, hi, a, b, d, c):  x0 = clamp(p x + q eps, lo, hi);  x_out = a x + b x0 + d eps + c z   afldm_sde_step
+
+The rows come from the scheduler that owns the update (DDIMScheduler.schedule / stochastic_schedule,
+DPMSolverMultistepScheduler.schedule, I2SBScheduler.ode_schedule / bridge_schedule, MyLDMPipeline.inversion_schedule) as Python
+floats and are rounded once to fp32 by `table`.  An "sde" schedule also states which steps draw noise and how: exactly the
+randn_tensor calls, in the same order, that the scheduler's eager `step()` makes, so that the engine can draw them from the
+caller's generator before the captured graphs need them.  `key` identifies everything the rows were computed from; the engine
+cache (engine.cached_engine) compares it, so two schedules with equal keys must replay the same graph."""
+from dataclasses import dataclass
+
+import torch
+
+from ..configs import FrozenConfig
+from ..utils import randn_tensor
+
+ROW_WIDTH = {"ddim": 4, "dpm": 8, "sde": 8}
+_MADE = {}          # key -> Schedule: the rows are ~0.1 ms of scalar tensor arithmetic each, and a sampler asks per call
+
+
+@dataclass(frozen=True, eq=False)
+class Schedule:
+    kind: str
+    timesteps: tuple
+    rows: tuple
+    draws: tuple
+    noise_dtype: object
+    init_noise_sigma: float
+    config: FrozenConfig          # the owner's config plus the settings: what `key` is the hashable form of
+    key: tuple
+
+    @classmethod
+    def of(cls, owner, kind, timesteps, rows, draws=None, noise_dtype=None, **settings):
+        """owner: the scheduler whose config the rows are computed from; settings: whatever else they depend on (the step
+        count, eta, is_ode, ...); rows: one per timestep, or a function of the timestep that is only called when no schedule
+        with this key has been made yet; draws: per step, whether the eager step draws a noise tensor ("sde" only);
+        noise_dtype: the dtype of that draw (None: the model's dtype, what DDIMScheduler.step draws in)."""
+        config = FrozenConfig(dict(owner.config, **settings))
+        key = (type(owner).__name__, tuple(sorted((k, repr(v)) for k, v in config.items())))
+        if key in _MADE:
+            return _MADE[key]
+        timesteps = tuple(int(t) for t in timesteps)
+        if callable(rows):
+            rows = [rows(t) for t in timesteps]
+        rows = tuple(tuple(float(v) for v in r) for r in rows)
+        draws = tuple(bool(d) for d in draws) if draws is not None else (False,) * len(rows)
+        assert len(timesteps) == len(rows) == len(draws) and all(len(r) == ROW_WIDTH[kind] for r in rows)
+        assert kind == "sde" or not any(draws)
+        if len(_MADE) >= 64:
+            _MADE.clear()
+        made = _MADE[key] = cls(kind, timesteps, rows, draws, noise_dtype, float(owner.init_noise_sigma), config, key)
+        return made
+
+    def table(self, device):
+        """float32 [nsteps, 4 or 8] device table, each entry rounded once from the Python float."""
+        return torch.tensor(self.rows, dtype=torch.float64).to(torch.float32).to(device)
+
+    # read-only spellings of the scheduler-shaped views this type replaced; tests/test_sde_host.py checks every row through them
+    update_kind = property(lambda self: self.kind)
+    _timesteps_host = property(lambda self: list(self.timesteps))
+    coefficient_table = table
+
+    def draw_noise(self, shape, generator, device, model_dtype):
+        """One step's noise, as the eager step draws it: randn_tensor(shape, generator, device, dtype).  With a CPU generator
+        the values do not depend on `device` (randn_tensor draws on the CPU and moves the result)."""
+        return randn_tensor(shape, generator=generator, device=device, dtype=self.noise_dtype or model_dtype)
+
+    def drawer(self, generator, shape, device, model_dtype):
+        """The `draw` callable DenoiseEngine.run takes: each call is the next step's draw_noise with the caller's generator (a
+        torch.Generator, a list of them - one per sample - or None for the device's default generator).  With CPU generators it
+        returns the CPU tensor, which the engine stages through pinned memory; otherwise the draw runs on `device`."""
+        g0 = generator[0] if isinstance(generator, list) and generator else generator
+        where = torch.device("cpu") if isinstance(g0, torch.Generator) and g0.device.type == "cpu" else device
+        return lambda: self.draw_noise(shape, generator, where, model_dtype)

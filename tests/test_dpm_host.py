@@ -241,7 +241,7 @@ def test_from_ffhq_ddim_config_gives_diffusers_defaults():
     assert (c.timestep_spacing, c.steps_offset, c.beta_schedule, c.beta_start, c.beta_end) == \
         ("leading", 1, "scaled_linear", 0.0015, 0.0195)
     assert "clip_sample" not in c and "set_alpha_to_one" not in c
-    assert s.order == 1 and s.init_noise_sigma == 1.0 and s.update_kind == "dpm"
+    assert s.order == 1 and s.init_noise_sigma == 1.0 and s.schedule(5).kind == "dpm"
     assert DPMSolverMultistepScheduler().config.timestep_spacing == "linspace"
     s.set_timesteps(20)
     assert s.timesteps.dtype == torch.int64 and s.timesteps.tolist() == [47 * k + 1 for k in range(20, 0, -1)]
@@ -292,7 +292,7 @@ class _FakeUnet:
 
 
 def test_pipeline_keeps_ddim_and_the_harness_rejects_dpm(monkeypatch):
-    from afldm_amd import harness
+    from afldm_amd import engine, harness
     from afldm_amd.pipelines import ldm_pipeline
     from afldm_amd.schedulers.ddim import DDIMScheduler, ffhq_ddim_scheduler
     from afldm_amd.schedulers.dpmsolver import DPMSolverMultistepScheduler
@@ -300,21 +300,21 @@ def test_pipeline_keeps_ddim_and_the_harness_rejects_dpm(monkeypatch):
 
     class Engine:
         def __init__(self, unet, sched, batch, steps, use_graph):
-            seen.append((type(sched), use_graph))
+            seen.append((sched.key[0], sched.kind, use_graph))
             self.scheduler = sched
 
         def run(self, latents):
             return latents
-    monkeypatch.setattr(ldm_pipeline, "DenoiseEngine", Engine)
+    monkeypatch.setattr(engine, "DenoiseEngine", Engine)
     pipe = ldm_pipeline.MyLDMPipeline(None, _FakeUnet(), ffhq_ddim_scheduler())
     pipe(latents=torch.zeros(1, 4, 8, 8), num_inference_steps=5, output_type="latent")
-    assert type(pipe.scheduler) is DDIMScheduler and seen[-1] == (DDIMScheduler, True)
+    assert type(pipe.scheduler) is DDIMScheduler and seen[-1] == ("DDIMScheduler", "ddim", True)
     pipe.scheduler = DPMSolverMultistepScheduler.from_config(pipe.scheduler.config, solver_order=3)
     pipe(latents=torch.zeros(1, 4, 8, 8), num_inference_steps=5, output_type="latent", eta=0.5, use_graph=False)
     assert type(pipe.scheduler) is DPMSolverMultistepScheduler and pipe.scheduler.config.solver_order == 3
-    assert seen[-1] == (DPMSolverMultistepScheduler, False)
+    assert seen[-1] == ("DPMSolverMultistepScheduler", "dpm", False)
     # same config keys, other class: the engine cache must not hand the DDIM engine back
-    assert len({k[5] for k in [next(iter(pipe._engines))]}) == 1 and next(iter(pipe._engines))[5] is DPMSolverMultistepScheduler
+    assert len({k[5] for k in [next(iter(pipe._engines))]}) == 1 and next(iter(pipe._engines))[5] == "DPMSolverMultistepScheduler"
     with pytest.raises(NotImplementedError, match="DPMSolverMultistepScheduler"):
         harness.shift_ldm(pipe, num_inference_steps=5)
     with pytest.raises(NotImplementedError, match="DPM"):

@@ -240,7 +240,8 @@ def test_interpolation_passes_vs_eager_and_oracle(dtype, tols):
     lat = pipe._frames(ends[0:1].cuda(), ends[1:2].cuda(), n, fracs, True)
     with _count_interp_launches() as calls:
         g = pipe._graph_passes(ends.cuda(), lat, steps, weights)
-    assert len(calls) == (steps + 1) * len(pipe._xframe_interp_sampler.procs)
+    (smp,) = pipe._xframe_interp_sampler.values()
+    assert len(calls) == (steps + 1) * len(smp.procs)
     e = pipe._eager_passes(lat.to(dtype), steps, weights)
     want = _oracle_passes(ucfg, usd, lat.cpu(), steps)
     r_ge, r_go, r_eo = rel_rms(g, e.float()), rel_rms(g, want), rel_rms(e.float(), want)
@@ -299,7 +300,8 @@ def test_interpolation_pipeline_ffhq_size_vs_oracle():
     pipe, (ucfg, usd, vcfg, vsd) = _tiny_pipeline(torch.float32, unet_name="ffhq")
     with _count_interp_launches() as calls:
         got = pipe(*images, num_frames=n, num_inference_steps=steps, output_type="latent")
-    assert len(calls) == (steps + 1) * len(pipe._xframe_interp_sampler.procs)
+    (smp,) = pipe._xframe_interp_sampler.values()
+    assert len(calls) == (steps + 1) * len(smp.procs)
     r = rel_rms(got, _oracle_frames(ucfg, usd, vcfg, vsd, images, n, steps))
     print(f"[interp FFHQ size, 3 frames, 4 steps] graph vs oracle {r:.2e}")
     assert r <= 1e-3
@@ -359,7 +361,8 @@ def test_sampler_first_run_keeps_the_inversion_graphs_weights():
     a = pipe(*images, num_frames=4, num_inference_steps=3, output_type="latent")
     b = pipe(*images, num_frames=4, num_inference_steps=3, output_type="latent")
     assert torch.equal(a, b)
-    assert sorted(pipe._xframe_interp_sampler.engines) == [("interp", False, 2), ("interp", True, 4)]
+    (smp,) = pipe._xframe_interp_sampler.values()
+    assert sorted(smp.engines) == [("interp", False, 2), ("interp", True, 4)]
     with torch.no_grad():
         unet.conv_in.weight.mul_(0.8)
     c = pipe(*images, num_frames=4, num_inference_steps=3, output_type="latent")

@@ -260,7 +260,7 @@ def test_shift_ldm_graph_path_matches_eager_loop_and_replays():
         for a, b in zip(fr_g, fr_e):
             assert (a - b).abs().max() <= 2e-4
         assert np.allclose(er_g, er_e, rtol=2e-3, atol=1e-9), (er_g, er_e)
-        smp = pipe._xframe_sampler
+        (smp,) = pipe._xframe_sampler.values()
         assert sorted(smp.engines) == [(False, 1), (True, 3)]
     # new weights: the sampler notices and re-captures instead of replaying the old model
     with torch.no_grad():
@@ -324,7 +324,8 @@ def test_shift_ldm_sr_graph_path_matches_eager_loop():
     img = torch.rand(1, 3, 64, 64, generator=torch.Generator().manual_seed(5)) * 2 - 1
     fg, eg = shift_ldm_sr(pipe, num_inference_steps=5, num_shift_steps=3, output_path=None, image=img)
     fe, ee = shift_ldm_sr(pipe, num_inference_steps=5, num_shift_steps=3, output_path=None, image=img, use_graph=False)
-    assert sorted(pipe._xframe_sampler.engines) == [(False, 1), (True, 3)]
+    (smp,) = pipe._xframe_sampler.values()
+    assert sorted(smp.engines) == [(False, 1), (True, 3)]
     for x, y in zip(fg, fe):
         assert (x - y).abs().max() <= 5e-4
     assert np.allclose(eg, ee, rtol=5e-3, atol=1e-9), (eg, ee)

@@ -105,7 +105,7 @@ def test_tiny_ddim_eta_graph_vs_eager_loop(kind):
     ga, gb, gc = _gens(kind, 11), _gens(kind, 11), _gens(kind, 11)
     a = pipe(latents=x, eta=0.7, num_inference_steps=8, generator=ga, output_type="latent")
     (key,) = pipe._engines
-    assert key[5].__name__ == "SdeSchedule"
+    assert key[5] == "DDIMScheduler" and pipe._engines[key].schedule.kind == "sde"
     b = pipe(latents=x, eta=0.7, num_inference_steps=8, generator=gb, output_type="latent", use_graph=False)
     err = rel_rms(a, b.float())
     print(f"[tiny DDIM eta=0.7, 8 steps, {kind} generator] graph vs eager loop rel-RMS {err:.2e}")

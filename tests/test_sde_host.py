@@ -189,7 +189,7 @@ def test_i2sb_rows_and_draws_reproduce_oracle_loop(is_ode, clip):
     assert err <= 1e-6, err                                            # the oracle runs in fp32
 
 
-def test_drawer_devices_and_generator_lists():
+def test_drawer_devices_and_generator_lists(monkeypatch):
     from afldm_amd.schedulers.ddim import ffhq_ddim_scheduler
     sde = ffhq_ddim_scheduler().stochastic_schedule(4, 1.0)
     gens = [torch.Generator().manual_seed(i) for i in range(3)]
@@ -198,7 +198,7 @@ def test_drawer_devices_and_generator_lists():
     for i in range(3):
         assert torch.equal(z[i:i + 1], torch.randn(1, 4, 8, 8, generator=torch.Generator().manual_seed(i), dtype=torch.bfloat16))
     calls = []
-    sde.draw_noise = lambda shape, gen, device, dt: calls.append(device)
+    monkeypatch.setattr(type(sde), "draw_noise", lambda self, shape, gen, device, dt: calls.append(device))
     sde.drawer(None, (1, 4, 8, 8), torch.device("cuda"), torch.float32)()
     assert calls == [torch.device("cuda")]                              # no generator: the device's default generator
 
@@ -248,7 +248,6 @@ def test_ldm_pipeline_routes_eta_to_the_sde_engine(monkeypatch):
     from afldm_amd.pipelines import ldm_pipeline
     from afldm_amd.schedulers.ddim import DDIMScheduler, ffhq_ddim_scheduler
     seen, steps_called = [], []
-    monkeypatch.setattr(ldm_pipeline, "DenoiseEngine", _fake_engine(seen))
     monkeypatch.setattr(engine, "DenoiseEngine", _fake_engine(seen))
     monkeypatch.setattr(DDIMScheduler, "step", lambda self, e, t, x, eta=0.0, generator=None, **k: steps_called.append(eta) or
                         type("O", (), {"prev_sample": x})())
