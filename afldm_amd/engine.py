@@ -21,7 +21,10 @@ line is afldm_dpm_step, which also keeps the solver's two previous converted out
 is afldm_sde_step, which also reads that step's row of an fp32 noise buffer [steps, B, C, H, W].  The noise is drawn per run by
 the caller's generator - run(latents, draw=...), the same randn calls the eager loop makes, in the same order - never inside a
 capture.  Draws on the CPU (a CPU generator) go through pinned staging: the next replay group's noise is drawn while the GPU
-runs the current group.
+runs the current group.  Kind "repaint" (DDIMScheduler.repaint_schedule: RePaint inpainting) has [steps, 12] rows and the last
+line is afldm_repaint_step, which reads up to three noise slots per step of a buffer [steps, 3, B, C, H, W], filled the same way,
+and two static per-run tensors, the known latents and the latent mask - run(latents, draw=..., known=(z0, mask)).  The captured
+graphs hold the buffers' addresses only, so another image or mask replays the same graphs.
 
 cached_engine keeps the engines (and the harness's samplers) a pipeline has built: one resident entry per slot.
 """
@@ -121,7 +124,7 @@ class DenoiseEngine:
         # counters of in-kernel reductions / cluster hand-overs: private to this engine (one per branch), so that its
         # captured graphs can replay next to another engine's on a different stream
         self._sync = [ops.new_sync_buffer(dev) for _ in range(self.branches)]
-        self.hist = self.noise = None
+        self.hist = self.noise = self.known = self.mask = None
         self._update, state = self.UPDATES[self.schedule.kind]
         self._state = state(self)
 
@@ -142,9 +145,21 @@ class DenoiseEngine:
         per = self.B // self.branches
         return [(self.noise[:, b * per:(b + 1) * per],) for b in range(self.branches)]
 
+    def _repaint_state(self):
+        """Three noise slots per step (z_k, z_u, z_b), filled per run like the "sde" rows - a slot that is not drawn keeps zeros and is
+        not read - and the run's known latents and latent mask.  Every branch takes its batch slice of all three."""
+        self.noise = torch.zeros((self.n, 3) + tuple(self.lat.shape), dtype=torch.float32, device=self.lat.device)
+        self.known = torch.zeros_like(self.lat)
+        self.mask = torch.zeros((self.B, 1) + tuple(self.lat.shape[2:]), dtype=torch.float32, device=self.lat.device)
+        self._stage = []
+        per = self.B // self.branches
+        return [(self.known[b * per:(b + 1) * per], self.mask[b * per:(b + 1) * per], self.noise[:, :, b * per:(b + 1) * per])
+                for b in range(self.branches)]
+
     # Schedule.kind -> the update of ops that ends a step, and what allocates the buffers it keeps between steps (one argument
     # tuple per branch, passed between eps and the coefficient table)
-    UPDATES = {"ddim": (ops.ddim_step, _no_state), "dpm": (ops.dpm_step, _dpm_state), "sde": (ops.sde_step, _sde_state)}
+    UPDATES = {"ddim": (ops.ddim_step, _no_state), "dpm": (ops.dpm_step, _dpm_state), "sde": (ops.sde_step, _sde_state),
+               "repaint": (ops.repaint_step, _repaint_state)}
 
     # one denoise step, entirely stream-ordered
     def _step(self):
@@ -277,45 +292,61 @@ class DenoiseEngine:
             self.graph.replay()
 
     def _fill(self, k0, k1, draw):
-        """Noise rows k0 .. k1 - 1: one draw() per step that draws, in step order.  A CPU draw is copied into pinned staging and
-        on to the device with non_blocking (stream-ordered before the replays that read it); the staging buffer is reused only
-        after the event behind its previous copy has passed.  A device draw is copied on the stream."""
-        ks = [k for k in range(k0, k1) if self.schedule.draws[k]]
-        if not ks:
+        """Noise rows k0 .. k1 - 1: one draw() per slot a step draws ("sde": one per step at the most, "repaint": up to three - z_k,
+        z_u, z_b), in step and slot order.  A CPU draw is copied into pinned staging and on to the device with non_blocking
+        (stream-ordered before the replays that read it); the staging buffer is reused only after the event behind its previous
+        copy has passed.  A device draw is copied on the stream."""
+        slots = self.noise.dim() - self.lat.dim() - 1          # 0: one row per step ("sde"); 1: [steps, 3, ...] ("repaint")
+        rows = [self.noise[k, j] if slots else self.noise[k] for k in range(k0, k1) for j in self.schedule.slots(k)]
+        if not rows:
             return
         stage = None
-        for i, k in enumerate(ks):
+        for i, row in enumerate(rows):
             z = draw()
-            if tuple(z.shape) != tuple(self.noise.shape[1:]):
-                raise ValueError(f"DenoiseEngine: draw() gave {tuple(z.shape)}, want {tuple(self.noise.shape[1:])}")
+            if tuple(z.shape) != tuple(self.lat.shape):
+                raise ValueError(f"DenoiseEngine: draw() gave {tuple(z.shape)}, want {tuple(self.lat.shape)}")
             if z.device.type != "cpu":
-                self.noise[k].copy_(z)
+                row.copy_(z)
                 continue
             if stage is None:
                 if len(self._stage) < 2:
-                    self._stage.append((torch.empty((self.steps_per_graph,) + tuple(self.noise.shape[1:]), dtype=torch.float32,
-                                                    pin_memory=True), torch.cuda.Event()))
+                    per_step = self.noise.shape[1] if slots else 1
+                    self._stage.append((torch.empty((self.steps_per_graph * per_step,) + tuple(self.lat.shape),
+                                                    dtype=torch.float32, pin_memory=True), torch.cuda.Event()))
                     stage = self._stage[-1]
                 else:
                     self._stage.append(self._stage.pop(0))          # the older of the two
                     stage = self._stage[-1]
                     stage[1].synchronize()
             stage[0][i].copy_(z)
-            self.noise[k].copy_(stage[0][i], non_blocking=True)
+            row.copy_(stage[0][i], non_blocking=True)
         if stage is not None:
             stage[1].record()
 
     @torch.no_grad()
-    def run(self, latents, draw=None):
-        """latents -> the sampled latents (fp32).  An "sde" schedule needs `draw`: a callable returning the next noise tensor
-        [B, C, H, W] (on the CPU or on the engine's device, any float dtype), called once per drawing step in step order -
-        for a seeded run, the scheduler's own randn_tensor call with the caller's generator (Schedule.drawer)."""
+    def run(self, latents, draw=None, known=None):
+        """latents -> the sampled latents (fp32).  An "sde" or "repaint" schedule needs `draw`: a callable returning the next
+        noise tensor [B, C, H, W] (on the CPU or on the engine's device, any float dtype), called once per draw in step (and
+        slot) order - for a seeded run, the scheduler's own randn_tensor call with the caller's generator (Schedule.drawer).
+        A "repaint" schedule also needs known = (z0, mask): the latents to keep [B, C, H, W] and the latent mask [B | 1, 1, H, W]
+        (1 = keep), written to the engine's static buffers before the first replay."""
+        if (self.known is None) != (known is None):
+            raise ValueError("DenoiseEngine: known=(z0, mask) goes with a 'repaint' schedule, and only with one")
+        if known is not None:
+            z0, mask = known
+            if tuple(z0.shape) != tuple(self.lat.shape) or tuple(mask.shape) not in ((1,) + tuple(self.mask.shape[1:]),
+                                                                                     tuple(self.mask.shape)):
+                raise ValueError(f"DenoiseEngine: known latents {tuple(z0.shape)} / mask {tuple(mask.shape)}, want "
+                                 f"{tuple(self.lat.shape)} / {tuple(self.mask.shape)} (or batch 1)")
         self.reset(latents)
+        if known is not None:
+            self.known.copy_(z0)
+            self.mask.copy_(mask)           # (a batch-1 mask is broadcast)
         if self.noise is None:
             self.step(self.n)
         else:
             if draw is None:
-                raise ValueError("DenoiseEngine: a stochastic ('sde') schedule needs run(latents, draw=...)")
+                raise ValueError(f"DenoiseEngine: a stochastic ({self.schedule.kind!r}) schedule needs run(latents, draw=...)")
             # group by replay: while the GPU runs one group, the host draws the next one's noise
             g = self.steps_per_graph if self.use_graph else 1
             self._fill(0, min(g, self.n), draw)

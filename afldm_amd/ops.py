@@ -1486,6 +1486,68 @@ def sde_step(x, eps_nhwc, noise, coef, step_idx, advance=False, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- RePaint inpainting
+def repaint_step(x, eps_nhwc, known, mask, noise, coef, step_idx, advance=False, out=None):
+    """x, known NCHW fp32 [B, C, H, W], mask fp32 [B, 1, H, W] (1 = keep), eps NHWC dtype; noise: fp32 view [steps, 3, B, C, H, W]
+    (slots z_k, z_u, z_b) whose last four dimensions are contiguous (a batch slice of a larger buffer is fine: the strides are
+    noise.stride(0) and noise.stride(1)); coef float[12*nsteps] rows (p, q, lo, hi, a, b, c, k0, k1, u0, u1, 0) and step_idx
+    int32[1] on device."""
+    _dev(x, "x"); _dev(eps_nhwc, "eps"); _dev(known, "known"); _dev(mask, "mask")
+    if not noise.is_cuda:
+        raise RuntimeError("afldm_amd: noise must live on an MI355X (cuda) device; there is no CPU path")
+    B, C, H, W = x.shape
+    assert x.dtype == known.dtype == mask.dtype == torch.float32 and known.shape == x.shape and tuple(mask.shape) == (B, 1, H, W)
+    assert noise.dtype == torch.float32 and noise.dim() == 6 and tuple(noise.shape[1:]) == (3, B, C, H, W)
+    assert noise[0, 0].is_contiguous() and noise.stride(1) >= B * C * H * W
+    assert noise.stride(0) >= 2 * noise.stride(1) + B * C * H * W
+    if out is None:
+        out = torch.empty_like(x)
+    check(lib.afldm_repaint_step(ptr(x), ptr(eps_nhwc), ptr(known), ptr(mask), ptr(noise), noise.stride(0), noise.stride(1),
+                                 ptr(out), ptr(coef), ptr(step_idx), int(advance), B, C, H, W, _code(eps_nhwc), stream_ptr()),
+          "repaint_step")
+    return out
+
+
+def repaint_step_flat(x, eps, known, mask, noises, row, out=None):
+    """x, eps, known, mask: same-shape contiguous fp32 CUDA tensors (the mask expanded to x's shape); noises = (z_k, z_u, z_b),
+    each such a tensor or None where its coefficient (k1, c, u1) is 0; row = the floats (p, q, lo, hi, a, b, c, k0, k1, u0, u1)."""
+    _dev(x, "x"); _dev(eps, "eps"); _dev(known, "known"); _dev(mask, "mask")
+    assert x.dtype == eps.dtype == known.dtype == mask.dtype == torch.float32
+    assert x.shape == eps.shape == known.shape == mask.shape
+    row = [float(c) for c in row[:11]]
+    for z, c, name in zip(noises, (row[8], row[6], row[10]), ("z_k", "z_u", "z_b")):
+        if z is None:
+            if c != 0.0:
+                raise ValueError(f"repaint_step_flat: {name} is None but its coefficient is {c}")
+            continue
+        _dev(z, name)
+        assert z.dtype == torch.float32 and z.shape == x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    check(lib.afldm_repaint_step_flat(ptr(x), ptr(eps), ptr(known), ptr(mask), *[ptr(z) for z in noises], ptr(out), *row,
+                                      x.numel(), stream_ptr()), "repaint_step_flat")
+    return out
+
+
+MASK_MIN, MASK_MEAN = 0, 1
+
+
+def mask_pool(mask, r, mode=MASK_MIN, out=None):
+    """mask fp32 [B, 1, H, W] -> [B, 1, H / r, W / r] over r x r blocks: MASK_MIN (a latent is kept only if every pixel under it is
+    kept) or MASK_MEAN.  r >= 1 must divide H and W."""
+    _dev(mask, "mask")
+    if mask.dtype != torch.float32 or mask.dim() != 4 or mask.shape[1] != 1:
+        raise ValueError(f"mask_pool: mask must be fp32 [B, 1, H, W], got {mask.dtype} {tuple(mask.shape)}")
+    B, _, H, W = mask.shape
+    r = int(r)
+    if r < 1 or H % r or W % r:
+        raise ValueError(f"mask_pool: r = {r} must be >= 1 and divide H = {H} and W = {W}")
+    if out is None:
+        out = torch.empty(B, 1, H // r, W // r, dtype=torch.float32, device=mask.device)
+    check(lib.afldm_mask_pool(ptr(mask), ptr(out), B, H, W, r, int(mode), stream_ptr()), "mask_pool")
+    return out
+
+
 def select_timestep(tvals, step_idx, t_out, pre_advance=False):
     check(lib.afldm_select_timestep(ptr(tvals), ptr(step_idx), ptr(t_out), int(pre_advance), stream_ptr()),
           "select_timestep")

@@ -82,6 +82,10 @@ class MyLDMPipeline(DiffusionPipeline):
         if self.vae is None:
             raise NotImplementedError("this pipeline was built without a VAE: use output_type='latent'")
         decoded = self.vae.decode(latents.to(self.vae.dtype) / self.vae.config.scaling_factor).sample
+        return self._images(decoded, output_type, return_dict)
+
+    def _images(self, decoded, output_type, return_dict):
+        """A decoded tensor in [-1, 1] as `output_type` 'pt', 'np' or 'pil' (_deliver)."""
         if output_type == "pt":
             return decoded
         arrays = (decoded / 2 + 0.5).clamp(0, 1).cpu().permute(0, 2, 3, 1).float().numpy()
@@ -127,3 +131,84 @@ class MyLDMPipeline(DiffusionPipeline):
             eps = self.unet(latent, t).sample
             latent = ops.ddim_step_flat(latent.float().contiguous(), eps.float().contiguous(), coef).to(latent.dtype)
         return latent
+
+    # ------------------------------------------------------------------------------------------------ RePaint inpainting
+    def _refuse_dpm(self, what):
+        if isinstance(self.scheduler, DPMSolverMultistepScheduler):
+            raise NotImplementedError(f"{what} needs a DDIMScheduler: RePaint with {type(self.scheduler).__name__} is not implemented")
+
+    @torch.no_grad()
+    def inpaint_latents(self, known_latents, latent_mask, num_inference_steps=50, eta=0.0, jump_length=10, jump_n_sample=10,
+                        generator=None, latents=None, use_graph=True):
+        """RePaint (Lugmayr et al., CVPR 2022, Algorithm 1; diffusers RePaintPipeline) in latent space: sample latents that agree
+        with `known_latents` [B, C, S, S] where `latent_mask` [B | 1, 1, S, S] is 1 and are generated where it is 0 (soft values
+        blend).  Needs no VAE.  The schedule is DDIMScheduler.repaint_schedule: every UNet evaluation ends in one
+        afldm_repaint_step, on replayed HIP graphs (use_graph) or in the eager loop below, which makes the same draws from
+        `generator` in the same order - the start latents (unless `latents` is given), then per evaluation z_k, z_u, z_b where
+        the schedule draws them - and carries the latents in fp32 like the engine.  Returns latents in the UNet's dtype; with
+        a hard mask the kept latents are `known_latents` exactly (to that dtype)."""
+        from .. import ops
+        self._refuse_dpm("inpaint_latents")
+        c, s = self.unet.config.in_channels, self.unet.config.sample_size
+        if known_latents.dim() != 4 or tuple(known_latents.shape[1:]) != (c, s, s):
+            raise ValueError(f"inpaint_latents: known_latents {tuple(known_latents.shape)}, want [B, {c}, {s}, {s}]")
+        B = known_latents.shape[0]
+        if latent_mask.dim() != 4 or tuple(latent_mask.shape[1:]) != (1, s, s) or latent_mask.shape[0] not in (1, B):
+            raise ValueError(f"inpaint_latents: latent_mask {tuple(latent_mask.shape)}, want [{B} or 1, 1, {s}, {s}]")
+        if latents is not None and tuple(latents.shape) != (B, c, s, s):
+            raise ValueError(f"inpaint_latents: latents {tuple(latents.shape)}, want {(B, c, s, s)}")
+        self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
+        sched = self.scheduler.repaint_schedule(num_inference_steps, eta, jump_length, jump_n_sample)
+        shape, dev = (B, c, s, s), self.unet.device
+        draw = sched.drawer(generator, shape, dev, self.unet.dtype)
+        if latents is None:
+            latents = draw()            # (on the CPU for CPU generators, else on the device: the per-evaluation draws' rule)
+        known = known_latents.to(device=dev, dtype=torch.float32)
+        mask = latent_mask.to(device=dev, dtype=torch.float32)
+        if use_graph:
+            eng = cached_engine(self, "_repaint_engines", sched, B, True, self.unet)
+            eng.scheduler = self.scheduler
+            return eng.run(latents, draw=draw, known=(known, mask)).to(self.unet.dtype)
+        x = (latents.to(device=dev, dtype=torch.float32) * sched.init_noise_sigma).contiguous()
+        known, mask = known.contiguous(), mask.expand(B, c, s, s).contiguous()
+        for k, (t, row) in enumerate(self.progress_bar(list(zip(sched.timesteps, sched.rows)))):
+            on = sched.slots(k)
+            zs = [draw().to(device=dev, dtype=torch.float32).contiguous() if j in on else None for j in range(3)]
+            eps = self.unet(x.to(self.unet.dtype), t).sample
+            x = ops.repaint_step_flat(x, eps.float().contiguous(), known, mask, zs, row)
+        return x.to(self.unet.dtype)
+
+    @torch.no_grad()
+    def inpaint(self, image, mask, num_inference_steps=50, eta=0.0, jump_length=10, jump_n_sample=10, generator=None, latents=None,
+                use_graph=True, mask_mode="min", composite=True, output_type="pil", return_dict=True):
+        """Inpaint `image` [B, 3, H, W] in [-1, 1] where `mask` [B | 1, 1, H, W] is 0 and keep it where the mask is 1.  The image is
+        encoded with the posterior mode times scaling_factor (harness.vae_encode_mode), the mask pooled to the latent grid over
+        the VAE's down-sampling blocks (afldm_mask_pool; mask_mode 'min': a latent is kept only if every pixel under it is,
+        'mean': the kept fraction as a soft mask), the latents sampled by inpaint_latents and decoded.  composite: the result is
+        m image + (1 - m) decoded in pixel space, in fp32, so that kept pixels are the input's exactly.  output_type as
+        __call__; 'latent' returns the sampled latents."""
+        from .. import ops
+        self._refuse_dpm("inpaint")
+        if self.vae is None:
+            raise NotImplementedError("this pipeline was built without a VAE: use inpaint_latents")
+        if mask_mode not in ("min", "mean"):
+            raise ValueError(f"inpaint: mask_mode {mask_mode!r} (want 'min' or 'mean')")
+        r = getattr(self.vae, "downsample_ratio", None) or 2 ** (len(self.vae.config.block_out_channels) - 1)
+        s = self.unet.config.sample_size
+        if image.dim() != 4 or tuple(image.shape[1:]) != (3, s * r, s * r):
+            raise ValueError(f"inpaint: image {tuple(image.shape)}, want [B, 3, {s * r}, {s * r}]")
+        if mask.dim() != 4 or tuple(mask.shape[1:]) != (1, s * r, s * r) or mask.shape[0] not in (1, image.shape[0]):
+            raise ValueError(f"inpaint: mask {tuple(mask.shape)}, want [{image.shape[0]} or 1, 1, {s * r}, {s * r}]")
+        dev = self.unet.device
+        image = image.to(device=dev, dtype=torch.float32)
+        mask = mask.to(device=dev, dtype=torch.float32).contiguous()
+        known = self.vae.encode(image.to(self.vae.dtype)).latent_dist.mode() * self.vae.config.scaling_factor
+        latent_mask = ops.mask_pool(mask, r, ops.MASK_MIN if mask_mode == "min" else ops.MASK_MEAN)
+        out = self.inpaint_latents(known, latent_mask, num_inference_steps, eta, jump_length, jump_n_sample, generator, latents,
+                                   use_graph)
+        if output_type == "latent":
+            return out
+        decoded = self.vae.decode(out.to(self.vae.dtype) / self.vae.config.scaling_factor).sample
+        if composite:
+            decoded = mask * image + (1 - mask) * decoded.float()
+        return self._images(decoded, output_type, return_dict)

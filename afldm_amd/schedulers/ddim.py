@@ -130,6 +130,67 @@ class DDIMScheduler:
         return Schedule.of(self, "sde", ts, lambda t: self.sde_coefficients(t, eta), [True] * len(ts),
                            _ddim_steps=int(num_inference_steps), _ddim_eta=float(eta))
 
+    @staticmethod
+    def repaint_evaluations(num_inference_steps, jump_length, jump_n_sample):
+        """The indices t (N - 1 = the noisiest of the scheduler's timesteps ... 0 = the last) of RePaint's UNet evaluations:
+        diffusers RePaintScheduler.set_timesteps walks down the schedule and, at every multiple of jump_length below
+        N - jump_length, goes back up jump_length indices jump_n_sample - 1 times; the downward moves are the evaluations."""
+        n, jl, js = int(num_inference_steps), int(jump_length), int(jump_n_sample)
+        jumps = {j: js - 1 for j in range(0, n - jl, jl)}
+        t, seq = n, []
+        while t >= 1:
+            t -= 1
+            seq.append(t)
+            if jumps.get(t, 0) > 0:
+                jumps[t] -= 1
+                for _ in range(jl):
+                    t += 1
+                    seq.append(t)
+        return [t for i, t in enumerate(seq) if i == 0 or t < seq[i - 1]]
+
+    def repaint_schedule(self, num_inference_steps, eta=0.0, jump_length=10, jump_n_sample=10):
+        """RePaint inpainting (Lugmayr et al., CVPR 2022, Algorithm 1; diffusers RePaintPipeline / RePaintScheduler) over this
+        scheduler's `num_inference_steps` timesteps g[0] > ... > g[N-1], as the Schedule DenoiseEngine replays with
+        afldm_repaint_step.  Index t stands for g[N-1-t]; level(t) = alphas_cumprod[g[N-1-t]], level(-1) =
+        final_alpha_cumprod.  For evaluation t, with ab = level(t), ab' = level(t-1) and sigma = eta sqrt(DDIM's _get_variance):
+          x0 = clamp((x - sqrt(1-ab) eps) / sqrt(ab));  unknown = sqrt(ab') x0 + sqrt(1 - ab' - sigma^2) eps + sigma z_u
+          known' = sqrt(ab') known + sqrt(1-ab') z_k;   y = m known' + (1 - m) unknown
+        and the last evaluation takes known' = known, so that kept latents are returned exactly.  Where the next evaluation t'
+        is not lower (t' >= t) the sample is noised back up to level(t'): x_out = sqrt(rho) y + sqrt(1 - rho) z_b with rho =
+        level(t') / level(t-1).  That ONE Gaussian step has the same distribution as diffusers' jump_length single-beta
+        `undo_step`s, with one draw where diffusers makes jump_length * stride of them: the sample follows RePaint's law, not
+        diffusers' random stream.  Draws per evaluation, in this order and each only where its coefficient is not 0: z_k, z_u,
+        z_b - one randn_tensor of the latent shape in the model's dtype each."""
+        n, jl, js = int(num_inference_steps), int(jump_length), int(jump_n_sample)
+        if jl < 1 or js < 1:
+            raise ValueError(f"repaint_schedule: jump_length = {jump_length} and jump_n_sample = {jump_n_sample} must be >= 1")
+        if self.config.prediction_type != "epsilon":
+            raise NotImplementedError("afldm_amd.DDIMScheduler.repaint_schedule implements epsilon prediction")
+        self.set_timesteps(n)
+        g = self._timesteps_host
+
+        def level(t):
+            return float(self.alphas_cumprod[g[n - 1 - t]]) if t >= 0 else float(self.final_alpha_cumprod)
+        bound = math.inf
+        if self.config.clip_sample:
+            bound = float(self.config["clip_sample_range"]) if "clip_sample_range" in self.config else 1.0
+        ev = self.repaint_evaluations(n, jl, js)
+        rows, draws = [], []
+        for i, t in enumerate(ev):
+            ab, ab_prev = level(t), level(t - 1)
+            sigma = float(eta) * math.sqrt((1 - ab_prev) / (1 - ab) * (1 - ab / ab_prev))
+            last = i == len(ev) - 1
+            k0, k1 = (1.0, 0.0) if last else (math.sqrt(ab_prev), math.sqrt(1 - ab_prev))
+            u0, u1 = 1.0, 0.0
+            if not last and ev[i + 1] >= t:
+                rho = level(ev[i + 1]) / ab_prev
+                u0, u1 = math.sqrt(rho), math.sqrt(1 - rho)
+            rows.append((1 / math.sqrt(ab), -math.sqrt(1 - ab) / math.sqrt(ab), -bound, bound, math.sqrt(ab_prev),
+                         math.sqrt(max(1 - ab_prev - sigma * sigma, 0.0)), sigma, k0, k1, u0, u1, 0.0))
+            draws.append((k1 != 0.0, sigma != 0.0, u1 != 0.0))
+        return Schedule.of(self, "repaint", [g[n - 1 - t] for t in ev], rows, draws, _repaint_steps=n, _repaint_eta=float(eta),
+                           _repaint_jump_length=jl, _repaint_jump_n_sample=js)
+
     def step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None,
              variance_noise=None, return_dict=True):
         if self.num_inference_steps is None:

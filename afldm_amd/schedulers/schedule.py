@@ -4,12 +4,15 @@ UNet evaluation, fixed when it is made.  `kind` names the update kernel that rea
     "ddim"  (c0, c1, c2, c3):            x0 = (x - c1 eps) / c0;  x_out = c2 x0 + c3 eps                  afldm_ddim_step
     "dpm"   (p, q, a, b0, b1, b2, 0, 0): m0 = p x + q eps;  x_out = a x + b0 m0 + b1 m1 + b2 m2           afldm_dpm_step
     "sde"   (p, q, lo, hi, a, b, d, c):  x0 = clamp(p x + q eps, lo, hi);  x_out = a x + b x0 + d eps + c z   afldm_sde_step
+    "repaint" (p, q, lo, hi, a, b, c, k0, k1, u0, u1, 0):  x0 = clamp(p x + q eps, lo, hi);  unknown = a x0 + b eps + c z_u;
+            y = m (k0 known + k1 z_k) + (1 - m) unknown;  x_out = u0 y + u1 z_b                           afldm_repaint_step
 
 The rows come from the scheduler that owns the update (DDIMScheduler.schedule / stochastic_schedule,
-DPMSolverMultistepScheduler.schedule, I2SBScheduler.ode_schedule / bridge_schedule, MyLDMPipeline.inversion_schedule) as Python
-floats and are rounded once to fp32 by `table`.  An "sde" schedule also states which steps draw noise and how: exactly the
-randn_tensor calls, in the same order, that the scheduler's eager `step()` makes, so that the engine can draw them from the
-caller's generator before the captured graphs need them.  `key` identifies everything the rows were computed from; the engine
+DDIMScheduler.repaint_schedule, DPMSolverMultistepScheduler.schedule, I2SBScheduler.ode_schedule / bridge_schedule,
+MyLDMPipeline.inversion_schedule) as Python floats and are rounded once to fp32 by `table`.  An "sde" schedule also states which
+steps draw noise and how: exactly the randn_tensor calls, in the same order, that the scheduler's eager `step()` makes, so that
+the engine can draw them from the caller's generator before the captured graphs need them.  A "repaint" schedule has up to
+three draws per step and states them per slot: `draws[k]` is (z_k, z_u, z_b), drawn in that order.  `key` identifies everything the rows were computed from; the engine
 cache (engine.cached_engine) compares it, so two schedules with equal keys must replay the same graph."""
 from dataclasses import dataclass
 
@@ -18,7 +21,8 @@ import torch
 from ..configs import FrozenConfig
 from ..utils import randn_tensor
 
-ROW_WIDTH = {"ddim": 4, "dpm": 8, "sde": 8}
+ROW_WIDTH = {"ddim": 4, "dpm": 8, "sde": 8, "repaint": 12}
+NOISE_SLOTS = {"sde": 1, "repaint": 3}          # draws per step at the most; the kinds not named draw nothing
 _MADE = {}          # key -> Schedule: the rows are ~0.1 ms of scalar tensor arithmetic each, and a sampler asks per call
 
 
@@ -37,7 +41,8 @@ class Schedule:
     def of(cls, owner, kind, timesteps, rows, draws=None, noise_dtype=None, **settings):
         """owner: the scheduler whose config the rows are computed from; settings: whatever else they depend on (the step
         count, eta, is_ode, ...); rows: one per timestep, or a function of the timestep that is only called when no schedule
-        with this key has been made yet; draws: per step, whether the eager step draws a noise tensor ("sde" only);
+        with this key has been made yet; draws: per step, whether the eager step draws a noise tensor ("sde"), or which of its three
+        slots do ("repaint": a triple of bools per step);
         noise_dtype: the dtype of that draw (None: the model's dtype, what DDIMScheduler.step draws in)."""
         config = FrozenConfig(dict(owner.config, **settings))
         key = (type(owner).__name__, tuple(sorted((k, repr(v)) for k, v in config.items())))
@@ -47,22 +52,31 @@ class Schedule:
         if callable(rows):
             rows = [rows(t) for t in timesteps]
         rows = tuple(tuple(float(v) for v in r) for r in rows)
-        draws = tuple(bool(d) for d in draws) if draws is not None else (False,) * len(rows)
+        if kind == "repaint":
+            draws = tuple(tuple(bool(v) for v in d) for d in draws)
+            assert all(len(d) == NOISE_SLOTS[kind] for d in draws)
+        else:
+            draws = tuple(bool(d) for d in draws) if draws is not None else (False,) * len(rows)
+            assert kind == "sde" or not any(draws)
         assert len(timesteps) == len(rows) == len(draws) and all(len(r) == ROW_WIDTH[kind] for r in rows)
-        assert kind == "sde" or not any(draws)
         if len(_MADE) >= 64:
             _MADE.clear()
         made = _MADE[key] = cls(kind, timesteps, rows, draws, noise_dtype, float(owner.init_noise_sigma), config, key)
         return made
 
     def table(self, device):
-        """float32 [nsteps, 4 or 8] device table, each entry rounded once from the Python float."""
+        """float32 [nsteps, ROW_WIDTH[kind]] device table, each entry rounded once from the Python float."""
         return torch.tensor(self.rows, dtype=torch.float64).to(torch.float32).to(device)
 
     # read-only spellings of the scheduler-shaped views this type replaced; tests/test_sde_host.py checks every row through them
     update_kind = property(lambda self: self.kind)
     _timesteps_host = property(lambda self: list(self.timesteps))
     coefficient_table = table
+
+    def slots(self, k):
+        """The noise slots step k draws, in drawing order: () or (0,) for "sde", a subset of (0, 1, 2) for "repaint"."""
+        d = self.draws[k]
+        return tuple(j for j, on in enumerate(d) if on) if isinstance(d, tuple) else ((0,) if d else ())
 
     def draw_noise(self, shape, generator, device, model_dtype):
         """One step's noise, as the eager step draws it: randn_tensor(shape, generator, device, dtype).  With a CPU generator

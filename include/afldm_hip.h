@@ -461,6 +461,32 @@ int afldm_dpm_step_flat(const float* x, const float* eps, float* x_out, float* h
 int afldm_sde_step(const float* x, const void* eps, const float* noise, size_t noise_step_stride, float* x_out,
                    const float* coef, int* step_idx, int advance, int B, int C, int H, int W, int dtype,
                    afldm_stream_t stream);
+/* ---- RePaint inpainting update (Lugmayr et al., CVPR 2022, Algorithm 1; diffusers RePaintPipeline) -------------
+ * Step s = *step_idx applies the row coef[12 s .. 12 s + 12) = (p, q, lo, hi, a, b, c, k0, k1, u0, u1, 0) and the three noise
+ * slots z_k, z_u, z_b = noise[s * noise_step_stride + slot * noise_slot_stride + i], slot = 0, 1, 2:
+ *   x0      = clamp(p x + q eps, lo, hi)              lo = -inf, hi = +inf: no clip; a NaN passes through
+ *   unknown = a x0 + b eps + c z_u                    the DDIM reverse step of the generated part
+ *   knownp  = k0 known + k1 z_k                       the kept latents, noised to the same level
+ *   y       = m knownp + (1 - m) unknown              m = mask[b, 0, h, w], 1 = keep, soft values allowed
+ *   x_out   = u0 y + u1 z_b                           the jump back up the schedule, one Gaussian step
+ * A slot whose coefficient (k1, c, u1) is exactly 0 is not read: what an unused slot holds does not reach x_out.
+ * x, known, x_out: NCHW fp32 [B,C,H,W], x_out may alias x; mask: fp32 [B,1,H,W]; eps: NHWC dtype; noise: fp32 slots of
+ * [B,C,H,W] NCHW (noise_slot_stride >= B*C*H*W, noise_step_stride >= 2 noise_slot_stride + B*C*H*W: a branch passes its
+ * batch slice of a [steps,3,B,C,H,W] buffer), drawn by the caller's generator outside any captured graph; step_idx /
+ * advance as the DDIM update above. */
+int afldm_repaint_step(const float* x, const void* eps, const float* known, const float* mask, const float* noise,
+                       size_t noise_step_stride, size_t noise_slot_stride, float* x_out, const float* coef, int* step_idx,
+                       int advance, int B, int C, int H, int W, int dtype, afldm_stream_t stream);
+/* Same update on flat same-layout fp32 tensors of n elements (the mask expanded to that layout too), the row by value, for
+ * an eager loop.  z_k / z_u / z_b may be NULL where k1 / c / u1 is 0. */
+int afldm_repaint_step_flat(const float* x, const float* eps, const float* known, const float* mask, const float* z_k,
+                            const float* z_u, const float* z_b, float* x_out, float p, float q, float lo, float hi, float a,
+                            float b, float c, float k0, float k1, float u0, float u1, size_t n, afldm_stream_t stream);
+/* Pixel mask -> latent mask: mask fp32 [B,1,H,W] -> out fp32 [B,1,H/r,W/r] over r x r blocks, any r >= 1 dividing H and W.
+ * AFLDM_MASK_MIN: the block minimum (a latent is kept only if every pixel under it is kept); AFLDM_MASK_MEAN: the block
+ * mean (summed in fp64, rounded once). */
+enum { AFLDM_MASK_MIN = 0, AFLDM_MASK_MEAN = 1 };
+int afldm_mask_pool(const float* mask, float* out, int B, int H, int W, int r, int mode, afldm_stream_t stream);
 /* tvals[step] -> t_out[0] (device->device), so the timestep also follows step_idx.  pre_advance != 0:
  * step_idx is incremented first (a sampler loop then starts from step_idx = -1 and needs no `advance`
  * launch behind afldm_ddim_step). */
