@@ -2102,21 +2102,26 @@ static void fill_convp(const afldm_conv_args* a, ConvP& p) {
   p.sc_C1 = a->sc_x1 ? a->sc_C1 : 0; p.sc_C2 = a->sc_x1 ? a->sc_C2 : 0;
 }
 
-// the 1x1 conv_shortcut folded into this 3x3 convolution (afldm_conv_args.sc_*): one k_conv3h launch with one tap per K step and
-// the whole K per workgroup; the shortcut's channel blocks must lie inside one of the two inputs, and no residual
+// the 1x1 conv_shortcut folded into this 3x3 convolution (afldm_conv_args.sc_*): one k_conv3h launch, either with one tap per K
+// step and the whole K per workgroup (returns 1), or with three taps per step - the 8^2 / 4^2 tiles and every tile of the small
+// batches - where K may be split, the slices sharing the shortcut's blocks, the slabs handed to afldm_af_act_slabs (defer_reduce)
+// or the GroupNorm that follows applied by the epilogue (y_norm) (returns 2); the shortcut's channel blocks must lie inside one
+// of the two inputs, and no residual.  0: not available.
 template <typename T>
-static bool shortcut_ok(const afldm_conv_args* a) {
+static int shortcut_ok(const afldm_conv_args* a) {
   const int kstep = KCH_DEFAULT * epr<T>();
   const long long M = (long long)a->B * a->H * a->W, Csc = (long long)a->sc_C1 + a->sc_C2;
   if (!a->sc_x1 || !a->sc_w || a->sc_C1 <= 0 || a->sc_C2 < 0 || a->sc_C1 % kstep || a->sc_C2 % kstep || (a->sc_C2 > 0) != (a->sc_x2 != nullptr))
-    return false;
-  if (!aligned16(a->sc_x1) || !aligned16(a->sc_x2) || !aligned16(a->sc_w)) return false;
-  if (a->KS != 3 || a->residual || a->defer_reduce || a->w_batch_stride || a->y_norm || a->y2 || a->out_mode != 0) return false;
+    return 0;
+  if (!aligned16(a->sc_x1) || !aligned16(a->sc_x2) || !aligned16(a->sc_w)) return 0;
+  if (a->KS != 3 || a->residual || a->w_batch_stride || a->y2 || a->out_mode != 0) return 0;
   const long long cmax = a->sc_C1 > a->sc_C2 ? a->sc_C1 : a->sc_C2;
-  if (M >= (1ll << 28) || M * cmax * (long long)sizeof(T) >= (1ll << 31) || (long long)a->Cout * Csc * (long long)sizeof(T) >= (1ll << 31)) return false;
-  if (lin_wreg_bm(a) || skinny_stats_splits(a)) return false;
+  if (M >= (1ll << 28) || M * cmax * (long long)sizeof(T) >= (1ll << 31) || (long long)a->Cout * Csc * (long long)sizeof(T) >= (1ll << 31)) return 0;
+  if (lin_wreg_bm(a) || skinny_stats_splits(a)) return 0;
   const Exec ex = resolve_exec<T>(a);
-  return ex.pl.kind == 0 && kVariants[ex.vid].ver == 6 && ex.splitk == 1 && !ex.fused && conv3h_shortcut_ok(ex.vid);
+  if (ex.pl.kind != 0 || kVariants[ex.vid].ver != 6 || ex.fused || !conv3h_shortcut_ok(ex.vid)) return 0;
+  if (conv3h_taps_per_step(ex.vid) == 3) return (a->defer_reduce && ex.splitk == 1) ? 0 : 2;     // (deferred: there must be slabs to hand over)
+  return (ex.splitk == 1 && !a->defer_reduce && !a->y_norm) ? 1 : 0;
 }
 
 // 8-channel-block operands (afldm_conv_args.x_layout / y_layout = 1): only where afldm_conv2d is ONE halo-patch launch with the
@@ -2363,8 +2368,8 @@ extern "C" int afldm_conv2d_norm_ok(const afldm_conv_args* a) {
 
 extern "C" int afldm_conv2d_shortcut_ok(const afldm_conv_args* a) {
   if (!a || conv_validate(a) || conv_batch_chunk(a) != a->B) return 0;
-  if (a->dtype == AFLDM_BF16) return shortcut_ok<bf16>(a) ? 1 : 0;
-  if (a->dtype == AFLDM_F32) return shortcut_ok<float>(a) ? 1 : 0;
+  if (a->dtype == AFLDM_BF16) return shortcut_ok<bf16>(a);
+  if (a->dtype == AFLDM_F32) return shortcut_ok<float>(a);
   return 0;
 }
 

@@ -485,12 +485,18 @@ bool conv3h_supported(int variant, int dtype_size, const ConvP& p) {
          p.Cout % 4 == 0 && aligned16(p.y) && aligned16(p.x1) && aligned16(p.w);
 }
 
-// the folded 1x1 shortcut (ConvP.sc_*) runs as one-tap K steps: k_conv3h variants with one tap per step over whole planes
+// the folded 1x1 shortcut (ConvP.sc_*) runs as centre-tap K steps of one channel block each: k_conv3h variants over whole planes,
+// with one tap per step (whole K per workgroup) or three (split-K allowed: a slice takes its share of the shortcut blocks)
 bool conv3h_shortcut_ok(int variant) {
   const int k = variant - kConv3hFirst;
   if (k < 0 || k >= kNumH3 || k == 22 || k == 23) return false;       // (22 / 23: k_conv3h_pers)
   const H3Variant& v = kH3[k];
-  return v.bm != 0 && v.tps == 1 && !v.sub && !(v.bm == 256 && v.w == 16);      // (the HAS_SC condition of conv3h_body.inc)
+  return v.bm != 0 && !v.sub && !(v.bm == 256 && v.w == 16) && !(v.tps == 3 && v.bn == 48);      // (the HAS_SC condition of conv3h_body.inc)
+}
+
+int conv3h_taps_per_step(int variant) {
+  const int k = variant - kConv3hFirst;
+  return (k < 0 || k >= kNumH3) ? 0 : kH3[k].tps;
 }
 
 template <typename T, int BM, int W_, int BN, int WGM, int WGN, int MF, int TPS, int STAGES = 3, bool SUB = false, int NPROD = 4, int MINW_ = 0>

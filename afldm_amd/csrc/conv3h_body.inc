@@ -18,6 +18,7 @@
   constexpr int SPC = 9 / TPS;                                   // K steps per channel block
   constexpr int WIT = BN / 8;                                    // weight instructions per tap
   constexpr int WI = TPS * WIT, WPW = WI / NPROD, PPW = (NPI + NPROD - 1) / NPROD;
+  constexpr int WPS = WPW / TPS;                                 // weight instructions per wave of a folded-shortcut step: ONE tap's worth
   constexpr int W_TAP = BN * 128, W_STAGE = TPS * W_TAP;
   constexpr int LDS_TOTAL = 2 * PATCH + STAGES * W_STAGE;
   constexpr unsigned OOB = 0x80000000u;
@@ -25,6 +26,7 @@
   static_assert(TPS == 1 || TPS == 3, "taps per step");
   static_assert(BM % W_ == 0 && ROWS % SEG == 0 && WI % NPROD == 0 && WMS % MF == 0 && WNS % MF == 0, "tile shape");
   static_assert((STAGES - 2) * WPW + PPW < 64, "vmcnt is a 6-bit counter");
+  static_assert(TPS == 1 || (STAGES == 3 && WIT % NPROD == 0), "three taps per step: a wave's first WPS instructions are the stage's first tap slot");
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave_all = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -55,11 +57,16 @@
   const int ncb = Ct / KSTEP;
   const int ks = H3_BZ;
   const int cb_lo = (ncb * ks) / p.splitk, cb_hi = (ncb * (ks + 1)) / p.splitk;   // this slice's channel blocks
-  // folded 1x1 shortcut (TPS == 1, whole K: conv3h_shortcut_ok): its nsc channel blocks follow the 3x3 ones as blocks cb_hi ..
-  // cb_end - 1 of ONE K step each - the centre tap of a patch whose halo is left zero (never read: no bytes fetched for it)
-  // (not on the 256-pixel tiles of whole 16x16 samples, variants 44 / 49: the extra loop spills there, and no shortcut site runs them)
-  constexpr bool HAS_SC = TPS == 1 && !SUB && !(BM == 256 && W_ == 16);
-  const int nsc = (HAS_SC && p.sc_x1) ? (p.sc_C1 + p.sc_C2) / KSTEP : 0;
+  // folded 1x1 shortcut (conv3h_shortcut_ok): its nsc channel blocks follow the 3x3 ones as blocks cb_hi .. cb_end - 1 of ONE K
+  // step each - the centre tap of a patch whose halo is left zero (never read: no bytes fetched for it).  Three taps per step:
+  // such a step fills the stage's first tap slot only; split-K slice ks takes the shortcut blocks [sc_lo, sc_lo + nsc) behind
+  // its own 3x3 blocks (the shares may differ by one; the slabs then carry conv + shortcut partial sums).
+  // (not on the 256-pixel tiles of whole 16x16 samples, variants 44 / 49: the extra loop spills there; not on the 48-cout tiles,
+  //  variants 67 / 68: 92 -> 102 / 137 VGPRs with it; no shortcut site runs either - conv2's K is never long enough for them)
+  constexpr bool HAS_SC = !SUB && !(BM == 256 && W_ == 16) && !(TPS == 3 && BN == 48);
+  const int nsc_all = (HAS_SC && p.sc_x1) ? (p.sc_C1 + p.sc_C2) / KSTEP : 0;
+  const int sc_lo = TPS == 3 ? (nsc_all * ks) / p.splitk : 0;
+  const int nsc = TPS == 3 ? (nsc_all * (ks + 1)) / p.splitk - sc_lo : nsc_all;
   const int cb_end = cb_hi + nsc;
   const int Gm = (cb_hi - cb_lo) * SPC, G = Gm + nsc;
   int m0, b_tile, oh0, ow0 = 0, sp_tile;                         // first pixel, sample, tile origin, tile index inside the sample
@@ -132,10 +139,11 @@
     auto issue_weights = [&]() {
       char* sbase = smem + 2 * PATCH + is_slot * W_STAGE;
       if (HAS_SC && is_g >= Gm && is_g < G) {
-        // shortcut step: the 1x1 weight rows [n0, n0 + BN) x channel block is_g - Gm, laid out as one tap of the 3x3 stream
-        const unsigned so = (unsigned)((is_g - Gm) * KSTEP * ESZ);
+        // shortcut step: the 1x1 weight rows [n0, n0 + BN) x channel block sc_lo + is_g - Gm, laid out as one tap of the 3x3
+        // stream (three taps per step: instructions j < WIT of the stage, i.e. a wave's first WPS - the other two slots stay as they are)
+        const unsigned so = (unsigned)((sc_lo + is_g - Gm) * KSTEP * ESZ);
 #pragma unroll
-        for (int i = 0; i < WPW; ++i) {
+        for (int i = 0; i < WPS; ++i) {
           const int r = 8 * (wave + NPROD * i) + (lane >> 3);
           const unsigned wo = ((unsigned)(n0 + r) * (unsigned)Csc + (unsigned)(h_chunk_at<MF>(lane & 7, h_sw_rows<MF>(r)) * EPC)) * ESZ;
           lds_ptr_t dst = (lds_ptr_t)(sbase + (wave + NPROD * i) * 1024);
@@ -164,7 +172,7 @@
         // shortcut block j: channels [j KSTEP, (j + 1) KSTEP) of the virtual concat sc_x1 | sc_x2 (NHWC); only the tile's own
         // pixels are fetched (the centre tap never reads the halo), addresses recomputed here - nine times a tile - rather
         // than kept in registers
-        const int c0 = (cb - cb_hi) * KSTEP;
+        const int c0 = (sc_lo + cb - cb_hi) * KSTEP;
         const bool in1 = c0 < p.sc_C1;
         const int Cs = in1 ? p.sc_C1 : p.sc_C2;
         __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(in1 ? p.sc_x1 : p.sc_x2), 0,
@@ -200,9 +208,24 @@
       // in flight behind the weights of step g: the weights of steps g+1 .. g+STAGES-2, and - for the STAGES-1 steps
       // after a patch issue - that patch (issued behind step g+STAGES-1's weights of its iteration).  A shortcut block is
       // one step long, so the next one's patch goes out IN FRONT of that step's weights and only those may stay in flight.
-      if (fresh) wait_vmcnt<(STAGES >= 3 ? WPW : 0)>();
-      else if (since <= STAGES - 1) wait_vmcnt<(STAGES - 2) * WPW + PPW>();
-      else wait_vmcnt<(STAGES - 2) * WPW>();
+      if constexpr (TPS == 1) {
+        if (fresh) wait_vmcnt<(STAGES >= 3 ? WPW : 0)>();
+        else if (since <= STAGES - 1) wait_vmcnt<(STAGES - 2) * WPW + PPW>();
+        else wait_vmcnt<(STAGES - 2) * WPW>();
+      } else {
+        // three-slot stages (STAGES == 3): behind step g's weights lie step g + 1's - WPS instructions when that is a shortcut
+        // step, else WPW (the zero-fill tail included) - and a patch issued one or two steps ago in front of a 3x3 block;
+        // a shortcut block's patch (fresh) lies in FRONT of step g + 1's weights and is waited for
+        const bool sc_next = HAS_SC && g + 1 >= Gm && g + 1 < G;
+        const bool patch_behind = !fresh && since <= STAGES - 1;
+        if (sc_next) {
+          if (patch_behind) wait_vmcnt<WPS + PPW>();
+          else wait_vmcnt<WPS>();
+        } else {
+          if (patch_behind) wait_vmcnt<WPW + PPW>();
+          else wait_vmcnt<WPW>();
+        }
+      }
       __builtin_amdgcn_s_barrier();
       ++since;
       fresh = false;
@@ -364,19 +387,21 @@
       }
       step_end();
     };
-    auto k_step = [&](auto ST) {
+    auto k_step = [&](auto ST) {                        // ST = -2 (TPS == 3): a folded-shortcut step - the centre tap against the stage's first slot
       constexpr int sst = decltype(ST)::value;
+      constexpr int NT = sst == -2 ? 1 : TPS;              // taps of this step
       if (!(p.dbg & 2)) {
         const char* sP = smem + pbuf * PATCH;
         const char* sW = smem + 2 * PATCH + slot * W_STAGE;
-        int boff[TPS][TM];
+        int boff[NT][TM];
 #pragma unroll
-        for (int ti = 0; ti < TPS; ++ti) {
+        for (int ti = 0; ti < NT; ++ti) {
           const int tap = st * TPS + ti;                         // TPS == 3: kh = st, kw = ti
           const int tapoff = (tap / 3) * PW + (tap - (tap / 3) * 3);
 #pragma unroll
           for (int t = 0; t < TM; ++t) {
             if constexpr (sst >= 0) boff[ti][t] = btab[sst * TPS + ti][t];
+            else if constexpr (sst == -2) boff[ti][t] = btab[TPS == 3 ? 4 : 0][t];
             else boff[ti][t] = frag_off(qb[t] + tapoff);
           }
         }
@@ -384,7 +409,7 @@
         // pixel fragments each): weight fragment i + AD is requested when group i starts, the pixel fragments of the
         // next phase in the middle of the current one.  (Left alone the compiler rotates two weight buffers with a
         // distance of ONE group: every group then waits out an LDS round trip.)
-        constexpr int NPH = TPS * NKK, NG = NPH * TN, AD = 3;
+        constexpr int NPH = NT * NKK, NG = NPH * TN, AD = 3;
         Chunk af[NG], bf[NPH][TM];
         auto lda = [&](int i) {
           const int ph = i / TN, ti = ph / NKK, kk = ph - ti * NKK;
@@ -454,13 +479,21 @@
       g = NRS;
     }
     if constexpr (TPS == 3) {
-      for (; g < G; g += 3) {                            // G - g is a multiple of SPC = 3
+      for (; g < Gm; g += 3) {                           // Gm - g is a multiple of SPC = 3
         __builtin_amdgcn_s_barrier();
         k_step(std::integral_constant<int, 0>{});
         __builtin_amdgcn_s_barrier();
         k_step(std::integral_constant<int, 1>{});
         __builtin_amdgcn_s_barrier();
         k_step(std::integral_constant<int, 2>{});
+      }
+      if constexpr (HAS_SC) {
+        for (; g < G; ++g) {                             // folded shortcut: one centre-tap step per channel block
+          __builtin_amdgcn_s_barrier();
+          k_step(std::integral_constant<int, -2>{});
+          st = 0;
+          pbuf ^= 1;
+        }
       }
     } else {
       for (; g < Gm; ++g) {

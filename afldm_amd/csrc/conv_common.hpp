@@ -50,9 +50,10 @@ struct ConvP {
   // 2x2 / 4x4 levels) - requested non-temporal (LDS-DMA aux = 2 / `nt` loads) so that it does not displace the activations the
   // next launches re-read from the L2s (MI355X_MICROARCH "nt-weights"; AFLDM_NT_WEIGHTS=0: off, A/B)
   int w_nt;
-  // the 1x1 conv_shortcut of a ResnetBlock2D folded into this 3x3 convolution (halo-patch kernel, one tap per step, whole K per
-  // workgroup): sc_x1 | sc_x2 NHWC [M][sc_C1] | [M][sc_C2] (the block input, a virtual concat), sc_w [Cout][sc_C1 + sc_C2] (the 1x1
-  // weight, OHWI).  Its channel blocks run as extra centre-tap K steps behind the 3x3 taps; sc_x1 == NULL: no shortcut.
+  // the 1x1 conv_shortcut of a ResnetBlock2D folded into this 3x3 convolution (halo-patch kernel; one tap per step and the whole K
+  // per workgroup, or three taps per step with K possibly split): sc_x1 | sc_x2 NHWC [M][sc_C1] | [M][sc_C2] (the block input, a
+  // virtual concat), sc_w [Cout][sc_C1 + sc_C2] (the 1x1 weight, OHWI).  Its channel blocks run as extra centre-tap K steps behind
+  // the 3x3 taps of the workgroup's K slice, each slice taking its share of them; sc_x1 == NULL: no shortcut.
   const void* sc_x1;
   const void* sc_x2;
   const void* sc_w;
@@ -70,6 +71,7 @@ __device__ __forceinline__ void wait_vmcnt() {
 constexpr int kConv3hFirst = 41;
 bool conv3h_supported(int variant, int dtype_size, const ConvP& p);      // p.splitk = the planned K slices
 bool conv3h_shortcut_ok(int variant);                                    // k_conv3h of this variant folds a 1x1 shortcut (ConvP.sc_*)
+int conv3h_taps_per_step(int variant);                                   // filter taps per K step of a k_conv3h variant (1 / 3; 0: no such variant)
 int conv3h_tile(int variant, int* bm, int* bn);
 void conv3h_launch(int variant, int dtype_size, const ConvP& p, hipStream_t st);
 // conv.hip: true when afldm_conv2d(a) is ONE k_conv3h launch (whole K per workgroup, statistics from its epilogue); fills the

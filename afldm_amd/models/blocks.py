@@ -34,6 +34,10 @@ _C8_EDGES = int(os.environ.get("AFLDM_C8_EDGES", "5"))
 # one bias b2 + b_sc - where afldm_conv2d_shortcut_ok allows it, instead of a launch of its own whose output conv2 re-reads as its
 # residual.  AFLDM_NO_SHORTCUT_FOLD=1: the two launches (A/B).
 _SC_FOLD = os.environ.get("AFLDM_NO_SHORTCUT_FOLD", "0") != "1"
+# The same fold on the halo-patch tiles that take THREE filter taps per K step (the 8^2 / 4^2 levels - split-K slabs included -
+# and every level at the small batches), a switch of its own so that the two are A/B-able independently (_SC_FOLD keeps meaning
+# the one-tap tiles).  AFLDM_NO_SHORTCUT_FOLD3=1: the two launches there.
+_SC_FOLD3 = os.environ.get("AFLDM_NO_SHORTCUT_FOLD3", "0") != "1"
 
 
 def _pair(x):
@@ -468,10 +472,11 @@ class ResnetBlock2D(nn.Module):
         return cache["sc_bias"]
 
     def _sc_fold_plan(self, input_tensor, c8):
-        """True when conv2 takes the 1x1 conv_shortcut as extra K steps (afldm_conv2d_shortcut_ok: one halo-patch launch with one
-        filter tap per step - the 32^2 / 16^2 levels at the larger batches) instead of its output as the residual.  c8: conv2 reads
-        8-channel blocks.  Only booleans are cached here (the packed weights live in the modules' `_afldm_cache`)."""
-        if (not _SC_FOLD or self.conv_shortcut is None or tuple(self.conv_shortcut.kernel_size) != (1, 1)
+        """True when conv2 takes the 1x1 conv_shortcut as extra K steps (afldm_conv2d_shortcut_ok) instead of its output as the
+        residual: on a halo-patch tile with one filter tap per step (the 32^2 / 16^2 levels at the larger batches; _SC_FOLD, plans
+        cached in `_afldm_sc_fold`) or with three (the 8^2 / 4^2 levels, the small batches; _SC_FOLD3, `_afldm_sc_fold3`).  c8: conv2
+        reads 8-channel blocks.  Only booleans are cached here (the packed weights live in the modules' `_afldm_cache`)."""
+        if ((not _SC_FOLD and not _SC_FOLD3) or self.conv_shortcut is None or tuple(self.conv_shortcut.kernel_size) != (1, 1)
                 or tuple(self.conv2.kernel_size) != (3, 3)):
             return False
         x1, x2 = _pair(input_tensor)
@@ -479,15 +484,26 @@ class ResnetBlock2D(nn.Module):
             return False
         B, N = x1.shape[0], x1.shape[1]
         key = (B, N, x1.shape[-1], None if x2 is None else x2.shape[-1], x1.dtype, x1.device, bool(c8))
-        cache = self.__dict__.setdefault("_afldm_sc_fold", {})
-        if key not in cache:
+
+        def kind():
             w2, _ = packed_conv(self.conv2, x1.dtype)
             wsc, _ = packed_conv(self.conv_shortcut, x1.dtype)
             h_in = torch.empty((B, N, N, self.out_channels), dtype=x1.dtype, device=x1.device)
             if c8:
                 h_in.c8 = True
-            cache[key] = ops.conv2d_shortcut_ok(h_in, w2, self._sc_bias(), (x1, x2, wsc))
-        return cache[key]
+            return ops.conv2d_shortcut_ok(h_in, w2, self._sc_bias(), (x1, x2, wsc))
+        if _SC_FOLD:
+            cache = self.__dict__.setdefault("_afldm_sc_fold", {})
+            if key not in cache:
+                cache[key] = kind() == 1
+            if cache[key]:
+                return True
+        if _SC_FOLD3:
+            cache = self.__dict__.setdefault("_afldm_sc_fold3", {})
+            if key not in cache:
+                cache[key] = kind() == 2
+            return cache[key]
+        return False
 
     def _conv2_sc_folded(self, h, input_tensor, next_gn):
         """conv2(h) + conv_shortcut(input_tensor) as ONE launch (see _sc_fold_plan); with next_gn, the attention block's GroupNorm
@@ -497,6 +513,9 @@ class ResnetBlock2D(nn.Module):
         wsc, _ = packed_conv(self.conv_shortcut, h.dtype)
         kw = {}
         if next_gn is not None:
+            out = self._conv2_to_next_norm_fused(h, None, next_gn, shortcut=(x1, x2, wsc))       # 4x4 planes: split-K slabs
+            if out is not None:
+                return out
             gamma, beta = packed_norm(next_gn)
             kw["norm_out"] = (gamma, beta, next_gn.num_groups, next_gn.eps)
         out = ops.conv2d(h, w2, self._sc_bias(), want_stats=True, shortcut=(x1, x2, wsc), **kw)
@@ -564,21 +583,27 @@ class ResnetBlock2D(nn.Module):
         return ops.af_act_slabs(slabs, nslab, bias, temb_proj, temb_stride, gamma, beta, norm.num_groups, norm.eps,
                                 B, N, Cout, h.dtype)
 
-    def _conv2_to_next_norm_fused(self, h, res, next_gn):
+    def _conv2_to_next_norm_fused(self, h, res, next_gn, shortcut=None):
         """conv2 (+ shortcut) of this block straight into the GroupNorm of the attention block that follows, on the
         2x2 / 4x4 planes when conv2 splits K (afldm_af_act_slabs, act = 0): the reduction launch and the GroupNorm
-        pass become one.  Returns this block's output with the normalised tensor attached as `.gn_applied =
-        (tensor, norm module)` for AttnProcessor2_0, or None when the shape / plan does not qualify."""
+        pass become one.  shortcut = (x1, x2, packed 1x1 weight) instead of `res`: the slabs carry the folded shortcut
+        (see _sc_fold_plan), the bias is b2 + b_sc and there is no residual.  Returns this block's output with the normalised
+        tensor attached as `.gn_applied = (tensor, norm module)` for AttnProcessor2_0, or None when the shape / plan does not qualify."""
         if (os.environ.get("AFLDM_NO_FUSED_ACT") or isinstance(h, tuple) or h.ndim != 4 or h.shape[1] != h.shape[2]
                 or h.shape[1] not in (2, 4)):
             return None
         B, N, _, Cin = h.shape
         conv = self.conv2
         Cout = conv.out_channels
-        if (tuple(conv.kernel_size) != (3, 3) or Cout % next_gn.num_groups or Cin % 8 or Cout % 8
-                or next_gn.num_channels != Cout or res.shape[-1] != Cout or not res.is_contiguous()):
+        if (tuple(conv.kernel_size) != (3, 3) or Cout % next_gn.num_groups or Cin % 8 or Cout % 8 or next_gn.num_channels != Cout
+                or (shortcut is None and (res.shape[-1] != Cout or not res.is_contiguous()))):
             return None          # (afldm_af_act_slabs reads the residual as dense [B, N, N, Cout]: no res_ld)
-        if N == 2 and not os.environ.get("AFLDM_NO_DENSE2X2"):
+        if shortcut is not None:
+            w, _ = packed_conv(conv, h.dtype)
+            if N == 2 or ops.conv2d_shortcut_ok(h, w, None, shortcut, slabs=True) != 2:
+                return None
+            got = ops.conv2d_slabs(h, w, shortcut=shortcut)
+        elif N == 2 and not os.environ.get("AFLDM_NO_DENSE2X2"):
             w2, _ = packed_conv_dense2x2(conv, h.dtype, Cin, 0)
             got = ops.conv2d_slabs(h.reshape(B, 4 * Cin), w2)
         else:
@@ -591,7 +616,8 @@ class ResnetBlock2D(nn.Module):
         cache = conv.__dict__.setdefault("_afldm_cache", {})
         if "bias_f32" not in cache:
             cache["bias_f32"] = None if conv.bias is None else conv.bias.detach().to(torch.float32).contiguous()
-        hn, y = ops.af_act_slabs(slabs, nslab, cache["bias_f32"], None, 0, gamma, beta, next_gn.num_groups, next_gn.eps,
+        hn, y = ops.af_act_slabs(slabs, nslab, self._sc_bias() if shortcut is not None else cache["bias_f32"], None, 0, gamma, beta,
+                                 next_gn.num_groups, next_gn.eps,
                                  B, N, Cout, h.dtype, residual=res, want_raw=True, act=False)
         y.gn_applied = (hn, next_gn)
         return y

@@ -785,22 +785,27 @@ def _set_shortcut(a, shortcut):
     a.keep = a.keep + (sx1, sx2, sw)
 
 
-def conv2d_shortcut_ok(x1, w, bias, shortcut, temb=None, temb_stride=0, want_stats=True):
-    """True when conv2d(x1, w, bias, shortcut=(sx1, sx2, sw)) runs the 1x1 shortcut inside the 3x3 convolution itself
-    (afldm_conv2d_shortcut_ok): one halo-patch launch, whole K per workgroup.  The probe carries what the real launch carries."""
+def conv2d_shortcut_ok(x1, w, bias, shortcut, temb=None, temb_stride=0, want_stats=True, slabs=False):
+    """Non-zero when conv2d(x1, w, bias, shortcut=(sx1, sx2, sw)) - slabs: conv2d_slabs(x1, w, shortcut=...) - runs the 1x1
+    shortcut inside the 3x3 convolution itself (afldm_conv2d_shortcut_ok): 1 on a halo-patch tile with one filter tap per K step
+    (whole K per workgroup), 2 on one with three taps per step (the 8^2 / 4^2 levels, the small batches; K may be split there).
+    The probe carries what the real launch carries, the split-K workspace included."""
     sx1, sx2, sw = shortcut
     if x1.ndim != 4 or sx1.ndim != 4 or w.shape[1] != 3 or sw.shape[1] != 1:
-        return False
+        return 0
     key = (tuple(x1.shape), is_c8(x1), x1.dtype, tuple(w.shape), tuple(sx1.shape), None if sx2 is None else tuple(sx2.shape),
-           temb is not None, int(temb_stride), bool(want_stats), str(x1.device))
+           temb is not None, int(temb_stride), bool(want_stats), bool(slabs), str(x1.device))
     if key not in _SC_OK:
-        a = conv_args(x1, w, bias, None, temb, temb_stride, None, None)
+        a = conv_args(x1, w, None if slabs else bias, None, temb, temb_stride, None, None)
         a.y = ptr(sx1)                 # (a non-NULL, aligned placeholder: the queries do not dereference it)
-        if want_stats and w.shape[0] % 4 == 0:
+        if want_stats and not slabs and w.shape[0] % 4 == 0:
             a.stats_out = ptr(sx1)
         _set_shortcut(a, shortcut)
-        # (a plan that would split K given the room is not the one-launch halo kernel)
-        _SC_OK[key] = (not lib.afldm_conv2d_workspace(ctypes.byref(a))) and bool(lib.afldm_conv2d_shortcut_ok(ctypes.byref(a)))
+        need = lib.afldm_conv2d_workspace(ctypes.byref(a))
+        if need:                       # (the plan splits K when it is given the room, as conv2d / conv2d_slabs give it)
+            a.workspace, a.workspace_bytes = ptr(sx1), need
+        a.defer_reduce = 1 if slabs else 0
+        _SC_OK[key] = int(lib.afldm_conv2d_shortcut_ok(ctypes.byref(a))) if (need or not slabs) else 0
     return _SC_OK[key]
 
 
@@ -993,13 +998,17 @@ def actconv_error(device=None):
     return worst
 
 
-def conv2d_slabs(x1, w, x2=None):
+def conv2d_slabs(x1, w, x2=None, shortcut=None):
     """The split-K slabs of conv2d(x1 | x2, w) WITHOUT the reduction launch (afldm_conv_args.defer_reduce): returns
     (slabs fp32 [nslab, M, Cout], nslab), or None when the plan for this shape does not split K (the caller then runs
-    the ordinary conv2d).  Bias, time embedding and residual are NOT applied: the consumer (af_act_slabs) adds them."""
+    the ordinary conv2d).  Bias, time embedding and residual are NOT applied: the consumer (af_act_slabs) adds them.
+    shortcut = (sx1, sx2, sw): the slabs carry conv3x3 + the folded 1x1 shortcut (conv2d_shortcut_ok(..., slabs=True));
+    the consumer then takes the sum of both biases and no residual."""
     Cout = w.shape[0]
     out = torch.empty(tuple(x1.shape[:-1]) + (Cout,), dtype=x1.dtype, device=x1.device)      # (never written when K is split)
     a = conv_args(x1, w, None, x2, out=out)
+    if shortcut is not None:
+        _set_shortcut(a, shortcut)
     need = lib.afldm_conv2d_workspace(ctypes.byref(a))
     if not need:
         return None
@@ -1018,7 +1027,8 @@ def conv2d_slabs(x1, w, x2=None):
         es = x1.element_size()
         kind = "conv3x3" if a.KS == 3 else ("conv1x1" if a.H * a.W > 1 and x1.ndim == 4 else "linear")
         keep = (a, workspace, out)
-        _end(tok, kind, 2.0 * M * a.Cout * a.KS * a.KS * Ct, (M * Ct + a.Cout * a.KS * a.KS * Ct + M * a.Cout) * es,
+        Csc = a.sc_C1 + a.sc_C2 if shortcut is not None else 0
+        _end(tok, kind, 2.0 * M * a.Cout * (a.KS * a.KS * Ct + Csc), (M * (Ct + Csc) + a.Cout * (a.KS * a.KS * Ct + Csc) + M * a.Cout) * es,
              replay=lambda keep=keep: conv2d_launch(keep[0]))
     return workspace[:nslab * a.B * a.H * a.W * Cout].view(nslab, a.B * a.H * a.W, Cout), nslab
 

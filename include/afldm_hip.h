@@ -318,8 +318,9 @@ typedef struct {
    * conv2 itself: y = conv3x3(x1) + conv1x1(sc_x1 | sc_x2, sc_w) + bias, where `bias` is conv2.bias + conv_shortcut.bias and there
    * is no `residual`.  sc_x1 [B*H*W][sc_C1] and sc_x2 [B*H*W][sc_C2] (NHWC, dtype T; sc_x2 NULL when sc_C2 = 0) are the block input
    * (a virtual concat on the up path), sc_w [Cout][sc_C1 + sc_C2] the 1x1 weight in the afldm_pack_weight (OHWI) form.  The
-   * shortcut's channels run as extra centre-tap K steps of the halo-patch kernel; only honoured where afldm_conv2d_shortcut_ok(args)
-   * == 1 (sc_x1 = NULL otherwise, and run the 1x1 convolution as its own call feeding `residual`). */
+   * shortcut's channels run as extra centre-tap K steps of the halo-patch kernel (one 128-byte channel block per step; where K is
+   * split, each slice takes its share of them and the slabs carry conv2 + shortcut partial sums); only honoured where
+   * afldm_conv2d_shortcut_ok(args) != 0 (sc_x1 = NULL otherwise, and run the 1x1 convolution as its own call feeding `residual`). */
   const void* sc_x1;
   const void* sc_x2;
   const void* sc_w;
@@ -330,8 +331,10 @@ int afldm_conv2d(const afldm_conv_args* args, afldm_stream_t stream);
 int afldm_conv2d_c8_ok(const afldm_conv_args* args);
 /* 1: afldm_conv2d(args) will apply the GroupNorm described by norm_gamma / norm_beta / norm_groups / norm_eps into y_norm itself. */
 int afldm_conv2d_norm_ok(const afldm_conv_args* args);
-/* 1: afldm_conv2d(args) accepts the folded shortcut described by sc_x1 / sc_x2 / sc_w / sc_C1 / sc_C2 (one halo-patch launch with one
- * filter tap per K step, whole K per workgroup, no residual; the 32^2 / 16^2 levels at the larger batches). */
+/* != 0: afldm_conv2d(args) accepts the folded shortcut described by sc_x1 / sc_x2 / sc_w / sc_C1 / sc_C2 (one halo-patch launch, no
+ * residual).  1: a tile with one filter tap per K step, whole K per workgroup (the 32^2 / 16^2 levels at the larger batches);
+ * 2: a tile with three taps per K step (the 8^2 / 4^2 levels, every level at the small batches) - K may be split there, with
+ * defer_reduce (the slabs to afldm_af_act_slabs, which then takes bias = b2 + b_sc and no residual) or y_norm. */
 int afldm_conv2d_shortcut_ok(const afldm_conv_args* args);
 /* Tuning hook (benchmarks only): force tile/pipeline variant `variant` (>= 0) and/or a split-K
  * factor (>= 1) for subsequent afldm_conv2d calls; -1 restores the automatic choice. */

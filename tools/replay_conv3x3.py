@@ -29,21 +29,24 @@ def record(batch=64):
     sigs = []
     orig = ops.conv2d
 
+    def sc_of(shortcut):          # channels of a folded 1x1 shortcut's two inputs (0, 0: none)
+        return (0, 0) if shortcut is None else (shortcut[0].shape[-1], 0 if shortcut[1] is None else shortcut[1].shape[-1])
+
     def spy(x, w, bias=None, x2=None, temb=None, temb_stride=0, residual=None, **kw):
         if w.shape[1] == 3:
             sigs.append(dict(B=x.shape[0], H=x.shape[1], W=x.shape[2], C1=x.shape[3], C2=0 if x2 is None else x2.shape[3],
                              Cout=w.shape[0], bias=bias is not None, temb=temb is not None, temb_stride=temb_stride,
-                             residual=residual is not None))
+                             residual=residual is not None, sc=sc_of(kw.get("shortcut"))))
         return orig(x, w, bias, x2=x2, temb=temb, temb_stride=temb_stride, residual=residual, **kw)
 
     orig_slabs = ops.conv2d_slabs
 
-    def spy_slabs(x, w, x2=None):
-        # conv1 of a 2x2 / 4x4 resnet whose K slices go straight to the activation kernel (no reduction launch)
-        got = orig_slabs(x, w, x2)
+    def spy_slabs(x, w, x2=None, shortcut=None):
+        # conv1 / conv2 of a 2x2 / 4x4 resnet whose K slices go straight to the activation kernel (no reduction launch)
+        got = orig_slabs(x, w, x2, shortcut=shortcut)
         if got is not None and w.shape[1] == 3:
             sigs.append(dict(B=x.shape[0], H=x.shape[1], W=x.shape[2], C1=x.shape[3], C2=0, Cout=w.shape[0], bias=False,
-                             temb=False, temb_stride=0, residual=False, slabs=True))
+                             temb=False, temb_stride=0, residual=False, slabs=True, sc=sc_of(shortcut)))
         return got
 
     ops.conv2d = spy
@@ -56,7 +59,8 @@ def record(batch=64):
     alg = 0
     for s in sigs:
         m = s["B"] * s["H"] * s["W"]
-        alg += 2 * (m * (s["C1"] + s["C2"]) + s["Cout"] * 9 * (s["C1"] + s["C2"]) + m * s["Cout"] * (2 if s["residual"] else 1))
+        csc = sum(s.get("sc", (0, 0)))      # a folded shortcut adds its input and its 1x1 weight
+        alg += 2 * (m * (s["C1"] + s["C2"] + csc) + s["Cout"] * (9 * (s["C1"] + s["C2"]) + csc) + m * s["Cout"] * (2 if s["residual"] else 1))
     print(json.dumps(dict(launches=len(sigs), algorithmic_bytes_per_step=alg)))
 
 
@@ -74,15 +78,21 @@ def replay(reps=3):
         temb = torch.randn(s["B"], s["Cout"], device=dev).to(dt) if s["temb"] else None
         res = torch.randn(s["B"], s["H"], s["W"], s["Cout"], device=dev).to(dt) if s["residual"] else None
         y = torch.empty(s["B"], s["H"], s["W"], s["Cout"], device=dev, dtype=dt)
-        bufs.append((x1, w, bias, x2, temb, s["Cout"] if s["temb"] else 0, res, y, bool(s.get("slabs"))))
+        c1s, c2s = s.get("sc", (0, 0))
+        sc = None
+        if c1s:
+            sc = (torch.randn(s["B"], s["H"], s["W"], c1s, device=dev).to(dt),
+                  torch.randn(s["B"], s["H"], s["W"], c2s, device=dev).to(dt) if c2s else None,
+                  (torch.randn(s["Cout"], 1, 1, c1s + c2s, device=dev) / (c1s + c2s) ** 0.5).to(dt))
+        bufs.append((x1, w, bias, x2, temb, s["Cout"] if s["temb"] else 0, res, y, bool(s.get("slabs")), sc))
     ws = torch.empty(64 << 20, dtype=torch.float32, device="cuda")
     torch.cuda.synchronize()
     for _ in range(reps):
-        for x1, w, bias, x2, temb, ts, res, y, slabs in bufs:
+        for x1, w, bias, x2, temb, ts, res, y, slabs, sc in bufs:
             if slabs:
-                ops.conv2d_slabs(x1, w)
+                ops.conv2d_slabs(x1, w, shortcut=sc)
             else:
-                ops.conv2d(x1, w, bias, x2=x2, temb=temb, temb_stride=ts, residual=res, out=y, workspace=ws)
+                ops.conv2d(x1, w, bias, x2=x2, temb=temb, temb_stride=ts, residual=res, out=y, workspace=ws, shortcut=sc)
     torch.cuda.synchronize()
     print(json.dumps(dict(launches=len(bufs), reps=reps)))
 
