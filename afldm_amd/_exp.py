@@ -2,7 +2,7 @@
 
 Not part of the product: merged activation / convolution launches, the cooperative 2x2-level trunk and the fused small-plane
 attention were built, validated and measured slower (profiles/r05/); nothing on the default path imports this module's
-library - it is loaded on first use by the opt-in switches (AFLDM_ACTCONV_N, AFLDM_TRUNK, AFLDM_ATTN_SMALL_T), the A/B tools
+library - it is loaded on first use by the opt-in switches (AFLDM_TRUNK, AFLDM_ATTN_SMALL_T), the A/B tools
 and the tests that keep the experiments correct."""
 import ctypes
 import os

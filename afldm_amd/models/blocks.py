@@ -13,23 +13,14 @@ concat" (the up-block skip torch.cat) is passed around as a tuple (x1, x2) and r
 the kernels (two base pointers), never materialised.
 """
 import math
-
 import os
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
 
 from .. import aql, ops
 
-# AFLDM_SHORTCUT_ORDER: where a ResnetBlock2D issues its 1x1 conv_shortcut (independent of norm1 -> conv1 -> norm2):
-# 0 (default) between the second activation and conv2, 1 behind the first activation, 2 in front of it.  Same results;
-# with an AQL policy armed (afldm_amd/aql.py) the launch marked `independent` runs beside its neighbour.
-_SC_ORDER = int(os.environ.get("AFLDM_SHORTCUT_ORDER", "0"))
-# Edges of a ResnetBlock2D that travel in 8-channel blocks at the 32^2 / 16^2 levels: 1 act1 -> conv1, 2 conv1 -> act2, 4 act2 -> conv2.
-# Default 5: the activations WRITE blocks (an item's output is one contiguous run: -9 % per launch) and the convolutions read
-# them; a convolution writing blocks loses more in its epilogue (16-byte pieces to 24 planes per row) than the activation
-# behind it gains: 4.804 (0) / 4.785 (7) / 4.827 (2) / 4.754 (5) ms/step, same box (profiles/r05/c8_layout_ab.txt).
-_C8_EDGES = int(os.environ.get("AFLDM_C8_EDGES", "5"))
 # A ResnetBlock2D's 1x1 conv_shortcut runs inside its conv2 - extra centre-tap K steps of the halo-patch kernel over the block input,
 # one bias b2 + b_sc - where afldm_conv2d_shortcut_ok allows it, instead of a launch of its own whose output conv2 re-reads as its
 # residual.  AFLDM_NO_SHORTCUT_FOLD=1: the two launches (A/B).
@@ -38,6 +29,15 @@ _SC_FOLD = os.environ.get("AFLDM_NO_SHORTCUT_FOLD", "0") != "1"
 # and every level at the small batches), a switch of its own so that the two are A/B-able independently (_SC_FOLD keeps meaning
 # the one-tap tiles).  AFLDM_NO_SHORTCUT_FOLD3=1: the two launches there.
 _SC_FOLD3 = os.environ.get("AFLDM_NO_SHORTCUT_FOLD3", "0") != "1"
+# Which launches a ResnetBlock2D issues for an input is resolved once into a _ResnetPlan, cached per module in `_afldm_plan` under a
+# key that holds the input's shape / dtype / device AND the current value of every switch the plan depends on (the two above,
+# _CONST2, ops._C8, ops._DENSE2_MIN_B, AFLDM_NO_FUSED_ACT, AFLDM_NO_DENSE2X2): flipping a switch gives another plan, there is no cache to drop.
+# Fixed, each after its measurement:
+#  - at the 32^2 / 16^2 levels the activations WRITE 8-channel blocks and the convolutions behind them read them, conv1 writes NHWC:
+#    4.754 ms/step against 4.804 (no blocks) / 4.785 (all three edges) / 4.827 (conv1 -> act2 only), profiles/r05/c8_layout_ab.txt;
+#  - a conv_shortcut that stays a launch sits between the second activation and conv2 (`aql.independent`): the other positions
+#    gained 0.006 - 0.018 ms under the AQL diagnostic library only, profiles/r05/aql_headers.txt;
+#  - no merged activation -> convolution launches (ops.af_act_conv2d): 4.99 -> 5.01 / 5.09 ms/step, profiles/r05/actconv_ab.txt.
 
 
 def _pair(x):
@@ -406,6 +406,33 @@ def _plane2_view(y, B, Cout):
     return out
 
 
+_WARPED = None
+
+
+def _warped_nonlinearity():
+    global _WARPED
+    if _WARPED is None:
+        from ..af_modules.af_blocks import WarpedNonlinearity as _WARPED          # (lazy: af_blocks imports this module)
+    return _WARPED
+
+
+def _fused_af_silu(act):
+    """True for the alias-free SiLU that the fused kernels compute (WarpedNonlinearity around nn.SiLU)."""
+    return isinstance(act, _warped_nonlinearity()) and act.fused_silu
+
+
+class _ResnetPlan(NamedTuple):
+    """What ResnetBlock2D.forward issues for one kind of input (ResnetBlock2D._plan)."""
+    const2: bool        # the route: the plane-constant 2x2 form (_forward_const2) instead of the general one
+    dense2: bool        # ... whose conv1 + temb -> norm2 -> act2 is the ONE launch afldm_conv2x2_const_norm_act
+    c8_1: bool          # act1 writes 8-channel blocks, conv1 reads them (and writes NHWC)
+    c8_2: bool          # act2 writes 8-channel blocks, conv2 reads them
+    fold: int           # conv2 takes the 1x1 shortcut as extra K steps: 0 no, 1 on a one-tap tile, 2 on a three-tap tile
+    slabs1: bool        # conv1 -> norm2 -> act2 from conv1's split-K slabs, if its plan splits K (ops.conv2d_slabs says at run time)
+    slabs2: bool        # conv2 -> next_gn likewise
+    norm_out: bool      # else conv2's epilogue is offered next_gn
+
+
 # ----------------------------------------------------------------------------- resnet
 class ResnetBlock2D(nn.Module):
     """diffusers ResnetBlock2D (time_embedding_norm='default', no up/down, output_scale 1).
@@ -438,27 +465,75 @@ class ResnetBlock2D(nn.Module):
         if self.use_in_shortcut:
             self.conv_shortcut = nn.Conv2d(in_channels, out_channels, kernel_size=1, stride=1, padding=0, bias=True)
 
-    def _c8_plan(self, input_tensor, temb_proj, temb_stride=0):
-        """(conv1 takes / writes 8-channel blocks, conv2 takes them): the layout of the tensors between this block's
-        alias-free activations and its 3x3 convolutions at the 32^2 / 16^2 levels (ops._C8; afldm_conv2d_c8_ok)."""
-        from ..af_modules.af_blocks import WarpedNonlinearity
-        x1, x2 = _pair(input_tensor)
-        if (not ops._C8 or x1.ndim != 4 or x1.dtype != torch.bfloat16 or x1.shape[1] != x1.shape[2] or x1.shape[1] not in (16, 32)
-                or not isinstance(self.nonlinearity, WarpedNonlinearity) or not self.nonlinearity.fused_silu
-                or tuple(self.conv1.kernel_size) != (3, 3) or tuple(self.conv2.kernel_size) != (3, 3)):
-            return False, False
-        B, N = x1.shape[0], x1.shape[1]
-        cin = x1.shape[-1] + (0 if x2 is None else x2.shape[-1])
-        key = (B, N, cin, x1.device, int(temb_stride))
-        cache = self.__dict__.setdefault("_afldm_c8", {})
-        if key not in cache:
-            w1, b1 = packed_conv(self.conv1, x1.dtype)
-            w2, b2 = packed_conv(self.conv2, x1.dtype)
-            a_in = torch.empty((B, N, N, cin), dtype=x1.dtype, device=x1.device)
-            h_in = torch.empty((B, N, N, self.out_channels), dtype=x1.dtype, device=x1.device)
-            cache[key] = (ops.conv2d_c8_ok(a_in, w1, b1, temb=temb_proj, temb_stride=temb_stride),
-                          ops.conv2d_c8_ok(h_in, w2, b2, residual=h_in))
-        return cache[key]
+    def _plan(self, x1, x2, temb_proj, temb_stride, next_gn):
+        """The _ResnetPlan of this input under the switches as they stand now (cached in `_afldm_plan`; the probes behind a new
+        plan run at the first call for a shape - an engine's warm-up step)."""
+        af = _fused_af_silu(self.nonlinearity)
+        key = (tuple(x1.shape), None if x2 is None else x2.shape[-1], x1.dtype, x1.device, temb_proj is not None, int(temb_stride),
+               None if next_gn is None else (next_gn.num_groups, next_gn.num_channels), af,
+               ops._C8, _SC_FOLD, _SC_FOLD3, _CONST2, ops._DENSE2_MIN_B,
+               os.environ.get("AFLDM_NO_FUSED_ACT"), os.environ.get("AFLDM_NO_DENSE2X2"))
+        plans = self.__dict__.setdefault("_afldm_plan", {})
+        if key not in plans:
+            plans[key] = self._make_plan(x1, x2, temb_proj, temb_stride, next_gn, af)
+        return plans[key]
+
+    def _make_plan(self, x1, x2, temb_proj, temb_stride, next_gn, af):
+        """af: the nonlinearity is the fused alias-free SiLU."""
+        B, N, C1, C2 = x1.shape[0], x1.shape[1], x1.shape[-1], 0 if x2 is None else x2.shape[-1]
+        Cin, Cout, dt = C1 + C2, self.out_channels, x1.dtype
+        fused = not os.environ.get("AFLDM_NO_FUSED_ACT")
+        square = x1.ndim == 4 and x1.shape[1] == x1.shape[2]
+        k3_1, k3_2 = tuple(self.conv1.kernel_size) == (3, 3), tuple(self.conv2.kernel_size) == (3, 3)
+        # conv2's result straight into next_gn: afldm_af_act_slabs reads the residual as dense [B, N, N, Cout] - there is no res_ld,
+        # so it must have Cout channels; that it is contiguous needs no check here (the shortcut's output is fresh, and a block input
+        # that is not contiguous is refused by ops._dev in the first gn_stats)
+        gn_ok = fused and next_gn is not None and Cout % next_gn.num_groups == 0 and next_gn.num_channels == Cout
+        res_ok = self.conv_shortcut is not None or C1 == Cout
+        if self._const2_form(x1, x2, af):
+            dense2 = fused and ops.conv2x2_const_norm_act_ok(Cin, Cout, self.norm2.num_groups, dt, batch=B)
+            return _ResnetPlan(True, dense2, False, False, 0, fused and not dense2, gn_ok and res_ok, False)
+        c8 = ops._C8 and square and k3_1 and k3_2 and af and dt == torch.bfloat16 and N in (16, 32)
+        can_fold = ((_SC_FOLD or _SC_FOLD3) and square and k3_2 and self.conv_shortcut is not None
+                    and tuple(self.conv_shortcut.kernel_size) == (1, 1))
+        c8_1 = c8_2 = False
+        fold, sc = 0, None
+        if c8 or can_fold:         # the probes carry what the real launches carry (ops.conv2d_c8_ok, ops.conv2d_shortcut_ok)
+            h_in = torch.empty((B, N, N, Cout), dtype=dt, device=x1.device)          # stands for conv2's input
+            w2, b2 = packed_conv(self.conv2, dt)
+        if c8:
+            w1, b1 = packed_conv(self.conv1, dt)
+            a_in = torch.empty((B, N, N, Cin), dtype=dt, device=x1.device)
+            c8_1 = ops.conv2d_c8_ok(a_in, w1, b1, temb=temb_proj, temb_stride=temb_stride)
+            c8_2 = ops.conv2d_c8_ok(h_in, w2, b2, residual=h_in)
+        if can_fold:
+            sc = (x1, x2, packed_conv(self.conv_shortcut, dt)[0])
+            if c8_2:
+                h_in.c8 = True
+            kind = ops.conv2d_shortcut_ok(h_in, w2, self._sc_bias(), sc)
+            fold = kind if (kind == 1 and _SC_FOLD) or (kind == 2 and _SC_FOLD3) else 0
+        slabs1 = square and self._slabs1_ok(N, Cin, af)
+        slabs2 = square and N in (2, 4) and Cout % 8 == 0 and gn_ok and k3_2
+        if fold:        # the slabs carry the shortcut only where the three-tap tile splits K (4x4 planes)
+            slabs2 = slabs2 and N == 4 and ops.conv2d_shortcut_ok(h_in, w2, None, sc, slabs=True) == 2
+        else:
+            slabs2 = slabs2 and res_ok
+        return _ResnetPlan(False, False, c8_1, c8_2, fold, slabs1, slabs2, next_gn is not None)
+
+    def _const2_form(self, x1, x2, af):
+        """The plane-constant 2x2 form applies: 2x2 planes under the fused alias-free SiLU, K of the two dense layers (Cin / Cout)
+        whole K steps of the GEMM kernels (128 bytes of elements)."""
+        C1, C2, Cout, kstep = x1.shape[-1], 0 if x2 is None else x2.shape[-1], self.out_channels, 128 // x1.element_size()
+        return (_CONST2 and not os.environ.get("AFLDM_NO_DENSE2X2") and x1.ndim == 4 and x1.shape[1] == 2 and x1.shape[2] == 2 and af
+                and tuple(self.conv1.kernel_size) == (3, 3) and tuple(self.conv2.kernel_size) == (3, 3)
+                and C1 % 8 == 0 and C2 % 8 == 0 and Cout % 8 == 0 and Cout % self.norm2.num_groups == 0
+                and (C1 + C2) % kstep == 0 and Cout % kstep == 0)
+
+    def _slabs1_ok(self, N, Cin, af):
+        """The static conditions of conv1 -> norm2 -> act2 from conv1's split-K slabs, on N x N planes of Cin channels."""
+        Cout = self.out_channels
+        return (af and not os.environ.get("AFLDM_NO_FUSED_ACT") and N in (2, 4) and tuple(self.conv1.kernel_size) == (3, 3)
+                and Cin % 8 == 0 and Cout % 8 == 0 and Cout % self.norm2.num_groups == 0)
 
     def _sc_bias(self):
         """conv2.bias + conv_shortcut.bias, summed in fp64 and rounded once to fp32: the bias of conv2 with the shortcut folded in."""
@@ -471,209 +546,89 @@ class ResnetBlock2D(nn.Module):
             cache["sc_bias"] = b.float().contiguous()
         return cache["sc_bias"]
 
-    def _sc_fold_plan(self, input_tensor, c8):
-        """True when conv2 takes the 1x1 conv_shortcut as extra K steps (afldm_conv2d_shortcut_ok) instead of its output as the
-        residual: on a halo-patch tile with one filter tap per step (the 32^2 / 16^2 levels at the larger batches; _SC_FOLD, plans
-        cached in `_afldm_sc_fold`) or with three (the 8^2 / 4^2 levels, the small batches; _SC_FOLD3, `_afldm_sc_fold3`).  c8: conv2
-        reads 8-channel blocks.  Only booleans are cached here (the packed weights live in the modules' `_afldm_cache`)."""
-        if ((not _SC_FOLD and not _SC_FOLD3) or self.conv_shortcut is None or tuple(self.conv_shortcut.kernel_size) != (1, 1)
-                or tuple(self.conv2.kernel_size) != (3, 3)):
-            return False
-        x1, x2 = _pair(input_tensor)
-        if x1.ndim != 4 or x1.shape[1] != x1.shape[2]:
-            return False
-        B, N = x1.shape[0], x1.shape[1]
-        key = (B, N, x1.shape[-1], None if x2 is None else x2.shape[-1], x1.dtype, x1.device, bool(c8))
-
-        def kind():
-            w2, _ = packed_conv(self.conv2, x1.dtype)
-            wsc, _ = packed_conv(self.conv_shortcut, x1.dtype)
-            h_in = torch.empty((B, N, N, self.out_channels), dtype=x1.dtype, device=x1.device)
-            if c8:
-                h_in.c8 = True
-            return ops.conv2d_shortcut_ok(h_in, w2, self._sc_bias(), (x1, x2, wsc))
-        if _SC_FOLD:
-            cache = self.__dict__.setdefault("_afldm_sc_fold", {})
-            if key not in cache:
-                cache[key] = kind() == 1
-            if cache[key]:
-                return True
-        if _SC_FOLD3:
-            cache = self.__dict__.setdefault("_afldm_sc_fold3", {})
-            if key not in cache:
-                cache[key] = kind() == 2
-            return cache[key]
-        return False
-
-    def _conv2_sc_folded(self, h, input_tensor, next_gn):
-        """conv2(h) + conv_shortcut(input_tensor) as ONE launch (see _sc_fold_plan); with next_gn, the attention block's GroupNorm
-        rides along where the epilogue can apply it (as the unfolded path does)."""
-        x1, x2 = _pair(input_tensor)
-        w2, _ = packed_conv(self.conv2, h.dtype)
-        wsc, _ = packed_conv(self.conv_shortcut, h.dtype)
-        kw = {}
-        if next_gn is not None:
-            out = self._conv2_to_next_norm_fused(h, None, next_gn, shortcut=(x1, x2, wsc))       # 4x4 planes: split-K slabs
-            if out is not None:
-                return out
-            gamma, beta = packed_norm(next_gn)
-            kw["norm_out"] = (gamma, beta, next_gn.num_groups, next_gn.eps)
-        out = ops.conv2d(h, w2, self._sc_bias(), want_stats=True, shortcut=(x1, x2, wsc), **kw)
-        hn = getattr(out, "norm_applied", None)
-        if hn is not None:
-            out.gn_applied = (hn, next_gn)
-        return out
-
     def _norm_act(self, norm, x, out_c8=False, out_const=False):
         """norm -> self.nonlinearity fused: GroupNorm statistics, then either the fused
         GN + WarpedNonlinearity kernel (alias-free model) or GN + SiLU."""
-        from ..af_modules.af_blocks import WarpedNonlinearity
         x1, x2 = _pair(x)
         gamma, beta = packed_norm(norm)
         stats = ops.gn_stats(x1, norm.num_groups, x2=x2)
-        if isinstance(self.nonlinearity, WarpedNonlinearity):
-            if self.nonlinearity.fused_silu:
-                return ops.af_act(x1, x2, stats, gamma, beta, norm.num_groups, norm.eps, out_c8=out_c8, out_const=out_const)
+        if _fused_af_silu(self.nonlinearity):
+            return ops.af_act(x1, x2, stats, gamma, beta, norm.num_groups, norm.eps, out_c8=out_c8, out_const=out_const)
+        if isinstance(self.nonlinearity, _warped_nonlinearity()):
             # a wrapped module other than SiLU: GroupNorm pass, then the module's own (unfused) alias-free form
             return self.nonlinearity(ops.gn_apply(x1, stats, gamma, beta, norm.num_groups, norm.eps, act=0, x2=x2))
         return ops.gn_apply(x1, stats, gamma, beta, norm.num_groups, norm.eps, act=1, x2=x2)
 
-    def _norm_act_conv(self, norm, x, conv, force=False, **kw):
-        """conv(nonlinearity(norm(x))): ONE merged launch at the 32^2 / 16^2 levels of the alias-free bf16 model
-        (ops.af_act_conv2d, csrc/actconv.hip), else the activation kernel followed by the convolution."""
-        from ..af_modules.af_blocks import WarpedNonlinearity
-        x1, x2 = _pair(x)
-        if (isinstance(self.nonlinearity, WarpedNonlinearity) and self.nonlinearity.fused_silu and x1.ndim == 4
-                and x1.dtype == torch.bfloat16 and (force or x1.shape[1] in ops._ACTCONV_N) and tuple(conv.kernel_size) == (3, 3)):
-            gamma, beta = packed_norm(norm)
-            stats = ops.gn_stats(x1, norm.num_groups, x2=x2)
-            w, b = packed_conv(conv, x1.dtype)
-            out = ops.af_act_conv2d(x1, x2, stats, gamma, beta, norm.num_groups, norm.eps, w, b, **kw)
-            if out is not None:
-                return out
-        return conv_forward(conv, self._norm_act(norm, x), **kw)
-
-    def _conv1_norm2_act_fused(self, h, temb_proj, temb_stride):
-        """conv1 -> norm2 -> WarpedNonlinearity on the 2x2 / 4x4 planes when conv1 splits K: the activation kernel takes
-        the convolution's fp32 slabs and finishes them itself (afldm_af_act_slabs) - no reduction launch, no stored
-        intermediate.  Returns None when this shape / plan does not qualify (the caller runs the ordinary sequence)."""
-        from ..af_modules.af_blocks import WarpedNonlinearity
-        if (os.environ.get("AFLDM_NO_FUSED_ACT") or not isinstance(self.nonlinearity, WarpedNonlinearity)
-                or not self.nonlinearity.fused_silu or isinstance(h, tuple) or h.ndim != 4 or h.shape[1] != h.shape[2] or h.shape[1] not in (2, 4)):
-            return None
+    def _slabs(self, conv, h, shortcut=None):
+        """The split-K slabs of conv(h) (+ the folded shortcut) on a 2x2 / 4x4 plane, or None when the plan of this shape does
+        not split K (the caller runs the ordinary sequence)."""
         B, N, _, Cin = h.shape
-        conv, norm = self.conv1, self.norm2
-        Cout = conv.out_channels
-        if tuple(conv.kernel_size) != (3, 3) or Cout % norm.num_groups or Cin % 8 or Cout % 8:
-            return None
-        if N == 2 and not os.environ.get("AFLDM_NO_DENSE2X2"):
+        if N == 2 and shortcut is None and not os.environ.get("AFLDM_NO_DENSE2X2"):
             w2, _ = packed_conv_dense2x2(conv, h.dtype, Cin, 0)          # one dense layer over the flattened plane
-            got = ops.conv2d_slabs(h.reshape(B, 4 * Cin), w2)
-        else:
-            w, _ = packed_conv(conv, h.dtype)
-            got = ops.conv2d_slabs(h, w)
-        if got is None:
-            return None
+            return ops.conv2d_slabs(h.reshape(B, 4 * Cin), w2)
+        return ops.conv2d_slabs(h, packed_conv(conv, h.dtype)[0], shortcut=shortcut)
+
+    def _finish_slabs(self, got, bias, norm, B, N, dtype, temb=None, temb_stride=0, act=True, residual=None, raw=False):
+        """A convolution's split-K slabs finished by the consumer of its output (afldm_af_act_slabs: no reduction launch, no
+        stored intermediate): + bias (+ temb) (+ residual) -> GroupNorm `norm` -> act (True: the alias-free activation, 2: its
+        plane-constant [B, C] form, False: none).  raw: the finished convolution output itself is stored too and returned, the
+        normalised tensor attached as `.gn_applied = (tensor, norm module)` for AttnProcessor2_0."""
         slabs, nslab = got
         gamma, beta = packed_norm(norm)
-        cache = conv.__dict__.setdefault("_afldm_cache", {})
-        if "bias_f32" not in cache:
-            cache["bias_f32"] = None if conv.bias is None else conv.bias.detach().to(torch.float32).contiguous()
-        bias = cache["bias_f32"]
-        return ops.af_act_slabs(slabs, nslab, bias, temb_proj, temb_stride, gamma, beta, norm.num_groups, norm.eps,
-                                B, N, Cout, h.dtype)
-
-    def _conv2_to_next_norm_fused(self, h, res, next_gn, shortcut=None):
-        """conv2 (+ shortcut) of this block straight into the GroupNorm of the attention block that follows, on the
-        2x2 / 4x4 planes when conv2 splits K (afldm_af_act_slabs, act = 0): the reduction launch and the GroupNorm
-        pass become one.  shortcut = (x1, x2, packed 1x1 weight) instead of `res`: the slabs carry the folded shortcut
-        (see _sc_fold_plan), the bias is b2 + b_sc and there is no residual.  Returns this block's output with the normalised
-        tensor attached as `.gn_applied = (tensor, norm module)` for AttnProcessor2_0, or None when the shape / plan does not qualify."""
-        if (os.environ.get("AFLDM_NO_FUSED_ACT") or isinstance(h, tuple) or h.ndim != 4 or h.shape[1] != h.shape[2]
-                or h.shape[1] not in (2, 4)):
-            return None
-        B, N, _, Cin = h.shape
-        conv = self.conv2
-        Cout = conv.out_channels
-        if (tuple(conv.kernel_size) != (3, 3) or Cout % next_gn.num_groups or Cin % 8 or Cout % 8 or next_gn.num_channels != Cout
-                or (shortcut is None and (res.shape[-1] != Cout or not res.is_contiguous()))):
-            return None          # (afldm_af_act_slabs reads the residual as dense [B, N, N, Cout]: no res_ld)
-        if shortcut is not None:
-            w, _ = packed_conv(conv, h.dtype)
-            if N == 2 or ops.conv2d_shortcut_ok(h, w, None, shortcut, slabs=True) != 2:
-                return None
-            got = ops.conv2d_slabs(h, w, shortcut=shortcut)
-        elif N == 2 and not os.environ.get("AFLDM_NO_DENSE2X2"):
-            w2, _ = packed_conv_dense2x2(conv, h.dtype, Cin, 0)
-            got = ops.conv2d_slabs(h.reshape(B, 4 * Cin), w2)
-        else:
-            w, _ = packed_conv(conv, h.dtype)
-            got = ops.conv2d_slabs(h, w)
-        if got is None:
-            return None
-        slabs, nslab = got
-        gamma, beta = packed_norm(next_gn)
-        cache = conv.__dict__.setdefault("_afldm_cache", {})
-        if "bias_f32" not in cache:
-            cache["bias_f32"] = None if conv.bias is None else conv.bias.detach().to(torch.float32).contiguous()
-        hn, y = ops.af_act_slabs(slabs, nslab, self._sc_bias() if shortcut is not None else cache["bias_f32"], None, 0, gamma, beta,
-                                 next_gn.num_groups, next_gn.eps,
-                                 B, N, Cout, h.dtype, residual=res, want_raw=True, act=False)
-        y.gn_applied = (hn, next_gn)
+        out = ops.af_act_slabs(slabs, nslab, bias, temb, temb_stride, gamma, beta, norm.num_groups, norm.eps, B, N, self.out_channels,
+                               dtype, residual=residual, want_raw=raw, act=act)
+        if not raw:
+            return out
+        hn, y = out
+        y.gn_applied = (hn, norm)
         return y
 
-    def _const2_ok(self, input_tensor):
-        from ..af_modules.af_blocks import WarpedNonlinearity
-        x1, x2 = _pair(input_tensor)
-        return (_CONST2 and not os.environ.get("AFLDM_NO_DENSE2X2") and x1.ndim == 4 and x1.shape[1] == 2 and x1.shape[2] == 2
-                and isinstance(self.nonlinearity, WarpedNonlinearity) and self.nonlinearity.fused_silu
-                and tuple(self.conv1.kernel_size) == (3, 3) and tuple(self.conv2.kernel_size) == (3, 3)
-                and x1.shape[-1] % 8 == 0 and (x2 is None or x2.shape[-1] % 8 == 0) and self.out_channels % 8 == 0
-                and self.out_channels % self.norm2.num_groups == 0
-                # K of the two dense layers = Cin / Cout: whole K steps of the GEMM kernels (128 bytes of elements)
-                and (x1.shape[-1] + (0 if x2 is None else x2.shape[-1])) % (128 // x1.element_size()) == 0
-                and self.out_channels % (128 // x1.element_size()) == 0)
+    def _conv1_norm2_act_fused(self, h, temb_proj, temb_stride):
+        """conv1 -> norm2 -> WarpedNonlinearity on the 2x2 / 4x4 planes when conv1 splits K: the activation kernel takes the
+        convolution's fp32 slabs and finishes them itself.  Returns None when this shape / plan does not qualify (the caller runs
+        the ordinary sequence)."""
+        if (isinstance(h, tuple) or h.ndim != 4 or h.shape[1] != h.shape[2]
+                or not self._slabs1_ok(h.shape[1], h.shape[-1], _fused_af_silu(self.nonlinearity))):
+            return None
+        return self._conv1_from_slabs(h, temb_proj, temb_stride)
 
-    def _forward_const2(self, input_tensor, temb_proj, temb_stride, next_gn):
+    def _conv1_from_slabs(self, h, temb_proj, temb_stride):
+        got = self._slabs(self.conv1, h)
+        if got is None:
+            return None
+        return self._finish_slabs(got, _bias_f32(self.conv1), self.norm2, h.shape[0], h.shape[1], h.dtype, temb_proj, temb_stride)
+
+    def _const2_ok(self, input_tensor):
+        x1, x2 = _pair(input_tensor)
+        return self._const2_form(x1, x2, _fused_af_silu(self.nonlinearity))
+
+    def _forward_const2(self, plan, input_tensor, temb_proj, temb_stride, next_gn):
         """The block on 2x2 planes: both alias-free activations are plane-constant there, so they are stored once per plane
         ([B, C]) and conv1 / conv2 run as dense layers over Cin / Cout columns with tap-summed weights
         (packed_conv_dense2x2_const) - same function, a quarter of the weight bytes and of the GEMM's K."""
         x1, x2 = _pair(input_tensor)
         B, dt, Cout = x1.shape[0], x1.dtype, self.out_channels
         a = self._norm_act(self.norm1, input_tensor, out_const=True)                 # [B, Cin]
-        g2, be2 = packed_norm(self.norm2)
-        h = None
-        got = None
-        if ops.conv2x2_const_norm_act_ok(a.shape[-1], Cout, self.norm2.num_groups, dt, batch=B) and not os.environ.get("AFLDM_NO_FUSED_ACT"):
+        if plan.dense2:
             # conv1 + temb -> norm2 -> activation in ONE launch: a workgroup owns a whole GroupNorm group of the dense layer's columns
+            g2, be2 = packed_norm(self.norm2)
             h = ops.conv2x2_const_norm_act(a, packed_conv_dense2x2_const_cm(self.conv1, dt), _bias_f32(self.conv1), temb_proj,
                                            temb_stride, g2, be2, self.norm2.num_groups, self.norm2.eps)
         else:
             w1, b1 = packed_conv_dense2x2_const(self.conv1, dt)
-            got = None if os.environ.get("AFLDM_NO_FUSED_ACT") else ops.conv2d_slabs(a, w1)
-        if h is not None:
-            pass
-        elif got is not None:                                                          # the plan splits K: the slabs' consumer finishes them
-            slabs, nslab = got
-            h = ops.af_act_slabs(slabs, nslab, _bias_f32(self.conv1), temb_proj, temb_stride, g2, be2, self.norm2.num_groups,
-                                 self.norm2.eps, B, 2, Cout, dt, act=2)
-        else:
-            kw = dict(temb=temb_proj, temb_stride=temb_stride, temb_mod=Cout) if temb_proj is not None else {}
-            y = ops.conv2d(a, w1, b1, want_stats=True, **kw)                         # [B, 4 * Cout]
-            h = self._norm_act(self.norm2, _plane2_view(y, B, Cout), out_const=True)
+            got = ops.conv2d_slabs(a, w1) if plan.slabs1 else None
+            if got is not None:
+                h = self._finish_slabs(got, _bias_f32(self.conv1), self.norm2, B, 2, dt, temb_proj, temb_stride, act=2)
+            else:
+                kw = dict(temb=temb_proj, temb_stride=temb_stride, temb_mod=Cout) if temb_proj is not None else {}
+                y = ops.conv2d(a, w1, b1, want_stats=True, **kw)                         # [B, 4 * Cout]
+                h = self._norm_act(self.norm2, _plane2_view(y, B, Cout), out_const=True)
         res = conv_forward(self.conv_shortcut, input_tensor) if self.conv_shortcut is not None else x1
         assert self.conv_shortcut is not None or x2 is None
         w2, b2 = packed_conv_dense2x2_const(self.conv2, dt)
-        if (next_gn is not None and not os.environ.get("AFLDM_NO_FUSED_ACT") and Cout % next_gn.num_groups == 0
-                and next_gn.num_channels == Cout and res.shape[-1] == Cout and res.is_contiguous()):
-            got = ops.conv2d_slabs(h, w2)
-            if got is not None:                # conv2 (+ shortcut) straight into the attention block's GroupNorm (see _conv2_to_next_norm_fused)
-                slabs, nslab = got
-                gamma, beta = packed_norm(next_gn)
-                hn, y = ops.af_act_slabs(slabs, nslab, _bias_f32(self.conv2), None, 0, gamma, beta, next_gn.num_groups, next_gn.eps,
-                                         B, 2, Cout, dt, residual=res, want_raw=True, act=False)
-                y.gn_applied = (hn, next_gn)
-                return y
+        got = ops.conv2d_slabs(h, w2) if plan.slabs2 else None
+        if got is not None:                    # conv2 + residual straight into the attention block's GroupNorm
+            return self._finish_slabs(got, _bias_f32(self.conv2), next_gn, B, 2, dt, residual=res, act=False, raw=True)
         y = ops.conv2d(h, w2, b2, residual=res.reshape(B, 4 * Cout), want_stats=True)
         return _plane2_view(y, B, Cout)
 
@@ -681,66 +636,47 @@ class ResnetBlock2D(nn.Module):
         """next_gn: the GroupNorm module of an attention block that consumes this block's output next (the block loops
         pass it): lets conv2 hand its result over already normalised where that saves launches."""
         x1, x2 = _pair(input_tensor)
-        if self._const2_ok(input_tensor):
-            return self._forward_const2(input_tensor, temb_proj, temb_stride, next_gn)
-        if x1.ndim == 4 and x1.shape[1] in ops._ACTCONV_N:
-            # 32^2 / 16^2 levels, opt-in (AFLDM_ACTCONV_N): norm -> activation -> conv pairs as merged launches where there is a kernel for them
-            h = self._norm_act_conv(self.norm1, input_tensor, self.conv1, temb=temb_proj, temb_stride=temb_stride, want_stats=True)
-            res = conv_forward(self.conv_shortcut, input_tensor) if self.conv_shortcut is not None else x1
-            assert self.conv_shortcut is not None or x2 is None
-            return self._norm_act_conv(self.norm2, h, self.conv2, residual=res, want_stats=True)
-        c8_1, c8_2 = self._c8_plan(input_tensor, temb_proj, temb_stride)
-        # which of the three edges travel in blocks (AFLDM_C8_EDGES, A/B): 1 act1 -> conv1, 2 conv1 -> act2, 4 act2 -> conv2
-        e1, e2, e3 = c8_1 and bool(_C8_EDGES & 1), c8_1 and bool(_C8_EDGES & 2), c8_2 and bool(_C8_EDGES & 4)
-        res = None
-        merged1 = bool(ops._ACTCONV_SITES) and x1.ndim == 4 and (x1.shape[1], x1.shape[-1] + (0 if x2 is None else x2.shape[-1])) in ops._ACTCONV_SITES
-        fold = not merged1 and self._sc_fold_plan(input_tensor, e3)
-        if merged1:
-            h = None
-        elif self.conv_shortcut is not None and _SC_ORDER == 2 and not fold:
-            # shortcut first, the activation beside it (AQL policy: afldm_amd/aql.py; tools/aql_shortcut_ab.py)
-            res = conv_forward(self.conv_shortcut, input_tensor)
-            with aql.independent("act1"):
-                h = self._norm_act(self.norm1, input_tensor, out_c8=e1)
+        plan = self._plan(x1, x2, temb_proj, temb_stride, next_gn)
+        if plan.const2:
+            return self._forward_const2(plan, input_tensor, temb_proj, temb_stride, next_gn)
+        # act1
+        h = self._norm_act(self.norm1, input_tensor, out_c8=plan.c8_1)
+        # conv1 (+ norm2 / act2): from conv1's split-K slabs in one launch, or conv1 (its epilogue emits norm2's statistics) -> act2
+        fused = self._conv1_from_slabs(h, temb_proj, temb_stride) if plan.slabs1 else None
+        if fused is None:
+            h = conv_forward(self.conv1, h, temb=temb_proj, temb_stride=temb_stride, want_stats=True)
+            h = self._norm_act(self.norm2, h, out_c8=plan.c8_2)
         else:
-            h = self._norm_act(self.norm1, input_tensor, out_c8=e1)
-        if self.conv_shortcut is not None and _SC_ORDER == 1 and not fold:
-            with aql.independent("shortcut"):
-                res = conv_forward(self.conv_shortcut, input_tensor)
-        fused = self._conv1_norm2_act_fused(h, temb_proj, temb_stride) if h is not None else None
-        if fused is not None:
             h = fused
-        elif h is None:
-            # per-site policy (ops._ACTCONV_SITES): norm1 -> activation -> conv1 as the merged launch (experimental library)
-            h = self._norm_act_conv(self.norm1, input_tensor, self.conv1, force=True, temb=temb_proj, temb_stride=temb_stride, want_stats=True)
-            h = self._norm_act(self.norm2, h, out_c8=e3)
-        else:
-            # (the convs whose outputs feed a GroupNorm emit its statistics from their epilogue)
-            h = conv_forward(self.conv1, h, temb=temb_proj, temb_stride=temb_stride, want_stats=True, out_c8=e2)
-            h = self._norm_act(self.norm2, h, out_c8=e3)
-        if fold:
-            return self._conv2_sc_folded(h, input_tensor, next_gn)
-        if res is not None:
-            pass
+        # shortcut: extra K steps of conv2, a launch of its own (independent of everything above: afldm_amd/aql.py), or the input
+        sc = res = None
+        if plan.fold:
+            sc = (x1, x2, packed_conv(self.conv_shortcut, h.dtype)[0])
         elif self.conv_shortcut is not None:
             with aql.independent("shortcut"):
                 res = conv_forward(self.conv_shortcut, input_tensor)
         else:
             assert x2 is None
             res = x1
-        if next_gn is not None:
-            out = self._conv2_to_next_norm_fused(h, res, next_gn)
-            if out is not None:
-                return out
-            # 8x8 planes: the attention block's GroupNorm from the epilogue of conv2 itself (one tile = one whole sample)
+        # conv2 (+ the next norm): from conv2's split-K slabs (4x4 / 2x2 planes), from its own epilogue (8x8: one tile = one
+        # whole sample), or left to the attention block
+        if plan.slabs2:
+            got = self._slabs(self.conv2, h, shortcut=sc)
+            if got is not None:
+                return self._finish_slabs(got, self._sc_bias() if plan.fold else _bias_f32(self.conv2), next_gn, h.shape[0],
+                                          h.shape[1], h.dtype, residual=res, act=False, raw=True)
+        kw = {}
+        if plan.norm_out:
             gamma, beta = packed_norm(next_gn)
-            out = conv_forward(self.conv2, h, residual=res, want_stats=True,
-                               norm_out=(gamma, beta, next_gn.num_groups, next_gn.eps))
-            hn = getattr(out, "norm_applied", None)
-            if hn is not None:
-                out.gn_applied = (hn, next_gn)
-            return out
-        return conv_forward(self.conv2, h, residual=res, want_stats=True)
+            kw["norm_out"] = (gamma, beta, next_gn.num_groups, next_gn.eps)
+        if plan.fold:
+            out = ops.conv2d(h, packed_conv(self.conv2, h.dtype)[0], self._sc_bias(), want_stats=True, shortcut=sc, **kw)
+        else:
+            out = conv_forward(self.conv2, h, residual=res, want_stats=True, **kw)
+        hn = getattr(out, "norm_applied", None)
+        if hn is not None:
+            out.gn_applied = (hn, next_gn)
+        return out
 
 
 def _next_gn(attn):

@@ -883,14 +883,6 @@ def conv2d(x1, w, bias=None, x2=None, temb=None, temb_stride=0, residual=None, o
 
 
 _ACTCONV = os.environ.get("AFLDM_NO_ACTCONV", "0") != "1"
-# plane sizes whose norm -> activation -> conv pairs ResnetBlock2D issues as merged launches.  EMPTY by default: built, bit-identical,
-# and measured SLOWER in the step (profiles/r05/actconv_ab.txt: 4.99 -> 5.01 ms with the 16^2 pairs, 5.09 with 32^2 too);
-# AFLDM_ACTCONV_N=16,32 turns them on (tests call the op directly)
-_ACTCONV_N = tuple(int(v) for v in os.environ.get("AFLDM_ACTCONV_N", "").split(",") if v)
-# per-site policy: "N:Cin,..." - the norm1 -> activation -> conv1 pair of the blocks whose (plane size, input channels) is listed
-# runs as the merged launch, everything else separately (the isolated A/B showed the merged act -> conv ahead only on the
-# concatenated inputs of the 16^2 up blocks: profiles/r05/actconv_ab.txt)
-_ACTCONV_SITES = frozenset(tuple(int(x) for x in v.split(":")) for v in os.environ.get("AFLDM_ACTCONV_SITES", "").split(",") if v)
 
 
 def act_conv_act(x1, x2, pre, w, bias=None, temb=None, temb_stride=0, residual=None, want_stats=False, post=None):

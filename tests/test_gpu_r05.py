@@ -364,9 +364,8 @@ def test_resnet_block_c8_flow_bit_identical_to_nhwc(monkeypatch):
         monkeypatch.setattr(ops, "af_act", lambda *a, **k: (calls.append(bool(k.get("out_c8"))), real(*a, **k))[1])
         monkeypatch.setattr(ops, "_C8", True)
         y1 = blk(x, temb, 0)
-        assert calls == [True, True], calls          # both activations write 8-channel blocks (AFLDM_C8_EDGES default 5)
+        assert calls == [True, True], calls          # both activations write 8-channel blocks
         monkeypatch.setattr(ops, "_C8", False)
-        blk.__dict__.pop("_afldm_c8", None)
         y0 = blk(x, temb, 0)
         assert calls[2:] == [False, False]
         assert torch.equal(y0, y1) and torch.equal(y0.gn_partial, y1.gn_partial)

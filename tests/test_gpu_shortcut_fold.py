@@ -81,6 +81,12 @@ def _block(cin, cout, dtype):
     return blk.cuda().to(dtype)
 
 
+def _plan_folds(blk, kind):
+    """True when one of the block's cached plans folds the shortcut into conv2 on a tile of this kind (1: one filter tap per K
+    step, 2: three)."""
+    return any(p.fold == kind for p in blk.__dict__.get("_afldm_plan", {}).values())
+
+
 class _CountConv:
     """ops.lib with the afldm_conv2d launches counted."""
 
@@ -116,7 +122,6 @@ def test_resnet_block_shortcut_fold_switch(monkeypatch, dtype, tol, N, C1, C2, C
     outs, calls = {}, {}
     for fold in (True, False):
         monkeypatch.setattr(blocks, "_SC_FOLD", fold)
-        blk.__dict__.pop("_afldm_sc_fold", None)
         counter = _CountConv(ops.lib)
         monkeypatch.setattr(ops, "lib", counter)
         y = blk(inp, temb.view(-1), 0)
@@ -148,8 +153,6 @@ def test_unet_forward_launches_without_shortcuts(monkeypatch):
     outs, calls = {}, {}
     for fold in (False, True):
         monkeypatch.setattr(blocks, "_SC_FOLD", fold)
-        for m in unet.modules():
-            m.__dict__.pop("_afldm_sc_fold", None)
         counter = _CountConv(ops.lib)
         monkeypatch.setattr(ops, "lib", counter)
         with torch.no_grad():
@@ -158,7 +161,7 @@ def test_unet_forward_launches_without_shortcuts(monkeypatch):
         monkeypatch.setattr(ops, "lib", counter.raw)
         outs[fold], calls[fold] = y.float().clone(), counter.n
         if fold:
-            folded_blocks = [m for m in unet.modules() if isinstance(m, blocks.ResnetBlock2D) and any(m.__dict__.get("_afldm_sc_fold", {}).values())]
+            folded_blocks = [m for m in unet.modules() if isinstance(m, blocks.ResnetBlock2D) and _plan_folds(m, 1)]
     # the halo-patch sites of batch 64: the three up-path blocks at 32^2, the first down block and the three up-path blocks at 16^2
     # (the 8^2 / 4^2 tiles take three taps per K step, the 2^2 level runs dense layers: two launches there)
     assert len(folded_blocks) == 7, len(folded_blocks)

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from test_gpu_r02 import build_unet, rel_rms
-from test_gpu_shortcut_fold import _CountConv, _block, _operands, _ref64
+from test_gpu_shortcut_fold import _CountConv, _block, _operands, _plan_folds, _ref64
 
 pytestmark = pytest.mark.gpu
 
@@ -203,7 +203,6 @@ def test_resnet_block_shortcut_fold3_switch(monkeypatch, dtype, tol, B, N, C1, C
     outs, calls = {}, {}
     for fold in (True, False):
         monkeypatch.setattr(blocks, "_SC_FOLD3", fold)
-        blk.__dict__.pop("_afldm_sc_fold3", None)
         counter = _CountConv(ops.lib)
         monkeypatch.setattr(ops, "lib", counter)
         y = blk(inp, temb.view(-1), 0)
@@ -211,7 +210,7 @@ def test_resnet_block_shortcut_fold3_switch(monkeypatch, dtype, tol, B, N, C1, C
         monkeypatch.setattr(ops, "lib", counter.raw)
         outs[fold], calls[fold] = y.float().clone(), counter.n
         assert getattr(y, "gn_partial", None) is not None
-        assert not any(blk.__dict__.get("_afldm_sc_fold", {}).values()), "no one-tap plan on these tiles"
+        assert not _plan_folds(blk, 1), "no one-tap plan on these tiles"
     assert calls[True] == calls[False] - (1 if folds else 0), calls
     if dtype == torch.float32:
         err = float((outs[True].double() - outs[False].double()).abs().max() / outs[False].double().abs().max())
@@ -238,8 +237,6 @@ def test_unet_forward_fold3_launches_and_graph_replay(monkeypatch):
     folded_blocks, outs, calls = [], {}, {}
     for fold in (False, True):
         monkeypatch.setattr(blocks, "_SC_FOLD3", fold)
-        for m in unet.modules():
-            m.__dict__.pop("_afldm_sc_fold3", None)
         counter = _CountConv(ops.lib)
         monkeypatch.setattr(ops, "lib", counter)
         with torch.no_grad():
@@ -248,7 +245,7 @@ def test_unet_forward_fold3_launches_and_graph_replay(monkeypatch):
         monkeypatch.setattr(ops, "lib", counter.raw)
         outs[fold], calls[fold] = y.float().clone(), counter.n
         if fold:
-            folded_blocks = [m for m in unet.modules() if isinstance(m, blocks.ResnetBlock2D) and any(m.__dict__.get("_afldm_sc_fold3", {}).values())]
+            folded_blocks = [m for m in unet.modules() if isinstance(m, blocks.ResnetBlock2D) and _plan_folds(m, 2)]
     assert len(folded_blocks) == 7 - len(CLASSES_OFF), len(folded_blocks)
     assert calls[False] - calls[True] == len(folded_blocks), (calls, len(folded_blocks))
     err = rel_rms(outs[True], outs[False].cpu())

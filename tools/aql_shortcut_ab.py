@@ -1,8 +1,8 @@
 #!/usr/bin/env python
-"""conv_shortcut beside its neighbour: the 17 shortcut GEMMs of a step do not depend on the activation they are launched
-next to; with the barrier bit of the marked launch cleared (afldm_amd/aql.py) the two run concurrently.
-AFLDM_SHORTCUT_ORDER=0/1/2 picks the neighbour.  Prints ms/step without and with the policy and the difference of the
-results after 10 steps (must be 0: same kernels, same inputs)."""
+"""conv_shortcut beside its neighbour: the shortcut GEMMs of a step that remain launches of their own do not depend on the
+second activation they are launched behind; with the barrier bit of the marked launch cleared (afldm_amd/aql.py) the two run
+concurrently.  Prints ms/step without and with the policy and the difference of the results after 10 steps (must be 0: same
+kernels, same inputs)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -33,7 +33,7 @@ aql.trace_begin()
 eng._step()
 torch.cuda.synchronize()
 n, marks = aql.trace_end()
-print(f"order {os.environ.get('AFLDM_SHORTCUT_ORDER', '0')}: {n} dispatches per step, {len(marks)} independent regions: {marks[:6]} ...", flush=True)
+print(f"{n} dispatches per step, {len(marks)} independent regions: {marks[:6]} ...", flush=True)
 aql.record(True); eng.reset(noise); torch.cuda.synchronize(); c0 = aql.counts()["dispatch"]; eng.graph.replay(); torch.cuda.synchronize()
 ng = aql.counts()["dispatch"] - c0
 aql.record(False)

@@ -12,11 +12,6 @@ for B in 64 1 8; do
     echo -n "B=$B const2 off: "; AFLDM_NO_CONST2=1 run $B
   done
 done
-for rep in 1 2; do
-  echo -n "B=64 sites none     : "; run 64
-  echo -n "B=64 sites 16:576   : "; AFLDM_ACTCONV_SITES=16:576 run 64
-  echo -n "B=64 sites 16:576,16:768 : "; AFLDM_ACTCONV_SITES=16:576,16:768 run 64
-done
 } > $O/ab.log 2>&1
 cat $O/ab.log
 bash profiles/run_profile.sh r06a > $O/prof.log 2>&1
