@@ -58,6 +58,20 @@ def _circulant(r):
     return first_col[(k[:, None] - k[None, :]) % N]
 
 
+def ilvr_filter(N, down_factor):
+    """The ILVR low-pass phi_N on an N x N plane as one [N, N] fp64 host matrix L (phi(x) = L x L^T): LPF_RFFT(cutoff = 1 /
+    down_factor)'s circulant.  An exact 0 / 1 frequency mask, so L is symmetric, L L = L, and it commutes with every circular
+    shift.  down_factor is any number > 0.  On a plane with N % 4 == 0 the reference's mask rule needs a bin below the cut-off,
+    lo = (N / down_factor) // 2 >= 1 (_rect_1d); a factor that leaves none raises ValueError."""
+    def lo(f):
+        return int((N * (1.0 / f)) // 2)          # (as _rect_1d computes it)
+    if down_factor <= 0 or (N % 4 == 0 and lo(down_factor) == 0):
+        valid = [f for f in range(1, N + 1) if N % 4 or lo(f) >= 1]
+        raise ValueError(f"ilvr: down_factor {down_factor} leaves no frequency band on a {N} x {N} plane; any factor up to "
+                         f"{valid[-1]} works, fractions included; valid integer factors: {', '.join(map(str, valid))}")
+    return torch.from_numpy(np.ascontiguousarray(_circulant(_rect_1d(N, 1.0 / down_factor, 0.0).numpy())))
+
+
 def _device_matrix(key, build, device):
     key = key + (str(device),)
     if key not in _MATRIX_CACHE:

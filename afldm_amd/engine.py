@@ -24,7 +24,11 @@ capture.  Draws on the CPU (a CPU generator) go through pinned staging: the next
 runs the current group.  Kind "repaint" (DDIMScheduler.repaint_schedule: RePaint inpainting) has [steps, 12] rows and the last
 line is afldm_repaint_step, which reads up to three noise slots per step of a buffer [steps, 3, B, C, H, W], filled the same way,
 and two static per-run tensors, the known latents and the latent mask - run(latents, draw=..., known=(z0, mask)).  The captured
-graphs hold the buffers' addresses only, so another image or mask replays the same graphs.
+graphs hold the buffers' addresses only, so another image or mask replays the same graphs.  Kind "ilvr"
+(DDIMScheduler.ilvr_schedule: ILVR reference-guided sampling) has [steps, 12] rows too and the last line is afldm_ilvr_step - the
+one update that is not elementwise: it low-passes a whole (b, c) plane in LDS.  It reads up to two noise slots per step of a buffer
+[steps, 2, B, C, H, W] and two static per-run tensors, the reference latents and the [S, S] filter matrix -
+run(latents, draw=..., known=(ref, L)); another reference or another cut-off replays the same graphs.
 
 cached_engine keeps the engines (and the harness's samplers) a pipeline has built: one resident entry per slot.
 """
@@ -124,7 +128,7 @@ class DenoiseEngine:
         # counters of in-kernel reductions / cluster hand-overs: private to this engine (one per branch), so that its
         # captured graphs can replay next to another engine's on a different stream
         self._sync = [ops.new_sync_buffer(dev) for _ in range(self.branches)]
-        self.hist = self.noise = self.known = self.mask = None
+        self.hist = self.noise = self.known = self.mask = self.filter = None
         self._update, state = self.UPDATES[self.schedule.kind]
         self._state = state(self)
 
@@ -156,10 +160,26 @@ class DenoiseEngine:
         return [(self.known[b * per:(b + 1) * per], self.mask[b * per:(b + 1) * per], self.noise[:, :, b * per:(b + 1) * per])
                 for b in range(self.branches)]
 
+    def _ilvr_state(self):
+        """Two noise slots per step (z_k, z_u), filled per run like the "repaint" ones, the run's reference latents and its
+        [S, S] low-pass matrix (used for both axes).  Every branch takes its batch slice of the reference and the noise; the
+        filter is shared."""
+        self.noise = torch.zeros((self.n, 2) + tuple(self.lat.shape), dtype=torch.float32, device=self.lat.device)
+        self.known = torch.zeros_like(self.lat)
+        self.filter = torch.zeros(tuple(self.lat.shape[2:]), dtype=torch.float32, device=self.lat.device)
+        self._stage = []
+        per = self.B // self.branches
+        return [(self.known[b * per:(b + 1) * per], self.noise[:, :, b * per:(b + 1) * per], self.filter, self.filter)
+                for b in range(self.branches)]
+
     # Schedule.kind -> the update of ops that ends a step, and what allocates the buffers it keeps between steps (one argument
     # tuple per branch, passed between eps and the coefficient table)
     UPDATES = {"ddim": (ops.ddim_step, _no_state), "dpm": (ops.dpm_step, _dpm_state), "sde": (ops.sde_step, _sde_state),
-               "repaint": (ops.repaint_step, _repaint_state)}
+               "repaint": (ops.repaint_step, _repaint_state), "ilvr": (ops.ilvr_step, _ilvr_state)}
+
+    # the kinds whose run() takes known=(latents, second tensor): the attribute that holds the second tensor's static buffer
+    # (its name in messages too), and whether a batch-1 one is broadcast
+    KNOWN = {"repaint": ("mask", True), "ilvr": ("filter", False)}
 
     # one denoise step, entirely stream-ordered
     def _step(self):
@@ -293,10 +313,10 @@ class DenoiseEngine:
 
     def _fill(self, k0, k1, draw):
         """Noise rows k0 .. k1 - 1: one draw() per slot a step draws ("sde": one per step at the most, "repaint": up to three - z_k,
-        z_u, z_b), in step and slot order.  A CPU draw is copied into pinned staging and on to the device with non_blocking
-        (stream-ordered before the replays that read it); the staging buffer is reused only after the event behind its previous
-        copy has passed.  A device draw is copied on the stream."""
-        slots = self.noise.dim() - self.lat.dim() - 1          # 0: one row per step ("sde"); 1: [steps, 3, ...] ("repaint")
+        z_u, z_b, "ilvr": up to two - z_k, z_u), in step and slot order.  A CPU draw is copied into pinned staging and on to the
+        device with non_blocking (stream-ordered before the replays that read it); the staging buffer is reused only after the
+        event behind its previous copy has passed.  A device draw is copied on the stream."""
+        slots = self.noise.dim() - self.lat.dim() - 1          # 0: one row per step ("sde"); 1: [steps, slots, ...] ("repaint", "ilvr")
         rows = [self.noise[k, j] if slots else self.noise[k] for k in range(k0, k1) for j in self.schedule.slots(k)]
         if not rows:
             return
@@ -325,23 +345,28 @@ class DenoiseEngine:
 
     @torch.no_grad()
     def run(self, latents, draw=None, known=None):
-        """latents -> the sampled latents (fp32).  An "sde" or "repaint" schedule needs `draw`: a callable returning the next
+        """latents -> the sampled latents (fp32).  An "sde", "repaint" or "ilvr" schedule needs `draw`: a callable returning the next
         noise tensor [B, C, H, W] (on the CPU or on the engine's device, any float dtype), called once per draw in step (and
         slot) order - for a seeded run, the scheduler's own randn_tensor call with the caller's generator (Schedule.drawer).
         A "repaint" schedule also needs known = (z0, mask): the latents to keep [B, C, H, W] and the latent mask [B | 1, 1, H, W]
-        (1 = keep), written to the engine's static buffers before the first replay."""
-        if (self.known is None) != (known is None):
-            raise ValueError("DenoiseEngine: known=(z0, mask) goes with a 'repaint' schedule, and only with one")
+        (1 = keep), an "ilvr" schedule known = (ref, L): the reference latents [B, C, H, W] and the low-pass matrix [H, H].
+        Both are written to the engine's static buffers before the first replay."""
+        entry = self.KNOWN.get(self.schedule.kind)
+        if (entry is None) != (known is None):
+            raise ValueError("DenoiseEngine: known=(z0, mask) goes with a 'repaint' schedule and known=(ref, L) with an 'ilvr' "
+                             "one, and only with those")
         if known is not None:
-            z0, mask = known
-            if tuple(z0.shape) != tuple(self.lat.shape) or tuple(mask.shape) not in ((1,) + tuple(self.mask.shape[1:]),
-                                                                                     tuple(self.mask.shape)):
-                raise ValueError(f"DenoiseEngine: known latents {tuple(z0.shape)} / mask {tuple(mask.shape)}, want "
-                                 f"{tuple(self.lat.shape)} / {tuple(self.mask.shape)} (or batch 1)")
+            name, broadcast = entry
+            second = getattr(self, name)
+            fits = [tuple(second.shape)] + ([(1,) + tuple(second.shape[1:])] if broadcast else [])
+            z0, extra = known
+            if tuple(z0.shape) != tuple(self.lat.shape) or tuple(extra.shape) not in fits:
+                raise ValueError(f"DenoiseEngine: known latents {tuple(z0.shape)} / {name} {tuple(extra.shape)}, want "
+                                 f"{tuple(self.lat.shape)} / {tuple(second.shape)}" + (" (or batch 1)" if broadcast else ""))
         self.reset(latents)
         if known is not None:
             self.known.copy_(z0)
-            self.mask.copy_(mask)           # (a batch-1 mask is broadcast)
+            second.copy_(extra)
         if self.noise is None:
             self.step(self.n)
         else:

@@ -1550,6 +1550,64 @@ def mask_pool(mask, r, mode=MASK_MIN, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- ILVR reference-guided sampling
+def _ilvr_plane(name, x, Lh, Lw):
+    """The checks ilvr_step and ilvr_step_flat share: fp32 [B, C, H, W] latents, Lh fp32 [H, H] and Lw fp32 [W, W] on the device.
+    Which planes there is a kernel for (square, 2 .. 64) is the library's to say: it refuses the others before any launch."""
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError(f"{name}: x must be fp32 [B, C, H, W], got {x.dtype} {tuple(x.shape)}")
+    for n, m, s in (("Lh", Lh, x.shape[2]), ("Lw", Lw, x.shape[3])):
+        _dev(m, n)
+        if m.dtype != torch.float32 or tuple(m.shape) != (s, s):
+            raise ValueError(f"{name}: {n} must be an fp32 [{s}, {s}] matrix, got {m.dtype} {tuple(m.shape)}")
+
+
+def ilvr_step(x, eps_nhwc, ref, noise, Lh, Lw, coef, step_idx, advance=False, out=None):
+    """x, ref NCHW fp32 [B, C, S, S], eps NHWC dtype, Lh / Lw fp32 [S, S] (phi(d) = Lh d Lw^T; may be the same tensor); noise:
+    fp32 view [steps, 2, B, C, S, S] (slots z_k, z_u) whose last four dimensions are contiguous (a batch slice of a larger buffer
+    is fine: the strides are noise.stride(0) and noise.stride(1)); coef float[12*nsteps] rows (p, q, lo, hi, a, b, c, k0, k1, w,
+    0, 0) and step_idx int32[1] on device."""
+    _dev(x, "x"); _dev(eps_nhwc, "eps"); _dev(ref, "ref")
+    if not noise.is_cuda:
+        raise RuntimeError("afldm_amd: noise must live on an MI355X (cuda) device; there is no CPU path")
+    _ilvr_plane("ilvr_step", x, Lh, Lw)
+    B, C, H, W = x.shape
+    assert ref.dtype == torch.float32 and ref.shape == x.shape and x.is_contiguous() and ref.is_contiguous()
+    assert tuple(eps_nhwc.shape) == (B, H, W, C) and eps_nhwc.is_contiguous()
+    assert noise.dtype == torch.float32 and noise.dim() == 6 and tuple(noise.shape[1:]) == (2, B, C, H, W)
+    assert noise[0, 0].is_contiguous() and noise.stride(1) >= B * C * H * W
+    assert noise.stride(0) >= noise.stride(1) + B * C * H * W
+    if out is None:
+        out = torch.empty_like(x)
+    check(lib.afldm_ilvr_step(ptr(x), ptr(eps_nhwc), ptr(ref), ptr(noise), noise.stride(0), noise.stride(1), ptr(Lh), ptr(Lw),
+                              ptr(out), ptr(coef), ptr(step_idx), int(advance), B, C, H, W, _code(eps_nhwc), stream_ptr()),
+          "ilvr_step")
+    return out
+
+
+def ilvr_step_flat(x, eps, ref, noises, Lh, Lw, row, out=None):
+    """x, eps, ref: same-shape contiguous fp32 CUDA tensors [B, C, S, S]; noises = (z_k, z_u), each such a tensor or None where it
+    is not read (z_k: k1 = 0 or w = 0; z_u: c = 0); Lh / Lw fp32 [S, S]; row = the floats (p, q, lo, hi, a, b, c, k0, k1, w)."""
+    _dev(x, "x"); _dev(eps, "eps"); _dev(ref, "ref")
+    _ilvr_plane("ilvr_step_flat", x, Lh, Lw)
+    assert eps.dtype == ref.dtype == torch.float32 and x.shape == eps.shape == ref.shape
+    assert x.is_contiguous() and eps.is_contiguous() and ref.is_contiguous()
+    row = [float(c) for c in row[:10]]
+    for z, c, name in zip(noises, (row[8] if row[9] != 0.0 else 0.0, row[6]), ("z_k", "z_u")):
+        if z is None:
+            if c != 0.0:
+                raise ValueError(f"ilvr_step_flat: {name} is None but its coefficient is {c}")
+            continue
+        _dev(z, name)
+        assert z.dtype == torch.float32 and z.shape == x.shape and z.is_contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    B, C, H, W = x.shape
+    check(lib.afldm_ilvr_step_flat(ptr(x), ptr(eps), ptr(ref), *[ptr(z) for z in noises], ptr(Lh), ptr(Lw), ptr(out), *row,
+                                   B * C, H, W, stream_ptr()), "ilvr_step_flat")
+    return out
+
+
 def select_timestep(tvals, step_idx, t_out, pre_advance=False):
     check(lib.afldm_select_timestep(ptr(tvals), ptr(step_idx), ptr(t_out), int(pre_advance), stream_ptr()),
           "select_timestep")

@@ -135,7 +135,7 @@ class MyLDMPipeline(DiffusionPipeline):
     # ------------------------------------------------------------------------------------------------ RePaint inpainting
     def _refuse_dpm(self, what):
         if isinstance(self.scheduler, DPMSolverMultistepScheduler):
-            raise NotImplementedError(f"{what} needs a DDIMScheduler: RePaint with {type(self.scheduler).__name__} is not implemented")
+            raise NotImplementedError(f"{what} needs a DDIMScheduler: it is not implemented with {type(self.scheduler).__name__}")
 
     @torch.no_grad()
     def inpaint_latents(self, known_latents, latent_mask, num_inference_steps=50, eta=0.0, jump_length=10, jump_n_sample=10,
@@ -212,3 +212,66 @@ class MyLDMPipeline(DiffusionPipeline):
         if composite:
             decoded = mask * image + (1 - mask) * decoded.float()
         return self._images(decoded, output_type, return_dict)
+
+    # ------------------------------------------------------------------------------------------------ ILVR reference guidance
+    @torch.no_grad()
+    def ilvr_latents(self, ref_latents, down_factor=4, range_t=0, num_inference_steps=50, eta=1.0, phi=None, generator=None,
+                     latents=None, use_graph=True):
+        """ILVR (Choi et al., ICCV 2021, Algorithm 1) in latent space: sample latents that share the low-frequency content of
+        `ref_latents` [B, C, S, S].  After every reverse step down to timestep `range_t` the low band phi(x') of the proposal is
+        replaced by that of the reference noised to the same level.  phi is the ideal low-pass LPF_RFFT(cutoff = 1 /
+        down_factor) as its [S, S] circulant L, phi(x) = L x L^T: an exact projection that commutes with every circular shift,
+        so the guidance is alias-free like the model (at S = 32 the factors 2, 4, 8 keep 15, 7, 3 frequencies per axis).  `phi`:
+        an [S, S] matrix used for both axes instead.  Needs no VAE.  The schedule is DDIMScheduler.ilvr_schedule: every UNet
+        evaluation ends in one afldm_ilvr_step, on replayed HIP graphs (use_graph) or in the eager loop below, which makes the
+        same draws from `generator` in the same order - the start latents (unless `latents` is given), then per evaluation z_k,
+        z_u where the schedule draws them - and carries the latents in fp32 like the engine.  Returns latents in the UNet's dtype."""
+        from .. import ops
+        from ..af_libs.ideal_lpf import ilvr_filter
+        self._refuse_dpm("ilvr_latents")
+        c, s = self.unet.config.in_channels, self.unet.config.sample_size
+        if ref_latents.dim() != 4 or tuple(ref_latents.shape[1:]) != (c, s, s):
+            raise ValueError(f"ilvr_latents: ref_latents {tuple(ref_latents.shape)}, want [B, {c}, {s}, {s}]")
+        B = ref_latents.shape[0]
+        if latents is not None and tuple(latents.shape) != (B, c, s, s):
+            raise ValueError(f"ilvr_latents: latents {tuple(latents.shape)}, want {(B, c, s, s)}")
+        if phi is not None and tuple(phi.shape) != (s, s):
+            raise ValueError(f"ilvr_latents: phi {tuple(phi.shape)}, want {(s, s)}")
+        dev = self.unet.device
+        L = (phi if phi is not None else ilvr_filter(s, down_factor)).to(device=dev, dtype=torch.float32).contiguous()
+        self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
+        sched = self.scheduler.ilvr_schedule(num_inference_steps, eta, range_t)
+        shape = (B, c, s, s)
+        draw = sched.drawer(generator, shape, dev, self.unet.dtype)
+        if latents is None:
+            latents = draw()            # (on the CPU for CPU generators, else on the device: the per-evaluation draws' rule)
+        ref = ref_latents.to(device=dev, dtype=torch.float32).contiguous()
+        if use_graph:
+            eng = cached_engine(self, "_ilvr_engines", sched, B, True, self.unet)
+            eng.scheduler = self.scheduler
+            return eng.run(latents, draw=draw, known=(ref, L)).to(self.unet.dtype)
+        x = (latents.to(device=dev, dtype=torch.float32) * sched.init_noise_sigma).contiguous()
+        for k, (t, row) in enumerate(self.progress_bar(list(zip(sched.timesteps, sched.rows)))):
+            on = sched.slots(k)
+            zs = [draw().to(device=dev, dtype=torch.float32).contiguous() if j in on else None for j in range(2)]
+            eps = self.unet(x.to(self.unet.dtype), t).sample
+            x = ops.ilvr_step_flat(x, eps.float().contiguous(), ref, zs, L, L, row)
+        return x.to(self.unet.dtype)
+
+    @torch.no_grad()
+    def ilvr(self, image, down_factor=4, range_t=0, num_inference_steps=50, eta=1.0, phi=None, generator=None, latents=None,
+             use_graph=True, output_type="pil", return_dict=True):
+        """Sample images that share the coarse content of `image` [B, 3, H, W] in [-1, 1]: the image is encoded with the
+        posterior mode times scaling_factor (as inpaint), the latents sampled by ilvr_latents and decoded.  output_type as
+        __call__; 'latent' returns the sampled latents."""
+        self._refuse_dpm("ilvr")
+        if self.vae is None:
+            raise NotImplementedError("this pipeline was built without a VAE: use ilvr_latents")
+        r = getattr(self.vae, "downsample_ratio", None) or 2 ** (len(self.vae.config.block_out_channels) - 1)
+        s = self.unet.config.sample_size
+        if image.dim() != 4 or tuple(image.shape[1:]) != (3, s * r, s * r):
+            raise ValueError(f"ilvr: image {tuple(image.shape)}, want [B, 3, {s * r}, {s * r}]")
+        image = image.to(device=self.unet.device, dtype=self.vae.dtype)
+        ref = self.vae.encode(image).latent_dist.mode() * self.vae.config.scaling_factor
+        out = self.ilvr_latents(ref, down_factor, range_t, num_inference_steps, eta, phi, generator, latents, use_graph)
+        return self._deliver(out, output_type, return_dict)

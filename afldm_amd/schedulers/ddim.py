@@ -130,6 +130,18 @@ class DDIMScheduler:
         return Schedule.of(self, "sde", ts, lambda t: self.sde_coefficients(t, eta), [True] * len(ts),
                            _ddim_steps=int(num_inference_steps), _ddim_eta=float(eta))
 
+    def _reverse_row(self, ab, ab_prev, eta):
+        """(p, q, lo, hi, a, b, c) of one reverse step from level ab to ab_prev (epsilon prediction), the first seven fields of
+        a "repaint" or "ilvr" row: x0 = clamp((x - sqrt(1-ab) eps) / sqrt(ab), -r, r) with r = clip_sample_range under
+        clip_sample and inf without; x' = sqrt(ab_prev) x0 + sqrt(1 - ab_prev - sigma^2) eps + sigma z, sigma = eta
+        sqrt(DDIM's _get_variance)."""
+        bound = math.inf
+        if self.config.clip_sample:
+            bound = float(self.config["clip_sample_range"]) if "clip_sample_range" in self.config else 1.0
+        sigma = float(eta) * math.sqrt((1 - ab_prev) / (1 - ab) * (1 - ab / ab_prev))
+        return (1 / math.sqrt(ab), -math.sqrt(1 - ab) / math.sqrt(ab), -bound, bound, math.sqrt(ab_prev),
+                math.sqrt(max(1 - ab_prev - sigma * sigma, 0.0)), sigma)
+
     @staticmethod
     def repaint_evaluations(num_inference_steps, jump_length, jump_n_sample):
         """The indices t (N - 1 = the noisiest of the scheduler's timesteps ... 0 = the last) of RePaint's UNet evaluations:
@@ -171,25 +183,49 @@ class DDIMScheduler:
 
         def level(t):
             return float(self.alphas_cumprod[g[n - 1 - t]]) if t >= 0 else float(self.final_alpha_cumprod)
-        bound = math.inf
-        if self.config.clip_sample:
-            bound = float(self.config["clip_sample_range"]) if "clip_sample_range" in self.config else 1.0
         ev = self.repaint_evaluations(n, jl, js)
         rows, draws = [], []
         for i, t in enumerate(ev):
             ab, ab_prev = level(t), level(t - 1)
-            sigma = float(eta) * math.sqrt((1 - ab_prev) / (1 - ab) * (1 - ab / ab_prev))
+            reverse = self._reverse_row(ab, ab_prev, eta)
+            sigma = reverse[6]
             last = i == len(ev) - 1
             k0, k1 = (1.0, 0.0) if last else (math.sqrt(ab_prev), math.sqrt(1 - ab_prev))
             u0, u1 = 1.0, 0.0
             if not last and ev[i + 1] >= t:
                 rho = level(ev[i + 1]) / ab_prev
                 u0, u1 = math.sqrt(rho), math.sqrt(1 - rho)
-            rows.append((1 / math.sqrt(ab), -math.sqrt(1 - ab) / math.sqrt(ab), -bound, bound, math.sqrt(ab_prev),
-                         math.sqrt(max(1 - ab_prev - sigma * sigma, 0.0)), sigma, k0, k1, u0, u1, 0.0))
+            rows.append(reverse + (k0, k1, u0, u1, 0.0))
             draws.append((k1 != 0.0, sigma != 0.0, u1 != 0.0))
         return Schedule.of(self, "repaint", [g[n - 1 - t] for t in ev], rows, draws, _repaint_steps=n, _repaint_eta=float(eta),
                            _repaint_jump_length=jl, _repaint_jump_n_sample=js)
+
+    def ilvr_schedule(self, num_inference_steps, eta=1.0, range_t=0):
+        """ILVR reference-guided sampling (Choi et al., ICCV 2021, Algorithm 1) over this scheduler's `num_inference_steps`
+        timesteps g[0] > ... > g[N-1], as the Schedule DenoiseEngine replays with afldm_ilvr_step.  For evaluation i, with
+        ab = alphas_cumprod[g[i]] and ab' the next level (final_alpha_cumprod after the last):
+          x' = the reverse step of repaint_schedule (eta = 1: DDPM's ancestral step, which the paper samples with)
+          y' = sqrt(ab') ref + sqrt(1-ab') z_k        the reference noised to level t-1, as Algorithm 1 states (the authors'
+                                                      public code noises it to level t); y' = ref on the last evaluation
+          x_out = x' + w phi(y' - x'),  w = 1 while g[i] > range_t and 0 from there on (the paper's conditioning range)
+        Draws per evaluation, in this order: z_k where w != 0 and its coefficient is not 0, z_u where sigma != 0 - one
+        randn_tensor of the latent shape in the model's dtype each."""
+        n = int(num_inference_steps)
+        if self.config.prediction_type != "epsilon":
+            raise NotImplementedError("afldm_amd.DDIMScheduler.ilvr_schedule implements epsilon prediction")
+        self.set_timesteps(n)
+        g = self._timesteps_host
+        rows, draws = [], []
+        for i, t in enumerate(g):
+            last = i == n - 1
+            ab = float(self.alphas_cumprod[t])
+            ab_prev = float(self.final_alpha_cumprod) if last else float(self.alphas_cumprod[g[i + 1]])
+            reverse = self._reverse_row(ab, ab_prev, eta)
+            k0, k1 = (1.0, 0.0) if last else (math.sqrt(ab_prev), math.sqrt(1 - ab_prev))
+            w = 1.0 if t > range_t else 0.0
+            rows.append(reverse + (k0, k1, w, 0.0, 0.0))
+            draws.append((w != 0.0 and k1 != 0.0, reverse[6] != 0.0))
+        return Schedule.of(self, "ilvr", g, rows, draws, _ilvr_steps=n, _ilvr_eta=float(eta), _ilvr_range_t=int(range_t))
 
     def step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None,
              variance_noise=None, return_dict=True):

@@ -490,6 +490,30 @@ int afldm_repaint_step_flat(const float* x, const float* eps, const float* known
  * mean (summed in fp64, rounded once). */
 enum { AFLDM_MASK_MIN = 0, AFLDM_MASK_MEAN = 1 };
 int afldm_mask_pool(const float* mask, float* out, int B, int H, int W, int r, int mode, afldm_stream_t stream);
+/* ---- ILVR reference-guided update (Choi et al., ICCV 2021, Algorithm 1) with a linear low-pass phi -----------------
+ * Step s = *step_idx applies the row coef[12 s .. 12 s + 12) = (p, q, lo, hi, a, b, c, k0, k1, w, 0, 0) and the two noise
+ * slots z_k, z_u = noise[s * noise_step_stride + slot * noise_slot_stride + i], slot = 0, 1:
+ *   x0    = clamp(p x + q eps, lo, hi)              lo = -inf, hi = +inf: no clip; a NaN passes through
+ *   xp    = a x0 + b eps + c z_u                    the unconditional proposal (the DDIM reverse step)
+ *   yk    = k0 ref + k1 z_k                         the reference, noised to the same level
+ *   x_out = xp + w (Lh (yk - xp) Lw^T)              per (b, c) plane: phi(d) = Lh d Lw^T
+ * It replaces, per step: the stochastic step, a subtraction, NCHW -> NHWC, afldm_af_resample (which rounds d to the model
+ * dtype), NHWC -> NCHW and an addition.  Lh, Lw: fp32 [S][S] row-major, general (no symmetry assumed), may be the same
+ * pointer.  Every sum runs k = 0 .. S-1 ascending in fp32 fmaf: a plane's bits do not depend on B or on the batch slice.
+ * z_k is not read where k1 = 0 or w = 0, z_u not where c = 0; with w = 0 neither are ref, Lh and Lw, and the launch is the
+ * plain stochastic step.  Planes are square, 2 <= H = W <= 64 (AFLDM_ESHAPE otherwise, before any launch).
+ * x, ref, x_out: NCHW fp32 [B,C,H,W], x_out may alias x; eps: NHWC dtype; noise: fp32 slots of [B,C,H,W] NCHW
+ * (noise_slot_stride >= B*C*H*W, noise_step_stride >= noise_slot_stride + B*C*H*W: a branch passes its batch slice of a
+ * [steps,2,B,C,H,W] buffer), drawn by the caller's generator outside any captured graph; step_idx / advance as the DDIM
+ * update above. */
+int afldm_ilvr_step(const float* x, const void* eps, const float* ref, const float* noise, size_t noise_step_stride,
+                    size_t noise_slot_stride, const float* Lh, const float* Lw, float* x_out, const float* coef, int* step_idx,
+                    int advance, int B, int C, int H, int W, int dtype, afldm_stream_t stream);
+/* Same update on same-layout fp32 tensors of `planes` contiguous H x W planes (eps too), the row by value, for an eager
+ * loop.  z_k / z_u may be NULL where they are not read; with w = 0 so may ref, Lh and Lw. */
+int afldm_ilvr_step_flat(const float* x, const float* eps, const float* ref, const float* z_k, const float* z_u,
+                         const float* Lh, const float* Lw, float* x_out, float p, float q, float lo, float hi, float a, float b,
+                         float c, float k0, float k1, float w, size_t planes, int H, int W, afldm_stream_t stream);
 /* tvals[step] -> t_out[0] (device->device), so the timestep also follows step_idx.  pre_advance != 0:
  * step_idx is incremented first (a sampler loop then starts from step_idx = -1 and needs no `advance`
  * launch behind afldm_ddim_step). */
