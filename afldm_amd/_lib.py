@@ -129,6 +129,10 @@ def _load():
         "afldm_flow_splat_workspace": ([ip] * 6, c_size_t),
         "afldm_flow_splat": ([vp, vp, vp, vp, c_longlong, ip, vp, vp, vp, c_size_t] + [ip] * 8 + [vp], c_int),
         "afldm_flow_warp": ([vp, vp, vp, vp] + [ip] * 9 + [vp], c_int),
+        "afldm_flowest_pyr_down": ([vp, vp, ip, ip, ip, ip, ip, vp], c_int),
+        "afldm_flowest_up2": ([vp, vp, ip, ip, ip, vp], c_int),
+        "afldm_flowest_lk_step": ([vp, vp, vp, vp, ip, ip, ip, ip, ip, fp, ip, vp], c_int),
+        "afldm_flowest_smooth": ([vp, vp, ip, ip, ip, vp], c_int),
         "afldm_select_timestep": ([vp, vp, vp, ip, vp], c_int),
         "afldm_select_step_row": ([vp, vp, vp, ip, vp, vp, c_size_t, vp], c_int),
         "afldm_probe_mfma": ([vp, ip, ip, vp], c_int),

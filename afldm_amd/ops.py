@@ -1695,3 +1695,69 @@ def flow_warp(x, flow, add_grid=True, nearest=False, mask=False):
     check(lib.afldm_flow_warp(ptr(x), ptr(flow), ptr(y), ptr(m), B, C, Hi, Wi, Ho, Wo, int(bool(add_grid)), int(bool(nearest)),
                               _code(x), stream_ptr()), "flow_warp")
     return (y, m) if mask else y
+
+
+def _flowest_planes(t, name):
+    _dev(t, name)
+    if t.dtype != torch.float32 or t.dim() < 2:
+        raise ValueError(f"{name} must be fp32 [..., H, W], got {t.dtype} {tuple(t.shape)}")
+    H, W = t.shape[-2:]
+    return t.numel() // (H * W), H, W
+
+
+def flowest_pyr_down(x, factor=2, out=None):
+    """afldm_flowest_pyr_down: x [..., H, W] (fp32 / bf16) -> fp32 [..., H/factor, W/factor]; factor 2 = [1, 3, 3, 1] / 8 along each
+    axis (replicate border) decimated by 2, factor 1 = the conversion to fp32."""
+    _dev(x, "x")
+    if x.dim() < 2 or factor not in (1, 2):
+        raise ValueError(f"flowest_pyr_down: x must be [..., H, W] and factor 1 or 2, got {tuple(x.shape)}, factor {factor!r}")
+    H, W = x.shape[-2:]
+    if factor == 2 and (H % 2 or W % 2):
+        raise ValueError(f"flowest_pyr_down: H = {H} and W = {W} must be even")
+    shape = tuple(x.shape[:-2]) + (H // factor, W // factor)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    _dev(out, "out")
+    assert out.dtype == torch.float32 and tuple(out.shape) == shape
+    check(lib.afldm_flowest_pyr_down(ptr(x), ptr(out), x.numel() // (H * W), H, W, factor, _code(x), stream_ptr()), "flowest_pyr_down")
+    return out
+
+
+def flowest_up2(u, out=None):
+    """afldm_flowest_up2: fp32 u [..., h, w] -> 2 * bilinear_up2(u) [..., 2h, 2w] (half-pixel centres, clamped)."""
+    n, h, w = _flowest_planes(u, "u")
+    shape = tuple(u.shape[:-2]) + (2 * h, 2 * w)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=u.device)
+    assert _flowest_planes(out, "out") == (n, 2 * h, 2 * w)
+    check(lib.afldm_flowest_up2(ptr(u), ptr(out), n, h, w, stream_ptr()), "flowest_up2")
+    return out
+
+
+def flowest_smooth(u, out=None):
+    """afldm_flowest_smooth: [1, 4, 6, 4, 1] / 16 along each axis of fp32 u [..., H, W], replicate border (not in place)."""
+    n, H, W = _flowest_planes(u, "u")
+    if out is None:
+        out = torch.empty_like(u)
+    assert _flowest_planes(out, "out") == (n, H, W)
+    check(lib.afldm_flowest_smooth(ptr(u), ptr(out), n, H, W, stream_ptr()), "flowest_smooth")
+    return out
+
+
+def flowest_lk_step(I1, I2, u, radius=3, lam=1e-3, out=None, tile=0):
+    """afldm_flowest_lk_step: one damped Lucas-Kanade update of the flow u [B, 2, H, W] (fp32, channel 0 = row displacement)
+    for the pair I1, I2 [B, C, H, W] (fp32, C <= 4) in one launch; returns u + du (not in place).  tile: 0 (chosen by the
+    call), 16 or 32: the workgroup's output tile; the result does not depend on it."""
+    _dev(I1, "I1"); _dev(I2, "I2"); _dev(u, "u")
+    if I1.dim() != 4 or I1.shape != I2.shape or I1.dtype != torch.float32 or I2.dtype != torch.float32:
+        raise ValueError(f"flowest_lk_step: I1 and I2 must be fp32 [B, C, H, W] of one shape, got {tuple(I1.shape)} and {tuple(I2.shape)}")
+    B, C, H, W = I1.shape
+    if u.dtype != torch.float32 or tuple(u.shape) != (B, 2, H, W):
+        raise ValueError(f"flowest_lk_step: u must be fp32 [{B}, 2, {H}, {W}], got {u.dtype} {tuple(u.shape)}")
+    if out is None:
+        out = torch.empty_like(u)
+    _dev(out, "out")
+    assert out.dtype == torch.float32 and out.shape == u.shape
+    check(lib.afldm_flowest_lk_step(ptr(I1), ptr(I2), ptr(u), ptr(out), B, C, H, W, int(radius), float(lam), int(tile),
+                                    stream_ptr()), "flowest_lk_step")
+    return out

@@ -87,9 +87,31 @@ class LDMInterpolationPipeline(MyLDMPipeline):
     """Two-image interpolation with the interpolating cross-frame attention.  Build it with from_pretrained(dir) (as
     MyLDMPipeline) or from another pipeline's modules: LDMInterpolationPipeline(**ldm_pipeline.components)."""
 
+    def __init__(self, vae, unet, scheduler, flow_model=None):
+        """flow_model: an optional flow estimator of shift_utils.flow_estimation (PyramidLKFlow).  With one, warp_method
+        0 / 1 / 2 without flows= estimate the flow between the two images; without one (the default) nothing changes."""
+        super().__init__(vae, unet, scheduler)
+        self.flow_model = flow_model            # not a registered module: `components` stays (vae, unet, scheduler)
+
     @property
     def vae_scale_factor(self):
         return 2 ** (len(self.vae.config.block_out_channels) - 1)
+
+    def _estimated_flows(self, image1, image2, timings=None):
+        """(the two preprocessed images, (fwd_flow, bwd_flow) from predict_flow(self.flow_model, ...) on them).  With a timings
+        dict the estimate's wall time goes to 'flow_s' (it runs before the phases 'total_s' covers)."""
+        import time
+        from ..shift_utils.flow_estimation import predict_flow
+        size = self.unet.config.sample_size * self.vae_scale_factor
+        images = [self._image(im, size) for im in (image1, image2)]
+        if timings is not None:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+        fwd_flow, _, bwd_flow, _ = predict_flow(self.flow_model, *(x.to(self.unet.device) for x in images))
+        if timings is not None:
+            torch.cuda.synchronize()
+            timings["flow_s"] = time.perf_counter() - t0
+        return images, (fwd_flow, bwd_flow)
 
     def _image(self, image, size):
         """PIL image / path -> [1, 3, size, size] in [-1, 1] (Lanczos resize, diffusers VaeImageProcessor's default); a [-1, 1]
@@ -126,8 +148,13 @@ class LDMInterpolationPipeline(MyLDMPipeline):
         warp_method 0 / 1 / 2 (reference :556-599) start the intermediate frames from the inverted noise warped along
         flows = (fwd_flow, bwd_flow), each [1, 2, S, S] at the image size in the convention of the reference's predict_flow
         (channel 0 = x: the output of a GMFlow-style estimator as it is); generator seeds their random draws (the fill of
-        disoccluded pixels, method 1's noise up-sampling).  warp_method 3 uses neither."""
+        disoccluded pixels, method 1's noise up-sampling).  warp_method 3 uses neither.  On a pipeline built with flow_model=,
+        flows=None lets it estimate them from the two preprocessed images (shift_utils.flow_estimation.predict_flow)."""
         from ..harness import _Clock
+        images = None
+        if self.flow_model is not None and flows is None and warp_method in (0, 1, 2) and self.vae is not None:
+            check_interp_args(self.scheduler, num_frames, 3)      # num_frames and the scheduler are refused before any work
+            images, flows = self._estimated_flows(image1, image2, timings)      # then exactly as if the caller had passed them
         check_interp_args(self.scheduler, num_frames, warp_method, flows,
                           self.unet.config.sample_size * self.vae_scale_factor if self.vae is not None else None)
         if self.vae is None:
@@ -136,7 +163,8 @@ class LDMInterpolationPipeline(MyLDMPipeline):
         unet, n = self.unet, int(num_frames)
         self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
         size = unet.config.sample_size * self.vae_scale_factor
-        images = [self._image(im, size) for im in (image1, image2)]
+        if images is None:
+            images = [self._image(im, size) for im in (image1, image2)]
         fracs, weights = interp_alphas(n)
         if not enable_interp:
             weights = [0.0] * n           # pass 0 only: alpha 0 is exactly the single-source attention

@@ -569,6 +569,30 @@ int afldm_flow_splat(const void* x, const float* flow, const float* scale, const
 int afldm_flow_warp(const void* x, const float* flow, void* y, unsigned char* mask, int B, int C, int Hin, int Win, int Hout,
                     int Wout, int add_grid, int nearest, int dtype, afldm_stream_t stream);
 
+/* ---- optical-flow estimation: dense pyramidal Lucas-Kanade ---------------------------
+ * Not a port: the reference estimates flow with GMFlow, a trained network.  This is a classical, deterministic estimator
+ * defined by this project (tests/flowest_oracle.py is its float64 statement).  All planes are fp32 except the input of
+ * afldm_flowest_pyr_down; flows are [B][2][H][W] with channel 0 = ROW displacement; every border is a replicate border
+ * (indices clamped into the plane); no atomics: two runs agree bit for bit.  Every call is stream-ordered, allocates
+ * nothing and may be captured.
+ * afldm_flowest_pyr_down: x [n][H][W] dtype -> y fp32.  factor 2: y [n][H/2][W/2], [1, 3, 3, 1] / 8 along the columns, then
+ *   along the rows, decimated by 2: output (i, j) reads rows 2i-1 .. 2i+2 and columns 2j-1 .. 2j+2 (H, W even).
+ *   factor 1: y [n][H][W] = x converted to fp32 (level 0 of the pyramid).
+ * afldm_flowest_up2: y [n][2h][2w] = 2 * bilinear(u [n][h][w]) at the source coordinate (i + 0.5) / 2 - 0.5 clamped to
+ *   [0, h - 1] (half-pixel centres): a flow carried to the next finer level.
+ * afldm_flowest_lk_step: one update of u_in [B][2][H][W] for the pair I1, I2 [B][C][H][W], C <= 4, in one launch:
+ *   I2w(p) = bilinear(I2, clamp(p + u_in(p))); g = (grad I1 + grad I2w) / 2 (central differences); It = I2w - I1; the
+ *   products gy gy, gy gx, gx gx, gy It, gx It summed over the channels and averaged over the (2 radius + 1)^2 window
+ *   (1 <= radius <= 4) to a, b, c, p, q; du = -[[a + lam, b], [b, c + lam]]^-1 [p, q] (closed form, lam > 0);
+ *   u_out = u_in + du min(1, 1 / |du|).  u_out must not be u_in.  tile: the side of a workgroup's output tile, 16 or 32,
+ *   or 0 to let the call choose (32 when that still gives 512 workgroups, else 16); the result does not depend on it.
+ * afldm_flowest_smooth: y = [1, 4, 6, 4, 1] / 16 along the columns, then along the rows, of u [n][H][W]; y must not be u. */
+int afldm_flowest_pyr_down(const void* x, float* y, int n, int H, int W, int factor, int dtype, afldm_stream_t stream);
+int afldm_flowest_up2(const float* u, float* y, int n, int h, int w, afldm_stream_t stream);
+int afldm_flowest_lk_step(const float* I1, const float* I2, const float* u_in, float* u_out, int B, int C, int H, int W,
+                          int radius, float lam, int tile, afldm_stream_t stream);
+int afldm_flowest_smooth(const float* u, float* y, int n, int H, int W, afldm_stream_t stream);
+
 /* ---- upfirdn2d ---------------------------------------------------------------------------
  * Zero-stuffing up-sample (upx, upy) -> pad (negative = crop) -> 2-D FIR -> decimate (downx, downy) on
  * NCHW planes: torch_utils/ops/upfirdn2d.py:140-194 (`_upfirdn2d_ref`; the reference's fast path is the

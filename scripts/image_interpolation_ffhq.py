@@ -34,12 +34,14 @@ def parse_args(argv=None):
                    help="how intermediate frames start (reference image_interpolation_pipeline.py:556-599): 0 = up-sampled noise "
                         "forward-warped along the flow (the reference script's choice), 1 = conditional noise up-sampling + warp, "
                         "2 = the latents warped, 3 = slerp only; 0-2 need --flow")
-    p.add_argument("--flow", type=str, default=None, metavar="FILE.npz",
+    p.add_argument("--flow", type=str, default=None, metavar="FILE.npz | estimate",
                    help="optical flow between the two images from any estimator: arrays `fwd` and `bwd`, each [2, S, S] or "
-                        "[1, 2, S, S] at the image size, channel 0 = x displacement (GMFlow's output convention)")
+                        "[1, 2, S, S] at the image size, channel 0 = x displacement (GMFlow's output convention); or the word "
+                        "`estimate`: the built-in pyramidal Lucas-Kanade estimator (shift_utils.flow_estimation.PyramidLKFlow: "
+                        "a classical estimator, not GMFlow)")
     args = p.parse_args(argv)
     if args.warp_method != 3 and not args.flow:
-        p.error("--warp-method 0, 1 and 2 warp along optical flow: pass --flow FILE.npz (arrays fwd, bwd)")
+        p.error("--warp-method 0, 1 and 2 warp along optical flow: pass --flow FILE.npz (arrays fwd, bwd) or --flow estimate")
     if args.n_frames < 2:
         p.error("--n_frames must be >= 2")
     if not args.random_init and not (args.input_path_1 and args.input_path_2):
@@ -69,6 +71,16 @@ def load_flows(path):
             f = torch.from_numpy(np.asarray(z[k], dtype=np.float32))
             out.append(f[None] if f.dim() == 3 else f)
     return tuple(out)
+
+
+def flow_source(pipe, flow):
+    """What --flow asks for: `estimate` hands the pipeline the built-in estimator (it then estimates the flows itself: None is
+    returned), a file gives the caller's (fwd_flow, bwd_flow), nothing gives None."""
+    if flow == "estimate":
+        from afldm_amd.shift_utils.flow_estimation import PyramidLKFlow
+        pipe.flow_model = PyramidLKFlow()
+        return None
+    return load_flows(flow) if flow else None
 
 
 def build_pipeline(args):
@@ -105,7 +117,7 @@ def main(argv=None):
         image1, image2 = synthetic_images(args.seed)
     else:
         image1, image2 = args.input_path_1, args.input_path_2
-    flows = load_flows(args.flow) if args.flow else None
+    flows = flow_source(pipe, args.flow)
     frames = pipe(image1, image2, num_frames=args.n_frames, num_inference_steps=args.n_steps, output_type="pt",
                   use_graph=not args.eager, warp_method=args.warp_method, flows=flows,
                   generator=torch.Generator().manual_seed(args.seed))
