@@ -126,6 +126,10 @@ def _load():
         "afldm_mask_pool": ([vp, vp, ip, ip, ip, ip, ip, vp], c_int),
         "afldm_ilvr_step": ([vp, vp, vp, vp, c_size_t, c_size_t, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, vp], c_int),
         "afldm_ilvr_step_flat": ([vp] * 8 + [fp] * 10 + [c_size_t, ip, ip, vp], c_int),
+        "afldm_pano_step": ([vp, vp, vp, c_size_t, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, POINTER(c_int), ip, POINTER(c_int), ip, ip,
+                             ip, ip, vp], c_int),
+        "afldm_window_fuse": ([vp, vp, vp, ip, ip, ip, ip, ip, POINTER(c_int), ip, POINTER(c_int), ip, ip, ip, ip, vp], c_int),
+        "afldm_window_crop": ([vp, vp, ip, ip, ip, ip, ip, POINTER(c_int), ip, POINTER(c_int), ip, ip, ip, vp], c_int),
         "afldm_flow_splat_workspace": ([ip] * 6, c_size_t),
         "afldm_flow_splat": ([vp, vp, vp, vp, c_longlong, ip, vp, vp, vp, c_size_t] + [ip] * 8 + [vp], c_int),
         "afldm_flow_warp": ([vp, vp, vp, vp] + [ip] * 9 + [vp], c_int),

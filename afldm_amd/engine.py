@@ -30,6 +30,11 @@ one update that is not elementwise: it low-passes a whole (b, c) plane in LDS.  
 [steps, 2, B, C, H, W] and two static per-run tensors, the reference latents and the [S, S] filter matrix -
 run(latents, draw=..., known=(ref, L)); another reference or another cut-off replays the same graphs.
 
+PanoramaEngine (kind "pano", DDIMScheduler.panorama_schedule: MultiDiffusion) samples a canvas [P, C, Hc, Wc] larger than the UNet's
+window: `lat` holds the P * nwin windows of a panorama.Geometry, the canvas is a second fp32 buffer, and the last line of a step is
+afldm_pano_step, which applies the "sde" row per window, averages over the windows that cover each canvas element and writes both
+the canvas and its crops (the next `lat`).  The noise buffer is canvas-shaped, [steps, P, C, Hc, Wc].
+
 cached_engine keeps the engines (and the harness's samplers) a pipeline has built: one resident entry per slot.
 """
 import contextlib
@@ -87,6 +92,8 @@ def cached_engine(owner, slot, schedule, batch, use_graph, unet, build=None, ext
 
 
 class DenoiseEngine:
+    ONE_BRANCH = False          # an update that needs the whole batch in one launch (PanoramaEngine) takes no parallel branches
+
     def __init__(self, unet, scheduler, batch_size, num_inference_steps=50, use_graph=True, steps_per_graph=5, branches=1):
         if unet.device.type != "cuda":
             raise RuntimeError("DenoiseEngine needs the UNet on an MI355X ('cuda') device; there is no CPU path")
@@ -120,7 +127,7 @@ class DenoiseEngine:
         self.temb_slices = unet.temb_slices(self.temb_row)
         self._model_key = model_state_key(unet)
         nb = int(os.environ.get("AFLDM_BRANCHES", branches))
-        self.branches = nb if nb > 1 and batch_size % nb == 0 else 1
+        self.branches = nb if nb > 1 and batch_size % nb == 0 and not self.ONE_BRANCH else 1
         self._side = [torch.cuda.Stream() for _ in range(self.branches - 1)]
         if self.branches > 1:
             from . import trunk
@@ -213,14 +220,13 @@ class DenoiseEngine:
         """One captured graph per entry of `counts`, each holding that many steps from the start of the schedule, after ONE
         warm-up step on a side stream.  before_step(i): called on the host before step i is launched or recorded (the harness
         tells its attention processors the timestep).  The engine's state is as before on return."""
-        keep = self.lat.clone()
-        keep_hist = None if self.hist is None else self.hist.clone()     # the warm-up step shifts the history too
+        carried = self._carried()                     # the warm-up step shifts the history too
+        keep = [t.clone() for t in carried]
 
         def rewind():
             self.step_idx.fill_(-1)
-            self.lat.copy_(keep)
-            if keep_hist is not None:
-                self.hist.copy_(keep_hist)
+            for t, k in zip(carried, keep):
+                t.copy_(k)
 
         def steps(k):
             for i in range(k):
@@ -244,6 +250,17 @@ class DenoiseEngine:
             graphs.append(g)
         rewind()
         return graphs
+
+    def _carried(self):
+        """The buffers a step reads and overwrites: what _capture puts back after its warm-up step and its captures."""
+        return [self.lat] + ([] if self.hist is None else [self.hist])
+
+    def _noise_row_shape(self):
+        """The shape of one draw: a noise row's, whatever precedes it in the buffer ([steps] or [steps, slots])."""
+        return tuple(self.noise.shape[-self.lat.dim():])
+
+    def _result(self):
+        return self.lat.clone()
 
     def check_errors(self):
         """Read (and clear) the error words of this engine's sync buffers.  The attention block's in-launch hand-over
@@ -316,6 +333,7 @@ class DenoiseEngine:
         z_u, z_b, "ilvr": up to two - z_k, z_u), in step and slot order.  A CPU draw is copied into pinned staging and on to the
         device with non_blocking (stream-ordered before the replays that read it); the staging buffer is reused only after the
         event behind its previous copy has passed.  A device draw is copied on the stream."""
+        shape = self._noise_row_shape()                        # ("pano": the canvas's, not lat's)
         slots = self.noise.dim() - self.lat.dim() - 1          # 0: one row per step ("sde"); 1: [steps, slots, ...] ("repaint", "ilvr")
         rows = [self.noise[k, j] if slots else self.noise[k] for k in range(k0, k1) for j in self.schedule.slots(k)]
         if not rows:
@@ -323,15 +341,15 @@ class DenoiseEngine:
         stage = None
         for i, row in enumerate(rows):
             z = draw()
-            if tuple(z.shape) != tuple(self.lat.shape):
-                raise ValueError(f"DenoiseEngine: draw() gave {tuple(z.shape)}, want {tuple(self.lat.shape)}")
+            if tuple(z.shape) != shape:
+                raise ValueError(f"DenoiseEngine: draw() gave {tuple(z.shape)}, want {shape}")
             if z.device.type != "cpu":
                 row.copy_(z)
                 continue
             if stage is None:
                 if len(self._stage) < 2:
                     per_step = self.noise.shape[1] if slots else 1
-                    self._stage.append((torch.empty((self.steps_per_graph * per_step,) + tuple(self.lat.shape),
+                    self._stage.append((torch.empty((self.steps_per_graph * per_step,) + shape,
                                                     dtype=torch.float32, pin_memory=True), torch.cuda.Event()))
                     stage = self._stage[-1]
                 else:
@@ -381,6 +399,62 @@ class DenoiseEngine:
                 self.step(m)
                 k += m
                 self._fill(k, min(k + g, self.n), draw)
-        out = self.lat.clone()
+        out = self._result()
         self.check_errors()                           # one 8-byte read per run: a run whose hand-over failed must not return latents
         return out
+
+
+class PanoramaEngine(DenoiseEngine):
+    """MultiDiffusion on the replayed graphs: P canvases [P, C, Hc, Wc], each seen by the UNet through the nwin windows of
+    `geometry` (panorama.Geometry) - batch_size = P * nwin window planes in `lat`, window k of canvas P at entry P * nwin + k.
+    A step is the plain sampler's launch list with afldm_pano_step in place of afldm_sde_step.  reset(canvas) writes the canvas and
+    crops the windows; run(canvas, draw=...) returns the final canvas, and needs `draw` (canvas-shaped) only when a step draws.
+    The geometry is baked into the captured graphs: it belongs in the cache key (cached_engine(..., extra=(geometry,)))."""
+    ONE_BRANCH = True           # the update reads all windows of a canvas
+
+    def __init__(self, unet, scheduler, batch_size, num_inference_steps=50, use_graph=True, steps_per_graph=5, branches=1,
+                 geometry=None):
+        geometry = geometry if geometry is not None else getattr(self, "geometry", None)      # (refresh_if_stale re-runs __init__)
+        if geometry is None:
+            raise ValueError("PanoramaEngine needs a panorama.Geometry")
+        c, s = unet.config.in_channels, unet.config.sample_size
+        if geometry.S != s or batch_size % geometry.nwin:
+            raise ValueError(f"PanoramaEngine: windows of {geometry.S} for a UNet of sample_size {s}, batch {batch_size} for "
+                             f"{geometry.nwin} windows per canvas")
+        self.geometry, self.P = geometry, batch_size // geometry.nwin
+        self.canvas = torch.zeros(self.P, c, geometry.Hc, geometry.Wc, dtype=torch.float32, device=unet.device)
+        self.wt = torch.ones(s, s, dtype=torch.float32, device=unet.device)      # MultiDiffusion's plain count average
+        super().__init__(unet, scheduler, batch_size, num_inference_steps, use_graph, steps_per_graph, 1)
+
+    def _pano_state(self):
+        """One canvas-shaped noise row per step, filled per run - only when some step draws (eta != 0); the steps that draw none
+        keep zeros and are not read (c = 0 there)."""
+        if any(self.schedule.draws):
+            self.noise = torch.zeros((self.n,) + tuple(self.canvas.shape), dtype=torch.float32, device=self.canvas.device)
+            self._stage = []
+        return [(self.noise, self.wt, self.geometry)]
+
+    UPDATES = {"pano": (ops.pano_step, _pano_state)}
+
+    def _substep(self, lat, x_nhwc, branch=0):
+        with ops.sync_scope(self._sync[branch]):
+            ops.to_nhwc(lat, self.unet.dtype, out=x_nhwc)
+            eps = self.unet.forward_nhwc(x_nhwc, self.t_cur, temb_slices=self.temb_slices)
+            self._update(self.canvas, eps, *self._state[branch], self.coef, self.step_idx, advance=False, out=self.canvas,
+                         windows_out=lat)
+
+    def _carried(self):
+        return [self.lat, self.canvas]
+
+    def _result(self):
+        return self.canvas.clone()
+
+    def reset(self, canvas):
+        """canvas: [P, C, Hc, Wc] (any device / float dtype); scaled by init_noise_sigma, written to the canvas buffer and cropped
+        into the windows."""
+        if tuple(canvas.shape) != tuple(self.canvas.shape):
+            raise ValueError(f"PanoramaEngine: canvas {tuple(canvas.shape)}, want {tuple(self.canvas.shape)}")
+        self.refresh_if_stale()
+        self.canvas.copy_(canvas.to(device=self.canvas.device, dtype=torch.float32) * self.schedule.init_noise_sigma)
+        ops.window_crop(self.canvas, self.geometry, out=self.lat)
+        self.step_idx.fill_(-1)

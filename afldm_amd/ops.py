@@ -1608,6 +1608,85 @@ def ilvr_step_flat(x, eps, ref, noises, Lh, Lw, row, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- MultiDiffusion: a canvas through windows
+def _geom_args(g):
+    """A panorama.Geometry as the C arguments (Hc, Wc, S, oy, ny, ox, nx, wrap_y, wrap_x); the origin lists are host arrays the
+    library reads during the call (the kernels get them by value)."""
+    oy, ox = (ctypes.c_int * len(g.oy))(*g.oy), (ctypes.c_int * len(g.ox))(*g.ox)
+    return g.Hc, g.Wc, g.S, oy, len(g.oy), ox, len(g.ox), int(g.wrap_y), int(g.wrap_x)
+
+
+def _pano_canvas(name, canvas, g):
+    _dev(canvas, "canvas")
+    if canvas.dim() != 4 or canvas.dtype != torch.float32 or tuple(canvas.shape[2:]) != (g.Hc, g.Wc):
+        raise ValueError(f"{name}: the canvas must be fp32 [P, C, {g.Hc}, {g.Wc}], got {canvas.dtype} {tuple(canvas.shape)}")
+    return canvas.shape[0], canvas.shape[1]
+
+
+def _pano_weights(name, wt, g):
+    _dev(wt, "wt")
+    if wt.dtype != torch.float32 or tuple(wt.shape) != (g.S, g.S):
+        raise ValueError(f"{name}: wt must be an fp32 [{g.S}, {g.S}] plane, got {wt.dtype} {tuple(wt.shape)}")
+
+
+def pano_step(canvas, eps_nhwc, noise, wt, geometry, coef, step_idx, advance=False, out=None, windows_out=None):
+    """The fused MultiDiffusion update (afldm_pano_step): canvas fp32 [P, C, Hc, Wc], eps NHWC dtype [P * nwin, S, S, C] (the UNet's
+    output on the windows of `geometry`, a panorama.Geometry), wt fp32 [S, S] > 0, noise: fp32 view [steps, P, C, Hc, Wc] whose
+    last four dimensions are contiguous, or None when no row has c != 0; coef float[8*nsteps] "sde" rows and step_idx int32[1] on
+    device.  Returns (canvas_out, windows_out): the new canvas (out= may be the canvas itself) and its crops, NCHW fp32
+    [P * nwin, C, S, S] - the next UNet input."""
+    g = geometry
+    P, C = _pano_canvas("pano_step", canvas, g)
+    _dev(eps_nhwc, "eps"); _pano_weights("pano_step", wt, g)
+    if tuple(eps_nhwc.shape) != (P * g.nwin, g.S, g.S, C):
+        raise ValueError(f"pano_step: eps {tuple(eps_nhwc.shape)}, want NHWC {(P * g.nwin, g.S, g.S, C)}")
+    stride = 0
+    if noise is not None:
+        if not noise.is_cuda:
+            raise RuntimeError("afldm_amd: noise must live on an MI355X (cuda) device; there is no CPU path")
+        assert noise.dtype == torch.float32 and noise.dim() == 5 and tuple(noise.shape[1:]) == tuple(canvas.shape)
+        assert noise[0].is_contiguous() and noise.stride(0) >= canvas.numel()
+        stride = noise.stride(0)
+    if out is None:
+        out = torch.empty_like(canvas)
+    if windows_out is None:
+        windows_out = torch.empty(P * g.nwin, C, g.S, g.S, dtype=torch.float32, device=canvas.device)
+    _dev(out, "out"); _dev(windows_out, "windows_out")
+    assert out.dtype == windows_out.dtype == torch.float32 and out.shape == canvas.shape
+    assert tuple(windows_out.shape) == (P * g.nwin, C, g.S, g.S)
+    check(lib.afldm_pano_step(ptr(canvas), ptr(eps_nhwc), ptr(noise), stride, ptr(wt), ptr(out), ptr(windows_out), ptr(coef),
+                              ptr(step_idx), int(advance), P, C, *_geom_args(g), _code(eps_nhwc), stream_ptr()), "pano_step")
+    return out, windows_out
+
+
+def window_fuse(windows, wt, geometry, out=None):
+    """windows NCHW fp32 / bf16 [P * nwin, C, S, S] -> the fp32 canvas [P, C, Hc, Wc] of their wt-weighted mean over the windows
+    that cover each element (afldm_window_fuse); wt fp32 [S, S] > 0."""
+    g = geometry
+    _dev(windows, "windows"); _pano_weights("window_fuse", wt, g)
+    if windows.dim() != 4 or windows.shape[0] % g.nwin or tuple(windows.shape[2:]) != (g.S, g.S):
+        raise ValueError(f"window_fuse: windows {tuple(windows.shape)}, want [P * {g.nwin}, C, {g.S}, {g.S}]")
+    P, C = windows.shape[0] // g.nwin, windows.shape[1]
+    if out is None:
+        out = torch.empty(P, C, g.Hc, g.Wc, dtype=torch.float32, device=windows.device)
+    assert (P, C) == _pano_canvas("window_fuse", out, g)
+    check(lib.afldm_window_fuse(ptr(windows), ptr(wt), ptr(out), P, C, *_geom_args(g), _code(windows), stream_ptr()), "window_fuse")
+    return out
+
+
+def window_crop(canvas, geometry, out=None):
+    """canvas fp32 [P, C, Hc, Wc] -> its windows NCHW fp32 [P * nwin, C, S, S], window k = iy * nx + ix of canvas P at batch entry
+    P * nwin + k, with wrap on the circular axes (afldm_window_crop).  Exact."""
+    g = geometry
+    P, C = _pano_canvas("window_crop", canvas, g)
+    if out is None:
+        out = torch.empty(P * g.nwin, C, g.S, g.S, dtype=torch.float32, device=canvas.device)
+    _dev(out, "out")
+    assert out.dtype == torch.float32 and tuple(out.shape) == (P * g.nwin, C, g.S, g.S)
+    check(lib.afldm_window_crop(ptr(canvas), ptr(out), P, C, *_geom_args(g), stream_ptr()), "window_crop")
+    return out
+
+
 def select_timestep(tvals, step_idx, t_out, pre_advance=False):
     check(lib.afldm_select_timestep(ptr(tvals), ptr(step_idx), ptr(t_out), int(pre_advance), stream_ptr()),
           "select_timestep")

@@ -64,3 +64,11 @@ class I2SBLDMPipeline(MyLDMPipeline):
             prediction = unet(sched.scale_model_input(latents, t).to(unet.dtype), t).sample
             latents = sched.step(prediction, t, latents, is_ode=is_ode, generator=generator).prev_sample
         return latents.to(dtype)
+
+    def panorama_latents(self, *args, **kwargs):
+        raise NotImplementedError("I2SBLDMPipeline: MultiDiffusion panoramas are defined for the unconditional sampler "
+                                  "(MyLDMPipeline.panorama_latents); the bridge starts from an encoded image of the window's size")
+
+    def panorama(self, *args, **kwargs):
+        raise NotImplementedError("I2SBLDMPipeline: MultiDiffusion panoramas are defined for the unconditional sampler "
+                                  "(MyLDMPipeline.panorama); the bridge starts from an encoded image of the window's size")

@@ -275,3 +275,100 @@ class MyLDMPipeline(DiffusionPipeline):
         ref = self.vae.encode(image).latent_dist.mode() * self.vae.config.scaling_factor
         out = self.ilvr_latents(ref, down_factor, range_t, num_inference_steps, eta, phi, generator, latents, use_graph)
         return self._deliver(out, output_type, return_dict)
+
+    # ------------------------------------------------------------------------------------------------ MultiDiffusion panoramas
+    def panorama_geometry(self, height, width, stride=None, circular=False):
+        """The panorama.Geometry of a height x width canvas (latent units) under this UNet's window: `stride` (default
+        sample_size // 4) on both axes, the x axis circular on request."""
+        from ..panorama import Geometry
+        s = self.unet.config.sample_size
+        stride = s // 4 if stride is None else int(stride)
+        return Geometry.grid(height, width, s, stride, stride, circular_x=circular)
+
+    @torch.no_grad()
+    def panorama_latents(self, height, width, stride=None, circular=False, eta=0.0, num_inference_steps=50, batch_size=1,
+                         generator=None, latents=None, use_graph=True):
+        """MultiDiffusion (Bar-Tal et al., ICML 2023; diffusers StableDiffusionPanoramaPipeline) in latent space: sample `batch_size`
+        canvases of height x width latents, larger than the sample_size^2 window the UNet was trained on.  Every evaluation runs
+        the UNet on the overlapping windows of the canvas (panorama.window_origins with `stride`, default sample_size // 4;
+        `circular` wraps the x axis, for a seamless 360-degree strip) as ONE batch of batch_size * nwin planes, takes the DDIM
+        reverse step (eta: its stochastic form) in every window and replaces each canvas element by the plain mean of the steps of
+        the windows that cover it.  That fusion assumes that windows offset by a fraction of a window agree where they overlap -
+        the shift-equivariance an alias-free model has.  The schedule is DDIMScheduler.panorama_schedule: every evaluation ends
+        in one afldm_pano_step, on replayed HIP graphs (use_graph), or runs statement by statement in the eager loop below, which
+        makes the same draws from `generator` in the same order - the start canvas (unless `latents` [P, C, height, width] is
+        given), then one canvas-shaped tensor in the model's dtype per evaluation whose sigma is not 0.  Needs no VAE.  Returns
+        the fp32 canvas [P, C, height, width]."""
+        from .. import ops
+        from ..engine import PanoramaEngine
+        self._refuse_dpm("panorama_latents")
+        geom = self.panorama_geometry(height, width, stride, circular)
+        c, s, dev = self.unet.config.in_channels, self.unet.config.sample_size, self.unet.device
+        P = int(batch_size) if latents is None else latents.shape[0]
+        shape = (P, c, geom.Hc, geom.Wc)
+        if latents is not None and tuple(latents.shape) != shape:
+            raise ValueError(f"panorama_latents: latents {tuple(latents.shape)}, want [P, {c}, {geom.Hc}, {geom.Wc}]")
+        self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
+        sched = self.scheduler.panorama_schedule(num_inference_steps, eta)
+        draw = sched.drawer(generator, shape, dev, self.unet.dtype)
+        if latents is None:
+            latents = draw()            # (on the CPU for CPU generators, else on the device: the per-evaluation draws' rule)
+        if use_graph:
+            B = P * geom.nwin
+            eng = cached_engine(self, "_pano_engines", sched, B, True, self.unet, extra=(geom,),
+                                build=lambda: PanoramaEngine(self.unet, sched, B, len(sched.timesteps), True, geometry=geom))
+            eng.scheduler = self.scheduler
+            return eng.run(latents, draw=draw if any(sched.draws) else None)
+        x = (latents.to(device=dev, dtype=torch.float32) * sched.init_noise_sigma).contiguous()
+        ones = torch.ones(s, s, dtype=torch.float32, device=dev)
+        for k, (t, row) in enumerate(self.progress_bar(list(zip(sched.timesteps, sched.rows)))):
+            p, q, lo, hi, a, b, d, cz = row
+            z = draw().to(device=dev, dtype=torch.float32) if sched.slots(k) else None
+            win = ops.window_crop(x, geom)                                    # [P * nwin, C, S, S]
+            eps = self.unet(win.to(self.unet.dtype), t).sample.float()
+            x0 = torch.clamp(p * win + q * eps, lo, hi)                       # every window's own prediction of the clean latents
+            x = a * x + b * ops.window_fuse(x0.contiguous(), ones, geom) + d * ops.window_fuse(eps.contiguous(), ones, geom)
+            if z is not None:
+                x = x + cz * z
+            x = x.contiguous()
+        return x
+
+    @torch.no_grad()
+    def decode_panorama(self, canvas, geometry):
+        """canvas [P, C, Hc, Wc] latents -> fp32 [P, 3, r Hc, r Wc] in [-1, 1]: the canvas is decoded window by window, at the
+        origins it was sampled with (one AF-VAE decode of batch nwin per canvas), and the decodes are blended by afldm_window_fuse
+        under the separable triangular feather t[i] = min(i + 1, n - i), n = r S.  This is a blend of INDEPENDENT window decodes,
+        not a decode of the whole canvas: the AF-VAE's filters and normalisations are global per plane, so a plane of another
+        size is another function, and the decoder only exists at the window's size."""
+        from .. import ops
+        from ..panorama import feather
+        if self.vae is None:
+            raise NotImplementedError("this pipeline was built without a VAE: use panorama_latents")
+        r = getattr(self.vae, "downsample_ratio", None) or 2 ** (len(self.vae.config.block_out_channels) - 1)
+        dev, n = self.unet.device, geometry.nwin
+        win = ops.window_crop(canvas.to(device=dev, dtype=torch.float32).contiguous(), geometry)
+        scale = self.vae.config.scaling_factor
+        dec = torch.cat([self.vae.decode(win[i:i + n].to(self.vae.dtype) / scale).sample for i in range(0, win.shape[0], n)])
+        t = torch.tensor(feather(geometry.S * r), dtype=torch.float32, device=dev)
+        return ops.window_fuse(dec.contiguous(), torch.outer(t, t).contiguous(), geometry.scaled(r))
+
+    @torch.no_grad()
+    def panorama(self, height=256, width=1024, stride=None, circular=False, eta=0.0, num_inference_steps=50, batch_size=1,
+                 generator=None, latents=None, use_graph=True, output_type="pil", return_dict=True):
+        """Sample images of height x width PIXELS (multiples of the VAE's scale factor r, as is `stride`; `latents`, if given, is the
+        start canvas in latent units): panorama_latents on the canvas of height / r x width / r latents, then decode_panorama.
+        output_type as __call__; 'latent' returns the fp32 canvas."""
+        self._refuse_dpm("panorama")
+        if self.vae is None:
+            raise NotImplementedError("this pipeline was built without a VAE: use panorama_latents")
+        r = getattr(self.vae, "downsample_ratio", None) or 2 ** (len(self.vae.config.block_out_channels) - 1)
+        for name, v in (("height", height), ("width", width), ("stride", stride)):
+            if v is not None and (int(v) % r or int(v) < r):
+                raise ValueError(f"panorama: {name} = {v} pixels must be a positive multiple of the VAE's scale factor {r}")
+        lstride = None if stride is None else int(stride) // r
+        canvas = self.panorama_latents(int(height) // r, int(width) // r, lstride, circular, eta, num_inference_steps, batch_size,
+                                       generator, latents, use_graph)
+        if output_type == "latent":
+            return canvas
+        decoded = self.decode_panorama(canvas, self.panorama_geometry(int(height) // r, int(width) // r, lstride, circular))
+        return self._images(decoded, output_type, return_dict)

@@ -130,6 +130,21 @@ class DDIMScheduler:
         return Schedule.of(self, "sde", ts, lambda t: self.sde_coefficients(t, eta), [True] * len(ts),
                            _ddim_steps=int(num_inference_steps), _ddim_eta=float(eta))
 
+    def panorama_schedule(self, num_inference_steps, eta=0.0):
+        """MultiDiffusion sampling of a canvas larger than the model's window (Bar-Tal et al., ICML 2023) over this scheduler's
+        `num_inference_steps` timesteps, as the Schedule PanoramaEngine replays with afldm_pano_step: the rows are
+        sde_coefficients(t, eta), applied per window and averaged over the windows that cover a canvas element.  Unlike
+        stochastic_schedule a step draws - one randn_tensor of the CANVAS's shape in the model's dtype - only where its sigma is
+        not 0: eta = 0 draws nothing, and with set_alpha_to_one neither does the last step."""
+        if self.config.clip_sample or self.config.prediction_type != "epsilon":
+            raise NotImplementedError("afldm_amd.DDIMScheduler implements the reference's setting: "
+                                      "epsilon prediction, clip_sample=False")
+        self.set_timesteps(num_inference_steps)
+        ts = self._timesteps_host
+        rows = [self.sde_coefficients(t, eta) for t in ts]
+        return Schedule.of(self, "pano", ts, rows, [r[7] != 0.0 for r in rows], _pano_steps=int(num_inference_steps),
+                           _pano_eta=float(eta))
+
     def _reverse_row(self, ab, ab_prev, eta):
         """(p, q, lo, hi, a, b, c) of one reverse step from level ab to ab_prev (epsilon prediction), the first seven fields of
         a "repaint" or "ilvr" row: x0 = clamp((x - sqrt(1-ab) eps) / sqrt(ab), -r, r) with r = clip_sample_range under

@@ -8,14 +8,16 @@ UNet evaluation, fixed when it is made.  `kind` names the update kernel that rea
             y = m (k0 known + k1 z_k) + (1 - m) unknown;  x_out = u0 y + u1 z_b                           afldm_repaint_step
     "ilvr"  (p, q, lo, hi, a, b, c, k0, k1, w, 0, 0):  x0 = clamp(p x + q eps, lo, hi);  xp = a x0 + b eps + c z_u;
             x_out = xp + w L ((k0 ref + k1 z_k) - xp) L^T, per plane                                      afldm_ilvr_step
+    "pano"  (p, q, lo, hi, a, b, d, c):  the "sde" row applied per window of a larger canvas and averaged over the windows that
+            cover an element (MultiDiffusion):  x_out = a x + b mean_k x0_k + d mean_k eps_k + c z                afldm_pano_step
 
 The rows come from the scheduler that owns the update (DDIMScheduler.schedule / stochastic_schedule,
-DDIMScheduler.repaint_schedule / ilvr_schedule, DPMSolverMultistepScheduler.schedule, I2SBScheduler.ode_schedule / bridge_schedule,
+DDIMScheduler.repaint_schedule / ilvr_schedule / panorama_schedule, DPMSolverMultistepScheduler.schedule, I2SBScheduler.ode_schedule / bridge_schedule,
 MyLDMPipeline.inversion_schedule) as Python floats and are rounded once to fp32 by `table`.  An "sde" schedule also states which
 steps draw noise and how: exactly the randn_tensor calls, in the same order, that the scheduler's eager `step()` makes, so that
 the engine can draw them from the caller's generator before the captured graphs need them.  A "repaint" schedule has up to
 three draws per step and states them per slot: `draws[k]` is (z_k, z_u, z_b), drawn in that order; an "ilvr" schedule has up
-to two, (z_k, z_u).  `key` identifies everything the rows were computed from; the engine
+to two, (z_k, z_u).  A "pano" schedule draws one canvas-shaped tensor per step, and only where the row's c is not 0.  `key` identifies everything the rows were computed from; the engine
 cache (engine.cached_engine) compares it, so two schedules with equal keys must replay the same graph."""
 from dataclasses import dataclass
 
@@ -24,8 +26,8 @@ import torch
 from ..configs import FrozenConfig
 from ..utils import randn_tensor
 
-ROW_WIDTH = {"ddim": 4, "dpm": 8, "sde": 8, "repaint": 12, "ilvr": 12}
-NOISE_SLOTS = {"sde": 1, "repaint": 3, "ilvr": 2}          # draws per step at the most; the kinds not named draw nothing
+ROW_WIDTH = {"ddim": 4, "dpm": 8, "sde": 8, "repaint": 12, "ilvr": 12, "pano": 8}
+NOISE_SLOTS = {"sde": 1, "repaint": 3, "ilvr": 2, "pano": 1}          # draws per step at the most; the kinds not named draw nothing
 _MADE = {}          # key -> Schedule: the rows are ~0.1 ms of scalar tensor arithmetic each, and a sampler asks per call
 
 
@@ -44,7 +46,7 @@ class Schedule:
     def of(cls, owner, kind, timesteps, rows, draws=None, noise_dtype=None, **settings):
         """owner: the scheduler whose config the rows are computed from; settings: whatever else they depend on (the step
         count, eta, is_ode, ...); rows: one per timestep, or a function of the timestep that is only called when no schedule
-        with this key has been made yet; draws: per step, whether the eager step draws a noise tensor ("sde"), or which of its
+        with this key has been made yet; draws: per step, whether the eager step draws a noise tensor ("sde", "pano"), or which of its
         slots do (a kind with NOISE_SLOTS[kind] > 1: that many bools per step - "repaint" three, "ilvr" two);
         noise_dtype: the dtype of that draw (None: the model's dtype, what DDIMScheduler.step draws in)."""
         config = FrozenConfig(dict(owner.config, **settings))
@@ -60,7 +62,7 @@ class Schedule:
             assert all(len(d) == NOISE_SLOTS[kind] for d in draws)
         else:
             draws = tuple(bool(d) for d in draws) if draws is not None else (False,) * len(rows)
-            assert kind == "sde" or not any(draws)
+            assert kind in ("sde", "pano") or not any(draws)
         assert len(timesteps) == len(rows) == len(draws) and all(len(r) == ROW_WIDTH[kind] for r in rows)
         if len(_MADE) >= 64:
             _MADE.clear()
@@ -77,7 +79,7 @@ class Schedule:
     coefficient_table = table
 
     def slots(self, k):
-        """The noise slots step k draws, in drawing order: () or (0,) for "sde", a subset of (0, 1, 2) for "repaint", of (0, 1) for
+        """The noise slots step k draws, in drawing order: () or (0,) for "sde" and "pano", a subset of (0, 1, 2) for "repaint", of (0, 1) for
         "ilvr"."""
         d = self.draws[k]
         return tuple(j for j, on in enumerate(d) if on) if isinstance(d, tuple) else ((0,) if d else ())

@@ -514,6 +514,38 @@ int afldm_ilvr_step(const float* x, const void* eps, const float* ref, const flo
 int afldm_ilvr_step_flat(const float* x, const float* eps, const float* ref, const float* z_k, const float* z_u,
                          const float* Lh, const float* Lw, float* x_out, float p, float q, float lo, float hi, float a, float b,
                          float c, float k0, float k1, float w, size_t planes, int H, int W, afldm_stream_t stream);
+/* ---- MultiDiffusion: one canvas sampled through overlapping windows (Bar-Tal et al., ICML 2023) -------------------
+ * A canvas is fp32 NCHW [P,C,Hc,Wc]; its nwin = ny * nx windows of S x S are the batch entries P * nwin + k, k = iy * nx + ix,
+ * with corners (oy[iy], ox[ix]).  An axis with wrap != 0 is circular: the window covers (o + u) mod extent, 0 <= o < extent;
+ * on the other axes 0 <= o <= extent - S.  oy / ox are HOST arrays, read during the call and passed to the kernel by value
+ * (a captured graph keeps them).  Before any launch AFLDM_ESHAPE refuses: more than 16 origins on an axis, S > extent, a
+ * window that leaves a non-wrapping axis, and origin lists that leave a coordinate uncovered.  wt: fp32 [S][S], strictly
+ * positive window weights (all ones: MultiDiffusion's count average).  Every sum runs over the covering windows in ascending
+ * k in fp32 fmaf, gathered per canvas element: no atomics, no workspace, a canvas's bits depend neither on P nor on its
+ * place in the batch.
+ *
+ * The fused update: step s = *step_idx applies the "sde" row coef[8 s .. 8 s + 8) = (p, q, lo, hi, a, b, d, c).  For the canvas
+ * element x at (P, ch, Y, X), with (u, v) its position inside covering window k and w = wt[u][v]:
+ *   e_k  = eps[P nwin + k][u][v][ch]                        (NHWC dtype [P nwin,S,S,C], the UNet's output on the windows)
+ *   x0_k = clamp(p x + q e_k, lo, hi)                       (a NaN passes through)
+ *   out  = a x + b (sum_k w x0_k / sum_k w) + d (sum_k w e_k / sum_k w) + c z
+ *   canvas_out[P][ch][Y][X] = out;  windows_out[P nwin + k][ch][u][v] = out for every covering k
+ * windows_out (NCHW fp32 [P nwin,C,S,S]) is the next UNet input: the crops of canvas_out.  With one window of weight 1 the
+ * result is the stochastic update's above, bit for bit.  z = noise[s * noise_step_stride + i], fp32 rows of the canvas's
+ * shape drawn by the caller's generator outside any captured graph; it is not read where c = 0, and noise may be NULL when
+ * no row has c != 0 (z is then 0).  canvas_out may alias canvas; step_idx / advance as the DDIM update above. */
+int afldm_pano_step(const float* canvas, const void* eps, const float* noise, size_t noise_step_stride, const float* wt,
+                    float* canvas_out, float* windows_out, const float* coef, int* step_idx, int advance, int P, int C, int Hc,
+                    int Wc, int S, const int* oy, int ny, const int* ox, int nx, int wrap_y, int wrap_x, int dtype,
+                    afldm_stream_t stream);
+/* canvas[P][ch][Y][X] = sum_k w windows[P nwin + k][ch][u][v] / sum_k w: windows NCHW dtype [P nwin,C,S,S], canvas fp32.  S,
+ * the origins and the extents are in the caller's units (the pixel-space blend of per-window decodes passes all of them
+ * times the VAE's scale factor). */
+int afldm_window_fuse(const void* windows, const float* wt, float* canvas, int P, int C, int Hc, int Wc, int S, const int* oy,
+                      int ny, const int* ox, int nx, int wrap_y, int wrap_x, int dtype, afldm_stream_t stream);
+/* windows[P nwin + k][ch][u][v] = canvas[P][ch][(oy + u) mod Hc][(ox + v) mod Wc], fp32 to fp32, exact. */
+int afldm_window_crop(const float* canvas, float* windows, int P, int C, int Hc, int Wc, int S, const int* oy, int ny,
+                      const int* ox, int nx, int wrap_y, int wrap_x, afldm_stream_t stream);
 /* tvals[step] -> t_out[0] (device->device), so the timestep also follows step_idx.  pre_advance != 0:
  * step_idx is incremented first (a sampler loop then starts from step_idx = -1 and needs no `advance`
  * launch behind afldm_ddim_step). */
