@@ -128,6 +128,10 @@ def _load():
         "afldm_ilvr_step_flat": ([vp] * 8 + [fp] * 10 + [c_size_t, ip, ip, vp], c_int),
         "afldm_pano_step": ([vp, vp, vp, c_size_t, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, POINTER(c_int), ip, POINTER(c_int), ip, ip,
                              ip, ip, vp], c_int),
+        "afldm_attn_identity_block_ok": ([ip, ip, ip, ip, ip], c_int),
+        "afldm_attn_identity_block": ([vp, vp, ip, vp, vp, ip, fp, vp, vp, vp, ip, ip, ip, ip, vp], c_int),
+        "afldm_pag_step": ([vp, vp, vp, c_size_t, vp, vp, vp, ip, ip, ip, ip, ip, ip, vp], c_int),
+        "afldm_pag_step_flat": ([vp] * 5 + [fp] * 12 + [ip, c_size_t, vp], c_int),
         "afldm_window_fuse": ([vp, vp, vp, ip, ip, ip, ip, ip, POINTER(c_int), ip, POINTER(c_int), ip, ip, ip, ip, vp], c_int),
         "afldm_window_crop": ([vp, vp, ip, ip, ip, ip, ip, POINTER(c_int), ip, POINTER(c_int), ip, ip, ip, vp], c_int),
         "afldm_flow_splat_workspace": ([ip] * 6, c_size_t),

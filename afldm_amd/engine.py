@@ -35,6 +35,10 @@ window: `lat` holds the P * nwin windows of a panorama.Geometry, the canvas is a
 afldm_pano_step, which applies the "sde" row per window, averages over the windows that cover each canvas element and writes both
 the canvas and its crops (the next `lat`).  The noise buffer is canvas-shaped, [steps, P, C, Hc, Wc].
 
+PAGEngine (kind "pag", DDIMScheduler.pag_schedule: perturbed-attention guidance) samples B latents with a UNet batch of 2 B: both
+halves of `x_nhwc` hold the same latents, the attention blocks named by `sites` run PAGAttnProcessor (the plain block on the first
+half, the identity-attention block on the second), and the last line of a step is afldm_pag_step, which reads both halves of eps.
+
 cached_engine keeps the engines (and the harness's samplers) a pipeline has built: one resident entry per slot.
 """
 import contextlib
@@ -458,3 +462,75 @@ class PanoramaEngine(DenoiseEngine):
         self.canvas.copy_(canvas.to(device=self.canvas.device, dtype=torch.float32) * self.schedule.init_noise_sigma)
         ops.window_crop(self.canvas, self.geometry, out=self.lat)
         self.step_idx.fill_(-1)
+
+
+@contextlib.contextmanager
+def pag_processors(unet, sites):
+    """PAGAttnProcessor on the attention modules `sites` names (module paths), the processors found there put back on the way
+    out, also on an exception."""
+    from .models.blocks import PAGAttnProcessor
+    mods = dict(unet.named_modules())
+    found = [(mods[name], mods[name].processor) for name in sites]
+    try:
+        for m, _ in found:
+            m.processor = PAGAttnProcessor()
+        yield
+    finally:
+        for m, old in found:
+            m.processor = old
+
+
+class PAGEngine(DenoiseEngine):
+    """Perturbed-attention guidance on the replayed graphs: `lat` [B] are the latents, `x_nhwc` [2 B] the UNet's input - the same
+    latents twice - and ONE forward_nhwc evaluates the UNet (rows 0 .. B-1) and the perturbed UNet (rows B .. 2B-1), whose
+    attention blocks at `sites` (names as the keys of get_unet_attn_processors) use the identity attention map.  A step is the
+    plain sampler's launch list at batch 2 B with afldm_pag_step in place of afldm_sde_step.  PAGAttnProcessor is installed on
+    the sites around every warm-up, capture and eager step and the previous processors are put back afterwards, also on an
+    exception: outside a call the UNet is as it was found.  The sites are baked into the captured graphs: they belong in the
+    cache key (cached_engine(..., extra=(sites,)))."""
+    ONE_BRANCH = True           # the update reads both halves of eps
+
+    def __init__(self, unet, scheduler, batch_size, num_inference_steps=50, use_graph=True, steps_per_graph=5, branches=1,
+                 sites=None):
+        sites = sites if sites is not None else getattr(self, "sites", None)      # (refresh_if_stale re-runs __init__)
+        if sites is None:
+            raise ValueError("PAGEngine needs the attention sites to perturb")
+        self.sites = tuple(sites)
+        super().__init__(unet, scheduler, batch_size, num_inference_steps, use_graph, steps_per_graph, 1)
+        self.x_nhwc = torch.empty((2 * batch_size,) + tuple(self.x_nhwc.shape[1:]), dtype=unet.dtype, device=unet.device)
+
+    def _pag_state(self):
+        """One noise row per step, filled per run - only when some step draws (eta != 0); without, the update gets no noise
+        pointer and reads none (c = 0 in every row)."""
+        if any(self.schedule.draws):
+            self.noise = torch.zeros((self.n,) + tuple(self.lat.shape), dtype=torch.float32, device=self.lat.device)
+            self._stage = []
+        return [(self.noise,)]
+
+    UPDATES = {"pag": (ops.pag_step, _pag_state)}
+
+    def perturbed(self):
+        return pag_processors(self.unet, self.sites)
+
+    def _substep(self, lat, x_nhwc, branch=0):
+        B = self.B
+        with ops.sync_scope(self._sync[branch]):
+            ops.to_nhwc(lat, self.unet.dtype, out=x_nhwc[:B])
+            ops.to_nhwc(lat, self.unet.dtype, out=x_nhwc[B:])
+            eps2 = self.unet.forward_nhwc(x_nhwc, self.t_cur, temb_slices=self.temb_slices)
+            self._update(lat, eps2, *self._state[branch], self.coef, self.step_idx, advance=False, out=lat)
+
+    def _capture(self, counts, before_step=None):
+        with self.perturbed():
+            return super()._capture(counts, before_step)
+
+    def step(self, k=1):
+        if self.use_graph and self.graph is not None:
+            return super().step(k)          # replays only: the graphs hold the perturbed launch list
+        with self.perturbed():
+            super().step(k)
+
+    def run(self, latents, draw=None):
+        if self.noise is None:
+            draw = None
+        return super().run(latents, draw=draw)

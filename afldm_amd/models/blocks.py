@@ -110,6 +110,22 @@ def packed_qkv(attn, dtype, which):
     return cache[key]
 
 
+def packed_vo(attn, dtype):
+    """The folded value-and-output projection of an attention block whose attention map is the identity (perturbed-attention
+    guidance): W_vo = W_o W_v formed in fp64 and rounded ONCE to `dtype` (packed like a Linear weight), b_vo = W_o b_v + b_o
+    formed in fp64 and kept in fp32.  One GEMM instead of to_v then to_out[0], and one rounding fewer than that chain.  Cached on
+    the module and dropped with the other packed copies (invalidate_packed / invalidate_stale_packed)."""
+    cache = attn.__dict__.setdefault("_afldm_cache", {})
+    key = ("vo", dtype)
+    if key not in cache:
+        wo, wv = attn.to_out[0].weight.detach().double(), attn.to_v.weight.detach().double()
+        b = attn.to_out[0].bias.detach().double()
+        if attn.to_v.bias is not None:
+            b = b + wo @ attn.to_v.bias.detach().double()
+        cache[key] = (ops.pack_weight((wo @ wv).float(), dtype), b.float().contiguous())
+    return cache[key]
+
+
 def packed_norm(mod):
     cache = mod.__dict__.setdefault("_afldm_cache", {})
     if "gn" not in cache:
@@ -766,6 +782,31 @@ class AttnProcessor2_0:
         else:
             o = ops.attention(q, k, vt, attn.heads, scale=attn.scale)
         return linear_forward(attn.to_out[0], o.view(B, H, W, C), residual=hidden_states, want_stats=True)
+
+
+class PAGAttnProcessor(AttnProcessor2_0):
+    """Perturbed-attention guidance (Ahn et al. 2024; diffusers PAGIdentitySelfAttnProcessor2_0) on a batch of 2 B: rows 0 .. B-1
+    run the plain block, rows B .. 2B-1 the block with its attention map replaced by the identity,
+    y = x + to_out(to_v(GN(x))), as one launch on the folded weight (ops.attn_identity_block, packed_vo).  The two halves are
+    joined by a concatenating copy into one [2B, H, W, C] tensor: the plain half is whatever launch list AttnProcessor2_0 chooses
+    for B rows and allocates its own output.  The result carries no GroupNorm partial sums (the next block makes its own pass),
+    and because _next_gn tests the processor type exactly, the resnet in front hands no pre-normed tensor to such a site."""
+
+    def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None, **kwargs):
+        assert encoder_hidden_states is None and attention_mask is None and not kwargs, "PAG perturbs plain self-attention"
+        B2, H, W, C = hidden_states.shape
+        if B2 % 2:
+            raise ValueError(f"PAGAttnProcessor: a batch of {B2} rows (want the plain rows followed by as many perturbed ones)")
+        B = B2 // 2
+        gn = attn.group_norm
+        gamma, beta = packed_norm(gn)
+        out = torch.empty_like(hidden_states)
+        out[:B].copy_(super().__call__(attn, hidden_states[:B]))
+        xp = hidden_states[B:]
+        stats = ops.gn_stats(xp, gn.num_groups)
+        w, b = packed_vo(attn, hidden_states.dtype)
+        ops.attn_identity_block(xp, stats, gamma, beta, gn.num_groups, gn.eps, w, b, out=out[B:])
+        return out
 
 
 class Attention(nn.Module):

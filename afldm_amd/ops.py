@@ -1608,6 +1608,97 @@ def ilvr_step_flat(x, eps, ref, noises, Lh, Lw, row, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- perturbed-attention guidance
+# fewest tokens per sample the one-launch identity block is used for.  Measured at 32 samples, bf16, captured and replayed,
+# alternated rounds (tools/bench_pag.py kernels), one launch against gn_apply + conv2d: T = 1024, C = 192:
+# 20.9 against 28.2 us; T = 256, C = 384: 25.0 / 20.9; T = 64, C = 384: 21.4 / 13.1; T = 16, C = 768: 49.3 / 15.6; T = 4, C = 768:
+# 56.7 / 11.2 - below the 32^2 level a handful of workgroups each walk the whole W_vo, and the two launches win.
+# AFLDM_IDENTITY_MIN_T=4 sends every level the library has a kernel for to the one launch (tests, A/B).
+_IDENTITY_MIN_T = int(os.environ.get("AFLDM_IDENTITY_MIN_T", "1024"))
+
+
+def attn_identity_block_ok(x, G):
+    """True when afldm_attn_identity_block has a kernel for tokens x [B, T, C] with G groups (bf16; the shapes: afldm_hip.h) and the
+    policy wants it (_IDENTITY_MIN_T)."""
+    B, T, C = x.shape
+    if x.dtype not in DTYPE_CODE or T < _IDENTITY_MIN_T:
+        return False
+    return bool(lib.afldm_attn_identity_block_ok(B, T, C, int(G), _code(x)))
+
+
+def attn_identity_block(x, stats, gamma, beta, G, eps, w_vo, b_vo, out=None):
+    """The attention block with its attention map replaced by the identity: y = x + GN(x) W_vo^T + b_vo on tokens x [B, T, C]
+    (or NHWC [B, H, W, C]); stats = GNStats of x, w_vo the packed folded weight (blocks.packed_vo), b_vo fp32 [C].  One launch
+    where attn_identity_block_ok says so; elsewhere (fp32, other shapes) the two existing launches on the same folded weight,
+    gn_apply + conv2d(residual=x).  `out`: a contiguous tensor of x's shape (a batch slice of a larger buffer), not x itself."""
+    _dev(x, "x")
+    assert x.is_contiguous() and stats.st2 is None and stats.st1.shape[2] == x.shape[-1]
+    C = x.shape[-1]
+    tokens = x.reshape(x.shape[0], -1, C)
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.shape == x.shape and out.dtype == x.dtype and out.is_contiguous() and out.data_ptr() != x.data_ptr()
+    if not attn_identity_block_ok(tokens, G):
+        hn = gn_apply(x, stats, gamma, beta, G, eps, act=0)
+        conv2d(hn, w_vo, b_vo, residual=x, out=out)
+        return out
+    B, T, _ = tokens.shape
+    tok = _begin()
+    check(lib.afldm_attn_identity_block(ptr(x), ptr(stats.st1), stats.S1, ptr(gamma), ptr(beta), int(G), float(eps), ptr(w_vo),
+                                        ptr(b_vo), ptr(out), B, T, C, _code(x), stream_ptr()), "attn_identity_block")
+    _end(tok, "attn_identity", 2.0 * B * T * C * C, (2 * B * T * C + C * C) * x.element_size())
+    return out
+
+
+def _pag_args(name, x, eps2):
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f"{name}: x must be contiguous fp32 [B, C, H, W], got {x.dtype} {tuple(x.shape)}")
+    B, C, H, W = x.shape
+    return B, C, H, W
+
+
+def pag_step(x, eps2_nhwc, noise, coef, step_idx, advance=False, out=None):
+    """x NCHW fp32 [B, C, H, W]; eps2 NHWC dtype [2B, H, W, C]: rows 0 .. B-1 the UNet's output, rows B .. 2B-1 the perturbed
+    UNet's; noise: None (no row has c != 0) or an fp32 view [steps, B, C, H, W] whose last four dimensions are contiguous; coef
+    float[12*nsteps] rows (p, q, lo, hi, a, b, d, c, s, phi, 0, 0) and step_idx int32[1] on device."""
+    _dev(x, "x"); _dev(eps2_nhwc, "eps2")
+    B, C, H, W = _pag_args("pag_step", x, eps2_nhwc)
+    assert tuple(eps2_nhwc.shape) == (2 * B, H, W, C) and eps2_nhwc.is_contiguous()
+    stride = 0
+    if noise is not None:
+        if not noise.is_cuda:
+            raise RuntimeError("afldm_amd: noise must live on an MI355X (cuda) device; there is no CPU path")
+        assert noise.dtype == torch.float32 and noise.dim() == 5 and tuple(noise.shape[1:]) == (B, C, H, W)
+        assert noise[0].is_contiguous() and noise.stride(0) >= B * C * H * W
+        stride = noise.stride(0)
+    if out is None:
+        out = torch.empty_like(x)
+    check(lib.afldm_pag_step(ptr(x), ptr(eps2_nhwc), ptr(noise), stride, ptr(out), ptr(coef), ptr(step_idx), int(advance),
+                             B, C, H, W, _code(eps2_nhwc), stream_ptr()), "pag_step")
+    return out
+
+
+def pag_step_flat(x, e, e_p, z, row, out=None):
+    """x, e, e_p: same-shape contiguous fp32 CUDA tensors [B, ...] (a sample = everything behind the first dimension); z such a
+    tensor, or None where the row's c is 0; row = the floats (p, q, lo, hi, a, b, d, c, s, phi[, 0, 0])."""
+    _dev(x, "x"); _dev(e, "e"); _dev(e_p, "e_p")
+    assert x.dtype == e.dtype == e_p.dtype == torch.float32 and x.shape == e.shape == e_p.shape and x.dim() >= 2
+    assert x.is_contiguous() and e.is_contiguous() and e_p.is_contiguous()
+    row = ([float(c) for c in row] + [0.0, 0.0])[:12]
+    if z is None:
+        if row[7] != 0.0:
+            raise ValueError(f"pag_step_flat: z is None but its coefficient is {row[7]}")
+    else:
+        _dev(z, "z")
+        assert z.dtype == torch.float32 and z.shape == x.shape and z.is_contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    B = x.shape[0]
+    check(lib.afldm_pag_step_flat(ptr(x), ptr(e), ptr(e_p), ptr(z), ptr(out), *row, B, x.numel() // max(B, 1), stream_ptr()),
+          "pag_step_flat")
+    return out
+
+
 # ----------------------------------------------------------------------------- MultiDiffusion: a canvas through windows
 def _geom_args(g):
     """A panorama.Geometry as the C arguments (Hc, Wc, S, oy, ny, ox, nx, wrap_y, wrap_x); the origin lists are host arrays the

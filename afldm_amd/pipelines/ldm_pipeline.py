@@ -276,6 +276,74 @@ class MyLDMPipeline(DiffusionPipeline):
         out = self.ilvr_latents(ref, down_factor, range_t, num_inference_steps, eta, phi, generator, latents, use_graph)
         return self._deliver(out, output_type, return_dict)
 
+    # ------------------------------------------------------------------------------------------------ perturbed-attention guidance
+    def pag_sites(self, pag_applied_layers):
+        """The attention modules `pag_applied_layers` names, as a sorted tuple of module paths.  A name is a key of
+        get_unet_attn_processors without its '.processor', or a prefix of one that ends on a '.' boundary: 'mid_block',
+        'up_blocks.1' and 'up_blocks.1.attentions.0' are all valid.  A name that matches nothing raises ValueError."""
+        from .cross_frame_attn import get_unet_attn_processors
+        if isinstance(pag_applied_layers, str):
+            pag_applied_layers = (pag_applied_layers,)
+        keys = [k[:-len(".processor")] for k in get_unet_attn_processors(self.unet)]
+        sites = set()
+        for name in pag_applied_layers:
+            hit = [k for k in keys if k == name or k.startswith(str(name) + ".")]
+            if not hit:
+                raise ValueError(f"pag_applied_layers: {name!r} matches no attention block (there are: {', '.join(keys)})")
+            sites.update(hit)
+        return tuple(sorted(sites))
+
+    @torch.no_grad()
+    def pag_latents(self, batch_size=1, pag_scale=3.0, pag_applied_layers=("mid_block",), guidance_rescale=0.0, eta=0.0,
+                    num_inference_steps=50, generator=None, latents=None, use_graph=True):
+        """Perturbed-attention guidance (Ahn et al. 2024; diffusers PAGMixin) in latent space: the guidance that needs no condition.
+        Every evaluation runs the UNet and, in the same batch, the UNet whose self-attention map at `pag_applied_layers`
+        (pag_sites) is the identity, e and e_p, and steps with g = e + pag_scale (e - e_p); `guidance_rescale` in [0, 1] pulls
+        the standard deviation of g back towards e's per sample (diffusers rescale_noise_cfg).  The schedule is
+        DDIMScheduler.pag_schedule: every evaluation ends in one afldm_pag_step on replayed HIP graphs (use_graph, PAGEngine) or
+        in the eager loop below over afldm_pag_step_flat, which makes the same draws from `generator` in the same order - the
+        start latents (unless `latents` is given), then with eta != 0 one tensor per evaluation - and carries the latents in
+        fp32 like the engine.  pag_scale = 0 is allowed and still evaluates both halves.  Needs no VAE.  Returns latents in
+        the UNet's dtype.  The UNet's attention processors are as they were on return, also after an exception."""
+        from .. import ops
+        from ..engine import PAGEngine, pag_processors
+        self._refuse_dpm("pag_latents")
+        sites = self.pag_sites(pag_applied_layers)
+        if not sites and float(pag_scale) > 0.0:
+            raise ValueError("pag_latents: pag_scale > 0 needs at least one attention block in pag_applied_layers")
+        c, s, dev = self.unet.config.in_channels, self.unet.config.sample_size, self.unet.device
+        B = int(batch_size) if latents is None else latents.shape[0]
+        shape = (B, c, s, s)
+        if latents is not None and tuple(latents.shape) != shape:
+            raise ValueError(f"pag_latents: latents {tuple(latents.shape)}, want [B, {c}, {s}, {s}]")
+        self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
+        sched = self.scheduler.pag_schedule(num_inference_steps, eta, pag_scale, guidance_rescale)
+        draw = sched.drawer(generator, shape, dev, self.unet.dtype)
+        if latents is None:
+            latents = draw()            # (on the CPU for CPU generators, else on the device: the per-evaluation draws' rule)
+        if use_graph:
+            eng = cached_engine(self, "_pag_engines", sched, B, True, self.unet, extra=(sites,),
+                                build=lambda: PAGEngine(self.unet, sched, B, len(sched.timesteps), True, sites=sites))
+            eng.scheduler = self.scheduler
+            return eng.run(latents, draw=draw).to(self.unet.dtype)
+        x = (latents.to(device=dev, dtype=torch.float32) * sched.init_noise_sigma).contiguous()
+        with pag_processors(self.unet, sites):
+            for k, (t, row) in enumerate(self.progress_bar(list(zip(sched.timesteps, sched.rows)))):
+                z = draw().to(device=dev, dtype=torch.float32).contiguous() if sched.slots(k) else None
+                eps2 = self.unet(torch.cat([x, x]).to(self.unet.dtype), t).sample.float()
+                x = ops.pag_step_flat(x, eps2[:B].contiguous(), eps2[B:].contiguous(), z, row)
+        return x.to(self.unet.dtype)
+
+    @torch.no_grad()
+    def pag(self, batch_size=1, pag_scale=3.0, pag_applied_layers=("mid_block",), guidance_rescale=0.0, eta=0.0,
+            num_inference_steps=50, generator=None, latents=None, use_graph=True, output_type="pil", return_dict=True):
+        """Sample images with perturbed-attention guidance: pag_latents, then decode.  output_type as __call__; 'latent' returns
+        the sampled latents."""
+        self._refuse_dpm("pag")
+        out = self.pag_latents(batch_size, pag_scale, pag_applied_layers, guidance_rescale, eta, num_inference_steps, generator,
+                               latents, use_graph)
+        return self._deliver(out, output_type, return_dict)
+
     # ------------------------------------------------------------------------------------------------ MultiDiffusion panoramas
     def panorama_geometry(self, height, width, stride=None, circular=False):
         """The panorama.Geometry of a height x width canvas (latent units) under this UNet's window: `stride` (default

@@ -145,6 +145,23 @@ class DDIMScheduler:
         return Schedule.of(self, "pano", ts, rows, [r[7] != 0.0 for r in rows], _pano_steps=int(num_inference_steps),
                            _pano_eta=float(eta))
 
+    def pag_schedule(self, num_inference_steps, eta=0.0, pag_scale=3.0, guidance_rescale=0.0):
+        """Perturbed-attention guidance (Ahn et al. 2024; diffusers PAGMixin) over this scheduler's `num_inference_steps`
+        timesteps, as the Schedule PAGEngine replays with afldm_pag_step: every evaluation runs the UNet and the perturbed UNet
+        as one batch, forms g = e + pag_scale (e - e_p), rescales it per sample towards std(e) by `guidance_rescale` (diffusers
+        rescale_noise_cfg) and applies the row of stochastic_schedule(num_inference_steps, eta) to g.  The first eight fields
+        of a row are that schedule's, float for float; then pag_scale, guidance_rescale, 0, 0.  With eta != 0 the draws are
+        stochastic_schedule's too (every step, in the model's dtype); eta = 0 has c = 0 in every row and draws nothing, like the
+        plain eta = 0 sampler."""
+        s, phi = float(pag_scale), float(guidance_rescale)
+        if s < 0.0 or not 0.0 <= phi <= 1.0:
+            raise ValueError(f"pag_schedule: pag_scale = {pag_scale} must be >= 0 and guidance_rescale = {guidance_rescale} in [0, 1]")
+        sde = self.stochastic_schedule(num_inference_steps, eta)
+        rows = [r + (s, phi, 0.0, 0.0) for r in sde.rows]
+        draws = sde.draws if float(eta) != 0.0 else [False] * len(rows)
+        return Schedule.of(self, "pag", sde.timesteps, rows, draws, _pag_steps=int(num_inference_steps), _pag_eta=float(eta),
+                           _pag_scale=s, _pag_rescale=phi)
+
     def _reverse_row(self, ab, ab_prev, eta):
         """(p, q, lo, hi, a, b, c) of one reverse step from level ab to ab_prev (epsilon prediction), the first seven fields of
         a "repaint" or "ilvr" row: x0 = clamp((x - sqrt(1-ab) eps) / sqrt(ab), -r, r) with r = clip_sample_range under

@@ -514,6 +514,42 @@ int afldm_ilvr_step(const float* x, const void* eps, const float* ref, const flo
 int afldm_ilvr_step_flat(const float* x, const float* eps, const float* ref, const float* z_k, const float* z_u,
                          const float* Lh, const float* Lw, float* x_out, float p, float q, float lo, float hi, float a, float b,
                          float c, float k0, float k1, float w, size_t planes, int H, int W, afldm_stream_t stream);
+/* ---- Perturbed-attention guidance (Ahn et al. 2024; diffusers PAGMixin) ------------------------------------------------
+ * The perturbed attention block: the attention map replaced by the identity, so that softmax(q k^T) v is v and the block is
+ *   y[b,t,:] = x[b,t,:] + GN(x)[b,t,:] W_vo^T + b_vo,    W_vo = W_o W_v,  b_vo = W_o b_v + b_o   (folded by the caller)
+ * in ONE launch.  x, y: [B,T,C] token-major (NHWC), y must not alias x; stats [B,S,C,2], gamma, beta, G, eps exactly as
+ * afldm_gn_apply takes them (mean / rstd are finished the same way); w_vo: [C,C] row-major in dtype (what afldm_pack_weight
+ * makes of a Linear weight); bias_vo: fp32 [C].  GroupNorm is applied to the token operand and rounded once to bf16 (what
+ * afldm_gn_apply stores); fp32 accumulation on MFMA, then + bias + x and one output rounding.
+ * afldm_attn_identity_block_ok: 1 where there is a kernel - bf16, G = 32, T in {4, 16, 64, 256, 1024}, C in {64, 128, 192,
+ * 384, 768}, any B >= 1 with B*T*C < 2^31; 0 otherwise (the caller then runs afldm_gn_apply + afldm_conv2d with `residual`
+ * on the same folded weight), and afldm_attn_identity_block itself returns AFLDM_ESHAPE there. */
+int afldm_attn_identity_block_ok(int B, int T, int C, int G, int dtype);
+int afldm_attn_identity_block(const void* x, const float* stats, int S, const float* gamma, const float* beta, int G,
+                              float eps, const void* w_vo, const float* bias_vo, void* y, int B, int T, int C, int dtype,
+                              afldm_stream_t stream);
+/* The guided update.  eps2: NHWC dtype [2B,H,W,C], rows 0 .. B-1 the UNet's output e, rows B .. 2B-1 the output e_p of the
+ * perturbed UNet on the same input.  Step s = *step_idx applies the row coef[12 s .. 12 s + 12) =
+ * (p, q, lo, hi, a, b, d, c, s, phi, 0, 0):
+ *   g     = e + s (e - e_p)
+ *   g     = g (phi sigma(e) / sigma(g) + 1 - phi)       only where phi != 0; sigma: the standard deviation over one sample's
+ *                                                       C*H*W elements (diffusers rescale_noise_cfg); the ratio is 1 where
+ *                                                       sigma(g) = 0
+ *   x0    = clamp(p x + q g, lo, hi)                    lo = -inf, hi = +inf: no clip; a NaN passes through
+ *   x_out = a x + b x0 + d g + c z                      z = noise[s * noise_step_stride + i], read only where c != 0
+ * One workgroup per sample holds the sample in registers: C*H*W <= 16384 (AFLDM_ESHAPE above that, before any launch).
+ * sigma is computed in fp32 in two passes (the mean, then the centred squares), each sum a fixed pairwise tree: no atomics,
+ * a sample's bits do not depend on B.  x, x_out: NCHW fp32 [B,C,H,W], x_out may alias x; noise: fp32 rows of [B,C,H,W],
+ * noise_step_stride floats apart, drawn by the caller outside any captured graph, or NULL when no row has c != 0;
+ * step_idx / advance as afldm_ddim_step. */
+int afldm_pag_step(const float* x, const void* eps2, const float* noise, size_t noise_step_stride, float* x_out,
+                   const float* coef, int* step_idx, int advance, int B, int C, int H, int W, int dtype,
+                   afldm_stream_t stream);
+/* Same update on same-layout fp32 tensors of B samples of n contiguous elements each (e and e_p too), the twelve fields of
+ * the row by value (the last two are reserved and ignored), for an eager loop.  z may be NULL where c = 0. */
+int afldm_pag_step_flat(const float* x, const float* e, const float* e_p, const float* z, float* x_out, float p, float q,
+                        float lo, float hi, float a, float b, float d, float c, float s, float phi, float r10, float r11,
+                        int B, size_t n, afldm_stream_t stream);
 /* ---- MultiDiffusion: one canvas sampled through overlapping windows (Bar-Tal et al., ICML 2023) -------------------
  * A canvas is fp32 NCHW [P,C,Hc,Wc]; its nwin = ny * nx windows of S x S are the batch entries P * nwin + k, k = iy * nx + ix,
  * with corners (oy[iy], ox[ix]).  An axis with wrap != 0 is circular: the window covers (o + u) mod extent, 0 <= o < extent;

@@ -1,0 +1,71 @@
+#!/usr/bin/env python
+"""FFHQ sampling with perturbed-attention guidance on MI355X - PAG (Ahn et al. 2024; diffusers PAGMixin) on the unconditional
+FFHQ latent-diffusion model (afldm_amd MyLDMPipeline.pag: every evaluation runs the UNet and, in the same batch, the UNet whose
+self-attention map at --pag-layers is the identity, on replayed HIP graphs, and steers away from the second prediction; decode).
+--pag-scale is the guidance scale s, --guidance-rescale pulls the guided prediction's standard deviation back towards the plain
+one's (diffusers' rescale_noise_cfg), --pag-layers names attention blocks: a module path such as mid_block.attentions.0 or any
+prefix of one on a '.' boundary (mid_block, up_blocks.1).
+
+No network on the target machines: pass --ckpt /path/to/alias_free_ldm_ffhq (diffusers-format directory with unet/,
+scheduler/, vae/) or --random-init for seeded random weights of the FFHQ architecture (demonstrates the full flow; the pictures
+are noise).  Writes one PNG per sample."""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+from ilvr_ffhq import build_pipeline  # noqa: E402  (the same pipeline sources: --ckpt or --random-init)
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument("--output", type=str, default="results/pag.png")
+    p.add_argument("--batch-size", type=int, default=1)
+    p.add_argument("--pag-scale", type=float, default=3.0)
+    p.add_argument("--pag-layers", type=str, default="mid_block", help="comma-separated attention blocks or prefixes of them")
+    p.add_argument("--guidance-rescale", type=float, default=0.0)
+    p.add_argument("--eta", type=float, default=0.0)
+    p.add_argument("--steps", type=int, default=50)
+    p.add_argument("--seed", type=int, default=1234)
+    src = p.add_mutually_exclusive_group()
+    src.add_argument("--ckpt", type=str, default=None)
+    src.add_argument("--random-init", action="store_true", help="seeded random weights of the FFHQ architecture")
+    p.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"])
+    p.add_argument("--eager", action="store_true", help="run the eager loop instead of replayed HIP graphs")
+    args = p.parse_args(argv)
+    if not args.random_init and not args.ckpt:
+        args.ckpt = os.environ.get("AFLDM_CKPT")
+    if not args.random_init and not args.ckpt:
+        p.error("pass --ckpt DIR or --random-init")
+    if args.pag_scale < 0 or not 0 <= args.guidance_rescale <= 1 or args.steps < 1 or args.batch_size < 1:
+        p.error("--pag-scale must be >= 0, --guidance-rescale in [0, 1], --steps and --batch-size >= 1")
+    args.pag_layers = tuple(s.strip() for s in args.pag_layers.split(",") if s.strip())
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    from afldm_amd.af_modules.af_api import make_af_unet, make_af_vae_from_config
+    dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
+    pipe = build_pipeline(args).to("cuda").to(dtype)
+    pipe.set_progress_bar_config(disable=True)
+    make_af_unet(pipe.unet)
+    make_af_vae_from_config(pipe.vae)
+    out = pipe.pag(batch_size=args.batch_size, pag_scale=args.pag_scale, pag_applied_layers=args.pag_layers,
+                   guidance_rescale=args.guidance_rescale, eta=args.eta, num_inference_steps=args.steps,
+                   generator=torch.Generator().manual_seed(args.seed), use_graph=not args.eager, output_type="pil")
+    d = os.path.dirname(args.output)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    stem, ext = os.path.splitext(args.output)
+    for i, im in enumerate(out.images):
+        im.save(args.output if len(out.images) == 1 else f"{stem}_{i}{ext}")
+    print(f"wrote {len(out.images)} image(s) to {args.output}: pag_scale {args.pag_scale}, layers {', '.join(pipe.pag_sites(args.pag_layers))}, "
+          f"guidance_rescale {args.guidance_rescale}")
+    return out.images
+
+
+if __name__ == "__main__":
+    main()
