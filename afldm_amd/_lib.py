@@ -132,6 +132,10 @@ def _load():
         "afldm_attn_identity_block": ([vp, vp, ip, vp, vp, ip, fp, vp, vp, vp, ip, ip, ip, ip, vp], c_int),
         "afldm_pag_step": ([vp, vp, vp, c_size_t, vp, vp, vp, ip, ip, ip, ip, ip, ip, vp], c_int),
         "afldm_pag_step_flat": ([vp] * 5 + [fp] * 12 + [ip, c_size_t, vp], c_int),
+        "afldm_attn_key_mass_ok": ([ip] * 5, c_int),
+        "afldm_attn_key_mass": ([vp, ip, vp, ip, vp, vp, ip, ip, ip, ip, fp, ip, vp], c_int),
+        "afldm_sag_degrade": ([vp] * 6 + [POINTER(c_float), ip, ip, ip, ip, ip, ip, ip, ip, vp], c_int),
+        "afldm_sag_degrade_flat": ([vp] * 4 + [fp, fp, POINTER(c_float), ip, ip, ip, ip, ip, ip, ip, vp], c_int),
         "afldm_window_fuse": ([vp, vp, vp, ip, ip, ip, ip, ip, POINTER(c_int), ip, POINTER(c_int), ip, ip, ip, ip, vp], c_int),
         "afldm_window_crop": ([vp, vp, ip, ip, ip, ip, ip, POINTER(c_int), ip, POINTER(c_int), ip, ip, ip, vp], c_int),
         "afldm_flow_splat_workspace": ([ip] * 6, c_size_t),

@@ -39,6 +39,11 @@ PAGEngine (kind "pag", DDIMScheduler.pag_schedule: perturbed-attention guidance)
 halves of `x_nhwc` hold the same latents, the attention blocks named by `sites` run PAGAttnProcessor (the plain block on the first
 half, the identity-attention block on the second), and the last line of a step is afldm_pag_step, which reads both halves of eps.
 
+SAGEngine (kind "sag", DDIMScheduler.sag_schedule: self-attention guidance) samples B latents with TWO dependent UNet evaluations
+of batch B per step: the first with SAGAttnProcessor at one site, which also writes the attention mass of every key into `mass`;
+afldm_sag_degrade turns x, e and the mass into the second evaluation's input; both outputs land in `eps2` [2 B] and the step ends
+in afldm_pag_step, unchanged.
+
 cached_engine keeps the engines (and the harness's samplers) a pipeline has built: one resident entry per slot.
 """
 import contextlib
@@ -529,6 +534,76 @@ class PAGEngine(DenoiseEngine):
             return super().step(k)          # replays only: the graphs hold the perturbed launch list
         with self.perturbed():
             super().step(k)
+
+    def run(self, latents, draw=None):
+        if self.noise is None:
+            draw = None
+        return super().run(latents, draw=draw)
+
+
+@contextlib.contextmanager
+def sag_processor(unet, site, mass=None):
+    """SAGAttnProcessor on the attention module `site` names (a module path), writing into `mass` (or into a tensor of its own
+    per call); yields the processor.  The processor found there is put back on the way out, also on an exception."""
+    from .models.blocks import SAGAttnProcessor
+    mod = dict(unet.named_modules())[site]
+    old = mod.processor
+    proc = SAGAttnProcessor(mass)
+    try:
+        mod.processor = proc
+        yield proc
+    finally:
+        mod.processor = old
+
+
+class SAGEngine(DenoiseEngine):
+    """Self-attention guidance on the replayed graphs.  A step: to_nhwc; forward_nhwc with SAGAttnProcessor at `site` (the
+    attention mass per key goes to `mass` [B, T]); afldm_sag_degrade (x, e, mass -> `x_nhwc`, the degraded input, NHWC in the
+    model dtype); forward_nhwc with the processors as found; both outputs in `eps2` [2 B, H, W, C]; afldm_pag_step.  The second
+    evaluation depends on the first, so the two cannot share a batch (PAGEngine's can).  The processor is installed around every
+    warm-up, capture and eager step and the one found is put back afterwards, also on an exception: outside a call the UNet is
+    as it was found.  Site, taps and boundary are baked into the captured graphs: they belong in the cache key
+    (cached_engine(..., extra=(site, taps, boundary)))."""
+    ONE_BRANCH = True           # the update reads both halves of eps2
+
+    def __init__(self, unet, scheduler, batch_size, num_inference_steps=50, use_graph=True, steps_per_graph=5, branches=1,
+                 site=None, taps=None, boundary=None):
+        site = site if site is not None else getattr(self, "site", None)      # (refresh_if_stale re-runs __init__)
+        taps = taps if taps is not None else getattr(self, "taps", None)
+        boundary = boundary if boundary is not None else getattr(self, "boundary", None)
+        if site is None or taps is None or boundary is None:
+            raise ValueError("SAGEngine needs the attention site, the blur taps and the boundary")
+        mod = dict(unet.named_modules()).get(site)
+        if mod is None or not hasattr(mod, "processor"):
+            raise ValueError(f"SAGEngine: {site!r} names no attention module")
+        self.site, self.taps, self.boundary = site, tuple(float(t) for t in taps), boundary
+        super().__init__(unet, scheduler, batch_size, num_inference_steps, use_graph, steps_per_graph, 1)
+        self.mass = None            # [B, T] fp32, made by the warm-up (or first eager) step, which knows the site's T
+        self.eps2 = torch.zeros((2 * batch_size,) + tuple(self.x_nhwc.shape[1:]), dtype=unet.dtype, device=unet.device)
+
+    def _sag_state(self):
+        """One noise row per step, filled per run - only when some step draws (eta != 0); without, the update gets no noise
+        pointer and reads none (c = 0 in every row)."""
+        if any(self.schedule.draws):
+            self.noise = torch.zeros((self.n,) + tuple(self.lat.shape), dtype=torch.float32, device=self.lat.device)
+            self._stage = []
+        return [(self.noise,)]
+
+    UPDATES = {"sag": (ops.pag_step, _sag_state)}
+
+    def _substep(self, lat, x_nhwc, branch=0):
+        B = self.B
+        with ops.sync_scope(self._sync[branch]):
+            ops.to_nhwc(lat, self.unet.dtype, out=x_nhwc)
+            with sag_processor(self.unet, self.site, self.mass) as proc:
+                e = self.unet.forward_nhwc(x_nhwc, self.t_cur, temb_slices=self.temb_slices)
+            if proc.mass is None:
+                raise RuntimeError(f"SAGEngine: the attention module {self.site!r} was not evaluated")
+            self.mass = proc.mass       # (the first step outside a capture makes it; from then on the processor writes into it)
+            self.eps2[:B].copy_(e)
+            ops.sag_degrade(lat, self.eps2[:B], self.mass, self.taps, self.boundary, self.coef, self.step_idx, out=x_nhwc)
+            self.eps2[B:].copy_(self.unet.forward_nhwc(x_nhwc, self.t_cur, temb_slices=self.temb_slices))
+            self._update(lat, self.eps2, *self._state[branch], self.coef, self.step_idx, advance=False, out=lat)
 
     def run(self, latents, draw=None):
         if self.noise is None:

@@ -712,21 +712,24 @@ class AttnProcessor2_0:
     (the protocol CrossFrameAttnProcessor uses, reference cross_frame_attn.py:125)."""
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None, kv=None, kv_sink=None,
-                 kv1=None, alpha=None):
+                 kv1=None, alpha=None, qk_sink=None):
         """kv / kv_sink (CrossFrameAttnProcessor with cache_kv): `kv_sink(k, vt)` receives this call's projected keys
         [B, T, C] (a view) and channel-major values [B, C, T] - the self-attention then runs on the three-launch path, where
         they exist in memory; `kv = (k, vt)` runs the attention against such a stored pair (Bk divides B) instead of projecting
         an encoder_hidden_states map: K / V of the stored pass are the same numbers whichever pass projects them.
         kv1 + alpha (the interpolating processor): a second stored pair, and the output is
         to_out((1 - alpha) attn(q, kv) + alpha attn(q, kv1)) + residual with alpha [B] fp32 on the device - one
-        afldm_attention_interp launch and one to_out GEMM (to_out is affine and the residual is common to both terms)."""
+        afldm_attention_interp launch and one to_out GEMM (to_out is affine and the residual is common to both terms).
+        qk_sink (SAGAttnProcessor): `qk_sink(q, k)` receives this call's projected queries and keys [B, T, C] (views of the
+        q | k buffer) in front of the attention launch; like kv_sink it sends the block to the three-launch path."""
         assert attention_mask is None
         assert kv1 is None or (kv is not None and alpha is not None)
         B, H, W, C = hidden_states.shape
         gamma, beta = packed_norm(attn.group_norm)
         gn = attn.group_norm
         pre = getattr(hidden_states, "gn_applied", None)
-        plain = kv is None and kv_sink is None
+        plain = kv is None and kv_sink is None and qk_sink is None
+        assert qk_sink is None or (kv is None and encoder_hidden_states is None), "qk_sink observes plain self-attention"
         assert kv is None or encoder_hidden_states is None
         if (plain and pre is None and encoder_hidden_states is None and C // attn.heads <= 32
                 and ops.attn_block_fused_ok(hidden_states.view(B, H * W, C), attn.heads, gn.num_groups)):
@@ -773,6 +776,8 @@ class AttnProcessor2_0:
             q, k = qk[:, :, :C], qk[:, :, C:]
             if kv_sink is not None:
                 kv_sink(k, vt)
+            if qk_sink is not None:
+                qk_sink(q, k)
         else:
             q = linear_forward(attn.to_q, tokens)
             w, b = packed_qkv(attn, tokens.dtype, ("k", "v"))
@@ -807,6 +812,29 @@ class PAGAttnProcessor(AttnProcessor2_0):
         w, b = packed_vo(attn, hidden_states.dtype)
         ops.attn_identity_block(xp, stats, gamma, beta, gn.num_groups, gn.eps, w, b, out=out[B:])
         return out
+
+
+class SAGAttnProcessor(AttnProcessor2_0):
+    """Self-attention guidance (Hong et al., ICCV 2023; diffusers StableDiffusionSAGPipeline's attention hook) at ONE site: the
+    plain block, run on the three-launch path where q and k exist in memory (the kv_sink route), plus one
+    ops.attn_key_mass call on them: the attention mass each key receives, fp32 [B, T], written into `mass` - a buffer the engine
+    owns (a captured graph writes the same address at every replay), or one made per call and kept in `self.mass` when none is
+    given.  The block's output is AttnProcessor2_0's with a no-op kv_sink, bit for bit: the extra launches only read q and k.
+    Because _next_gn tests the processor type exactly, the resnet in front hands no pre-normed tensor to such a site."""
+
+    def __init__(self, mass=None):
+        self.mass = mass
+        self._given = mass is not None
+
+    def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None, **kwargs):
+        assert encoder_hidden_states is None and attention_mask is None and not kwargs, "SAG observes plain self-attention"
+        if hidden_states.shape[-1] // attn.heads > 32:
+            raise NotImplementedError("SAGAttnProcessor: head_dim > 32 has no key-mass kernel")
+
+        def sink(q, k):
+            self.mass = ops.attn_key_mass(q, k, attn.heads, scale=attn.scale, out=self.mass if self._given else None)
+
+        return super().__call__(attn, hidden_states, qk_sink=sink)
 
 
 class Attention(nn.Module):

@@ -1699,6 +1699,94 @@ def pag_step_flat(x, e, e_p, z, row, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- self-attention guidance
+def gaussian_taps(kernel_size=9, sigma=1.0):
+    """diffusers' gaussian_blur_2d window, w = exp(-0.5 (linspace(-k, k, 2 k + 1) / sigma)^2) normalised, k = (kernel_size - 1) / 2,
+    computed in float64 and rounded once to fp32: a tuple of Python floats that are exactly those fp32 values (hashable: it goes
+    into an engine's cache key)."""
+    n = int(kernel_size)
+    if n < 1 or n > 15 or n % 2 == 0 or not float(sigma) > 0.0:
+        raise ValueError(f"gaussian_taps: kernel_size = {kernel_size} must be odd, 1 .. 15, and sigma = {sigma} positive")
+    k = (n - 1) * 0.5
+    w = torch.exp(-0.5 * (torch.linspace(-k, k, n, dtype=torch.float64) / float(sigma)) ** 2)
+    return tuple(float(v) for v in (w / w.sum()).float())
+
+
+def attn_key_mass_ok(q, heads):
+    """True when afldm_attn_key_mass has a kernel for q [B, T, heads * d] (the shapes: afldm_hip.h)."""
+    B, T, C = q.shape
+    return q.dtype in DTYPE_CODE and C % heads == 0 and bool(lib.afldm_attn_key_mass_ok(B, int(heads), T, C // heads, _code(q)))
+
+
+def attn_key_mass(q, k, heads, scale=None, out=None):
+    """The attention mass every key receives, mass[b, j] = (1 / heads) sum_h sum_i softmax_j(scale q_bhi . k_bhj), fp32 [B, T]: q, k
+    [B, T, C] token-major as ops.attention takes them (column slices of a wider buffer are fine: the leading dimension is
+    stride(1)), self-attention only.  The T x T probabilities never reach memory.  A shape without a kernel is an error."""
+    if not (q.is_cuda and k.is_cuda):
+        raise RuntimeError("afldm_amd: attn_key_mass inputs must live on an MI355X (cuda) device; there is no CPU path")
+    B, T, C = q.shape
+    assert k.shape == q.shape and k.dtype == q.dtype, "attn_key_mass: self-attention (k shaped like q)"
+    ldq, ldk = q.stride(1), k.stride(1)
+    assert q.stride(2) == 1 and k.stride(2) == 1 and q.stride(0) == T * ldq and k.stride(0) == T * ldk
+    d = C // heads
+    if scale is None:
+        scale = d ** -0.5
+    if out is None:
+        out = torch.empty((B, T), dtype=torch.float32, device=q.device)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (B, T) and out.is_contiguous() and out.is_cuda
+    ws = torch.empty((B * heads * T * 2,), dtype=torch.float32, device=q.device)
+    tok = _begin()
+    check(lib.afldm_attn_key_mass(ptr(q), ldq, ptr(k), ldk, ptr(out), ptr(ws), B, int(heads), T, d, float(scale), _code(q),
+                                  stream_ptr()), "attn_key_mass")
+    _end(tok, "attn_key_mass", 6.0 * B * heads * T * T * d, (4 * B * T * C) * q.element_size())
+    return out
+
+
+def _sag_args(name, x, mass, taps, boundary):
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f"{name}: x must be contiguous fp32 [B, C, H, W], got {x.dtype} {tuple(x.shape)}")
+    B, C, H, W = x.shape
+    _dev(mass, "mass")
+    if mass.dtype != torch.float32 or mass.dim() != 2 or mass.shape[0] != B or not mass.is_contiguous():
+        raise ValueError(f"{name}: mass must be contiguous fp32 [{B}, hm * hm], got {mass.dtype} {tuple(mass.shape)}")
+    hm = int(round(mass.shape[1] ** 0.5))
+    if hm * hm != mass.shape[1]:
+        raise ValueError(f"{name}: {mass.shape[1]} masses per sample are no square map")
+    if boundary not in ("reflect", "circular"):
+        raise ValueError(f"{name}: boundary {boundary!r} (want 'reflect' or 'circular')")
+    w = (ctypes.c_float * len(taps))(*[float(t) for t in taps])
+    return B, C, H, W, hm, w, len(taps), int(boundary == "circular")
+
+
+def sag_degrade(x, e_nhwc, mass, taps, boundary, coef, step_idx, out=None):
+    """SAG's degraded UNet input in one launch (afldm_sag_degrade): x NCHW fp32 [B, C, H, W], e NHWC dtype [B, H, W, C] (the UNet's
+    output), mass fp32 [B, hm * hm] (attn_key_mass of the chosen site), taps a sequence of fp32-exact floats (gaussian_taps),
+    boundary 'reflect' | 'circular'; (p, q) = the first two fields of the 12-float row of `coef` at *step_idx.  Returns x_d NHWC
+    in e's dtype: x + M (G x0 - x0) / p with x0 = p x + q e and M = mass > 1 up-sampled to the latent grid."""
+    _dev(x, "x"); _dev(e_nhwc, "e")
+    B, C, H, W, hm, w, n, bnd = _sag_args("sag_degrade", x, mass, taps, boundary)
+    assert tuple(e_nhwc.shape) == (B, H, W, C) and e_nhwc.is_contiguous()
+    if out is None:
+        out = torch.empty_like(e_nhwc)
+    assert out.shape == e_nhwc.shape and out.dtype == e_nhwc.dtype and out.is_contiguous() and out.data_ptr() != e_nhwc.data_ptr()
+    check(lib.afldm_sag_degrade(ptr(x), ptr(e_nhwc), ptr(mass), ptr(out), ptr(coef), ptr(step_idx), w, n, bnd, B, C, H, W, hm,
+                                _code(e_nhwc), stream_ptr()), "sag_degrade")
+    return out
+
+
+def sag_degrade_flat(x, e, mass, taps, boundary, p, q, out=None):
+    """The same on NCHW fp32 tensors throughout with p and q by value (the eager loop): x, e [B, C, H, W] -> x_d [B, C, H, W]."""
+    _dev(x, "x"); _dev(e, "e")
+    B, C, H, W, hm, w, n, bnd = _sag_args("sag_degrade_flat", x, mass, taps, boundary)
+    assert e.shape == x.shape and e.dtype == torch.float32 and e.is_contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.shape == x.shape and out.dtype == torch.float32 and out.is_contiguous()
+    check(lib.afldm_sag_degrade_flat(ptr(x), ptr(e), ptr(mass), ptr(out), float(p), float(q), w, n, bnd, B, C, H, W, hm,
+                                     stream_ptr()), "sag_degrade_flat")
+    return out
+
+
 # ----------------------------------------------------------------------------- MultiDiffusion: a canvas through windows
 def _geom_args(g):
     """A panorama.Geometry as the C arguments (Hc, Wc, S, oy, ny, ox, nx, wrap_y, wrap_x); the origin lists are host arrays the

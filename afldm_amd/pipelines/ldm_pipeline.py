@@ -344,6 +344,102 @@ class MyLDMPipeline(DiffusionPipeline):
                                latents, use_graph)
         return self._deliver(out, output_type, return_dict)
 
+    # ------------------------------------------------------------------------------------------------ self-attention guidance
+    def sag_site_of(self, sag_site):
+        """The ONE attention module `sag_site` names, as a module path: a key of get_unet_attn_processors without its
+        '.processor', or a prefix of one on a '.' boundary (as pag_sites resolves names) that selects exactly one module -
+        'mid_block' and 'up_blocks.1.attentions.0' are valid, 'up_blocks.1' is not where that block has several attentions.
+        Anything else raises ValueError listing the candidates."""
+        from .cross_frame_attn import get_unet_attn_processors
+        keys = [k[:-len(".processor")] for k in get_unet_attn_processors(self.unet)]
+        hit = [k for k in keys if k == sag_site or k.startswith(str(sag_site) + ".")] if isinstance(sag_site, str) else []
+        if len(hit) != 1:
+            raise ValueError(f"sag_site: {sag_site!r} names {len(hit)} attention blocks, want exactly one of: {', '.join(keys)}")
+        return hit[0]
+
+    @torch.no_grad()
+    def sag_latents(self, batch_size=1, sag_scale=0.75, sag_site="mid_block", blur_kernel_size=9, blur_sigma=1.0,
+                    blur_boundary="reflect", guidance_rescale=0.0, eta=0.0, num_inference_steps=50, generator=None,
+                    latents=None, use_graph=True, masks=None, return_masks=False):
+        """Self-attention guidance (Hong et al., ICCV 2023; diffusers StableDiffusionSAGPipeline restricted to an unconditional
+        UNet) in latent space.  Every step evaluates the UNet, e = UNet(x, t), while the attention block `sag_site` (sag_site_of)
+        also reports the attention mass each of its keys receives (afldm_attn_key_mass; heads-mean, summed over the queries);
+        where that mass exceeds 1 the predicted x0 = p x + q e is Gaussian-blurred (`blur_kernel_size` taps, `blur_sigma`;
+        `blur_boundary` 'reflect' as diffusers pads, or 'circular', under which the degradation commutes with circular integer
+        shifts) and re-noised with e itself, x_d = x + M (G x0 - x0) / p (afldm_sag_degrade); e_d = UNet(x_d, t) with the
+        processors as found; and the step is pag_latents' with g = e + sag_scale (e - e_d) (`guidance_rescale` likewise).  The two
+        evaluations are dependent, so a step costs two UNet launches of batch B.
+
+        `sag_site` defaults to diffusers' "mid_block", which on the FFHQ model is the 2 x 2 level: a map of only 4 tokens, each
+        covering a quarter of the latent plane.  scripts/sag_ffhq.py picks the 8 x 8 up-block attention instead.
+
+        The schedule is DDIMScheduler.sag_schedule: replayed HIP graphs (use_graph, SAGEngine) or the eager loop below over
+        afldm_sag_degrade_flat and afldm_pag_step_flat, which makes the same draws from `generator` in the same order as pag_latents
+        - the start latents (unless `latents` is given), then with eta != 0 one tensor per step - and carries the latents in fp32
+        like the engine.  Eager loop only: return_masks=True returns (latents, masses) with the fp32 [B, T] masses of every
+        step, and masks= replays a list of [B, T] boolean masks, one per step, instead of thresholding (with use_graph=True it
+        raises ValueError).  sag_scale = 0 is allowed and still runs both evaluations.  Needs no VAE.  Returns latents in the
+        UNet's dtype.  The UNet's attention processors are as they were on return, also after an exception."""
+        from .. import ops
+        from ..engine import SAGEngine, sag_processor
+        self._refuse_dpm("sag_latents")
+        site = self.sag_site_of(sag_site)
+        taps = ops.gaussian_taps(blur_kernel_size, blur_sigma)
+        if blur_boundary not in ("reflect", "circular"):
+            raise ValueError(f"sag_latents: blur_boundary {blur_boundary!r} (want 'reflect' or 'circular')")
+        if use_graph and (masks is not None or return_masks):
+            raise ValueError("sag_latents: masks= and return_masks=True belong to the eager loop (use_graph=False)")
+        c, s, dev = self.unet.config.in_channels, self.unet.config.sample_size, self.unet.device
+        B = int(batch_size) if latents is None else latents.shape[0]
+        shape = (B, c, s, s)
+        if latents is not None and tuple(latents.shape) != shape:
+            raise ValueError(f"sag_latents: latents {tuple(latents.shape)}, want [B, {c}, {s}, {s}]")
+        self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
+        sched = self.scheduler.sag_schedule(num_inference_steps, eta, sag_scale, guidance_rescale)
+        if masks is not None and len(masks) != len(sched.timesteps):
+            raise ValueError(f"sag_latents: {len(masks)} masks for {len(sched.timesteps)} steps")
+        draw = sched.drawer(generator, shape, dev, self.unet.dtype)
+        if latents is None:
+            latents = draw()            # (on the CPU for CPU generators, else on the device: the per-evaluation draws' rule)
+        if use_graph:
+            eng = cached_engine(self, "_sag_engines", sched, B, True, self.unet, extra=(site, taps, blur_boundary),
+                                build=lambda: SAGEngine(self.unet, sched, B, len(sched.timesteps), True, site=site, taps=taps,
+                                                        boundary=blur_boundary))
+            eng.scheduler = self.scheduler
+            return eng.run(latents, draw=draw).to(self.unet.dtype)
+        x = (latents.to(device=dev, dtype=torch.float32) * sched.init_noise_sigma).contiguous()
+        pq = sched.table("cpu")[:, :2].tolist()         # (p, q) as the engine's kernel reads them: rounded once to fp32
+        masses = []
+        for k, (t, row) in enumerate(self.progress_bar(list(zip(sched.timesteps, sched.rows)))):
+            z = draw().to(device=dev, dtype=torch.float32).contiguous() if sched.slots(k) else None
+            with sag_processor(self.unet, site) as proc:
+                e = self.unet(x.to(self.unet.dtype), t).sample.float().contiguous()
+            mass = proc.mass
+            masses.append(mass)
+            if masks is not None:
+                m = masks[k]
+                if tuple(m.shape) != tuple(mass.shape) or m.dtype != torch.bool:
+                    raise ValueError(f"sag_latents: masks[{k}] is {m.dtype} {tuple(m.shape)}, want bool {tuple(mass.shape)}")
+                mass = m.to(dev).float() * 2.0          # 2 > 1: masked; 0: not
+            x_d = ops.sag_degrade_flat(x, e, mass.contiguous(), taps, blur_boundary, *pq[k])
+            e_d = self.unet(x_d.to(self.unet.dtype), t).sample.float().contiguous()
+            x = ops.pag_step_flat(x, e, e_d, z, row)
+        out = x.to(self.unet.dtype)
+        return (out, masses) if return_masks else out
+
+    @torch.no_grad()
+    def sag(self, batch_size=1, sag_scale=0.75, sag_site="mid_block", blur_kernel_size=9, blur_sigma=1.0, blur_boundary="reflect",
+            guidance_rescale=0.0, eta=0.0, num_inference_steps=50, generator=None, latents=None, use_graph=True, masks=None,
+            return_masks=False, output_type="pil", return_dict=True):
+        """Sample images with self-attention guidance: sag_latents, then decode.  output_type as __call__; 'latent' returns the
+        sampled latents.  With return_masks=True (eager loop) the result is (images, masses)."""
+        self._refuse_dpm("sag")
+        out = self.sag_latents(batch_size, sag_scale, sag_site, blur_kernel_size, blur_sigma, blur_boundary, guidance_rescale, eta,
+                               num_inference_steps, generator, latents, use_graph, masks, return_masks)
+        if return_masks:
+            return self._deliver(out[0], output_type, return_dict), out[1]
+        return self._deliver(out, output_type, return_dict)
+
     # ------------------------------------------------------------------------------------------------ MultiDiffusion panoramas
     def panorama_geometry(self, height, width, stride=None, circular=False):
         """The panorama.Geometry of a height x width canvas (latent units) under this UNet's window: `stride` (default

@@ -162,6 +162,20 @@ class DDIMScheduler:
         return Schedule.of(self, "pag", sde.timesteps, rows, draws, _pag_steps=int(num_inference_steps), _pag_eta=float(eta),
                            _pag_scale=s, _pag_rescale=phi)
 
+    def sag_schedule(self, num_inference_steps, eta=0.0, sag_scale=0.75, guidance_rescale=0.0):
+        """Self-attention guidance (Hong et al., ICCV 2023; diffusers StableDiffusionSAGPipeline) over this scheduler's
+        `num_inference_steps` timesteps, as the Schedule SAGEngine replays: every step evaluates the UNet, degrades its input where
+        one site's attention mass exceeds 1 (afldm_sag_degrade, which reads p and q of the row), evaluates the UNet again and
+        applies afldm_pag_step with the second output in the perturbed one's place, g = e + sag_scale (e - e_d).  Rows and draws
+        are pag_schedule(num_inference_steps, eta, sag_scale, guidance_rescale)'s, float for float; the kind is "sag", so that
+        an engine of one kind never replays the other's schedule."""
+        s, phi = float(sag_scale), float(guidance_rescale)
+        if s < 0.0 or not 0.0 <= phi <= 1.0:
+            raise ValueError(f"sag_schedule: sag_scale = {sag_scale} must be >= 0 and guidance_rescale = {guidance_rescale} in [0, 1]")
+        pag = self.pag_schedule(num_inference_steps, eta, s, phi)
+        return Schedule.of(self, "sag", pag.timesteps, pag.rows, pag.draws, _sag_steps=int(num_inference_steps),
+                           _sag_eta=float(eta), _sag_scale=s, _sag_rescale=phi)
+
     def _reverse_row(self, ab, ab_prev, eta):
         """(p, q, lo, hi, a, b, c) of one reverse step from level ab to ab_prev (epsilon prediction), the first seven fields of
         a "repaint" or "ilvr" row: x0 = clamp((x - sqrt(1-ab) eps) / sqrt(ab), -r, r) with r = clip_sample_range under

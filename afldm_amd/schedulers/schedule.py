@@ -13,9 +13,12 @@ UNet evaluation, fixed when it is made.  `kind` names the update kernel that rea
     "pag"   (p, q, lo, hi, a, b, d, c, s, phi, 0, 0):  perturbed-attention guidance on a batch of 2 B, e the UNet's output and e_p
             the perturbed UNet's:  g = e + s (e - e_p);  phi != 0: g <- g (phi std(e) / std(g) + 1 - phi) per sample;  then the
             "sde" row applied to g:  x0 = clamp(p x + q g, lo, hi);  x_out = a x + b x0 + d g + c z          afldm_pag_step
+    "sag"   the "pag" row, float for float (s = sag_scale): self-attention guidance, two DEPENDENT evaluations per step - e, then
+            e_d on the input degraded where the attention mass of one site exceeds 1 (afldm_sag_degrade reads p and q of the
+            row) - and the same guided update with e_d in e_p's place                                        afldm_pag_step
 
 The rows come from the scheduler that owns the update (DDIMScheduler.schedule / stochastic_schedule,
-DDIMScheduler.repaint_schedule / ilvr_schedule / panorama_schedule / pag_schedule, DPMSolverMultistepScheduler.schedule, I2SBScheduler.ode_schedule / bridge_schedule,
+DDIMScheduler.repaint_schedule / ilvr_schedule / panorama_schedule / pag_schedule / sag_schedule, DPMSolverMultistepScheduler.schedule, I2SBScheduler.ode_schedule / bridge_schedule,
 MyLDMPipeline.inversion_schedule) as Python floats and are rounded once to fp32 by `table`.  An "sde" schedule also states which
 steps draw noise and how: exactly the randn_tensor calls, in the same order, that the scheduler's eager `step()` makes, so that
 the engine can draw them from the caller's generator before the captured graphs need them.  A "repaint" schedule has up to
@@ -29,8 +32,8 @@ import torch
 from ..configs import FrozenConfig
 from ..utils import randn_tensor
 
-ROW_WIDTH = {"ddim": 4, "dpm": 8, "sde": 8, "repaint": 12, "ilvr": 12, "pano": 8, "pag": 12}
-NOISE_SLOTS = {"sde": 1, "repaint": 3, "ilvr": 2, "pano": 1, "pag": 1}          # draws per step at the most; the kinds not named draw nothing
+ROW_WIDTH = {"ddim": 4, "dpm": 8, "sde": 8, "repaint": 12, "ilvr": 12, "pano": 8, "pag": 12, "sag": 12}
+NOISE_SLOTS = {"sde": 1, "repaint": 3, "ilvr": 2, "pano": 1, "pag": 1, "sag": 1}          # draws per step at the most; the kinds not named draw nothing
 _MADE = {}          # key -> Schedule: the rows are ~0.1 ms of scalar tensor arithmetic each, and a sampler asks per call
 
 
@@ -49,7 +52,7 @@ class Schedule:
     def of(cls, owner, kind, timesteps, rows, draws=None, noise_dtype=None, **settings):
         """owner: the scheduler whose config the rows are computed from; settings: whatever else they depend on (the step
         count, eta, is_ode, ...); rows: one per timestep, or a function of the timestep that is only called when no schedule
-        with this key has been made yet; draws: per step, whether the eager step draws a noise tensor ("sde", "pano", "pag"), or which of its
+        with this key has been made yet; draws: per step, whether the eager step draws a noise tensor ("sde", "pano", "pag", "sag"), or which of its
         slots do (a kind with NOISE_SLOTS[kind] > 1: that many bools per step - "repaint" three, "ilvr" two);
         noise_dtype: the dtype of that draw (None: the model's dtype, what DDIMScheduler.step draws in)."""
         config = FrozenConfig(dict(owner.config, **settings))
@@ -65,7 +68,7 @@ class Schedule:
             assert all(len(d) == NOISE_SLOTS[kind] for d in draws)
         else:
             draws = tuple(bool(d) for d in draws) if draws is not None else (False,) * len(rows)
-            assert kind in ("sde", "pano", "pag") or not any(draws)
+            assert kind in ("sde", "pano", "pag", "sag") or not any(draws)
         assert len(timesteps) == len(rows) == len(draws) and all(len(r) == ROW_WIDTH[kind] for r in rows)
         if len(_MADE) >= 64:
             _MADE.clear()

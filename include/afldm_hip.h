@@ -550,6 +550,42 @@ int afldm_pag_step(const float* x, const void* eps2, const float* noise, size_t 
 int afldm_pag_step_flat(const float* x, const float* e, const float* e_p, const float* z, float* x_out, float p, float q,
                         float lo, float hi, float a, float b, float d, float c, float s, float phi, float r10, float r11,
                         int B, size_t n, afldm_stream_t stream);
+/* ---- Self-attention guidance (Hong et al., ICCV 2023; diffusers StableDiffusionSAGPipeline) ---------------------------
+ * The attention mass every KEY of a self-attention receives (diffusers: attn_map.mean(1).sum(1)):
+ *   mass[b,j] = (1 / heads) sum_h sum_i softmax_j(scale q[b,i,h,:] . k[b,j,h,:])                    fp32 [B,T]
+ * q, k: [B,T,ld] token-major with head h at columns [h*d, (h+1)*d), exactly afldm_attention's self-attention operands (the
+ * two column halves of one [B,T,2C] buffer, or contiguous tensors): 16-byte aligned, ldq and ldk multiples of 8 and at least
+ * heads*d; dtype bf16 or fp32.  Behind the operand reads everything is fp32: q k^T on MFMA with fp32 accumulation (bf16
+ * products are exact there), the softmax with its row maximum subtracted, probabilities never rounded to bf16 and never
+ * stored.  Two launches: (max, 1 / sum) of every softmax row into stats_ws, fp32 [B*heads*T*2], 8-byte aligned, which the
+ * caller provides and may reuse afterwards; then the column sums on the transposed product.  No atomics and every sum in a
+ * fixed order: a sample's bits depend neither on B nor on its place in the batch.
+ * afldm_attn_key_mass_ok: 1 for d in {8, 16, 24, 32}, T in {4, 16, 64, 256, 1024}, heads >= 1, B >= 1 with B*heads*T < 2^28;
+ * 0 otherwise, and afldm_attn_key_mass itself returns AFLDM_ESHAPE there, and for a scale that is not positive, before any
+ * launch. */
+int afldm_attn_key_mass_ok(int B, int heads, int T, int d, int dtype);
+int afldm_attn_key_mass(const void* q, int ldq, const void* k, int ldk, float* mass, float* stats_ws, int B, int heads, int T,
+                        int d, float scale, int dtype, afldm_stream_t stream);
+/* The degradation, one launch.  With (p, q) = (1/sqrt(abar_t), -sqrt(1-abar_t)/sqrt(abar_t)), the first two fields of the
+ * 12-float row coef[12 s .. 12 s + 12), s = *step_idx (read, never advanced: it is the row the afldm_pag_step behind the
+ * second UNet evaluation applies; indexing as afldm_ddim_step):
+ *   x0  = p x + q e                                            (fmaf(p, x, q e))
+ *   G   = the separable blur with `taps` (ntaps odd, 1 .. 15; a HOST array read during the call and passed to the kernel by
+ *         value - a captured graph keeps it): a horizontal then a vertical pass, each sum in ascending tap order in fmaf from
+ *         0; boundary 0 = reflect without edge repeat (F.pad mode="reflect", diffusers gaussian_blur_2d), 1 = circular
+ *   M   = mass[b][(Y / r) hm + X / r] > 1.0f,  r = H / hm      (nearest up-sampling of the [hm,hm] map; strict; a NaN is false)
+ *   x_d = M ? x + (G x0 - x0) / p : x                          (an unmasked element is x, rounded to the output dtype)
+ * which is diffusers' add_noise(x0 + M (G x0 - x0), noise = e, t).  x: NCHW fp32 [B,C,H,W]; e: NHWC dtype [B,H,W,C] (the UNet's
+ * output); mass: fp32 [B,hm*hm]; x_d: NHWC dtype [B,H,W,C] (the UNet's next input), not aliasing e.  One workgroup per (b, c)
+ * plane, the plane twice in LDS.  Before any launch AFLDM_ESHAPE unless H = W, 8 <= H <= 64, C*H*W <= 16384, hm divides H and
+ * the half width ntaps / 2 < H.  Plain vector stores only. */
+int afldm_sag_degrade(const float* x, const void* e, const float* mass, void* x_d, const float* coef, const int* step_idx,
+                      const float* taps, int ntaps, int boundary, int B, int C, int H, int W, int hm, int dtype,
+                      afldm_stream_t stream);
+/* The same on NCHW fp32 tensors throughout (e and x_d too) with p and q by value, for an eager loop: the same device function
+ * in the same arithmetic order - with dtype fp32 the engine form's x_d is this one's, bit for bit, in the other layout. */
+int afldm_sag_degrade_flat(const float* x, const float* e, const float* mass, float* x_d, float p, float q, const float* taps,
+                           int ntaps, int boundary, int B, int C, int H, int W, int hm, afldm_stream_t stream);
 /* ---- MultiDiffusion: one canvas sampled through overlapping windows (Bar-Tal et al., ICML 2023) -------------------
  * A canvas is fp32 NCHW [P,C,Hc,Wc]; its nwin = ny * nx windows of S x S are the batch entries P * nwin + k, k = iy * nx + ix,
  * with corners (oy[iy], ox[ix]).  An axis with wrap != 0 is circular: the window covers (o + u) mod extent, 0 <= o < extent;
