@@ -58,8 +58,8 @@ def _fingerprint(cmd, deps):
 def build(force=False, verbose=True):
     os.makedirs(OUT_DIR, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, h) for h in ("common.hpp", "conv_common.hpp", "conv3h_tile.hpp", "conv3h_body.inc", "af_plane.hpp",
-                                               "af_plane_passes.inc")] + [os.path.join(HERE, "..", "include", "afldm_hip.h")]
+    headers = [os.path.join(CSRC, h) for h in ("common.hpp", "step_common.hpp", "conv_common.hpp", "conv3h_tile.hpp", "conv3h_body.inc",
+                                               "af_plane.hpp", "af_plane_passes.inc")] + [os.path.join(HERE, "..", "include", "afldm_hip.h")]
     exp_headers = headers + [os.path.join(HERE, "..", "include", "afldm_hip_experimental.h")]
     def command(src, obj):
         mode = os.environ.get("AFLDM_VGPR_FORM", "")

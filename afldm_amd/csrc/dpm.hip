@@ -5,40 +5,11 @@
 // HBM-bound elementwise: every thread owns 4 consecutive pixels of one (b, c) plane (16-byte loads of x / h1 / h2 /
 // x_out), grid capped at 2048 blocks and grid-stride beyond (guide G11).  Each thread reads and writes its own
 // indices only, so x and x_out may alias and the history shifts in place.
-#include "common.hpp"
+#include "step_common.hpp"
 
 namespace afldm {
 
 namespace {
-
-template <int V>
-struct vecf {
-  float v[V];
-};
-
-template <int V>
-__device__ __forceinline__ vecf<V> ld(const float* p) {
-  vecf<V> r;
-  if constexpr (V == 4) {
-    f32x4 q = *reinterpret_cast<const f32x4*>(p);
-    r.v[0] = q[0]; r.v[1] = q[1]; r.v[2] = q[2]; r.v[3] = q[3];
-  } else {
-#pragma unroll
-    for (int k = 0; k < V; ++k) r.v[k] = p[k];
-  }
-  return r;
-}
-
-template <int V>
-__device__ __forceinline__ void st(float* p, const vecf<V>& r) {
-  if constexpr (V == 4) {
-    f32x4 q = {r.v[0], r.v[1], r.v[2], r.v[3]};
-    *reinterpret_cast<f32x4*>(p) = q;
-  } else {
-#pragma unroll
-    for (int k = 0; k < V; ++k) p[k] = r.v[k];
-  }
-}
 
 struct dpm_row {
   float p, q, a, b0, b1, b2;
@@ -75,11 +46,7 @@ __global__ void __launch_bounds__(256) k_dpm_step(const float* x, const T* __res
   const size_t groups = n / V;
   for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (size_t)gridDim.x * blockDim.x) {
     const size_t i = g * V;
-    const int pix = (int)(i % HW);
-    const size_t plane = i / HW;
-    const int ch = (int)(plane % C);
-    const size_t b = plane / C;
-    const T* ep = eps + ((size_t)b * HW + pix) * C + ch;
+    const T* ep = eps_at(eps, nchw_at(i, C, HW), C, HW);
     float e[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) e[k] = to_f32(ep[(size_t)k * C]);
@@ -109,13 +76,6 @@ __global__ void __launch_bounds__(256) k_dpm_step_flat(const float* x, const flo
   }
 }
 
-__global__ void k_dpm_advance(int* step_idx) { *step_idx += 1; }
-
-static inline int dpm_grid(size_t work) {
-  size_t g = (work + 255) / 256;
-  return (int)(g < 2048 ? (g ? g : 1) : 2048);
-}
-
 }  // namespace afldm
 
 using namespace afldm;
@@ -128,16 +88,10 @@ extern "C" int afldm_dpm_step(const float* x, const void* eps, float* x_out, flo
   const int HW = H * W;
   const size_t n = (size_t)B * C * HW;
   const bool v4 = HW % 4 == 0 && aligned16(x) && aligned16(x_out) && aligned16(hist);
-  if (v4) {
-    DISPATCH_T(dtype, (k_dpm_step<float, 4><<<dpm_grid(n / 4), 256, 0, st>>>(x, (const float*)eps, x_out, hist, coef, step_idx, B, C, HW)),
-               (k_dpm_step<bf16, 4><<<dpm_grid(n / 4), 256, 0, st>>>(x, (const bf16*)eps, x_out, hist, coef, step_idx, B, C, HW)),
-               "afldm_dpm_step");
-  } else {
-    DISPATCH_T(dtype, (k_dpm_step<float, 1><<<dpm_grid(n), 256, 0, st>>>(x, (const float*)eps, x_out, hist, coef, step_idx, B, C, HW)),
-               (k_dpm_step<bf16, 1><<<dpm_grid(n), 256, 0, st>>>(x, (const bf16*)eps, x_out, hist, coef, step_idx, B, C, HW)),
-               "afldm_dpm_step");
-  }
-  if (advance) k_dpm_advance<<<1, 1, 0, st>>>(step_idx);
+#define LAUNCH(T, V) (k_dpm_step<T, V><<<step_grid(n / V), 256, 0, st>>>(x, (const T*)eps, x_out, hist, coef, step_idx, B, C, HW))
+  STEP_DISPATCH(dtype, v4, LAUNCH, "afldm_dpm_step");
+#undef LAUNCH
+  step_advance(advance, step_idx, st);
   return check_launch("afldm_dpm_step");
 }
 
@@ -149,8 +103,8 @@ extern "C" int afldm_dpm_step_flat(const float* x, const float* eps, float* x_ou
   const dpm_row c{p, q, a, b0, b1, b2};
   // the second history plane starts n floats in: 16-byte groups need n % 4 == 0 as well as aligned bases
   if (n % 4 == 0 && aligned16(x) && aligned16(eps) && aligned16(x_out) && aligned16(hist))
-    k_dpm_step_flat<4><<<dpm_grid(n / 4), 256, 0, st>>>(x, eps, x_out, hist, c, n);
+    k_dpm_step_flat<4><<<step_grid(n / 4), 256, 0, st>>>(x, eps, x_out, hist, c, n);
   else
-    k_dpm_step_flat<1><<<dpm_grid(n), 256, 0, st>>>(x, eps, x_out, hist, c, n);
+    k_dpm_step_flat<1><<<step_grid(n), 256, 0, st>>>(x, eps, x_out, hist, c, n);
   return check_launch("afldm_dpm_step_flat");
 }

@@ -13,7 +13,7 @@
 // arrived in.  All of a plane's global reads of x come before the first barrier and all stores after the last: x_out may alias x.
 // Uniform branches (the row is the same for every thread): a slot whose coefficient (k1, c) is exactly 0 is not loaded, and with
 // w = 0 neither are ref, z_k, Lh and Lw, and the two passes are skipped - the launch is then the plain stochastic step.
-#include "common.hpp"
+#include "step_common.hpp"
 
 namespace afldm {
 
@@ -25,45 +25,6 @@ struct ilvr_row {
 
 constexpr int ILVR_SMAX = 64;
 constexpr int ILVR_THREADS = 256;
-
-// clamp that keeps a NaN a NaN (as torch.clamp does); lo = -inf, hi = +inf: no clip.
-__device__ __forceinline__ float ilvr_clamp(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-template <int V>
-struct ivec {
-  float v[V];
-};
-
-template <int V>
-__device__ __forceinline__ ivec<V> ild(const float* p) {
-  ivec<V> r;
-  if constexpr (V == 4) {
-    f32x4 q = *reinterpret_cast<const f32x4*>(p);
-    r.v[0] = q[0]; r.v[1] = q[1]; r.v[2] = q[2]; r.v[3] = q[3];
-  } else {
-    r.v[0] = p[0];
-  }
-  return r;
-}
-
-template <int V>
-__device__ __forceinline__ ivec<V> ild_if(bool on, const float* p) {
-  if (on) return ild<V>(p);
-  ivec<V> r;
-#pragma unroll
-  for (int k = 0; k < V; ++k) r.v[k] = 0.0f;
-  return r;
-}
-
-template <int V>
-__device__ __forceinline__ void ist(float* p, const ivec<V>& r) {
-  if constexpr (V == 4) {
-    f32x4 q = {r.v[0], r.v[1], r.v[2], r.v[3]};
-    *reinterpret_cast<f32x4*>(p) = q;
-  } else {
-    p[0] = r.v[0];
-  }
-}
 
 // global row-major [S][S] -> LDS tile of pitch P
 __device__ __forceinline__ void ilvr_load_matrix(const float* __restrict__ L, float* tile, int S, int P, int tid) {
@@ -131,18 +92,18 @@ __device__ __forceinline__ void ilvr_plane(const float* xpl, const T* __restrict
   float* td = lds;                   // d, then the result of the column pass
   float* tt = lds + S * P;           // the row pass's output
   float* tm = lds + 2 * S * P;       // Lw, then Lh
-  ivec<V> xp[MAXG];
+  vecf<V> xp[MAXG];
 #pragma unroll
   for (int u = 0; u < MAXG; ++u) {
     const int g = tid + u * ILVR_THREADS;
     if (g < groups) {
       const int i = g * V;
-      const ivec<V> xv = ild<V>(xpl + i), zuv = ild_if<V>(has_u, zu + i);
-      const ivec<V> rv = ild_if<V>(guided, rpl + i), zkv = ild_if<V>(guided && has_k, zk + i);
+      const vecf<V> xv = ld<V>(xpl + i), zuv = ld_if<V>(has_u, zu + i);
+      const vecf<V> rv = ld_if<V>(guided, rpl + i), zkv = ld_if<V>(guided && has_k, zk + i);
 #pragma unroll
       for (int k = 0; k < V; ++k) {
         const float e = to_f32(ep[(size_t)(i + k) * es]);
-        const float x0 = ilvr_clamp(r.p * xv.v[k] + r.q * e, r.lo, r.hi);
+        const float x0 = clamp_nan(r.p * xv.v[k] + r.q * e, r.lo, r.hi);
         xp[u].v[k] = r.a * x0 + r.b * e + r.c * zuv.v[k];
         if (guided) {
           const float yk = r.k0 * rv.v[k] + r.k1 * zkv.v[k];
@@ -176,7 +137,7 @@ __device__ __forceinline__ void ilvr_plane(const float* xpl, const T* __restrict
           xp[u].v[k] += r.w * td[row * P + (i + k - row * S)];
         }
       }
-      ist<V>(opl + i, xp[u]);
+      st<V>(opl + i, xp[u]);
     }
   }
 }
@@ -214,8 +175,6 @@ __global__ void __launch_bounds__(ILVR_THREADS) k_ilvr_step_flat(const float* x,
   ilvr_plane<float, V>(x + o, eps + o, 1, ref + o, zk + o, zu + o, Lh, Lw, x_out + o, r, S, ilvr_lds);
 }
 
-__global__ void k_ilvr_advance(int* step_idx) { *step_idx += 1; }
-
 static inline size_t ilvr_lds_bytes(int S) { return (size_t)3 * S * (S | 1) * sizeof(float); }
 
 }  // namespace afldm
@@ -242,22 +201,12 @@ extern "C" int afldm_ilvr_step(const float* x, const void* eps, const float* ref
   // every slot starts a multiple of the two strides after the base: 16-byte groups need both % 4 == 0 too
   const bool v4 = (S * S) % 4 == 0 && noise_step_stride % 4 == 0 && noise_slot_stride % 4 == 0 && aligned16(x) && aligned16(ref) &&
                   aligned16(x_out) && aligned16(noise);
-  if (v4) {
-    DISPATCH_T(dtype,
-               (k_ilvr_step<float, 4><<<grid, ILVR_THREADS, lds, st>>>(x, (const float*)eps, ref, noise, noise_step_stride,
-                                                                       noise_slot_stride, Lh, Lw, x_out, coef, step_idx, C, S)),
-               (k_ilvr_step<bf16, 4><<<grid, ILVR_THREADS, lds, st>>>(x, (const bf16*)eps, ref, noise, noise_step_stride,
-                                                                      noise_slot_stride, Lh, Lw, x_out, coef, step_idx, C, S)),
-               "afldm_ilvr_step");
-  } else {
-    DISPATCH_T(dtype,
-               (k_ilvr_step<float, 1><<<grid, ILVR_THREADS, lds, st>>>(x, (const float*)eps, ref, noise, noise_step_stride,
-                                                                       noise_slot_stride, Lh, Lw, x_out, coef, step_idx, C, S)),
-               (k_ilvr_step<bf16, 1><<<grid, ILVR_THREADS, lds, st>>>(x, (const bf16*)eps, ref, noise, noise_step_stride,
-                                                                      noise_slot_stride, Lh, Lw, x_out, coef, step_idx, C, S)),
-               "afldm_ilvr_step");
-  }
-  if (advance) k_ilvr_advance<<<1, 1, 0, st>>>(step_idx);
+#define LAUNCH(T, V)                                                                                                     \
+  (k_ilvr_step<T, V><<<grid, ILVR_THREADS, lds, st>>>(x, (const T*)eps, ref, noise, noise_step_stride, noise_slot_stride, Lh, Lw, \
+                                                      x_out, coef, step_idx, C, S))
+  STEP_DISPATCH(dtype, v4, LAUNCH, "afldm_ilvr_step");
+#undef LAUNCH
+  step_advance(advance, step_idx, st);
   return check_launch("afldm_ilvr_step");
 }
 

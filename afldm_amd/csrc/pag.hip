@@ -22,7 +22,7 @@
 //    64 lanes by xor-shuffles, 16 waves out of LDS in a fixed tree): depth log2(16384), no atomics, bits independent of B.  The
 //    ratio is sqrt(ss_e / ss_g) (the 1 / (n - 1) of the two deviations cancels), 1 where ss_g = 0; with phi = 0 the reduction is
 //    skipped.  z is read only where c != 0.  All of a sample's reads of x come before its stores: x_out may alias x.
-#include "common.hpp"
+#include "step_common.hpp"
 
 namespace afldm {
 
@@ -187,9 +187,6 @@ constexpr int PAG_THREADS = 1024;
 constexpr int PAG_PER_THREAD = 16;
 constexpr int PAG_NMAX = PAG_THREADS * PAG_PER_THREAD;      // elements per sample
 
-// clamp that keeps a NaN a NaN (as torch.clamp does); lo = -inf, hi = +inf: no clip.
-__device__ __forceinline__ float pag_clamp(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // Sum of (a, b) over the workgroup, the same bits in every thread: xor-shuffles inside a wave, then the 16 wave sums out of LDS in a
 // fixed pairwise tree.  `red` holds 2 x 16 floats; two barriers, so it can be reused by the next call.
 __device__ __forceinline__ void pag_block_sum(float& a, float& b, float* red) {
@@ -312,7 +309,7 @@ __device__ __forceinline__ void pag_sample(const float* xs, const T* __restrict_
       }
 #pragma unroll
       for (int k = 0; k < V; ++k) {
-        const float x0 = pag_clamp(r.p * xv[k] + r.q * g[u][k], r.lo, r.hi);
+        const float x0 = clamp_nan(r.p * xv[k] + r.q * g[u][k], r.lo, r.hi);
         out[u][k] = r.a * xv[k] + r.b * x0 + r.d * g[u][k] + r.c * zv[k];
       }
     }
@@ -349,8 +346,6 @@ __global__ void __launch_bounds__(PAG_THREADS) k_pag_step_flat(const float* x, c
   const size_t o = (size_t)blockIdx.x * n;
   pag_sample<float, V, true>(x + o, e + o, ep + o, z ? z + o : nullptr, x_out + o, r, 1, n, n, red);
 }
-
-__global__ void k_pag_advance(int* step_idx) { *step_idx += 1; }
 
 }  // namespace
 
@@ -397,22 +392,11 @@ extern "C" int afldm_pag_step(const float* x, const void* eps2, const float* noi
   hipStream_t st = (hipStream_t)stream;
   const int HW = H * W;
   const bool v4 = HW % 4 == 0 && aligned16(x) && aligned16(x_out) && (!noise || (noise_step_stride % 4 == 0 && aligned16(noise)));
-  if (v4) {
-    DISPATCH_T(dtype,
-               (k_pag_step<float, 4><<<B, PAG_THREADS, 0, st>>>(x, (const float*)eps2, noise, noise_step_stride, x_out, coef, step_idx,
-                                                               B, C, HW)),
-               (k_pag_step<bf16, 4><<<B, PAG_THREADS, 0, st>>>(x, (const bf16*)eps2, noise, noise_step_stride, x_out, coef, step_idx,
-                                                              B, C, HW)),
-               "afldm_pag_step");
-  } else {
-    DISPATCH_T(dtype,
-               (k_pag_step<float, 1><<<B, PAG_THREADS, 0, st>>>(x, (const float*)eps2, noise, noise_step_stride, x_out, coef, step_idx,
-                                                               B, C, HW)),
-               (k_pag_step<bf16, 1><<<B, PAG_THREADS, 0, st>>>(x, (const bf16*)eps2, noise, noise_step_stride, x_out, coef, step_idx,
-                                                              B, C, HW)),
-               "afldm_pag_step");
-  }
-  if (advance) k_pag_advance<<<1, 1, 0, st>>>(step_idx);
+#define LAUNCH(T, V) \
+  (k_pag_step<T, V><<<B, PAG_THREADS, 0, st>>>(x, (const T*)eps2, noise, noise_step_stride, x_out, coef, step_idx, B, C, HW))
+  STEP_DISPATCH(dtype, v4, LAUNCH, "afldm_pag_step");
+#undef LAUNCH
+  step_advance(advance, step_idx, st);
   return check_launch("afldm_pag_step");
 }
 

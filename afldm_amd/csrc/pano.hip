@@ -15,7 +15,7 @@
 // the NHWC eps pixel of a window is one 16-byte (fp32) or 8-byte (bf16) load.  At FFHQ size the update moves a few hundred KB:
 // latency-bound, like sde.hip.  The origin lists travel by value in the kernel arguments (at most 16 per axis), so a captured
 // graph holds its geometry.
-#include "common.hpp"
+#include "step_common.hpp"
 
 namespace afldm {
 
@@ -32,15 +32,12 @@ struct pano_row {
   float p, q, lo, hi, a, b, d, c;
 };
 
-// (as sde.hip) clamp that keeps a NaN a NaN, like torch.clamp
-__device__ __forceinline__ float pano_clamp(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // The two expressions of sde.hip's sde_update with every product and sum rounded on its own (no contraction into fma), left to
 // right: what afldm_sde_step's one-element-per-thread form computes, so that one window of weight 1 gives its bits.  (That
 // kernel's 16-byte form contracts some of them; the two differ in the last bit.)
 __device__ __forceinline__ float pano_x0(float x, float e, const pano_row& r) {
 #pragma clang fp contract(off)
-  return pano_clamp(r.p * x + r.q * e, r.lo, r.hi);
+  return clamp_nan(r.p * x + r.q * e, r.lo, r.hi);
 }
 __device__ __forceinline__ float pano_out(float x, float x0, float e, float z, const pano_row& r) {
 #pragma clang fp contract(off)
@@ -52,11 +49,6 @@ __device__ __forceinline__ int pano_pos(int Y, int o, int extent, int wrap) {
   int u = Y - o;
   if (wrap && u < 0) u += extent;
   return u;
-}
-
-static inline int pano_grid(size_t work) {
-  size_t g = (work + 255) / 256;
-  return (int)(g < 2048 ? (g ? g : 1) : 2048);
 }
 
 // The checks the three entry points share, before any launch: at most 16 origins per axis, S <= extent, every window inside a
@@ -168,8 +160,6 @@ __global__ void __launch_bounds__(256) k_pano_step(const float* canvas, const T*
   }
 }
 
-__global__ void k_pano_advance(int* step_idx) { *step_idx += 1; }
-
 // win: NCHW T [P * nwin, C, S, S]; canvas fp32 [P, C, Hc, Wc]; one canvas element per thread
 template <typename T>
 __global__ void __launch_bounds__(256) k_window_fuse(const T* __restrict__ win, const float* __restrict__ wt,
@@ -238,22 +228,12 @@ extern "C" int afldm_pano_step(const float* canvas, const void* eps, const float
   hipStream_t st = (hipStream_t)stream;
   // the four channels of a pixel as one load: 16 bytes of fp32, 8 of bf16
   const bool c4 = C == 4 && (reinterpret_cast<uintptr_t>(eps) & (dtype == AFLDM_F32 ? 15 : 7)) == 0;
-  if (c4) {
-    DISPATCH_T(dtype,
-               (k_pano_step<float, 4><<<pano_grid(n / 4), 256, 0, st>>>(canvas, (const float*)eps, noise, noise_step_stride, wt,
-                                                                        canvas_out, windows_out, coef, step_idx, P, C, g)),
-               (k_pano_step<bf16, 4><<<pano_grid(n / 4), 256, 0, st>>>(canvas, (const bf16*)eps, noise, noise_step_stride, wt,
-                                                                       canvas_out, windows_out, coef, step_idx, P, C, g)),
-               "afldm_pano_step");
-  } else {
-    DISPATCH_T(dtype,
-               (k_pano_step<float, 1><<<pano_grid(n), 256, 0, st>>>(canvas, (const float*)eps, noise, noise_step_stride, wt,
-                                                                    canvas_out, windows_out, coef, step_idx, P, C, g)),
-               (k_pano_step<bf16, 1><<<pano_grid(n), 256, 0, st>>>(canvas, (const bf16*)eps, noise, noise_step_stride, wt, canvas_out,
-                                                                   windows_out, coef, step_idx, P, C, g)),
-               "afldm_pano_step");
-  }
-  if (advance) k_pano_advance<<<1, 1, 0, st>>>(step_idx);
+#define LAUNCH(T, CV)                                                                                               \
+  (k_pano_step<T, CV><<<step_grid(n / CV), 256, 0, st>>>(canvas, (const T*)eps, noise, noise_step_stride, wt, canvas_out, \
+                                                         windows_out, coef, step_idx, P, C, g))
+  STEP_DISPATCH(dtype, c4, LAUNCH, "afldm_pano_step");
+#undef LAUNCH
+  step_advance(advance, step_idx, st);
   return check_launch("afldm_pano_step");
 }
 
@@ -268,8 +248,8 @@ extern "C" int afldm_window_fuse(const void* windows, const float* wt, float* ca
   if (rc != AFLDM_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   const size_t n = (size_t)P * C * Hc * Wc;
-  DISPATCH_T(dtype, (k_window_fuse<float><<<pano_grid(n), 256, 0, st>>>((const float*)windows, wt, canvas, P, C, g)),
-             (k_window_fuse<bf16><<<pano_grid(n), 256, 0, st>>>((const bf16*)windows, wt, canvas, P, C, g)), "afldm_window_fuse");
+  DISPATCH_T(dtype, (k_window_fuse<float><<<step_grid(n), 256, 0, st>>>((const float*)windows, wt, canvas, P, C, g)),
+             (k_window_fuse<bf16><<<step_grid(n), 256, 0, st>>>((const bf16*)windows, wt, canvas, P, C, g)), "afldm_window_fuse");
   return check_launch("afldm_window_fuse");
 }
 
@@ -281,6 +261,6 @@ extern "C" int afldm_window_crop(const float* canvas, float* windows, int P, int
   const int rc = pano_check("afldm_window_crop", Hc, Wc, S, oy, ny, ox, nx, wrap_y, wrap_x, g);
   if (rc != AFLDM_OK) return rc;
   const size_t n = (size_t)P * ny * nx * C * S * S;
-  k_window_crop<<<pano_grid(n), 256, 0, (hipStream_t)stream>>>(canvas, windows, P, C, g);
+  k_window_crop<<<step_grid(n), 256, 0, (hipStream_t)stream>>>(canvas, windows, P, C, g);
   return check_launch("afldm_window_crop");
 }

@@ -11,7 +11,7 @@
 // generator outside the graph, as for sde.hip.  HBM-bound elementwise, laid out as sde.hip: every thread owns 4 consecutive
 // pixels of one (b, c) plane (16-byte loads of x / known / mask / z, stores of x_out), grid capped at 2048 blocks and grid-stride
 // beyond (guide G11).  Each thread reads and writes its own indices only, so x and x_out may alias.
-#include "common.hpp"
+#include "step_common.hpp"
 
 namespace afldm {
 
@@ -21,9 +21,6 @@ struct repaint_row {
   float p, q, lo, hi, a, b, c, k0, k1, u0, u1;
 };
 
-// clamp that keeps a NaN a NaN (as torch.clamp does); fmaxf / fminf would turn it into a bound.  lo = -inf, hi = +inf: no clip.
-__device__ __forceinline__ float clamp_nan(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // zk / zu / zb: 0 where the slot is not loaded (its coefficient is 0 then, and the product an exact 0)
 __device__ __forceinline__ float repaint_update(float x, float e, float kn, float m, float zk, float zu, float zb,
                                                 const repaint_row& r) {
@@ -32,42 +29,6 @@ __device__ __forceinline__ float repaint_update(float x, float e, float kn, floa
   const float knownp = r.k0 * kn + r.k1 * zk;
   const float y = m * knownp + (1.0f - m) * unknown;
   return r.u0 * y + r.u1 * zb;
-}
-
-template <int V>
-struct vecf {
-  float v[V];
-};
-
-template <int V>
-__device__ __forceinline__ vecf<V> ld(const float* p) {
-  vecf<V> r;
-  if constexpr (V == 4) {
-    f32x4 q = *reinterpret_cast<const f32x4*>(p);
-    r.v[0] = q[0]; r.v[1] = q[1]; r.v[2] = q[2]; r.v[3] = q[3];
-  } else {
-    r.v[0] = p[0];
-  }
-  return r;
-}
-
-template <int V>
-__device__ __forceinline__ vecf<V> ld_if(bool on, const float* p) {
-  if (on) return ld<V>(p);
-  vecf<V> r;
-#pragma unroll
-  for (int k = 0; k < V; ++k) r.v[k] = 0.0f;
-  return r;
-}
-
-template <int V>
-__device__ __forceinline__ void st(float* p, const vecf<V>& r) {
-  if constexpr (V == 4) {
-    f32x4 q = {r.v[0], r.v[1], r.v[2], r.v[3]};
-    *reinterpret_cast<f32x4*>(p) = q;
-  } else {
-    p[0] = r.v[0];
-  }
 }
 
 }  // namespace
@@ -91,12 +52,9 @@ __global__ void __launch_bounds__(256) k_repaint_step(const float* x, const T* _
   const size_t groups = n / V;
   for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (size_t)gridDim.x * blockDim.x) {
     const size_t i = g * V;
-    const int pix = (int)(i % HW);
-    const size_t plane = i / HW;
-    const int ch = (int)(plane % C);
-    const size_t b = plane / C;
-    const T* ep = eps + ((size_t)b * HW + pix) * C + ch;
-    const vecf<V> xv = ld<V>(x + i), kv = ld<V>(known + i), mv = ld<V>(mask + b * HW + pix);
+    const nchw_pos at = nchw_at(i, C, HW);
+    const T* ep = eps_at(eps, at, C, HW);
+    const vecf<V> xv = ld<V>(x + i), kv = ld<V>(known + i), mv = ld<V>(mask + at.b * HW + at.pix);
     const vecf<V> zkv = ld_if<V>(has_k, zk + i), zuv = ld_if<V>(has_u, zu + i), zbv = ld_if<V>(has_b, zb + i);
     vecf<V> o;
 #pragma unroll
@@ -129,8 +87,6 @@ __global__ void __launch_bounds__(256) k_repaint_step_flat(const float* x, const
     x_out[i] = repaint_update(x[i], eps[i], known[i], mask[i], has_k ? zk[i] : 0.0f, has_u ? zu[i] : 0.0f, has_b ? zb[i] : 0.0f, r);
 }
 
-__global__ void k_repaint_advance(int* step_idx) { *step_idx += 1; }
-
 // mask [B][1][H][W] -> out [B][1][H / r][W / r]: one thread per output, the r x r block under it.  MEAN = false: the minimum
 // (a latent is kept only if every pixel under it is); MEAN = true: the mean, summed in fp64 (correctly rounded for any r a mask
 // has) and rounded once.  A NaN in the block comes out as NaN in both modes.
@@ -160,11 +116,6 @@ __global__ void __launch_bounds__(256) k_mask_pool(const float* __restrict__ mas
   }
 }
 
-static inline int repaint_grid(size_t work) {
-  size_t g = (work + 255) / 256;
-  return (int)(g < 2048 ? (g ? g : 1) : 2048);
-}
-
 }  // namespace afldm
 
 using namespace afldm;
@@ -183,26 +134,12 @@ extern "C" int afldm_repaint_step(const float* x, const void* eps, const float* 
   // every slot starts a multiple of the two strides after the base: 16-byte groups need both % 4 == 0 too
   const bool v4 = HW % 4 == 0 && noise_step_stride % 4 == 0 && noise_slot_stride % 4 == 0 && aligned16(x) && aligned16(known) &&
                   aligned16(mask) && aligned16(x_out) && aligned16(noise);
-  if (v4) {
-    DISPATCH_T(dtype,
-               (k_repaint_step<float, 4><<<repaint_grid(n / 4), 256, 0, st>>>(x, (const float*)eps, known, mask, noise,
-                                                                              noise_step_stride, noise_slot_stride, x_out, coef,
-                                                                              step_idx, B, C, HW)),
-               (k_repaint_step<bf16, 4><<<repaint_grid(n / 4), 256, 0, st>>>(x, (const bf16*)eps, known, mask, noise,
-                                                                             noise_step_stride, noise_slot_stride, x_out, coef,
-                                                                             step_idx, B, C, HW)),
-               "afldm_repaint_step");
-  } else {
-    DISPATCH_T(dtype,
-               (k_repaint_step<float, 1><<<repaint_grid(n), 256, 0, st>>>(x, (const float*)eps, known, mask, noise,
-                                                                          noise_step_stride, noise_slot_stride, x_out, coef,
-                                                                          step_idx, B, C, HW)),
-               (k_repaint_step<bf16, 1><<<repaint_grid(n), 256, 0, st>>>(x, (const bf16*)eps, known, mask, noise,
-                                                                         noise_step_stride, noise_slot_stride, x_out, coef,
-                                                                         step_idx, B, C, HW)),
-               "afldm_repaint_step");
-  }
-  if (advance) k_repaint_advance<<<1, 1, 0, st>>>(step_idx);
+#define LAUNCH(T, V)                                                                                                \
+  (k_repaint_step<T, V><<<step_grid(n / V), 256, 0, st>>>(x, (const T*)eps, known, mask, noise, noise_step_stride, \
+                                                          noise_slot_stride, x_out, coef, step_idx, B, C, HW))
+  STEP_DISPATCH(dtype, v4, LAUNCH, "afldm_repaint_step");
+#undef LAUNCH
+  step_advance(advance, step_idx, st);
   return check_launch("afldm_repaint_step");
 }
 
@@ -219,9 +156,9 @@ extern "C" int afldm_repaint_step_flat(const float* x, const float* eps, const f
   const bool v4 = aligned16(x) && aligned16(eps) && aligned16(known) && aligned16(mask) && aligned16(x_out) &&
                   (k1 == 0.0f || aligned16(z_k)) && (c == 0.0f || aligned16(z_u)) && (u1 == 0.0f || aligned16(z_b));
   if (v4)
-    k_repaint_step_flat<4><<<repaint_grid(n / 4), 256, 0, st>>>(x, eps, known, mask, z_k, z_u, z_b, x_out, r, n);
+    k_repaint_step_flat<4><<<step_grid(n / 4), 256, 0, st>>>(x, eps, known, mask, z_k, z_u, z_b, x_out, r, n);
   else
-    k_repaint_step_flat<1><<<repaint_grid(n), 256, 0, st>>>(x, eps, known, mask, z_k, z_u, z_b, x_out, r, n);
+    k_repaint_step_flat<1><<<step_grid(n), 256, 0, st>>>(x, eps, known, mask, z_k, z_u, z_b, x_out, r, n);
   return check_launch("afldm_repaint_step_flat");
 }
 
@@ -235,8 +172,8 @@ extern "C" int afldm_mask_pool(const float* mask, float* out, int B, int H, int 
   const int Ho = H / r, Wo = W / r;
   const size_t total = (size_t)B * Ho * Wo;
   if (mode == AFLDM_MASK_MEAN)
-    k_mask_pool<true><<<repaint_grid(total), 256, 0, st>>>(mask, out, total, Ho, Wo, W, r);
+    k_mask_pool<true><<<step_grid(total), 256, 0, st>>>(mask, out, total, Ho, Wo, W, r);
   else
-    k_mask_pool<false><<<repaint_grid(total), 256, 0, st>>>(mask, out, total, Ho, Wo, W, r);
+    k_mask_pool<false><<<step_grid(total), 256, 0, st>>>(mask, out, total, Ho, Wo, W, r);
   return check_launch("afldm_mask_pool");
 }

@@ -6,7 +6,7 @@
 // sample is the eager loop's to fp32 rounding.  HBM-bound elementwise, laid out as dpm.hip: every thread owns 4
 // consecutive pixels of one (b, c) plane (16-byte loads of x / z, stores of x_out), grid capped at 2048 blocks and
 // grid-stride beyond (guide G11).  Each thread reads and writes its own indices only, so x and x_out may alias.
-#include "common.hpp"
+#include "step_common.hpp"
 
 namespace afldm {
 
@@ -15,9 +15,6 @@ namespace {
 struct sde_row {
   float p, q, lo, hi, a, b, d, c;
 };
-
-// clamp that keeps a NaN a NaN (as torch.clamp does); fmaxf / fminf would turn it into a bound.  lo = -inf, hi = +inf: no clip.
-__device__ __forceinline__ float clamp_nan(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 __device__ __forceinline__ float sde_update(float x, float e, float z, const sde_row& r) {
   const float x0 = clamp_nan(r.p * x + r.q * e, r.lo, r.hi);
@@ -39,11 +36,7 @@ __global__ void __launch_bounds__(256) k_sde_step(const float* x, const T* __res
   const size_t groups = n / V;
   for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (size_t)gridDim.x * blockDim.x) {
     const size_t i = g * V;
-    const int pix = (int)(i % HW);
-    const size_t plane = i / HW;
-    const int ch = (int)(plane % C);
-    const size_t b = plane / C;
-    const T* ep = eps + ((size_t)b * HW + pix) * C + ch;
+    const T* ep = eps_at(eps, nchw_at(i, C, HW), C, HW);
     if constexpr (V == 4) {
       const f32x4 xv = *reinterpret_cast<const f32x4*>(x + i);
       const f32x4 zv = *reinterpret_cast<const f32x4*>(z + i);
@@ -55,13 +48,6 @@ __global__ void __launch_bounds__(256) k_sde_step(const float* x, const T* __res
       x_out[i] = sde_update(x[i], to_f32(ep[0]), z[i], r);
     }
   }
-}
-
-__global__ void k_sde_advance(int* step_idx) { *step_idx += 1; }
-
-static inline int sde_grid(size_t work) {
-  size_t g = (work + 255) / 256;
-  return (int)(g < 2048 ? (g ? g : 1) : 2048);
 }
 
 }  // namespace afldm
@@ -79,21 +65,10 @@ extern "C" int afldm_sde_step(const float* x, const void* eps, const float* nois
   hipStream_t st = (hipStream_t)stream;
   // every noise row starts noise_step_stride floats after the previous one: 16-byte groups need that stride % 4 == 0 too
   const bool v4 = HW % 4 == 0 && noise_step_stride % 4 == 0 && aligned16(x) && aligned16(x_out) && aligned16(noise);
-  if (v4) {
-    DISPATCH_T(dtype,
-               (k_sde_step<float, 4><<<sde_grid(n / 4), 256, 0, st>>>(x, (const float*)eps, noise, noise_step_stride, x_out, coef,
-                                                                      step_idx, B, C, HW)),
-               (k_sde_step<bf16, 4><<<sde_grid(n / 4), 256, 0, st>>>(x, (const bf16*)eps, noise, noise_step_stride, x_out, coef,
-                                                                     step_idx, B, C, HW)),
-               "afldm_sde_step");
-  } else {
-    DISPATCH_T(dtype,
-               (k_sde_step<float, 1><<<sde_grid(n), 256, 0, st>>>(x, (const float*)eps, noise, noise_step_stride, x_out, coef,
-                                                                  step_idx, B, C, HW)),
-               (k_sde_step<bf16, 1><<<sde_grid(n), 256, 0, st>>>(x, (const bf16*)eps, noise, noise_step_stride, x_out, coef,
-                                                                 step_idx, B, C, HW)),
-               "afldm_sde_step");
-  }
-  if (advance) k_sde_advance<<<1, 1, 0, st>>>(step_idx);
+#define LAUNCH(T, V) \
+  (k_sde_step<T, V><<<step_grid(n / V), 256, 0, st>>>(x, (const T*)eps, noise, noise_step_stride, x_out, coef, step_idx, B, C, HW))
+  STEP_DISPATCH(dtype, v4, LAUNCH, "afldm_sde_step");
+#undef LAUNCH
+  step_advance(advance, step_idx, st);
   return check_launch("afldm_sde_step");
 }

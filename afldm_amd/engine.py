@@ -44,7 +44,14 @@ of batch B per step: the first with SAGAttnProcessor at one site, which also wri
 afldm_sag_degrade turns x, e and the mass into the second evaluation's input; both outputs land in `eps2` [2 B] and the step ends
 in afldm_pag_step, unchanged.
 
-cached_engine keeps the engines (and the harness's samplers) a pipeline has built: one resident entry per slot.
+Structure.  __init__ validates and stores its arguments; _allocate makes every device buffer and is what refresh_if_stale calls
+again after unet.to(dtype / device).  A kind is one entry of UPDATES - the update op of ops that ends a step, and a function that
+allocates what the kind keeps between steps and returns, per branch, the tensors the op takes between eps and the coefficient
+table.  Those functions share _noise (the one noise allocator: the slot count comes from schedule.KINDS, and _fill reads the row
+shape and slot layout it recorded), _slice (a branch's batch slice) and _static (the second tensor run(known=...) fills, with its
+broadcast rule).  A step is _eps (NCHW latents -> the UNet's output) and _apply (the update); a subclass overrides the half that
+differs.  cached_engine keeps the engines (and the harness's samplers) a pipeline has built, one resident entry per slot, and
+builds the key from the engine class and its own keyword arguments.
 """
 import contextlib
 import gc
@@ -53,7 +60,7 @@ import os
 import torch
 
 from . import ops
-from .schedulers.schedule import Schedule
+from .schedulers.schedule import KINDS, Schedule
 
 
 @contextlib.contextmanager
@@ -87,15 +94,19 @@ def model_state_key(model):
     return hash((mods, params, bufs))
 
 
-def cached_engine(owner, slot, schedule, batch, use_graph, unet, build=None, extra=()):
-    """The engine `owner` (a pipeline) keeps in its attribute `slot` for this schedule, batch, use_graph and the UNet's dtype and
-    device, built on a miss: DenoiseEngine(unet, schedule, batch, steps, use_graph), or build() for a slot that holds something
-    else (the harness's samplers; `extra`: what else identifies it).  A slot is a one-entry dict {key: engine}: a miss replaces
-    it, and with it the captured graphs and static buffers of the previous one.  Every field a graph bakes in must be in the key:
-    a missed one replays a stale graph."""
-    key = (batch, len(schedule.timesteps), use_graph, unet.dtype, str(unet.device)) + schedule.key + tuple(extra)
+def cached_engine(owner, slot, schedule, batch, use_graph, unet, cls=None, build=None, extra=(), **kw):
+    """The engine `owner` (a pipeline) keeps in its attribute `slot` for this schedule, batch, use_graph, the UNet's dtype and
+    device, the engine class `cls` (default DenoiseEngine) and that class's own keyword arguments `kw` (hashable: what else its
+    graphs bake in), built on a miss: cls(unet, schedule, batch, steps, use_graph, **kw).  A slot that holds something else (the
+    harness's samplers) passes build() and `extra`: what else identifies it.  A slot is a one-entry dict {key: engine}: a miss
+    replaces it, and with it the captured graphs and static buffers of the previous one.  Every field a graph bakes in must be
+    in the key: a missed one replays a stale graph."""
+    assert (not extra) if build is None else (cls is None and not kw), "cached_engine: either cls and its kw, or build= and extra="
+    cls = cls or DenoiseEngine
+    key = (batch, len(schedule.timesteps), use_graph, unet.dtype, str(unet.device)) + schedule.key
+    key += tuple(extra) if build is not None else (cls.__name__,) + tuple(sorted(kw.items()))
     if key not in owner.__dict__.get(slot, ()):
-        made = build() if build is not None else DenoiseEngine(unet, schedule, batch, len(schedule.timesteps), use_graph)
+        made = build() if build is not None else cls(unet, schedule, batch, len(schedule.timesteps), use_graph, **kw)
         owner.__dict__[slot] = {key: made}
     return owner.__dict__[slot][key]
 
@@ -113,40 +124,61 @@ class DenoiseEngine:
         if self.schedule.kind not in self.UPDATES:
             raise NotImplementedError(f"DenoiseEngine: update_kind {self.schedule.kind!r}")
         self.B, self.n = batch_size, num_inference_steps
-        dev = unet.device
-        c, s = unet.config.in_channels, unet.config.sample_size
         self.timesteps = list(self.schedule.timesteps)
-        self.t_table = torch.tensor(self.timesteps, dtype=torch.float32).to(dev)
-        self.coef = self.schedule.table(dev).reshape(-1).contiguous()
-        self.step_idx = torch.full((1,), -1, dtype=torch.int32, device=dev)
-        self.t_cur = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.lat = torch.zeros(batch_size, c, s, s, dtype=torch.float32, device=dev)
-        self.x_nhwc = torch.empty(batch_size, s, s, c, dtype=unet.dtype, device=dev)
-        self.graph = None
-        self.graph_multi = None
         # a replay boundary costs ~9 us of idle GPU (host launch + graph start): besides the one-step graph a
         # `steps_per_graph`-step graph is captured and used for every full group of steps
         self.steps_per_graph = max(1, int(os.environ.get("AFLDM_STEPS_PER_GRAPH", steps_per_graph)))
         self.use_graph = use_graph
-        self.kernels_per_step = None
+        nb = int(os.environ.get("AFLDM_BRANCHES", branches))
+        self.branches = nb if nb > 1 and batch_size % nb == 0 and not self.ONE_BRANCH else 1
+        if self.branches > 1:
+            from . import trunk
+            trunk.block("DenoiseEngine with parallel branches")      # (the experimental cooperative trunk needs the GPU to itself)
+        self._allocate()
+
+    def _allocate(self):
+        """Every device buffer, in the UNet's current dtype and on its device, and the kind's state; drops the graphs."""
+        unet, dev = self.unet, self.unet.device
+        c, s = unet.config.in_channels, unet.config.sample_size
+        self.t_table = torch.tensor(self.timesteps, dtype=torch.float32).to(dev)
+        self.coef = self.schedule.table(dev).reshape(-1).contiguous()
+        self.step_idx = torch.full((1,), -1, dtype=torch.int32, device=dev)
+        self.t_cur = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.lat = torch.zeros(self.B, c, s, s, dtype=torch.float32, device=dev)
+        self.x_nhwc = torch.empty(self.B, s, s, c, dtype=unet.dtype, device=dev)
+        self.graph = self.graph_multi = None
         # everything of the UNet that depends on the timestep only (time_proj -> time_embedding -> SiLU -> the 27
         # time_emb_proj layers) is tabulated once for the schedule: [steps, sum Cout]; a step copies its row
         self.temb_table = torch.cat([unet.temb_projection(t) for t in self.timesteps], 0).contiguous()
         self.temb_row = torch.empty_like(self.temb_table[:1])
         self.temb_slices = unet.temb_slices(self.temb_row)
         self._model_key = model_state_key(unet)
-        nb = int(os.environ.get("AFLDM_BRANCHES", branches))
-        self.branches = nb if nb > 1 and batch_size % nb == 0 and not self.ONE_BRANCH else 1
         self._side = [torch.cuda.Stream() for _ in range(self.branches - 1)]
-        if self.branches > 1:
-            from . import trunk
-            trunk.block("DenoiseEngine with parallel branches")      # (the experimental cooperative trunk needs the GPU to itself)
         # counters of in-kernel reductions / cluster hand-overs: private to this engine (one per branch), so that its
         # captured graphs can replay next to another engine's on a different stream (ADVICE r04)
         self._sync = [ops.new_sync_buffer(dev) for _ in range(self.branches)]
-        self.hist = self.noise = self.known = self.mask = self.filter = None
+        self.hist = self.noise = self.known = self.mask = self.filter = self._static = None
         self._update, state = self.UPDATES[self.schedule.kind]
         self._state = state(self)
+
+    def _slice(self, b, *tensors, dim=0):
+        """Branch b's batch slice (the batch at `dim`) of each of `tensors`; with one branch, the tensors themselves."""
+        per = self.B // self.branches
+        return tensors if self.branches == 1 else tuple(t.narrow(dim, b * per, per) for t in tensors)
+
+    def _noise(self, row_shape, only_if_drawn=False):
+        """The one noise allocator: an fp32 buffer [steps, *row_shape], or [steps, slots, *row_shape] for a kind of several slots
+        (KINDS), filled per run by _fill; what is not drawn keeps zeros and is not read (its coefficient is 0, and 0 * NaN of
+        stale memory is not 0).  only_if_drawn: no buffer when no step of the schedule draws (the update then gets no noise
+        pointer).  Records the row shape and the slot count for _fill and sets up the pinned staging for CPU draws (one buffer
+        per replay group in flight).  Returns one entry per branch: its batch slice of the buffer, or None."""
+        slots = KINDS[self.schedule.kind][1]
+        self._row, self._stage = (tuple(row_shape), slots), []
+        if only_if_drawn and not any(self.schedule.draws):
+            return [None] * self.branches
+        self.noise = torch.zeros((self.n,) + ((slots,) if slots > 1 else ()) + tuple(row_shape), dtype=torch.float32,
+                                 device=self.lat.device)
+        return [self._slice(b, self.noise, dim=1 + (slots > 1))[0] for b in range(self.branches)]
 
     def _no_state(self):
         return [()] * self.branches
@@ -158,44 +190,33 @@ class DenoiseEngine:
         return [(self.hist[b],) for b in range(self.branches)]
 
     def _sde_state(self):
-        """One noise row per step, filled per run; the steps that draw none keep zeros (c = 0 there, and 0 * NaN of stale memory
-        is not 0).  Pinned staging for CPU draws, one buffer per replay group in flight."""
-        self.noise = torch.zeros((self.n,) + tuple(self.lat.shape), dtype=torch.float32, device=self.lat.device)
-        self._stage = []
-        per = self.B // self.branches
-        return [(self.noise[:, b * per:(b + 1) * per],) for b in range(self.branches)]
+        """One noise row per step."""
+        return [(z,) for z in self._noise(self.lat.shape)]
 
     def _repaint_state(self):
-        """Three noise slots per step (z_k, z_u, z_b), filled per run like the "sde" rows - a slot that is not drawn keeps zeros and is
-        not read - and the run's known latents and latent mask.  Every branch takes its batch slice of all three."""
-        self.noise = torch.zeros((self.n, 3) + tuple(self.lat.shape), dtype=torch.float32, device=self.lat.device)
+        """Three noise slots per step (z_k, z_u, z_b) and the run's known latents and latent mask (a batch-1 mask is broadcast).
+        Every branch takes its batch slice of all three."""
         self.known = torch.zeros_like(self.lat)
         self.mask = torch.zeros((self.B, 1) + tuple(self.lat.shape[2:]), dtype=torch.float32, device=self.lat.device)
-        self._stage = []
-        per = self.B // self.branches
-        return [(self.known[b * per:(b + 1) * per], self.mask[b * per:(b + 1) * per], self.noise[:, :, b * per:(b + 1) * per])
-                for b in range(self.branches)]
+        self._static = ("mask", self.mask, True)
+        return [self._slice(b, self.known, self.mask) + (z,) for b, z in enumerate(self._noise(self.lat.shape))]
 
     def _ilvr_state(self):
-        """Two noise slots per step (z_k, z_u), filled per run like the "repaint" ones, the run's reference latents and its
-        [S, S] low-pass matrix (used for both axes).  Every branch takes its batch slice of the reference and the noise; the
-        filter is shared."""
-        self.noise = torch.zeros((self.n, 2) + tuple(self.lat.shape), dtype=torch.float32, device=self.lat.device)
+        """Two noise slots per step (z_k, z_u), the run's reference latents and its [S, S] low-pass matrix (used for both axes).
+        Every branch takes its batch slice of the reference and the noise; the filter is shared."""
         self.known = torch.zeros_like(self.lat)
         self.filter = torch.zeros(tuple(self.lat.shape[2:]), dtype=torch.float32, device=self.lat.device)
-        self._stage = []
-        per = self.B // self.branches
-        return [(self.known[b * per:(b + 1) * per], self.noise[:, :, b * per:(b + 1) * per], self.filter, self.filter)
-                for b in range(self.branches)]
+        self._static = ("filter", self.filter, False)
+        return [self._slice(b, self.known) + (z, self.filter, self.filter) for b, z in enumerate(self._noise(self.lat.shape))]
 
-    # Schedule.kind -> the update of ops that ends a step, and what allocates the buffers it keeps between steps (one argument
-    # tuple per branch, passed between eps and the coefficient table)
+    def _guided_state(self):
+        """One noise row per step, only when some step draws (eta != 0): "pag" and "sag"."""
+        return [(z,) for z in self._noise(self.lat.shape, only_if_drawn=True)]
+
+    # Schedule.kind -> the update of ops that ends a step, and what allocates the buffers it keeps between steps: it returns one
+    # argument tuple per branch, passed between eps and the coefficient table, and sets _static where run() takes known=
     UPDATES = {"ddim": (ops.ddim_step, _no_state), "dpm": (ops.dpm_step, _dpm_state), "sde": (ops.sde_step, _sde_state),
                "repaint": (ops.repaint_step, _repaint_state), "ilvr": (ops.ilvr_step, _ilvr_state)}
-
-    # the kinds whose run() takes known=(latents, second tensor): the attribute that holds the second tensor's static buffer
-    # (its name in messages too), and whether a batch-1 one is broadcast
-    KNOWN = {"repaint": ("mask", True), "ilvr": ("filter", False)}
 
     # one denoise step, entirely stream-ordered
     def _step(self):
@@ -210,20 +231,26 @@ class DenoiseEngine:
         # of the large convolutions (one tile per CU: nothing inside a launch overlaps them) and the latency-bound
         # launches of the 8x8 .. 2x2 levels.
         main = torch.cuda.current_stream()
-        per = self.B // nb
         for i, s in enumerate(self._side):
             s.wait_stream(main)
             with torch.cuda.stream(s):
-                self._substep(self.lat[(i + 1) * per:(i + 2) * per], self.x_nhwc[(i + 1) * per:(i + 2) * per], branch=i + 1)
-        self._substep(self.lat[:per], self.x_nhwc[:per])
+                self._substep(*self._slice(i + 1, self.lat, self.x_nhwc), branch=i + 1)
+        self._substep(*self._slice(0, self.lat, self.x_nhwc))
         for s in self._side:
             main.wait_stream(s)
 
     def _substep(self, lat, x_nhwc, branch=0):
         with ops.sync_scope(self._sync[branch]):
-            ops.to_nhwc(lat, self.unet.dtype, out=x_nhwc)
-            eps = self.unet.forward_nhwc(x_nhwc, self.t_cur, temb_slices=self.temb_slices)
-            self._update(lat, eps, *self._state[branch], self.coef, self.step_idx, advance=False, out=lat)
+            self._apply(lat, self._eps(lat, x_nhwc), branch)
+
+    def _eps(self, lat, x_nhwc):
+        """The first half of a step: the NCHW fp32 latents through `x_nhwc` to the UNet's output (NHWC, the model's dtype)."""
+        ops.to_nhwc(lat, self.unet.dtype, out=x_nhwc)
+        return self.unet.forward_nhwc(x_nhwc, self.t_cur, temb_slices=self.temb_slices)
+
+    def _apply(self, lat, eps, branch):
+        """The second half: the kind's update, in place."""
+        self._update(lat, eps, *self._state[branch], self.coef, self.step_idx, advance=False, out=lat)
 
     def _capture(self, counts, before_step=None):
         """One captured graph per entry of `counts`, each holding that many steps from the start of the schedule, after ONE
@@ -264,10 +291,6 @@ class DenoiseEngine:
         """The buffers a step reads and overwrites: what _capture puts back after its warm-up step and its captures."""
         return [self.lat] + ([] if self.hist is None else [self.hist])
 
-    def _noise_row_shape(self):
-        """The shape of one draw: a noise row's, whatever precedes it in the buffer ([steps] or [steps, slots])."""
-        return tuple(self.noise.shape[-self.lat.dim():])
-
     def _result(self):
         return self.lat.clone()
 
@@ -301,9 +324,7 @@ class DenoiseEngine:
         if self.unet.dtype != self.x_nhwc.dtype or self.unet.device != self.x_nhwc.device:
             # .to(dtype / device): every dtype-typed static buffer of the engine is stale, not just the table
             invalidate_stale_packed(self.unet)
-            scheduler = self.scheduler
-            self.__init__(self.unet, self.schedule, self.B, self.n, self.use_graph, self.steps_per_graph, self.branches)
-            self.scheduler = scheduler
+            self._allocate()
             return True
         self.graph = self.graph_multi = None
         # in-place parameter edits do not pass through the modules' own hooks; another engine of this model may have repacked
@@ -342,9 +363,8 @@ class DenoiseEngine:
         z_u, z_b, "ilvr": up to two - z_k, z_u), in step and slot order.  A CPU draw is copied into pinned staging and on to the
         device with non_blocking (stream-ordered before the replays that read it); the staging buffer is reused only after the
         event behind its previous copy has passed.  A device draw is copied on the stream."""
-        shape = self._noise_row_shape()                        # ("pano": the canvas's, not lat's)
-        slots = self.noise.dim() - self.lat.dim() - 1          # 0: one row per step ("sde"); 1: [steps, slots, ...] ("repaint", "ilvr")
-        rows = [self.noise[k, j] if slots else self.noise[k] for k in range(k0, k1) for j in self.schedule.slots(k)]
+        shape, slots = self._row                               # as _noise allocated ("pano": the canvas's shape, not lat's)
+        rows = [self.noise[k, j] if slots > 1 else self.noise[k] for k in range(k0, k1) for j in self.schedule.slots(k)]
         if not rows:
             return
         stage = None
@@ -357,8 +377,7 @@ class DenoiseEngine:
                 continue
             if stage is None:
                 if len(self._stage) < 2:
-                    per_step = self.noise.shape[1] if slots else 1
-                    self._stage.append((torch.empty((self.steps_per_graph * per_step,) + shape,
+                    self._stage.append((torch.empty((self.steps_per_graph * slots,) + shape,
                                                     dtype=torch.float32, pin_memory=True), torch.cuda.Event()))
                     stage = self._stage[-1]
                 else:
@@ -377,23 +396,22 @@ class DenoiseEngine:
         slot) order - for a seeded run, the scheduler's own randn_tensor call with the caller's generator (Schedule.drawer).
         A "repaint" schedule also needs known = (z0, mask): the latents to keep [B, C, H, W] and the latent mask [B | 1, 1, H, W]
         (1 = keep), an "ilvr" schedule known = (ref, L): the reference latents [B, C, H, W] and the low-pass matrix [H, H].
-        Both are written to the engine's static buffers before the first replay."""
-        entry = self.KNOWN.get(self.schedule.kind)
-        if (entry is None) != (known is None):
+        Both are written to the engine's static buffers before the first replay.  `draw` is ignored when the engine has no noise
+        buffer (a "pano", "pag" or "sag" schedule none of whose steps draws, "ddim", "dpm")."""
+        if (self._static is None) != (known is None):
             raise ValueError("DenoiseEngine: known=(z0, mask) goes with a 'repaint' schedule and known=(ref, L) with an 'ilvr' "
                              "one, and only with those")
         if known is not None:
-            name, broadcast = entry
-            second = getattr(self, name)
+            name, second, broadcast = self._static
             fits = [tuple(second.shape)] + ([(1,) + tuple(second.shape[1:])] if broadcast else [])
             z0, extra = known
             if tuple(z0.shape) != tuple(self.lat.shape) or tuple(extra.shape) not in fits:
                 raise ValueError(f"DenoiseEngine: known latents {tuple(z0.shape)} / {name} {tuple(extra.shape)}, want "
                                  f"{tuple(self.lat.shape)} / {tuple(second.shape)}" + (" (or batch 1)" if broadcast else ""))
         self.reset(latents)
-        if known is not None:
+        if known is not None:          # (after reset: a dtype or device change re-allocates the static buffers)
             self.known.copy_(z0)
-            second.copy_(extra)
+            self._static[1].copy_(extra)
         if self.noise is None:
             self.step(self.n)
         else:
@@ -418,39 +436,32 @@ class PanoramaEngine(DenoiseEngine):
     `geometry` (panorama.Geometry) - batch_size = P * nwin window planes in `lat`, window k of canvas P at entry P * nwin + k.
     A step is the plain sampler's launch list with afldm_pano_step in place of afldm_sde_step.  reset(canvas) writes the canvas and
     crops the windows; run(canvas, draw=...) returns the final canvas, and needs `draw` (canvas-shaped) only when a step draws.
-    The geometry is baked into the captured graphs: it belongs in the cache key (cached_engine(..., extra=(geometry,)))."""
+    The geometry is baked into the captured graphs."""
     ONE_BRANCH = True           # the update reads all windows of a canvas
 
-    def __init__(self, unet, scheduler, batch_size, num_inference_steps=50, use_graph=True, steps_per_graph=5, branches=1,
-                 geometry=None):
-        geometry = geometry if geometry is not None else getattr(self, "geometry", None)      # (refresh_if_stale re-runs __init__)
+    def __init__(self, unet, scheduler, batch_size, num_inference_steps=50, use_graph=True, steps_per_graph=5, branches=1, *,
+                 geometry):
         if geometry is None:
             raise ValueError("PanoramaEngine needs a panorama.Geometry")
-        c, s = unet.config.in_channels, unet.config.sample_size
+        s = unet.config.sample_size
         if geometry.S != s or batch_size % geometry.nwin:
             raise ValueError(f"PanoramaEngine: windows of {geometry.S} for a UNet of sample_size {s}, batch {batch_size} for "
                              f"{geometry.nwin} windows per canvas")
         self.geometry, self.P = geometry, batch_size // geometry.nwin
-        self.canvas = torch.zeros(self.P, c, geometry.Hc, geometry.Wc, dtype=torch.float32, device=unet.device)
-        self.wt = torch.ones(s, s, dtype=torch.float32, device=unet.device)      # MultiDiffusion's plain count average
         super().__init__(unet, scheduler, batch_size, num_inference_steps, use_graph, steps_per_graph, 1)
 
     def _pano_state(self):
-        """One canvas-shaped noise row per step, filled per run - only when some step draws (eta != 0); the steps that draw none
-        keep zeros and are not read (c = 0 there)."""
-        if any(self.schedule.draws):
-            self.noise = torch.zeros((self.n,) + tuple(self.canvas.shape), dtype=torch.float32, device=self.canvas.device)
-            self._stage = []
-        return [(self.noise, self.wt, self.geometry)]
+        """The fp32 canvas, MultiDiffusion's plain count average as the window weight, and one canvas-shaped noise row per step,
+        only when some step draws (eta != 0)."""
+        g, dev = self.geometry, self.unet.device
+        self.canvas = torch.zeros(self.P, self.lat.shape[1], g.Hc, g.Wc, dtype=torch.float32, device=dev)
+        self.wt = torch.ones(g.S, g.S, dtype=torch.float32, device=dev)
+        return [(self._noise(self.canvas.shape, only_if_drawn=True)[0], self.wt, g)]
 
     UPDATES = {"pano": (ops.pano_step, _pano_state)}
 
-    def _substep(self, lat, x_nhwc, branch=0):
-        with ops.sync_scope(self._sync[branch]):
-            ops.to_nhwc(lat, self.unet.dtype, out=x_nhwc)
-            eps = self.unet.forward_nhwc(x_nhwc, self.t_cur, temb_slices=self.temb_slices)
-            self._update(self.canvas, eps, *self._state[branch], self.coef, self.step_idx, advance=False, out=self.canvas,
-                         windows_out=lat)
+    def _apply(self, lat, eps, branch):
+        self._update(self.canvas, eps, *self._state[branch], self.coef, self.step_idx, advance=False, out=self.canvas, windows_out=lat)
 
     def _carried(self):
         return [self.lat, self.canvas]
@@ -491,39 +502,28 @@ class PAGEngine(DenoiseEngine):
     attention blocks at `sites` (names as the keys of get_unet_attn_processors) use the identity attention map.  A step is the
     plain sampler's launch list at batch 2 B with afldm_pag_step in place of afldm_sde_step.  PAGAttnProcessor is installed on
     the sites around every warm-up, capture and eager step and the previous processors are put back afterwards, also on an
-    exception: outside a call the UNet is as it was found.  The sites are baked into the captured graphs: they belong in the
-    cache key (cached_engine(..., extra=(sites,)))."""
+    exception: outside a call the UNet is as it was found.  The sites are baked into the captured graphs."""
     ONE_BRANCH = True           # the update reads both halves of eps
 
-    def __init__(self, unet, scheduler, batch_size, num_inference_steps=50, use_graph=True, steps_per_graph=5, branches=1,
-                 sites=None):
-        sites = sites if sites is not None else getattr(self, "sites", None)      # (refresh_if_stale re-runs __init__)
+    def __init__(self, unet, scheduler, batch_size, num_inference_steps=50, use_graph=True, steps_per_graph=5, branches=1, *, sites):
         if sites is None:
             raise ValueError("PAGEngine needs the attention sites to perturb")
         self.sites = tuple(sites)
         super().__init__(unet, scheduler, batch_size, num_inference_steps, use_graph, steps_per_graph, 1)
-        self.x_nhwc = torch.empty((2 * batch_size,) + tuple(self.x_nhwc.shape[1:]), dtype=unet.dtype, device=unet.device)
 
-    def _pag_state(self):
-        """One noise row per step, filled per run - only when some step draws (eta != 0); without, the update gets no noise
-        pointer and reads none (c = 0 in every row)."""
-        if any(self.schedule.draws):
-            self.noise = torch.zeros((self.n,) + tuple(self.lat.shape), dtype=torch.float32, device=self.lat.device)
-            self._stage = []
-        return [(self.noise,)]
+    def _allocate(self):
+        super()._allocate()
+        self.x_nhwc = torch.empty((2 * self.B,) + tuple(self.x_nhwc.shape[1:]), dtype=self.unet.dtype, device=self.unet.device)
 
-    UPDATES = {"pag": (ops.pag_step, _pag_state)}
+    UPDATES = {"pag": (ops.pag_step, DenoiseEngine._guided_state)}
 
     def perturbed(self):
         return pag_processors(self.unet, self.sites)
 
-    def _substep(self, lat, x_nhwc, branch=0):
-        B = self.B
-        with ops.sync_scope(self._sync[branch]):
-            ops.to_nhwc(lat, self.unet.dtype, out=x_nhwc[:B])
-            ops.to_nhwc(lat, self.unet.dtype, out=x_nhwc[B:])
-            eps2 = self.unet.forward_nhwc(x_nhwc, self.t_cur, temb_slices=self.temb_slices)
-            self._update(lat, eps2, *self._state[branch], self.coef, self.step_idx, advance=False, out=lat)
+    def _eps(self, lat, x_nhwc):
+        ops.to_nhwc(lat, self.unet.dtype, out=x_nhwc[:self.B])
+        ops.to_nhwc(lat, self.unet.dtype, out=x_nhwc[self.B:])
+        return self.unet.forward_nhwc(x_nhwc, self.t_cur, temb_slices=self.temb_slices)
 
     def _capture(self, counts, before_step=None):
         with self.perturbed():
@@ -534,11 +534,6 @@ class PAGEngine(DenoiseEngine):
             return super().step(k)          # replays only: the graphs hold the perturbed launch list
         with self.perturbed():
             super().step(k)
-
-    def run(self, latents, draw=None):
-        if self.noise is None:
-            draw = None
-        return super().run(latents, draw=draw)
 
 
 @contextlib.contextmanager
@@ -562,15 +557,11 @@ class SAGEngine(DenoiseEngine):
     model dtype); forward_nhwc with the processors as found; both outputs in `eps2` [2 B, H, W, C]; afldm_pag_step.  The second
     evaluation depends on the first, so the two cannot share a batch (PAGEngine's can).  The processor is installed around every
     warm-up, capture and eager step and the one found is put back afterwards, also on an exception: outside a call the UNet is
-    as it was found.  Site, taps and boundary are baked into the captured graphs: they belong in the cache key
-    (cached_engine(..., extra=(site, taps, boundary)))."""
+    as it was found.  Site, taps and boundary are baked into the captured graphs."""
     ONE_BRANCH = True           # the update reads both halves of eps2
 
-    def __init__(self, unet, scheduler, batch_size, num_inference_steps=50, use_graph=True, steps_per_graph=5, branches=1,
-                 site=None, taps=None, boundary=None):
-        site = site if site is not None else getattr(self, "site", None)      # (refresh_if_stale re-runs __init__)
-        taps = taps if taps is not None else getattr(self, "taps", None)
-        boundary = boundary if boundary is not None else getattr(self, "boundary", None)
+    def __init__(self, unet, scheduler, batch_size, num_inference_steps=50, use_graph=True, steps_per_graph=5, branches=1, *,
+                 site, taps, boundary):
         if site is None or taps is None or boundary is None:
             raise ValueError("SAGEngine needs the attention site, the blur taps and the boundary")
         mod = dict(unet.named_modules()).get(site)
@@ -578,34 +569,23 @@ class SAGEngine(DenoiseEngine):
             raise ValueError(f"SAGEngine: {site!r} names no attention module")
         self.site, self.taps, self.boundary = site, tuple(float(t) for t in taps), boundary
         super().__init__(unet, scheduler, batch_size, num_inference_steps, use_graph, steps_per_graph, 1)
+
+    def _allocate(self):
+        super()._allocate()
         self.mass = None            # [B, T] fp32, made by the warm-up (or first eager) step, which knows the site's T
-        self.eps2 = torch.zeros((2 * batch_size,) + tuple(self.x_nhwc.shape[1:]), dtype=unet.dtype, device=unet.device)
+        self.eps2 = torch.zeros((2 * self.B,) + tuple(self.x_nhwc.shape[1:]), dtype=self.unet.dtype, device=self.unet.device)
 
-    def _sag_state(self):
-        """One noise row per step, filled per run - only when some step draws (eta != 0); without, the update gets no noise
-        pointer and reads none (c = 0 in every row)."""
-        if any(self.schedule.draws):
-            self.noise = torch.zeros((self.n,) + tuple(self.lat.shape), dtype=torch.float32, device=self.lat.device)
-            self._stage = []
-        return [(self.noise,)]
+    UPDATES = {"sag": (ops.pag_step, DenoiseEngine._guided_state)}
 
-    UPDATES = {"sag": (ops.pag_step, _sag_state)}
-
-    def _substep(self, lat, x_nhwc, branch=0):
+    def _eps(self, lat, x_nhwc):
         B = self.B
-        with ops.sync_scope(self._sync[branch]):
-            ops.to_nhwc(lat, self.unet.dtype, out=x_nhwc)
-            with sag_processor(self.unet, self.site, self.mass) as proc:
-                e = self.unet.forward_nhwc(x_nhwc, self.t_cur, temb_slices=self.temb_slices)
-            if proc.mass is None:
-                raise RuntimeError(f"SAGEngine: the attention module {self.site!r} was not evaluated")
-            self.mass = proc.mass       # (the first step outside a capture makes it; from then on the processor writes into it)
-            self.eps2[:B].copy_(e)
-            ops.sag_degrade(lat, self.eps2[:B], self.mass, self.taps, self.boundary, self.coef, self.step_idx, out=x_nhwc)
-            self.eps2[B:].copy_(self.unet.forward_nhwc(x_nhwc, self.t_cur, temb_slices=self.temb_slices))
-            self._update(lat, self.eps2, *self._state[branch], self.coef, self.step_idx, advance=False, out=lat)
-
-    def run(self, latents, draw=None):
-        if self.noise is None:
-            draw = None
-        return super().run(latents, draw=draw)
+        ops.to_nhwc(lat, self.unet.dtype, out=x_nhwc)
+        with sag_processor(self.unet, self.site, self.mass) as proc:
+            e = self.unet.forward_nhwc(x_nhwc, self.t_cur, temb_slices=self.temb_slices)
+        if proc.mass is None:
+            raise RuntimeError(f"SAGEngine: the attention module {self.site!r} was not evaluated")
+        self.mass = proc.mass       # (the first step outside a capture makes it; from then on the processor writes into it)
+        self.eps2[:B].copy_(e)
+        ops.sag_degrade(lat, self.eps2[:B], self.mass, self.taps, self.boundary, self.coef, self.step_idx, out=x_nhwc)
+        self.eps2[B:].copy_(self.unet.forward_nhwc(x_nhwc, self.t_cur, temb_slices=self.temb_slices))
+        return self.eps2

@@ -3,6 +3,7 @@ of device memory and streams; every op below is one or two HIP kernel launches f
 libafldm_hip.so on torch's current stream.  All activations are NHWC ([B, H, W, C]) or
 token-major ([B, T, C]) contiguous CUDA tensors in fp32 or bf16.  CPU tensors raise."""
 import ctypes
+import math
 import os
 
 import torch
@@ -1470,20 +1471,45 @@ def dpm_step_flat(x, eps, hist, row, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- the step updates' shared checks
+def _noise_view(noise, row_shape, slots=None):
+    """The noise view of a step update: on the device, fp32, [steps, *row_shape] (slots None) or [steps, slots, *row_shape], each row
+    contiguous and the rows (and slots) not overlapping - a batch slice of a larger buffer is fine.  Returns the pointer and
+    the strides to pass on: (ptr, step stride) or (ptr, step stride, slot stride)."""
+    if not noise.is_cuda:
+        raise RuntimeError("afldm_amd: noise must live on an MI355X (cuda) device; there is no CPU path")
+    lead, n = (() if slots is None else (slots,)), math.prod(row_shape)
+    assert noise.dtype == torch.float32 and noise.dim() == 1 + len(lead) + len(row_shape)
+    assert tuple(noise.shape[1:]) == lead + tuple(row_shape)
+    assert noise[(0,) * (1 + len(lead))].is_contiguous() and noise.stride(len(lead)) >= n
+    if slots is None:
+        return ptr(noise), noise.stride(0)
+    assert noise.stride(0) >= (slots - 1) * noise.stride(1) + n
+    return ptr(noise), noise.stride(0), noise.stride(1)
+
+
+def _slot_tensors(name, x, noises, coefs, names, contiguous=False):
+    """The *_step_flat rule for optional noise slots: a None slot must have a zero coefficient; the others are fp32 device tensors
+    shaped like x."""
+    for z, c, zname in zip(noises, coefs, names):
+        if z is None:
+            if c != 0.0:
+                raise ValueError(f"{name}: {zname} is None but its coefficient is {c}")
+            continue
+        _dev(z, zname)
+        assert z.dtype == torch.float32 and z.shape == x.shape and (z.is_contiguous() or not contiguous)
+
+
 # ----------------------------------------------------------------------------- stochastic update (DDIM eta != 0, I2SB bridge)
 def sde_step(x, eps_nhwc, noise, coef, step_idx, advance=False, out=None):
     """x NCHW fp32 [B, C, H, W], eps NHWC dtype; noise: fp32 view [steps, B, C, H, W] whose last four dimensions are contiguous
     (a batch slice of a larger buffer is fine: the row stride is noise.stride(0)); coef float[8*nsteps] rows
     (p, q, lo, hi, a, b, d, c) and step_idx int32[1] on device."""
     _dev(x, "x"); _dev(eps_nhwc, "eps")
-    if not noise.is_cuda:
-        raise RuntimeError("afldm_amd: noise must live on an MI355X (cuda) device; there is no CPU path")
     B, C, H, W = x.shape
-    assert noise.dtype == torch.float32 and noise.dim() == 5 and tuple(noise.shape[1:]) == (B, C, H, W)
-    assert noise[0].is_contiguous() and noise.stride(0) >= B * C * H * W
     if out is None:
         out = torch.empty_like(x)
-    check(lib.afldm_sde_step(ptr(x), ptr(eps_nhwc), ptr(noise), noise.stride(0), ptr(out), ptr(coef), ptr(step_idx),
+    check(lib.afldm_sde_step(ptr(x), ptr(eps_nhwc), *_noise_view(noise, x.shape), ptr(out), ptr(coef), ptr(step_idx),
                              int(advance), B, C, H, W, _code(eps_nhwc), stream_ptr()), "sde_step")
     return out
 
@@ -1495,18 +1521,13 @@ def repaint_step(x, eps_nhwc, known, mask, noise, coef, step_idx, advance=False,
     noise.stride(0) and noise.stride(1)); coef float[12*nsteps] rows (p, q, lo, hi, a, b, c, k0, k1, u0, u1, 0) and step_idx
     int32[1] on device."""
     _dev(x, "x"); _dev(eps_nhwc, "eps"); _dev(known, "known"); _dev(mask, "mask")
-    if not noise.is_cuda:
-        raise RuntimeError("afldm_amd: noise must live on an MI355X (cuda) device; there is no CPU path")
     B, C, H, W = x.shape
     assert x.dtype == known.dtype == mask.dtype == torch.float32 and known.shape == x.shape and tuple(mask.shape) == (B, 1, H, W)
-    assert noise.dtype == torch.float32 and noise.dim() == 6 and tuple(noise.shape[1:]) == (3, B, C, H, W)
-    assert noise[0, 0].is_contiguous() and noise.stride(1) >= B * C * H * W
-    assert noise.stride(0) >= 2 * noise.stride(1) + B * C * H * W
+    noise_args = _noise_view(noise, x.shape, 3)
     if out is None:
         out = torch.empty_like(x)
-    check(lib.afldm_repaint_step(ptr(x), ptr(eps_nhwc), ptr(known), ptr(mask), ptr(noise), noise.stride(0), noise.stride(1),
-                                 ptr(out), ptr(coef), ptr(step_idx), int(advance), B, C, H, W, _code(eps_nhwc), stream_ptr()),
-          "repaint_step")
+    check(lib.afldm_repaint_step(ptr(x), ptr(eps_nhwc), ptr(known), ptr(mask), *noise_args, ptr(out), ptr(coef), ptr(step_idx),
+                                 int(advance), B, C, H, W, _code(eps_nhwc), stream_ptr()), "repaint_step")
     return out
 
 
@@ -1517,13 +1538,7 @@ def repaint_step_flat(x, eps, known, mask, noises, row, out=None):
     assert x.dtype == eps.dtype == known.dtype == mask.dtype == torch.float32
     assert x.shape == eps.shape == known.shape == mask.shape
     row = [float(c) for c in row[:11]]
-    for z, c, name in zip(noises, (row[8], row[6], row[10]), ("z_k", "z_u", "z_b")):
-        if z is None:
-            if c != 0.0:
-                raise ValueError(f"repaint_step_flat: {name} is None but its coefficient is {c}")
-            continue
-        _dev(z, name)
-        assert z.dtype == torch.float32 and z.shape == x.shape
+    _slot_tensors("repaint_step_flat", x, noises, (row[8], row[6], row[10]), ("z_k", "z_u", "z_b"))
     if out is None:
         out = torch.empty_like(x)
     check(lib.afldm_repaint_step_flat(ptr(x), ptr(eps), ptr(known), ptr(mask), *[ptr(z) for z in noises], ptr(out), *row,
@@ -1568,18 +1583,14 @@ def ilvr_step(x, eps_nhwc, ref, noise, Lh, Lw, coef, step_idx, advance=False, ou
     is fine: the strides are noise.stride(0) and noise.stride(1)); coef float[12*nsteps] rows (p, q, lo, hi, a, b, c, k0, k1, w,
     0, 0) and step_idx int32[1] on device."""
     _dev(x, "x"); _dev(eps_nhwc, "eps"); _dev(ref, "ref")
-    if not noise.is_cuda:
-        raise RuntimeError("afldm_amd: noise must live on an MI355X (cuda) device; there is no CPU path")
     _ilvr_plane("ilvr_step", x, Lh, Lw)
     B, C, H, W = x.shape
     assert ref.dtype == torch.float32 and ref.shape == x.shape and x.is_contiguous() and ref.is_contiguous()
     assert tuple(eps_nhwc.shape) == (B, H, W, C) and eps_nhwc.is_contiguous()
-    assert noise.dtype == torch.float32 and noise.dim() == 6 and tuple(noise.shape[1:]) == (2, B, C, H, W)
-    assert noise[0, 0].is_contiguous() and noise.stride(1) >= B * C * H * W
-    assert noise.stride(0) >= noise.stride(1) + B * C * H * W
+    noise_args = _noise_view(noise, x.shape, 2)
     if out is None:
         out = torch.empty_like(x)
-    check(lib.afldm_ilvr_step(ptr(x), ptr(eps_nhwc), ptr(ref), ptr(noise), noise.stride(0), noise.stride(1), ptr(Lh), ptr(Lw),
+    check(lib.afldm_ilvr_step(ptr(x), ptr(eps_nhwc), ptr(ref), *noise_args, ptr(Lh), ptr(Lw),
                               ptr(out), ptr(coef), ptr(step_idx), int(advance), B, C, H, W, _code(eps_nhwc), stream_ptr()),
           "ilvr_step")
     return out
@@ -1593,13 +1604,7 @@ def ilvr_step_flat(x, eps, ref, noises, Lh, Lw, row, out=None):
     assert eps.dtype == ref.dtype == torch.float32 and x.shape == eps.shape == ref.shape
     assert x.is_contiguous() and eps.is_contiguous() and ref.is_contiguous()
     row = [float(c) for c in row[:10]]
-    for z, c, name in zip(noises, (row[8] if row[9] != 0.0 else 0.0, row[6]), ("z_k", "z_u")):
-        if z is None:
-            if c != 0.0:
-                raise ValueError(f"ilvr_step_flat: {name} is None but its coefficient is {c}")
-            continue
-        _dev(z, name)
-        assert z.dtype == torch.float32 and z.shape == x.shape and z.is_contiguous()
+    _slot_tensors("ilvr_step_flat", x, noises, (row[8] if row[9] != 0.0 else 0.0, row[6]), ("z_k", "z_u"), contiguous=True)
     if out is None:
         out = torch.empty_like(x)
     B, C, H, W = x.shape
@@ -1664,16 +1669,10 @@ def pag_step(x, eps2_nhwc, noise, coef, step_idx, advance=False, out=None):
     _dev(x, "x"); _dev(eps2_nhwc, "eps2")
     B, C, H, W = _pag_args("pag_step", x, eps2_nhwc)
     assert tuple(eps2_nhwc.shape) == (2 * B, H, W, C) and eps2_nhwc.is_contiguous()
-    stride = 0
-    if noise is not None:
-        if not noise.is_cuda:
-            raise RuntimeError("afldm_amd: noise must live on an MI355X (cuda) device; there is no CPU path")
-        assert noise.dtype == torch.float32 and noise.dim() == 5 and tuple(noise.shape[1:]) == (B, C, H, W)
-        assert noise[0].is_contiguous() and noise.stride(0) >= B * C * H * W
-        stride = noise.stride(0)
+    noise_args = (None, 0) if noise is None else _noise_view(noise, x.shape)
     if out is None:
         out = torch.empty_like(x)
-    check(lib.afldm_pag_step(ptr(x), ptr(eps2_nhwc), ptr(noise), stride, ptr(out), ptr(coef), ptr(step_idx), int(advance),
+    check(lib.afldm_pag_step(ptr(x), ptr(eps2_nhwc), *noise_args, ptr(out), ptr(coef), ptr(step_idx), int(advance),
                              B, C, H, W, _code(eps2_nhwc), stream_ptr()), "pag_step")
     return out
 
@@ -1685,12 +1684,7 @@ def pag_step_flat(x, e, e_p, z, row, out=None):
     assert x.dtype == e.dtype == e_p.dtype == torch.float32 and x.shape == e.shape == e_p.shape and x.dim() >= 2
     assert x.is_contiguous() and e.is_contiguous() and e_p.is_contiguous()
     row = ([float(c) for c in row] + [0.0, 0.0])[:12]
-    if z is None:
-        if row[7] != 0.0:
-            raise ValueError(f"pag_step_flat: z is None but its coefficient is {row[7]}")
-    else:
-        _dev(z, "z")
-        assert z.dtype == torch.float32 and z.shape == x.shape and z.is_contiguous()
+    _slot_tensors("pag_step_flat", x, (z,), (row[7],), ("z",), contiguous=True)
     if out is None:
         out = torch.empty_like(x)
     B = x.shape[0]
@@ -1819,13 +1813,7 @@ def pano_step(canvas, eps_nhwc, noise, wt, geometry, coef, step_idx, advance=Fal
     _dev(eps_nhwc, "eps"); _pano_weights("pano_step", wt, g)
     if tuple(eps_nhwc.shape) != (P * g.nwin, g.S, g.S, C):
         raise ValueError(f"pano_step: eps {tuple(eps_nhwc.shape)}, want NHWC {(P * g.nwin, g.S, g.S, C)}")
-    stride = 0
-    if noise is not None:
-        if not noise.is_cuda:
-            raise RuntimeError("afldm_amd: noise must live on an MI355X (cuda) device; there is no CPU path")
-        assert noise.dtype == torch.float32 and noise.dim() == 5 and tuple(noise.shape[1:]) == tuple(canvas.shape)
-        assert noise[0].is_contiguous() and noise.stride(0) >= canvas.numel()
-        stride = noise.stride(0)
+    noise_args = (None, 0) if noise is None else _noise_view(noise, canvas.shape)
     if out is None:
         out = torch.empty_like(canvas)
     if windows_out is None:
@@ -1833,7 +1821,7 @@ def pano_step(canvas, eps_nhwc, noise, wt, geometry, coef, step_idx, advance=Fal
     _dev(out, "out"); _dev(windows_out, "windows_out")
     assert out.dtype == windows_out.dtype == torch.float32 and out.shape == canvas.shape
     assert tuple(windows_out.shape) == (P * g.nwin, C, g.S, g.S)
-    check(lib.afldm_pano_step(ptr(canvas), ptr(eps_nhwc), ptr(noise), stride, ptr(wt), ptr(out), ptr(windows_out), ptr(coef),
+    check(lib.afldm_pano_step(ptr(canvas), ptr(eps_nhwc), *noise_args, ptr(wt), ptr(out), ptr(windows_out), ptr(coef),
                               ptr(step_idx), int(advance), P, C, *_geom_args(g), _code(eps_nhwc), stream_ptr()), "pano_step")
     return out, windows_out
 

@@ -13,7 +13,7 @@ from ..engine import cached_engine
 from ..models.unet_2d import UNet2DModel
 from ..schedulers.ddim import DDIMScheduler
 from ..schedulers.dpmsolver import DPMSolverMultistepScheduler
-from ..schedulers.schedule import Schedule
+from ..schedulers.schedule import KINDS, Schedule
 from ..utils import randn_tensor
 from .pipeline_utils import DiffusionPipeline, ImagePipelineOutput
 
@@ -55,6 +55,8 @@ class MyLDMPipeline(DiffusionPipeline):
             # order - before the replays that read it.  The latent is carried in fp32 between steps, as for eta = 0; with a
             # bf16 UNet the loop below stores it in bf16 (the reference's storage), so the two differ by that rounding.
             sde = self.scheduler.stochastic_schedule(num_inference_steps, eta)
+            # (not through _sample, on purpose: _sample shows the engine the re-created scheduler, and this engine's .scheduler
+            # stays the Schedule it was built from, which tests/test_sde_host.py relies on)
             eng = cached_engine(self, "_engines", sde, latents.shape[0], use_graph, self.unet)
             draw = sde.drawer(generator, tuple(latents.shape), self.unet.device, self.unet.dtype)
             latents = eng.run(latents, draw=draw).to(self.unet.dtype)
@@ -91,6 +93,37 @@ class MyLDMPipeline(DiffusionPipeline):
         arrays = (decoded / 2 + 0.5).clamp(0, 1).cpu().permute(0, 2, 3, 1).float().numpy()
         images = self.numpy_to_pil(arrays) if output_type == "pil" else arrays
         return ImagePipelineOutput(images=images) if return_dict else (images,)
+
+    def _sample(self, sched, shape, generator, latents, use_graph, slot, eager, cls=None, batch=None, known=None, **kw):
+        """The protocol every sampler on a Schedule shares.  The draws come from `generator` through sched.drawer(shape): the start
+        latents first (unless `latents` is given; on the CPU for CPU generators, else on the device: the per-evaluation draws'
+        rule), then per evaluation the slots sched.slots(k) in slot order.  use_graph: the engine cached in `slot` - cls (default
+        DenoiseEngine) with its own keyword arguments kw, at `batch` (default shape[0]) - runs them, with the static per-run
+        tensors `known`.  Otherwise the eager loop: the latents scaled by init_noise_sigma and carried in fp32 like the engine,
+        x <- eager(x, t, row, zs) per evaluation, zs the kind's slots as fp32 device tensors, None where not drawn.  Returns fp32."""
+        dev = self.unet.device
+        draw = sched.drawer(generator, shape, dev, self.unet.dtype)
+        if latents is None:
+            latents = draw()
+        if use_graph:
+            eng = cached_engine(self, slot, sched, shape[0] if batch is None else batch, True, self.unet, cls, **kw)
+            eng.scheduler = self.scheduler
+            return eng.run(latents, draw=draw, **({} if known is None else {"known": known}))
+        x = (latents.to(device=dev, dtype=torch.float32) * sched.init_noise_sigma).contiguous()
+        for k, (t, row) in enumerate(self.progress_bar(list(zip(sched.timesteps, sched.rows)))):
+            on = sched.slots(k)
+            zs = [draw().to(device=dev, dtype=torch.float32).contiguous() if j in on else None for j in range(KINDS[sched.kind][1])]
+            x = eager(x, t, row, zs)
+        return x
+
+    def _vae_ratio(self):
+        """Pixels per latent along an axis."""
+        return getattr(self.vae, "downsample_ratio", None) or 2 ** (len(self.vae.config.block_out_channels) - 1)
+
+    def _encode_mode(self, image):
+        """image in [-1, 1] -> the posterior mode times scaling_factor."""
+        from ..harness import vae_encode_mode
+        return vae_encode_mode(self.vae, image.to(device=self.unet.device, dtype=self.vae.dtype))
 
     def _inversion_rows(self):
         """(timestep, (mu_prev, sigma_prev, mu, sigma)) per step of the inversion over the scheduler's current timesteps, reversed:
@@ -159,24 +192,16 @@ class MyLDMPipeline(DiffusionPipeline):
             raise ValueError(f"inpaint_latents: latents {tuple(latents.shape)}, want {(B, c, s, s)}")
         self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
         sched = self.scheduler.repaint_schedule(num_inference_steps, eta, jump_length, jump_n_sample)
-        shape, dev = (B, c, s, s), self.unet.device
-        draw = sched.drawer(generator, shape, dev, self.unet.dtype)
-        if latents is None:
-            latents = draw()            # (on the CPU for CPU generators, else on the device: the per-evaluation draws' rule)
-        known = known_latents.to(device=dev, dtype=torch.float32)
+        dev = self.unet.device
+        known = known_latents.to(device=dev, dtype=torch.float32).contiguous()
         mask = latent_mask.to(device=dev, dtype=torch.float32)
-        if use_graph:
-            eng = cached_engine(self, "_repaint_engines", sched, B, True, self.unet)
-            eng.scheduler = self.scheduler
-            return eng.run(latents, draw=draw, known=(known, mask)).to(self.unet.dtype)
-        x = (latents.to(device=dev, dtype=torch.float32) * sched.init_noise_sigma).contiguous()
-        known, mask = known.contiguous(), mask.expand(B, c, s, s).contiguous()
-        for k, (t, row) in enumerate(self.progress_bar(list(zip(sched.timesteps, sched.rows)))):
-            on = sched.slots(k)
-            zs = [draw().to(device=dev, dtype=torch.float32).contiguous() if j in on else None for j in range(3)]
+        full = None if use_graph else mask.expand(B, c, s, s).contiguous()
+
+        def eager(x, t, row, zs):
             eps = self.unet(x.to(self.unet.dtype), t).sample
-            x = ops.repaint_step_flat(x, eps.float().contiguous(), known, mask, zs, row)
-        return x.to(self.unet.dtype)
+            return ops.repaint_step_flat(x, eps.float().contiguous(), known, full, zs, row)
+        return self._sample(sched, (B, c, s, s), generator, latents, use_graph, "_repaint_engines", eager,
+                            known=(known, mask)).to(self.unet.dtype)
 
     @torch.no_grad()
     def inpaint(self, image, mask, num_inference_steps=50, eta=0.0, jump_length=10, jump_n_sample=10, generator=None, latents=None,
@@ -193,7 +218,7 @@ class MyLDMPipeline(DiffusionPipeline):
             raise NotImplementedError("this pipeline was built without a VAE: use inpaint_latents")
         if mask_mode not in ("min", "mean"):
             raise ValueError(f"inpaint: mask_mode {mask_mode!r} (want 'min' or 'mean')")
-        r = getattr(self.vae, "downsample_ratio", None) or 2 ** (len(self.vae.config.block_out_channels) - 1)
+        r = self._vae_ratio()
         s = self.unet.config.sample_size
         if image.dim() != 4 or tuple(image.shape[1:]) != (3, s * r, s * r):
             raise ValueError(f"inpaint: image {tuple(image.shape)}, want [B, 3, {s * r}, {s * r}]")
@@ -202,7 +227,7 @@ class MyLDMPipeline(DiffusionPipeline):
         dev = self.unet.device
         image = image.to(device=dev, dtype=torch.float32)
         mask = mask.to(device=dev, dtype=torch.float32).contiguous()
-        known = self.vae.encode(image.to(self.vae.dtype)).latent_dist.mode() * self.vae.config.scaling_factor
+        known = self._encode_mode(image)
         latent_mask = ops.mask_pool(mask, r, ops.MASK_MIN if mask_mode == "min" else ops.MASK_MEAN)
         out = self.inpaint_latents(known, latent_mask, num_inference_steps, eta, jump_length, jump_n_sample, generator, latents,
                                    use_graph)
@@ -241,22 +266,13 @@ class MyLDMPipeline(DiffusionPipeline):
         L = (phi if phi is not None else ilvr_filter(s, down_factor)).to(device=dev, dtype=torch.float32).contiguous()
         self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
         sched = self.scheduler.ilvr_schedule(num_inference_steps, eta, range_t)
-        shape = (B, c, s, s)
-        draw = sched.drawer(generator, shape, dev, self.unet.dtype)
-        if latents is None:
-            latents = draw()            # (on the CPU for CPU generators, else on the device: the per-evaluation draws' rule)
         ref = ref_latents.to(device=dev, dtype=torch.float32).contiguous()
-        if use_graph:
-            eng = cached_engine(self, "_ilvr_engines", sched, B, True, self.unet)
-            eng.scheduler = self.scheduler
-            return eng.run(latents, draw=draw, known=(ref, L)).to(self.unet.dtype)
-        x = (latents.to(device=dev, dtype=torch.float32) * sched.init_noise_sigma).contiguous()
-        for k, (t, row) in enumerate(self.progress_bar(list(zip(sched.timesteps, sched.rows)))):
-            on = sched.slots(k)
-            zs = [draw().to(device=dev, dtype=torch.float32).contiguous() if j in on else None for j in range(2)]
+
+        def eager(x, t, row, zs):
             eps = self.unet(x.to(self.unet.dtype), t).sample
-            x = ops.ilvr_step_flat(x, eps.float().contiguous(), ref, zs, L, L, row)
-        return x.to(self.unet.dtype)
+            return ops.ilvr_step_flat(x, eps.float().contiguous(), ref, zs, L, L, row)
+        return self._sample(sched, (B, c, s, s), generator, latents, use_graph, "_ilvr_engines", eager,
+                            known=(ref, L)).to(self.unet.dtype)
 
     @torch.no_grad()
     def ilvr(self, image, down_factor=4, range_t=0, num_inference_steps=50, eta=1.0, phi=None, generator=None, latents=None,
@@ -267,13 +283,11 @@ class MyLDMPipeline(DiffusionPipeline):
         self._refuse_dpm("ilvr")
         if self.vae is None:
             raise NotImplementedError("this pipeline was built without a VAE: use ilvr_latents")
-        r = getattr(self.vae, "downsample_ratio", None) or 2 ** (len(self.vae.config.block_out_channels) - 1)
+        r = self._vae_ratio()
         s = self.unet.config.sample_size
         if image.dim() != 4 or tuple(image.shape[1:]) != (3, s * r, s * r):
             raise ValueError(f"ilvr: image {tuple(image.shape)}, want [B, 3, {s * r}, {s * r}]")
-        image = image.to(device=self.unet.device, dtype=self.vae.dtype)
-        ref = self.vae.encode(image).latent_dist.mode() * self.vae.config.scaling_factor
-        out = self.ilvr_latents(ref, down_factor, range_t, num_inference_steps, eta, phi, generator, latents, use_graph)
+        out = self.ilvr_latents(self._encode_mode(image), down_factor, range_t, num_inference_steps, eta, phi, generator, latents, use_graph)
         return self._deliver(out, output_type, return_dict)
 
     # ------------------------------------------------------------------------------------------------ perturbed-attention guidance
@@ -318,21 +332,13 @@ class MyLDMPipeline(DiffusionPipeline):
             raise ValueError(f"pag_latents: latents {tuple(latents.shape)}, want [B, {c}, {s}, {s}]")
         self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
         sched = self.scheduler.pag_schedule(num_inference_steps, eta, pag_scale, guidance_rescale)
-        draw = sched.drawer(generator, shape, dev, self.unet.dtype)
-        if latents is None:
-            latents = draw()            # (on the CPU for CPU generators, else on the device: the per-evaluation draws' rule)
-        if use_graph:
-            eng = cached_engine(self, "_pag_engines", sched, B, True, self.unet, extra=(sites,),
-                                build=lambda: PAGEngine(self.unet, sched, B, len(sched.timesteps), True, sites=sites))
-            eng.scheduler = self.scheduler
-            return eng.run(latents, draw=draw).to(self.unet.dtype)
-        x = (latents.to(device=dev, dtype=torch.float32) * sched.init_noise_sigma).contiguous()
-        with pag_processors(self.unet, sites):
-            for k, (t, row) in enumerate(self.progress_bar(list(zip(sched.timesteps, sched.rows)))):
-                z = draw().to(device=dev, dtype=torch.float32).contiguous() if sched.slots(k) else None
+
+        def eager(x, t, row, zs):
+            with pag_processors(self.unet, sites):
                 eps2 = self.unet(torch.cat([x, x]).to(self.unet.dtype), t).sample.float()
-                x = ops.pag_step_flat(x, eps2[:B].contiguous(), eps2[B:].contiguous(), z, row)
-        return x.to(self.unet.dtype)
+            return ops.pag_step_flat(x, eps2[:B].contiguous(), eps2[B:].contiguous(), zs[0], row)
+        return self._sample(sched, shape, generator, latents, use_graph, "_pag_engines", eager, PAGEngine,
+                            sites=sites).to(self.unet.dtype)
 
     @torch.no_grad()
     def pag(self, batch_size=1, pag_scale=3.0, pag_applied_layers=("mid_block",), guidance_rescale=0.0, eta=0.0,
@@ -398,20 +404,11 @@ class MyLDMPipeline(DiffusionPipeline):
         sched = self.scheduler.sag_schedule(num_inference_steps, eta, sag_scale, guidance_rescale)
         if masks is not None and len(masks) != len(sched.timesteps):
             raise ValueError(f"sag_latents: {len(masks)} masks for {len(sched.timesteps)} steps")
-        draw = sched.drawer(generator, shape, dev, self.unet.dtype)
-        if latents is None:
-            latents = draw()            # (on the CPU for CPU generators, else on the device: the per-evaluation draws' rule)
-        if use_graph:
-            eng = cached_engine(self, "_sag_engines", sched, B, True, self.unet, extra=(site, taps, blur_boundary),
-                                build=lambda: SAGEngine(self.unet, sched, B, len(sched.timesteps), True, site=site, taps=taps,
-                                                        boundary=blur_boundary))
-            eng.scheduler = self.scheduler
-            return eng.run(latents, draw=draw).to(self.unet.dtype)
-        x = (latents.to(device=dev, dtype=torch.float32) * sched.init_noise_sigma).contiguous()
         pq = sched.table("cpu")[:, :2].tolist()         # (p, q) as the engine's kernel reads them: rounded once to fp32
-        masses = []
-        for k, (t, row) in enumerate(self.progress_bar(list(zip(sched.timesteps, sched.rows)))):
-            z = draw().to(device=dev, dtype=torch.float32).contiguous() if sched.slots(k) else None
+        masses, steps = [], iter(range(len(sched.timesteps)))
+
+        def eager(x, t, row, zs):
+            k = next(steps)
             with sag_processor(self.unet, site) as proc:
                 e = self.unet(x.to(self.unet.dtype), t).sample.float().contiguous()
             mass = proc.mass
@@ -423,8 +420,9 @@ class MyLDMPipeline(DiffusionPipeline):
                 mass = m.to(dev).float() * 2.0          # 2 > 1: masked; 0: not
             x_d = ops.sag_degrade_flat(x, e, mass.contiguous(), taps, blur_boundary, *pq[k])
             e_d = self.unet(x_d.to(self.unet.dtype), t).sample.float().contiguous()
-            x = ops.pag_step_flat(x, e, e_d, z, row)
-        out = x.to(self.unet.dtype)
+            return ops.pag_step_flat(x, e, e_d, zs[0], row)
+        out = self._sample(sched, shape, generator, latents, use_graph, "_sag_engines", eager, SAGEngine, site=site, taps=taps,
+                           boundary=blur_boundary).to(self.unet.dtype)
         return (out, masses) if return_masks else out
 
     @torch.no_grad()
@@ -474,28 +472,19 @@ class MyLDMPipeline(DiffusionPipeline):
             raise ValueError(f"panorama_latents: latents {tuple(latents.shape)}, want [P, {c}, {geom.Hc}, {geom.Wc}]")
         self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
         sched = self.scheduler.panorama_schedule(num_inference_steps, eta)
-        draw = sched.drawer(generator, shape, dev, self.unet.dtype)
-        if latents is None:
-            latents = draw()            # (on the CPU for CPU generators, else on the device: the per-evaluation draws' rule)
-        if use_graph:
-            B = P * geom.nwin
-            eng = cached_engine(self, "_pano_engines", sched, B, True, self.unet, extra=(geom,),
-                                build=lambda: PanoramaEngine(self.unet, sched, B, len(sched.timesteps), True, geometry=geom))
-            eng.scheduler = self.scheduler
-            return eng.run(latents, draw=draw if any(sched.draws) else None)
-        x = (latents.to(device=dev, dtype=torch.float32) * sched.init_noise_sigma).contiguous()
         ones = torch.ones(s, s, dtype=torch.float32, device=dev)
-        for k, (t, row) in enumerate(self.progress_bar(list(zip(sched.timesteps, sched.rows)))):
+
+        def eager(x, t, row, zs):
             p, q, lo, hi, a, b, d, cz = row
-            z = draw().to(device=dev, dtype=torch.float32) if sched.slots(k) else None
             win = ops.window_crop(x, geom)                                    # [P * nwin, C, S, S]
             eps = self.unet(win.to(self.unet.dtype), t).sample.float()
             x0 = torch.clamp(p * win + q * eps, lo, hi)                       # every window's own prediction of the clean latents
             x = a * x + b * ops.window_fuse(x0.contiguous(), ones, geom) + d * ops.window_fuse(eps.contiguous(), ones, geom)
-            if z is not None:
-                x = x + cz * z
-            x = x.contiguous()
-        return x
+            if zs[0] is not None:
+                x = x + cz * zs[0]
+            return x.contiguous()
+        return self._sample(sched, shape, generator, latents, use_graph, "_pano_engines", eager, PanoramaEngine, P * geom.nwin,
+                            geometry=geom)
 
     @torch.no_grad()
     def decode_panorama(self, canvas, geometry):
@@ -508,7 +497,7 @@ class MyLDMPipeline(DiffusionPipeline):
         from ..panorama import feather
         if self.vae is None:
             raise NotImplementedError("this pipeline was built without a VAE: use panorama_latents")
-        r = getattr(self.vae, "downsample_ratio", None) or 2 ** (len(self.vae.config.block_out_channels) - 1)
+        r = self._vae_ratio()
         dev, n = self.unet.device, geometry.nwin
         win = ops.window_crop(canvas.to(device=dev, dtype=torch.float32).contiguous(), geometry)
         scale = self.vae.config.scaling_factor
@@ -525,7 +514,7 @@ class MyLDMPipeline(DiffusionPipeline):
         self._refuse_dpm("panorama")
         if self.vae is None:
             raise NotImplementedError("this pipeline was built without a VAE: use panorama_latents")
-        r = getattr(self.vae, "downsample_ratio", None) or 2 ** (len(self.vae.config.block_out_channels) - 1)
+        r = self._vae_ratio()
         for name, v in (("height", height), ("width", width), ("stride", stride)):
             if v is not None and (int(v) % r or int(v) < r):
                 raise ValueError(f"panorama: {name} = {v} pixels must be a positive multiple of the VAE's scale factor {r}")

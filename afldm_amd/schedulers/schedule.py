@@ -32,8 +32,10 @@ import torch
 from ..configs import FrozenConfig
 from ..utils import randn_tensor
 
-ROW_WIDTH = {"ddim": 4, "dpm": 8, "sde": 8, "repaint": 12, "ilvr": 12, "pano": 8, "pag": 12, "sag": 12}
-NOISE_SLOTS = {"sde": 1, "repaint": 3, "ilvr": 2, "pano": 1, "pag": 1, "sag": 1}          # draws per step at the most; the kinds not named draw nothing
+# kind -> (row width, noise slots per step, may a step draw): the one place that states them.  Several slots: `draws` is per slot
+KINDS = {"ddim": (4, 1, False), "dpm": (8, 1, False), "sde": (8, 1, True), "repaint": (12, 3, True), "ilvr": (12, 2, True),
+         "pano": (8, 1, True), "pag": (12, 1, True), "sag": (12, 1, True)}
+ROW_WIDTH, NOISE_SLOTS = {k: v[0] for k, v in KINDS.items()}, {k: v[1] for k, v in KINDS.items() if v[2]}      # derived views
 _MADE = {}          # key -> Schedule: the rows are ~0.1 ms of scalar tensor arithmetic each, and a sampler asks per call
 
 
@@ -52,9 +54,8 @@ class Schedule:
     def of(cls, owner, kind, timesteps, rows, draws=None, noise_dtype=None, **settings):
         """owner: the scheduler whose config the rows are computed from; settings: whatever else they depend on (the step
         count, eta, is_ode, ...); rows: one per timestep, or a function of the timestep that is only called when no schedule
-        with this key has been made yet; draws: per step, whether the eager step draws a noise tensor ("sde", "pano", "pag", "sag"), or which of its
-        slots do (a kind with NOISE_SLOTS[kind] > 1: that many bools per step - "repaint" three, "ilvr" two);
-        noise_dtype: the dtype of that draw (None: the model's dtype, what DDIMScheduler.step draws in)."""
+        with this key has been made yet; draws: per step, whether the eager step draws a noise tensor, or for a kind of several
+        slots one bool per slot (KINDS); noise_dtype: the dtype of that draw (None: the model's dtype, as DDIMScheduler.step)."""
         config = FrozenConfig(dict(owner.config, **settings))
         key = (type(owner).__name__, tuple(sorted((k, repr(v)) for k, v in config.items())))
         if key in _MADE:
@@ -63,20 +64,20 @@ class Schedule:
         if callable(rows):
             rows = [rows(t) for t in timesteps]
         rows = tuple(tuple(float(v) for v in r) for r in rows)
-        if NOISE_SLOTS.get(kind, 0) > 1:
+        width, nslots, may_draw = KINDS[kind]
+        if nslots > 1:
             draws = tuple(tuple(bool(v) for v in d) for d in draws)
-            assert all(len(d) == NOISE_SLOTS[kind] for d in draws)
+            assert all(len(d) == nslots for d in draws)
         else:
             draws = tuple(bool(d) for d in draws) if draws is not None else (False,) * len(rows)
-            assert kind in ("sde", "pano", "pag", "sag") or not any(draws)
-        assert len(timesteps) == len(rows) == len(draws) and all(len(r) == ROW_WIDTH[kind] for r in rows)
+        assert len(timesteps) == len(rows) == len(draws) and all(len(r) == width for r in rows) and (may_draw or not any(draws))
         if len(_MADE) >= 64:
             _MADE.clear()
         made = _MADE[key] = cls(kind, timesteps, rows, draws, noise_dtype, float(owner.init_noise_sigma), config, key)
         return made
 
     def table(self, device):
-        """float32 [nsteps, ROW_WIDTH[kind]] device table, each entry rounded once from the Python float."""
+        """float32 [nsteps, row width] device table, each entry rounded once from the Python float."""
         return torch.tensor(self.rows, dtype=torch.float64).to(torch.float32).to(device)
 
     # read-only spellings of the scheduler-shaped views this type replaced; tests/test_sde_host.py checks every row through them
@@ -85,8 +86,7 @@ class Schedule:
     coefficient_table = table
 
     def slots(self, k):
-        """The noise slots step k draws, in drawing order: () or (0,) for "sde" and "pano", a subset of (0, 1, 2) for "repaint", of (0, 1) for
-        "ilvr"."""
+        """The noise slots step k draws, in drawing order: a subset of range(KINDS[kind][1])."""
         d = self.draws[k]
         return tuple(j for j, on in enumerate(d) if on) if isinstance(d, tuple) else ((0,) if d else ())
 

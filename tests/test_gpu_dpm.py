@@ -35,6 +35,18 @@ def build(cfg_name, dtype):
     return unet.to("cuda").to(dtype), cfg, sd
 
 
+def _run_across_a_dtype_change(make, x):
+    """run on the fp32 UNet, unet.to(bfloat16), run again on the same engine: (engine, whether refresh_if_stale said the model moved,
+    the second result, the result of an engine newly made on the bf16 UNet)."""
+    eng = make()
+    eng.run(x)
+    eng.unet.to(torch.bfloat16)
+    said, plain = [], eng.refresh_if_stale
+    eng.refresh_if_stale = lambda: said.append(plain()) or said[-1]
+    got = eng.run(x)
+    return eng, said, got, make().run(x)
+
+
 def dpm(**kw):
     from afldm_amd.configs import FFHQ_DDIM_CONFIG
     from afldm_amd.schedulers.dpmsolver import DPMSolverMultistepScheduler

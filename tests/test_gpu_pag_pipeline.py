@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import pag_oracle as po
-from test_gpu_dpm import build, rel_rms
+from test_gpu_dpm import _run_across_a_dtype_change, build, rel_rms
 from test_gpu_sde import _gens, _ldm, _same_state
 
 pytestmark = pytest.mark.gpu
@@ -145,7 +145,7 @@ def test_engine_cache_and_refold_after_a_weight_edit():
     assert next(iter(pipe._pag_engines.values())) is eng and eng.graph is graph and not torch.equal(a, b)
     pipe.pag_latents(latents=x, pag_scale=2.0, **kw)                          # another scale: another schedule key
     (eng2,) = pipe._pag_engines.values()
-    assert eng2 is not eng
+    assert eng2 is not eng and eng2.sites == pipe.pag_sites(UP)
     pipe.pag_latents(latents=x, pag_scale=2.0, pag_applied_layers=("up_blocks.1",), num_inference_steps=4)      # other sites
     (eng3,) = pipe._pag_engines.values()
     assert eng3 is not eng2 and eng3.sites == pipe.pag_sites(("up_blocks.1",))
@@ -205,3 +205,19 @@ def test_ffhq_bf16(monkeypatch, min_t):
     det, e0, e1, ge = _bf16_case("ffhq", ("down_blocks.2", "down_blocks.3", "mid_block"))
     assert e0 <= 1.5 * det and e1 <= 1.5 * 3 * det, (det, e0, e1)
     assert ge <= 1e-5, ge
+
+
+# ------------------------------------------------------------------------------------------------ a dtype change under a live engine
+def test_engine_survives_a_dtype_change():
+    from afldm_amd.engine import PAGEngine
+    from afldm_amd.schedulers.ddim import ffhq_ddim_scheduler
+    unet, _, _ = build("tiny", torch.float32)
+    before = _processors(unet)
+    sites, sched = _ldm(unet).pag_sites(UP), ffhq_ddim_scheduler().pag_schedule(3, 0.0, 3.0, 0.0)
+    eng, said, got, fresh = _run_across_a_dtype_change(lambda: PAGEngine(unet, sched, 2, 3, sites=sites), _x())
+    assert said == [True]
+    assert eng.x_nhwc.dtype == torch.bfloat16 and eng.x_nhwc.shape[0] == 4 and eng.lat.shape[0] == 2
+    assert eng.sites == sites
+    assert torch.isfinite(got).all() and torch.equal(got, fresh)
+    after = _processors(unet)
+    assert after.keys() == before.keys() and all(after[k] is before[k] for k in before)

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import pano_oracle as po
-from test_gpu_dpm import build, rel_rms
+from test_gpu_dpm import _run_across_a_dtype_change, build, rel_rms
 from test_gpu_sde import _gens, _ldm, _same_state
 
 pytestmark = pytest.mark.gpu
@@ -111,13 +111,33 @@ def test_tiny_engine_cache(tiny):
     assert rel_rms(b, a) > 1e-2 and rel_rms(b, pipe.panorama_latents(16, 40, latents=x2, use_graph=False, **kw)) <= 1e-5
     pipe.panorama_latents(16, 32, latents=x1[..., :32], **kw)             # another width: another geometry replaces the entry
     (key2,) = pipe._pano_engines
-    assert key2 != key and pipe._pano_engines[key2] is not eng and pipe._pano_engines[key2].geometry.Wc == 32
+    eng2 = pipe._pano_engines[key2]
+    assert key2 != key and eng2 is not eng and eng2.geometry.Wc == 32 and not eng2.geometry.wrap_x
     pipe.panorama_latents(16, 32, latents=x1[..., :32], circular=True, **kw)
     (key3,) = pipe._pano_engines
     assert key3 != key2                                                    # ... and so does the same width with a wrapping axis
+    assert pipe._pano_engines[key3] is not eng2 and pipe._pano_engines[key3].geometry == pipe.panorama_geometry(16, 32, 8, True)
     from afldm_amd.engine import DenoiseEngine
     with pytest.raises(NotImplementedError):                              # the plain engine has no canvas
         DenoiseEngine(tiny["unet"], pipe.scheduler.panorama_schedule(N, 0.0), 4, N)
+
+
+# ------------------------------------------------------------------------------------------------ a dtype change under a live engine
+def test_tiny_engine_survives_a_dtype_change():
+    from afldm_amd.engine import PanoramaEngine
+    from afldm_amd.pipelines.cross_frame_attn import get_unet_attn_processors
+    from afldm_amd.schedulers.ddim import ffhq_ddim_scheduler
+    unet, _, _ = build("tiny", torch.float32)
+    before = get_unet_attn_processors(unet)
+    geom, sched = _ldm(unet).panorama_geometry(16, 24, 8), ffhq_ddim_scheduler().panorama_schedule(3, 0.0)
+    x = torch.randn(1, 4, 16, 24, generator=torch.Generator().manual_seed(4))
+    eng, said, got, fresh = _run_across_a_dtype_change(lambda: PanoramaEngine(unet, sched, geom.nwin, 3, geometry=geom), x)
+    assert said == [True]
+    assert eng.x_nhwc.dtype == torch.bfloat16 and tuple(eng.lat.shape) == (2, 4, 16, 16) and tuple(eng.canvas.shape) == (1, 4, 16, 24)
+    assert eng.geometry is geom and eng.P == 1
+    assert torch.isfinite(got).all() and torch.equal(got, fresh)
+    after = get_unet_attn_processors(unet)
+    assert after.keys() == before.keys() and all(after[k] is before[k] for k in before)
 
 
 # ------------------------------------------------------------------------------------------------ FFHQ size, bf16

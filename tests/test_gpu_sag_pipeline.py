@@ -16,7 +16,7 @@ import pytest
 import torch
 
 import sag_oracle as so
-from test_gpu_dpm import build, rel_rms
+from test_gpu_dpm import _run_across_a_dtype_change, build, rel_rms
 from test_gpu_sde import _ldm, _same_state
 
 pytestmark = pytest.mark.gpu
@@ -92,7 +92,7 @@ def test_engine_is_keyed_by_site_taps_and_boundary(tiny32):
         assert all(e2 is not s for s in seen), change
         seen.append(e2)
     assert seen[1].site == "up_blocks.1.attentions.0" and tuple(seen[1].mass.shape) == (2, 64)
-    assert len(seen[2].taps) == 5 and seen[4].boundary == "circular"
+    assert len(seen[2].taps) == 5 and seen[0].boundary == "reflect" and seen[4].boundary == "circular"
 
 
 def test_scale_zero_is_the_plain_sampler(tiny32):
@@ -234,3 +234,22 @@ def test_tiny_bf16():
 
 def test_ffhq_bf16():
     _bf16_case("ffhq", "up_blocks.2.attentions.0")
+
+
+# ------------------------------------------------------------------------------------------------ a dtype change under a live engine
+def test_engine_survives_a_dtype_change():
+    from afldm_amd import ops
+    from afldm_amd.engine import SAGEngine
+    from afldm_amd.schedulers.ddim import ffhq_ddim_scheduler
+    unet, _, _ = build("tiny", torch.float32)
+    before = _processors(unet)
+    site, taps = _ldm(unet).sag_site_of("mid_block"), ops.gaussian_taps()
+    sched = ffhq_ddim_scheduler().sag_schedule(3, 0.0, 0.75, 0.0)
+    make = lambda: SAGEngine(unet, sched, 2, 3, site=site, taps=taps, boundary="reflect")
+    eng, said, got, fresh = _run_across_a_dtype_change(make, so.start_latents(so.GRAPH_XSEED, 2))
+    assert said == [True]
+    assert eng.x_nhwc.dtype == eng.eps2.dtype == torch.bfloat16 and eng.x_nhwc.shape[0] == 2 and eng.eps2.shape[0] == 4
+    assert (eng.site, eng.taps, eng.boundary) == (site, taps, "reflect")
+    assert torch.isfinite(got).all() and torch.equal(got, fresh)
+    after = _processors(unet)
+    assert after.keys() == before.keys() and all(after[k] is before[k] for k in before)
