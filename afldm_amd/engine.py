@@ -44,6 +44,11 @@ of batch B per step: the first with SAGAttnProcessor at one site, which also wri
 afldm_sag_degrade turns x, e and the mass into the second evaluation's input; both outputs land in `eps2` [2 B] and the step ends
 in afldm_pag_step, unchanged.
 
+SlotEngine has no schedule of its own: every batch row ("slot") walks its own stretch of one device row table with a cursor of
+its own, so "ddim" requests of different step counts share the graphs and a finished slot is harvested and refilled between replays
+(afldm_slot_select in place of afldm_select_step_row, afldm_slot_step in place of afldm_ddim_step, afldm_slot_exchange at the
+boundary); afldm_amd/serving.py drives it.
+
 Structure.  __init__ validates and stores its arguments; _allocate makes every device buffer and is what refresh_if_stale calls
 again after unet.to(dtype / device).  A kind is one entry of UPDATES - the update op of ops that ends a step, and a function that
 allocates what the kind keeps between steps and returns, per branch, the tensors the op takes between eps and the coefficient
@@ -260,7 +265,7 @@ class DenoiseEngine:
         keep = [t.clone() for t in carried]
 
         def rewind():
-            self.step_idx.fill_(-1)
+            self._rewind()
             for t, k in zip(carried, keep):
                 t.copy_(k)
 
@@ -290,6 +295,10 @@ class DenoiseEngine:
     def _carried(self):
         """The buffers a step reads and overwrites: what _capture puts back after its warm-up step and its captures."""
         return [self.lat] + ([] if self.hist is None else [self.hist])
+
+    def _rewind(self):
+        """The step counter back to the start of the schedule (_capture, before every capture and on return)."""
+        self.step_idx.fill_(-1)
 
     def _result(self):
         return self.lat.clone()
@@ -330,9 +339,13 @@ class DenoiseEngine:
         # in-place parameter edits do not pass through the modules' own hooks; another engine of this model may have repacked
         # (and captured on the new copies) already
         invalidate_stale_packed(self.unet)
-        self.temb_table.copy_(torch.cat([self.unet.temb_projection(t) for t in self.timesteps], 0))
+        self._retabulate()
         self._model_key = key
         return True
+
+    def _retabulate(self):
+        """The time-embedding table of the model as it is now, written in place (the graphs hold its address)."""
+        self.temb_table.copy_(torch.cat([self.unet.temb_projection(t) for t in self.timesteps], 0))
 
     def reset(self, latents):
         """latents: [B, C, H, W] (any device / float dtype); scaled by init_noise_sigma like the reference."""
@@ -589,3 +602,202 @@ class SAGEngine(DenoiseEngine):
         ops.sag_degrade(lat, self.eps2[:B], self.mass, self.taps, self.boundary, self.coef, self.step_idx, out=x_nhwc)
         self.eps2[B:].copy_(self.unet.forward_nhwc(x_nhwc, self.t_cur, temb_slices=self.temb_slices))
         return self.eps2
+
+
+class SlotTable:
+    """The host's record of a SlotEngine's row table: the rows of every schedule added so far, each stored once under
+    `schedule.key`, and the distinct timesteps they use in the order of the time-embedding table.  Plain Python - what the
+    serving layer's host tests run against; SlotEngine uploads what `add` appends."""
+
+    def __init__(self, row_capacity, temb_capacity):
+        self.R, self.T = int(row_capacity), int(temb_capacity)
+        self.coef, self.t, self.temb = [], [], []          # per row: (c0, c1, c2, c3), the timestep, its time-embedding row
+        self.timesteps, self._index = [], {}               # per time-embedding row: its timestep; timestep -> row
+        self.spans = {}                                    # schedule.key -> (begin, end)
+
+    def add(self, schedule):
+        """(begin, end) of the schedule's rows, appended (with its unseen timesteps) on the first call for this key.  Raises
+        NotImplementedError for a kind other than "ddim" and RuntimeError when a table is full; a refused schedule leaves the
+        tables as they were."""
+        if schedule.kind != "ddim":
+            raise NotImplementedError(f"SlotEngine: update_kind {schedule.kind!r}: slots take 'ddim' schedules only (the other "
+                                      "kinds need a noise feed or a history per slot)")
+        if schedule.key in self.spans:
+            return self.spans[schedule.key]
+        unseen = [t for t in dict.fromkeys(schedule.timesteps) if t not in self._index]
+        begin, n = len(self.t), len(schedule.timesteps)
+        if begin + n > self.R:
+            raise RuntimeError(f"SlotEngine: the row table is full ({begin} of {self.R} rows used, {n} more asked for): build the "
+                               "engine with a larger row_capacity")
+        if len(self.timesteps) + len(unseen) > self.T:
+            raise RuntimeError(f"SlotEngine: the time-embedding table is full ({len(self.timesteps)} of {self.T} rows used, "
+                               f"{len(unseen)} more asked for): build the engine with a larger temb_capacity")
+        for t in unseen:
+            self._index[t] = len(self.timesteps)
+            self.timesteps.append(t)
+        for t, row in zip(schedule.timesteps, schedule.rows):
+            self.coef.append(tuple(row))
+            self.t.append(float(t))
+            self.temb.append(self._index[t])
+        self.spans[schedule.key] = (begin, begin + n)
+        return self.spans[schedule.key]
+
+
+class SlotEngine(DenoiseEngine):
+    """Continuous batching on the replayed graphs: every batch row ("slot") has its own cursor (pos, end) into one row table on
+    the device, so requests of different schedules share a batch and a slot that finishes is harvested and refilled between
+    replays while its neighbours go on.  A step is the plain sampler's launch list with afldm_slot_select in place of
+    afldm_select_step_row (it advances the cursors of the active slots and gathers one time-embedding row per slot, which the
+    UNet reads with a row stride) and afldm_slot_step in place of afldm_ddim_step (each active slot's own coefficient row; a
+    finished or empty slot is frozen: evaluated, but not written).  So any grouping of steps into replays gives the same
+    latents; grouping only affects utilisation, and is the serving layer's business (afldm_amd/serving.py).
+
+    add_schedule(schedule) -> (begin, end) stores a "ddim" schedule's rows once per `schedule.key`; the tables have fixed
+    capacities and fixed addresses, and are only appended to.  exchange(harvests, refills) is the boundary between replays:
+    one afldm_slot_exchange launch behind non-blocking uploads of the command buffer and the fresh latents from pinned
+    staging, then one non-blocking device-to-host copy per harvested slot out of the output ring, each with its event.
+    The engine has no schedule of its own: reset / run are the base class's and do not apply."""
+    ONE_BRANCH = True           # one cursor table, one select launch: no parallel branches
+
+    def __init__(self, unet, batch_size, use_graph=True, steps_per_graph=5, *, row_capacity=1024, temb_capacity=256,
+                 out_capacity=None):
+        if unet.device.type != "cuda":
+            raise RuntimeError("SlotEngine needs the UNet on an MI355X ('cuda') device; there is no CPU path")
+        odd = sorted({type(m.processor).__name__ for m in unet.modules() if hasattr(m, "processor")} - {"AttnProcessor2_0"})
+        if odd:
+            raise ValueError(f"SlotEngine: the UNet has attention processors {odd}; slots need the plain one")
+        self.unet, self.scheduler, self.schedule = unet, None, None
+        self.B, self.branches, self.use_graph = int(batch_size), 1, use_graph
+        self.steps_per_graph = max(1, int(os.environ.get("AFLDM_STEPS_PER_GRAPH", steps_per_graph)))
+        self.table = SlotTable(row_capacity, temb_capacity)
+        self.out_capacity = 2 * self.B if out_capacity is None else int(out_capacity)
+        if self.out_capacity < 1:
+            raise ValueError("SlotEngine: out_capacity must be at least 1")
+        self._busy = set()
+        self._allocate()
+
+    timesteps = property(lambda self: self.table.timesteps)
+
+    def _allocate(self):
+        """Every device buffer in the UNet's current dtype and on its device, every slot empty, the tables filled from the
+        host's record; drops the graphs."""
+        unet, dev, B, tb = self.unet, self.unet.device, self.B, self.table
+        c, s = unet.config.in_channels, unet.config.sample_size
+        i32 = dict(dtype=torch.int32, device=dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.lat = torch.zeros(B, c, s, s, **f32)
+        self.x_nhwc = torch.empty(B, s, s, c, dtype=unet.dtype, device=dev)
+        self.graph = self.graph_multi = None
+        # per slot: the cursor, one past the last row, this step's activity flag and timestep, and this step's row of projections
+        self.pos, self.end, self.active = torch.full((B,), -1, **i32), torch.zeros(B, **i32), torch.zeros(B, **i32)
+        self.t_cur = torch.zeros(B, **f32)
+        width = unet._temb_weights(unet.dtype)[3]               # sum Cout of the time_emb_proj layers
+        self.temb_table = torch.zeros(tb.T, width, dtype=unet.dtype, device=dev)
+        self.temb_rows = torch.zeros(B, width, dtype=unet.dtype, device=dev)       # (zeros: a never-filled slot evaluates finite)
+        self.temb_slices = unet.temb_slices(self.temb_rows, per_sample=True)
+        self.row_coef, self.row_t, self.row_temb = torch.zeros(tb.R, 4, **f32), torch.zeros(tb.R, **f32), torch.zeros(tb.R, **i32)
+        # the boundary's buffers: commands and fresh latents (two pinned stagings each, so the host can prepare one boundary
+        # while the previous one's upload waits behind a replay), and the output ring with its pinned mirror
+        self.cmd, self.fresh = torch.full((B, 4), -1, **i32), torch.zeros_like(self.lat)
+        self.out = torch.zeros((self.out_capacity, c, s, s), **f32)
+        self.out_host = torch.zeros((self.out_capacity, c, s, s), dtype=torch.float32, pin_memory=True)
+        self._staging = [(torch.empty((B, 4), dtype=torch.int32, pin_memory=True),
+                          torch.empty((B, c, s, s), dtype=torch.float32, pin_memory=True), torch.cuda.Event()) for _ in range(2)]
+        self._upload(0, 0)
+        self._model_key = model_state_key(unet)
+        self._side, self._sync = [], [ops.new_sync_buffer(dev)]
+        self.hist = self.noise = self.known = self.mask = self.filter = self._static = None
+        self._busy.clear()
+
+    def _upload(self, row0, temb0):
+        """Rows row0 .. and time-embedding rows temb0 .. of the host's record, written into the device tables in place."""
+        tb = self.table
+        if len(tb.t) > row0:
+            dev = self.row_coef.device
+            self.row_coef[row0:len(tb.t)].copy_(torch.tensor(tb.coef[row0:], dtype=torch.float64).to(torch.float32).to(dev))
+            self.row_t[row0:len(tb.t)].copy_(torch.tensor(tb.t[row0:], dtype=torch.float32).to(dev))
+            self.row_temb[row0:len(tb.t)].copy_(torch.tensor(tb.temb[row0:], dtype=torch.int32).to(dev))
+        if len(tb.timesteps) > temb0:
+            self.temb_table[temb0:len(tb.timesteps)].copy_(torch.cat([self.unet.temb_projection(t) for t in tb.timesteps[temb0:]], 0))
+
+    def _retabulate(self):
+        self._upload(len(self.table.t), 0)
+
+    def add_schedule(self, schedule):
+        """(begin, end): the schedule's rows in the row table, appended - with its unseen timesteps' projections - on the first
+        call for this `schedule.key`."""
+        rows, tembs = len(self.table.t), len(self.table.timesteps)
+        span = self.table.add(schedule)
+        self._upload(rows, tembs)
+        return span
+
+    def refresh_if_stale(self):
+        """As the base class; the slots are emptied by a dtype or device change, so the model may only change between requests."""
+        if self._busy and model_state_key(self.unet) != self._model_key:
+            raise RuntimeError(f"SlotEngine: the model changed while {len(self._busy)} requests were in their slots")
+        return super().refresh_if_stale()
+
+    def _step(self):
+        ops.slot_select(self.row_t, self.row_temb, self.pos, self.end, self.t_cur, self.active, self.temb_table, self.temb_rows)
+        self._substep(self.lat, self.x_nhwc)
+
+    def _apply(self, lat, eps, branch):
+        ops.slot_step(lat, eps, self.row_coef, self.pos, self.active)
+
+    def _carried(self):
+        return [self.lat, self.pos, self.t_cur, self.temb_rows, self.active]
+
+    def _rewind(self):
+        pass                        # (the cursors are carried: _capture puts them back)
+
+    def reset(self, latents):
+        raise NotImplementedError("SlotEngine has no schedule of its own: fill its slots with exchange()")
+
+    run = reset
+
+    def exchange(self, harvests, refills):
+        """The boundary between replays.  harvests {slot: ring index}: the slot's latents go to out[index] and on to the pinned
+        out_host[index]; refills {slot: (latents [C, H, W] or [1, C, H, W], already scaled, begin, end)}: the slot starts over on
+        rows begin .. end - 1.  A slot in both is harvested first.  Returns {slot: event behind its device-to-host copy}.
+        Nothing is launched when both are empty."""
+        if not harvests and not refills:
+            return {}
+        for idx in harvests.values():
+            if not 0 <= idx < self.out_capacity:
+                raise ValueError(f"SlotEngine: output ring index {idx} of {self.out_capacity}")
+        self._staging.append(self._staging.pop(0))
+        cmd_host, fresh_host, uploaded = self._staging[-1]
+        uploaded.synchronize()                        # (its previous upload: two boundaries ago)
+        cmd = [[-1, -1, 0, 0] for _ in range(self.B)]
+        on_device = []
+        for i, (slot, (z, begin, end)) in enumerate(refills.items()):
+            if not (0 <= begin <= end <= len(self.table.t)):
+                raise ValueError(f"SlotEngine: rows {begin} .. {end} of {len(self.table.t)}")
+            cmd[slot][1:] = [i, begin, end]
+            z = z.reshape(self.lat.shape[1:])
+            if z.device.type == "cpu":
+                fresh_host[i].copy_(z)
+            else:
+                on_device.append((i, z))
+        for slot, idx in harvests.items():
+            cmd[slot][0] = idx
+        cmd_host.copy_(torch.tensor(cmd, dtype=torch.int32))
+        self.cmd.copy_(cmd_host, non_blocking=True)
+        if len(refills) > len(on_device):
+            self.fresh[:len(refills)].copy_(fresh_host[:len(refills)], non_blocking=True)
+        uploaded.record()
+        for i, z in on_device:
+            self.fresh[i].copy_(z)
+        ops.slot_exchange(self.cmd, self.lat, self.out, self.fresh, self.pos, self.end)
+        self._busy.difference_update(harvests)
+        self._busy.update(refills)
+        events = {}
+        for slot, idx in harvests.items():
+            self.out_host[idx].copy_(self.out[idx], non_blocking=True)
+            events[slot] = torch.cuda.Event()
+            events[slot].record()
+        return events
+
+    def take(self, idx):
+        """out_host[idx] as a tensor of its own [1, C, H, W]; the caller has waited for the harvest's event."""
+        return self.out_host[idx].clone().unsqueeze(0)

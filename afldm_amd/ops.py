@@ -1869,6 +1869,58 @@ def select_step_row(tvals, step_idx, t_out, table, row_out, pre_advance=False):
     return t_out
 
 
+# ----------------------------------------------------------------------------- slot sampler (a step counter per batch row)
+def _slot_ints(B, **tensors):
+    for name, t in tensors.items():
+        _dev(t, name)
+        assert t.dtype == torch.int32 and t.numel() == B, f"slot sampler: {name} must be int32 [{B}]"
+
+
+def slot_select(row_t, row_temb, pos, end, t_out, active, temb_table, temb_rows):
+    """afldm_slot_select: for every slot b with pos[b] + 1 < end[b]: pos[b] += 1, t_out[b] = row_t[pos[b]], active[b] = 1 and
+    temb_rows[b] <- temb_table[row_temb[pos[b]]]; otherwise active[b] = 0 and nothing else.  row_t fp32 [R], row_temb int32 [R],
+    pos / end / active int32 [B], t_out fp32 [B], temb_table [T, n], temb_rows [B, n] (rows of whole 16-byte chunks)."""
+    B, R, T = pos.numel(), row_t.numel(), temb_table.shape[0]
+    _slot_ints(B, pos=pos, end=end, active=active)
+    for name, t in (("row_t", row_t), ("row_temb", row_temb), ("t_out", t_out), ("temb_table", temb_table), ("temb_rows", temb_rows)):
+        _dev(t, name)
+    assert row_t.dtype == t_out.dtype == torch.float32 and row_temb.dtype == torch.int32 and row_temb.numel() == R
+    assert t_out.numel() == B and temb_table.dim() == 2 and tuple(temb_rows.shape) == (B, temb_table.shape[1])
+    assert temb_table.dtype == temb_rows.dtype
+    nbytes = temb_table.shape[1] * temb_table.element_size()
+    check(lib.afldm_slot_select(ptr(row_t), ptr(row_temb), ptr(pos), ptr(end), ptr(t_out), ptr(active), ptr(temb_table),
+                                ptr(temb_rows), B, R, T, nbytes, stream_ptr()), "slot_select")
+    return t_out
+
+
+def slot_step(x, eps_nhwc, row_coef, pos, active):
+    """afldm_slot_step, in place: slot b of x (NCHW fp32) with active[b] != 0 takes ddim_step's update with the row
+    row_coef[pos[b]] (row_coef fp32 [R, 4]); the other slots are not touched.  eps NHWC dtype."""
+    _dev(x, "x"); _dev(eps_nhwc, "eps"); _dev(row_coef, "row_coef")
+    B, C, H, W = x.shape
+    _slot_ints(B, pos=pos, active=active)
+    assert x.dtype == row_coef.dtype == torch.float32 and row_coef.dim() == 2 and row_coef.shape[1] == 4
+    assert tuple(eps_nhwc.shape) == (B, H, W, C)
+    check(lib.afldm_slot_step(ptr(x), ptr(eps_nhwc), ptr(row_coef), ptr(pos), ptr(active), B, row_coef.shape[0], C, H, W,
+                              _code(eps_nhwc), stream_ptr()), "slot_step")
+    return x
+
+
+def slot_exchange(cmd, lat, out, fresh, pos, end):
+    """afldm_slot_exchange: cmd int32 [B, 4] = {harvest, refill, begin, end} per slot - out[harvest] <- lat[b] where harvest >= 0,
+    then lat[b] <- fresh[refill], pos[b] = begin - 1, end[b] = end where refill >= 0.  lat [B, ...], out [No, ...], fresh
+    [Nf, ...] fp32 with equal trailing shapes."""
+    B = lat.shape[0]
+    for name, t in (("cmd", cmd), ("lat", lat), ("out", out), ("fresh", fresh)):
+        _dev(t, name)
+    _slot_ints(B, pos=pos, end=end)
+    assert cmd.dtype == torch.int32 and tuple(cmd.shape) == (B, 4)
+    assert lat.dtype == out.dtype == fresh.dtype == torch.float32 and lat.shape[1:] == out.shape[1:] == fresh.shape[1:]
+    check(lib.afldm_slot_exchange(ptr(cmd), ptr(lat), ptr(out), ptr(fresh), ptr(pos), ptr(end), B, lat[0].numel(), out.shape[0],
+                                  fresh.shape[0], stream_ptr()), "slot_exchange")
+    return lat
+
+
 FLOW_PICK, FLOW_POOL = 0, 1
 
 

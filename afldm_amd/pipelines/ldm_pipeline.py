@@ -76,6 +76,33 @@ class MyLDMPipeline(DiffusionPipeline):
         latents = eng.run(latents).to(self.unet.dtype)
         return self._deliver(latents, output_type, return_dict)
 
+    @torch.no_grad()
+    def sample_mixed(self, num_inference_steps, generator=None, latents=None, output_type="pil", return_dict=True, slots=None,
+                     steps_per_graph=5, engines=1):
+        """One DDIM sample (eta = 0) per entry of `num_inference_steps`, each with its own step count, in request order - through a
+        SamplingServer (afldm_amd/serving.py): the requests share the batch-`slots` graphs (default: one slot per request, 64 at
+        the most, per engine) and a slot that finishes takes the next request.  generator: None, one torch.Generator (the start
+        latents are drawn from it request by request) or one per request; latents: the start latents [n, C, S, S] instead.
+        Request i is pipe(batch_size=1, num_inference_steps=num_inference_steps[i], generator=generator[i]) to the rounding of
+        the convolutions at another batch size.  output_type as __call__.  The server is kept for the next call."""
+        from ..serving import SamplingServer
+        counts = [int(n) for n in num_inference_steps]
+        if isinstance(generator, (list, tuple)) and len(generator) != len(counts):
+            raise ValueError(f"sample_mixed: {len(generator)} generators for {len(counts)} requests")
+        if latents is not None and latents.shape[0] != len(counts):
+            raise ValueError(f"sample_mixed: {latents.shape[0]} start latents for {len(counts)} requests")
+        slots = max(1, min(len(counts), 64)) if slots is None else int(slots)
+        key = (id(self.unet), slots, int(steps_per_graph), int(engines))
+        if key not in self.__dict__.get("_slot_servers", ()):
+            self.__dict__["_slot_servers"] = {key: SamplingServer(self, slots, steps_per_graph, engines)}
+        server = self.__dict__["_slot_servers"][key]
+        tickets = [server.submit(n, generator[i] if isinstance(generator, (list, tuple)) else generator,
+                                 None if latents is None else latents[i:i + 1]) for i, n in enumerate(counts)]
+        server.run()
+        if not tickets:
+            raise ValueError("sample_mixed: no requests")
+        return server.decode(tickets, output_type, return_dict)
+
     def _deliver(self, latents, output_type, return_dict):
         """'latent' -> the latents; 'pt' -> decoded tensor in [-1, 1]; 'np' / 'pil' -> [0, 1] NHWC arrays / PIL images
         (wrapped in ImagePipelineOutput unless return_dict is False)."""

@@ -1,0 +1,213 @@
+"""SamplingServer — continuous batching over SlotEngine (afldm_amd/engine.py): requests of different step counts share the
+batch-`slots` graphs, and a slot that finishes is harvested and refilled from the queue while its neighbours go on.
+
+    server = SamplingServer(pipe, slots=64)
+    tickets = [server.submit(n, generator=torch.Generator().manual_seed(i)) for i, n in enumerate((20, 50, 35))]
+    server.run()
+    latents = [t.result() for t in tickets]          # fp32 [1, C, H, W] each, in request order
+
+The host keeps an exact mirror of every slot - whose request it holds and how many evaluations it still needs - so it never
+reads the device to schedule.  One turn of an engine is a boundary and a replay group:
+
+    harvest   every slot whose mirror says it is finished, into a free entry of the output ring
+    refill    the free slots from the queue, in arrival order, lowest slot first
+    group     k = min(steps_per_graph, m) evaluations, m = the SMALLEST remaining count among the occupied slots while requests
+              wait (no slot then sits finished while a request could have it), the LARGEST once the queue is empty (frozen slots
+              cost nothing more, and no boundary is needed before the last request ends)
+
+The kernels freeze a finished slot, so every grouping gives the same latents; the policy only decides utilisation.  The host
+runs ahead of the GPU: a turn only queues work.  Results leave the ring by non-blocking device-to-host copies with one event per
+ticket; a ring entry is free again once its ticket has been collected, and a turn that finds the ring full waits for the oldest.
+
+engines=2 builds two engines of `slots` slots each on two streams and deals the requests out alternately: two jobs in flight on
+one GPU, each filling the other's launch ramps and tails."""
+import collections
+import contextlib
+
+import torch
+
+from .utils import randn_tensor
+
+
+class Ticket:
+    """One submitted sample.  done(): its latents have arrived on the host; result(): the fp32 latents [1, C, H, W] (waits for the
+    copy if the sample has been harvested, raises if it has not: drive the server with run() or poll())."""
+
+    def __init__(self, server, index, engine, steps, span, latents):
+        self.server, self.index, self.engine, self.steps = server, index, engine, steps
+        self._span, self._start, self._ring, self._event, self._latents = span, latents, None, None, None
+
+    def done(self):
+        return self._latents is not None or (self._event is not None and self._event.query())
+
+    def result(self):
+        if self._latents is None:
+            if self._event is None:
+                raise RuntimeError(f"Ticket {self.index}: not sampled yet - call SamplingServer.run() or poll()")
+            self.server._collect(self)
+        self.server._verify(self.engine)
+        return self._latents
+
+
+class SamplingServer:
+    def __init__(self, pipe, slots=64, steps_per_graph=5, engines=1, use_graph=True, engine_factory=None, **capacities):
+        """pipe: a MyLDMPipeline (its UNet and scheduler config); slots: per engine; capacities: SlotEngine's row_capacity,
+        temb_capacity, out_capacity.  engine_factory(i): builds engine i instead (the host tests pass a counting fake)."""
+        if slots < 1 or engines < 1 or steps_per_graph < 1:
+            raise ValueError("SamplingServer: slots, engines and steps_per_graph must be at least 1")
+        self.pipe, self.slots, self.steps_per_graph = pipe, int(slots), int(steps_per_graph)
+        self._streams, self.engines = [], []
+        for i in range(engines):
+            # one stream per engine when there are several; a single engine works on the caller's current stream
+            self._streams.append(torch.cuda.Stream() if engines > 1 and engine_factory is None else None)
+            with self._on(i):
+                if engine_factory is not None:
+                    self.engines.append(engine_factory(i))
+                else:
+                    from .engine import SlotEngine
+                    self.engines.append(SlotEngine(pipe.unet, self.slots, use_graph, self.steps_per_graph, **capacities))
+        if any(s is not None for s in self._streams):
+            torch.cuda.synchronize()
+        self._queue = [collections.deque() for _ in self.engines]
+        self._slot = [[None] * self.slots for _ in self.engines]       # the mirror: None or [ticket, evaluations still to run]
+        self._free = [list(range(e.out_capacity)) for e in self.engines]
+        self._pending = [collections.deque() for _ in self.engines]    # harvested tickets that still hold a ring entry, oldest first
+        self._unchecked = [False] * engines
+        self._count = 0
+        self.replays = self.evaluations = self.useful = 0              # graph replays, slot evaluations, those of occupied slots
+
+    def _on(self, e):
+        s = self._streams[e]
+        return contextlib.nullcontext() if s is None else torch.cuda.stream(s)
+
+    # ------------------------------------------------------------------------------------------------ requests
+    def _schedule(self, num_inference_steps):
+        from .schedulers.ddim import DDIMScheduler
+        from .schedulers.dpmsolver import DPMSolverMultistepScheduler
+        sched = self.pipe.scheduler
+        if isinstance(sched, DPMSolverMultistepScheduler):
+            raise NotImplementedError("SamplingServer needs a DDIMScheduler: slots take 'ddim' schedules only")
+        return DDIMScheduler.from_config(sched.config).schedule(int(num_inference_steps))
+
+    def submit(self, num_inference_steps=50, generator=None, latents=None, schedule=None):
+        """Queue ONE sample of `num_inference_steps` DDIM steps (eta = 0), or of any "ddim"-kind Schedule given as `schedule`.
+        The start latents are drawn as pipe(batch_size=1, generator=...) draws them - randn_tensor([1, C, S, S]) with the
+        caller's generator - unless `latents` [1, C, S, S] is given, and scaled by the schedule's init_noise_sigma."""
+        sched = schedule if schedule is not None else self._schedule(num_inference_steps)
+        e = self._count % len(self.engines)
+        with self._on(e):
+            span = self.engines[e].add_schedule(sched)
+        cfg = self.pipe.unet.config
+        shape = (1, cfg.in_channels, cfg.sample_size, cfg.sample_size)
+        if latents is None:
+            latents = randn_tensor(shape, generator=generator)
+        elif tuple(latents.shape) != shape:
+            raise ValueError(f"SamplingServer.submit: latents {tuple(latents.shape)}, want {shape}")
+        start = latents.to(torch.float32) * sched.init_noise_sigma
+        ticket = Ticket(self, self._count, e, span[1] - span[0], span, start)
+        self._count += 1
+        if ticket.steps == 0:
+            ticket._latents, ticket._start = start.cpu(), None
+        else:
+            self._queue[e].append(ticket)
+        return ticket
+
+    # ------------------------------------------------------------------------------------------------ the policy
+    def group_size(self, remaining, waiting):
+        """Evaluations in the next replay group: `remaining` the counts of the occupied slots (all > 0), `waiting` whether the
+        queue holds requests.  See the module docstring."""
+        return min(self.steps_per_graph, min(remaining) if waiting else max(remaining))
+
+    def _turn(self, e):
+        """One boundary and one replay group of engine e; whether there was anything to do."""
+        eng, slots, queue = self.engines[e], self._slot[e], self._queue[e]
+        if queue and all(s is None for s in slots):
+            # between requests only: a dtype or device change re-allocates the engine's buffers, the output ring among them
+            while self._pending[e]:
+                self._collect(self._pending[e][0])
+            with self._on(e):
+                eng.refresh_if_stale()
+        finished = [b for b, s in enumerate(slots) if s is not None and s[1] == 0]
+        self._reap(e, min(len(finished), eng.out_capacity))
+        finished = finished[:len(self._free[e])]        # (a ring smaller than the batch: the others wait a turn, frozen)
+        harvests, refills, harvested = {}, {}, {}
+        for b in finished:
+            ticket = harvested[b] = slots[b][0]
+            ticket._ring = harvests[b] = self._free[e].pop()
+            self._pending[e].append(ticket)
+            slots[b] = None
+        for b in range(len(slots)):
+            if slots[b] is None and queue:
+                ticket = queue.popleft()
+                refills[b] = (ticket._start, *ticket._span)
+                slots[b] = [ticket, ticket.steps]
+                ticket._start = None
+        with self._on(e):
+            events = eng.exchange(harvests, refills)
+            for b, ticket in harvested.items():
+                ticket._event = events[b]
+            remaining = [s[1] for s in slots if s is not None and s[1] > 0]
+            if not remaining:
+                return any(s is not None for s in slots)
+            k = self.group_size(remaining, bool(queue))
+            eng.step(k)
+        self._unchecked[e] = True
+        self.replays += k // self.steps_per_graph + k % self.steps_per_graph
+        self.evaluations += k * len(slots)
+        for s in slots:
+            if s is not None:
+                self.useful += min(k, s[1])
+                s[1] = max(0, s[1] - k)
+        return True
+
+    def _reap(self, e, need):
+        """Collect every harvested ticket of engine e whose copy has arrived, then - only if fewer than `need` ring entries are
+        free - wait for the oldest ones."""
+        for ticket in [t for t in self._pending[e] if t._event is not None and t._event.query()]:
+            self._collect(ticket)
+        while len(self._free[e]) < need:
+            if not self._pending[e]:
+                raise RuntimeError(f"SamplingServer: an output ring of {self.engines[e].out_capacity} for {need} finished slots")
+            self._collect(self._pending[e][0])
+
+    def _collect(self, ticket):
+        e = ticket.engine
+        ticket._event.synchronize()
+        ticket._latents = self.engines[e].take(ticket._ring)
+        self._free[e].append(ticket._ring)
+        self._pending[e].remove(ticket)
+        ticket._ring = None
+
+    def _verify(self, e):
+        """The engine's hand-over error words, read once after the replays that could have set them (DenoiseEngine.check_errors)."""
+        if self._unchecked[e]:
+            self._unchecked[e] = False
+            with self._on(e):
+                self.engines[e].check_errors()
+
+    # ------------------------------------------------------------------------------------------------ driving
+    def poll(self, max_replays=None):
+        """Turns of every engine in rotation until nothing is left to do or `max_replays` graph replays have been queued (the
+        turn that reaches the bound is completed).  Returns the number of replays queued.  Does not wait for the GPU."""
+        before = self.replays
+        busy = True
+        while busy and (max_replays is None or self.replays - before < max_replays):
+            busy = False
+            for e in range(len(self.engines)):
+                if self._turn(e):
+                    busy = True
+        return self.replays - before
+
+    def run(self):
+        """Until the queue and the slots are empty and every result is on the host."""
+        self.poll()
+        for e in range(len(self.engines)):
+            while self._pending[e]:
+                self._collect(self._pending[e][0])
+            self._verify(e)
+
+    def decode(self, tickets, output_type="pil", return_dict=True):
+        """The tickets' latents, in the order given, through the pipeline's delivery (MyLDMPipeline._deliver)."""
+        unet = self.pipe.unet
+        latents = torch.cat([t.result() for t in tickets]).to(device=unet.device, dtype=unet.dtype)
+        return self.pipe._deliver(latents, output_type, return_dict)

@@ -630,6 +630,35 @@ int afldm_select_timestep(const float* tvals, int* step_idx, float* t_out, int p
 int afldm_select_step_row(const float* tvals, int* step_idx, float* t_out, int pre_advance, const void* table,
                           void* row_out, size_t row_bytes, afldm_stream_t stream);
 
+/* ---- slot sampler: a step counter per batch row (continuous batching) ------------------------------------------------
+ * Every batch row b of B (a "slot") walks its own stretch [begin, end) of one shared row table of capacity R:
+ *   pos[b], end[b]  device int32: the row of the slot's last evaluation (begin - 1 before the first) and one past its last row;
+ *                   the slot is ACTIVE in a step iff pos[b] + 1 < end[b]
+ *   row_coef [R][4] the "ddim" row (c0, c1, c2, c3);  row_t [R] the timestep (float);  row_temb [R] int32: the row of the
+ *                   time-embedding table [T][row_bytes] of that timestep (schedules that share a timestep share the row)
+ * The tables' contents may change between replays of a captured graph; their addresses are what the graph holds.  All three
+ * calls are stream-ordered, capturable and allocate nothing.  An index read from device memory that falls outside its table
+ * makes the slot inactive (select), skips it (step) or skips the command (exchange): nothing is read or written out of range.
+ *
+ * afldm_slot_select - the step prologue, ONE launch of B workgroups, and the only place a cursor moves.  Active slot:
+ *   pos[b] += 1; t_out[b] = row_t[pos[b]]; active[b] = 1; temb_rows[b] <- temb_table[row_temb[pos[b]]] (row_bytes % 16 == 0,
+ *   16-byte chunks).  Inactive slot: active[b] = 0 and nothing else - t_out[b] and its row of temb_rows keep their last
+ *   contents, so the evaluation of a frozen slot stays finite. */
+int afldm_slot_select(const float* row_t, const int* row_temb, int* pos, const int* end, float* t_out, int* active,
+                      const void* temb_table, void* temb_rows, int B, int R, int T, size_t row_bytes, afldm_stream_t stream);
+/* afldm_slot_step - the update, in place: for every element of a slot with active[b] != 0
+ *   x0 = (x - c1 eps) / c0;  x = c2 x0 + c3 eps,  (c0 .. c3) = row_coef[pos[b]]
+ * in afldm_ddim_step's float operations and order (a slot gives afldm_ddim_step's bits for the same row).  Elements of an
+ * inactive slot are neither read nor written; pos is only read.  x: NCHW fp32 [B,C,H,W]; eps: NHWC dtype. */
+int afldm_slot_step(float* x, const void* eps, const float* row_coef, const int* pos, const int* active, int B, int R, int C,
+                    int H, int W, int dtype, afldm_stream_t stream);
+/* afldm_slot_exchange - between replays, driven by the device command buffer cmd [B][4] = {harvest, refill, begin, end} (int32):
+ *   harvest >= 0: out[harvest] <- lat[b];  then refill >= 0: lat[b] <- fresh[refill], pos[b] = begin - 1, end[b] = end
+ * (the harvest of an element precedes its refill, in the same thread); {-1, -1, ., .} leaves the slot alone.  lat [B], out
+ * [out_rows], fresh [fresh_rows]: fp32 rows of slot_elems floats. */
+int afldm_slot_exchange(const int* cmd, float* lat, float* out, const float* fresh, int* pos, int* end, int B, size_t slot_elems,
+                        int out_rows, int fresh_rows, afldm_stream_t stream);
+
 /* ---- masked equivariance metrics (shift_utils/metrics.py:5-20) ------------------------------
  * One pass over a, b [B][n] (dtype) and mask [B][n] fp32: out[b] = { sum ((a - b) mask)^2, sum mask,
  * max(a mask), min(a mask), max(b mask), min(b mask) } (fp32 [B][6]).  mask_mse = mean_b out[b][0] / out[b][1];
