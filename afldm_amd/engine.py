@@ -35,6 +35,11 @@ window: `lat` holds the P * nwin windows of a panorama.Geometry, the canvas is a
 afldm_pano_step, which applies the "sde" row per window, averages over the windows that cover each canvas element and writes both
 the canvas and its crops (the next `lat`).  The noise buffer is canvas-shaped, [steps, P, C, Hc, Wc].
 
+OutpaintEngine (kind "outpaint", DDIMScheduler.outpaint_schedule: RePaint on such a canvas) is PanoramaEngine with
+afldm_pano_repaint_step as the last line: the "repaint" row per window, the same averages, then the blend with a known canvas under
+a canvas mask - run(canvas, draw=..., known=(known_canvas, canvas_mask)) - and RePaint's jump back up.  The noise buffer is
+[steps, 3, P, C, Hc, Wc].
+
 PAGEngine (kind "pag", DDIMScheduler.pag_schedule: perturbed-attention guidance) samples B latents with a UNet batch of 2 B: both
 halves of `x_nhwc` hold the same latents, the attention blocks named by `sites` run PAGAttnProcessor (the plain block on the first
 half, the identity-attention block on the second), and the last line of a step is afldm_pag_step, which reads both halves of eps.
@@ -402,6 +407,22 @@ class DenoiseEngine:
         if stage is not None:
             stage[1].record()
 
+    def _check_known(self, known):
+        """run()'s known=, checked against the static buffers of the kind before anything is written: (z0, extra), or (None, None)
+        for a kind that takes none."""
+        if (self._static is None) != (known is None):
+            raise ValueError("DenoiseEngine: known=(z0, mask) goes with a 'repaint' schedule and known=(ref, L) with an 'ilvr' "
+                             "one, and only with those")
+        if known is None:
+            return None, None
+        name, second, broadcast = self._static
+        fits = [tuple(second.shape)] + ([(1,) + tuple(second.shape[1:])] if broadcast else [])
+        z0, extra = known
+        if tuple(z0.shape) != tuple(self.lat.shape) or tuple(extra.shape) not in fits:
+            raise ValueError(f"DenoiseEngine: known latents {tuple(z0.shape)} / {name} {tuple(extra.shape)}, want "
+                             f"{tuple(self.lat.shape)} / {tuple(second.shape)}" + (" (or batch 1)" if broadcast else ""))
+        return z0, extra
+
     @torch.no_grad()
     def run(self, latents, draw=None, known=None):
         """latents -> the sampled latents (fp32).  An "sde", "repaint" or "ilvr" schedule needs `draw`: a callable returning the next
@@ -411,16 +432,7 @@ class DenoiseEngine:
         (1 = keep), an "ilvr" schedule known = (ref, L): the reference latents [B, C, H, W] and the low-pass matrix [H, H].
         Both are written to the engine's static buffers before the first replay.  `draw` is ignored when the engine has no noise
         buffer (a "pano", "pag" or "sag" schedule none of whose steps draws, "ddim", "dpm")."""
-        if (self._static is None) != (known is None):
-            raise ValueError("DenoiseEngine: known=(z0, mask) goes with a 'repaint' schedule and known=(ref, L) with an 'ilvr' "
-                             "one, and only with those")
-        if known is not None:
-            name, second, broadcast = self._static
-            fits = [tuple(second.shape)] + ([(1,) + tuple(second.shape[1:])] if broadcast else [])
-            z0, extra = known
-            if tuple(z0.shape) != tuple(self.lat.shape) or tuple(extra.shape) not in fits:
-                raise ValueError(f"DenoiseEngine: known latents {tuple(z0.shape)} / {name} {tuple(extra.shape)}, want "
-                                 f"{tuple(self.lat.shape)} / {tuple(second.shape)}" + (" (or batch 1)" if broadcast else ""))
+        z0, extra = self._check_known(known)
         self.reset(latents)
         if known is not None:          # (after reset: a dtype or device change re-allocates the static buffers)
             self.known.copy_(z0)
@@ -491,6 +503,37 @@ class PanoramaEngine(DenoiseEngine):
         self.canvas.copy_(canvas.to(device=self.canvas.device, dtype=torch.float32) * self.schedule.init_noise_sigma)
         ops.window_crop(self.canvas, self.geometry, out=self.lat)
         self.step_idx.fill_(-1)
+
+
+class OutpaintEngine(PanoramaEngine):
+    """Outpainting on the replayed graphs: RePaint on a MultiDiffusion canvas.  PanoramaEngine with afldm_pano_repaint_step in
+    afldm_pano_step's place: the "repaint" row per window, the means over the covering windows, then RePaint's blend with the
+    content to keep and its jump back up, all on the canvas.  run(canvas, draw=..., known=(known_canvas, canvas_mask)): the content
+    [P, C, Hc, Wc] and the mask [P | 1, 1, Hc, Wc] (1 = keep) are per-run static buffers, so another image or mask replays the
+    same graphs; `draw` returns canvas-shaped tensors, up to three per evaluation (z_k, z_u, z_b)."""
+
+    def _outpaint_state(self):
+        """The fp32 canvas, the count average as the window weight, the run's known canvas and canvas mask (a batch-1 mask is
+        broadcast) and three canvas-shaped noise slots per step."""
+        g, dev = self.geometry, self.unet.device
+        self.canvas = torch.zeros(self.P, self.lat.shape[1], g.Hc, g.Wc, dtype=torch.float32, device=dev)
+        self.wt = torch.ones(g.S, g.S, dtype=torch.float32, device=dev)
+        self.known = torch.zeros_like(self.canvas)
+        self.mask = torch.zeros(self.P, 1, g.Hc, g.Wc, dtype=torch.float32, device=dev)
+        self._static = ("mask", self.mask, True)
+        return [(self.known, self.mask, self._noise(self.canvas.shape)[0], self.wt, g)]
+
+    UPDATES = {"outpaint": (ops.pano_repaint_step, _outpaint_state)}
+
+    def _check_known(self, known):
+        if known is None:
+            raise ValueError("OutpaintEngine: run(canvas, draw=..., known=(known_canvas, canvas_mask)) needs the content to keep")
+        z0, mask = known
+        want = tuple(self.canvas.shape)
+        if tuple(z0.shape) != want or tuple(mask.shape) not in [tuple(self.mask.shape), (1,) + tuple(self.mask.shape[1:])]:
+            raise ValueError(f"OutpaintEngine: known canvas {tuple(z0.shape)} / mask {tuple(mask.shape)}, want {want} / "
+                             f"{tuple(self.mask.shape)} (or batch 1)")
+        return z0, mask
 
 
 @contextlib.contextmanager

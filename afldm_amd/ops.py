@@ -1826,6 +1826,36 @@ def pano_step(canvas, eps_nhwc, noise, wt, geometry, coef, step_idx, advance=Fal
     return out, windows_out
 
 
+def pano_repaint_step(canvas, eps_nhwc, known, mask, noise, wt, geometry, coef, step_idx, advance=False, out=None, windows_out=None):
+    """The fused outpainting update (afldm_pano_repaint_step): RePaint on a MultiDiffusion canvas.  canvas, known fp32
+    [P, C, Hc, Wc], mask fp32 [P, 1, Hc, Wc] (1 = keep), eps and wt as pano_step; noise: fp32 view [steps, 3, P, C, Hc, Wc] (slots
+    z_k, z_u, z_b) whose last four dimensions are contiguous; coef float[12*nsteps] "repaint" rows and step_idx int32[1] on device.
+    Returns (canvas_out, windows_out) as pano_step."""
+    g = geometry
+    P, C = _pano_canvas("pano_repaint_step", canvas, g)
+    _dev(eps_nhwc, "eps"); _dev(known, "known"); _dev(mask, "mask"); _pano_weights("pano_repaint_step", wt, g)
+    if tuple(eps_nhwc.shape) != (P * g.nwin, g.S, g.S, C):
+        raise ValueError(f"pano_repaint_step: eps {tuple(eps_nhwc.shape)}, want NHWC {(P * g.nwin, g.S, g.S, C)}")
+    if known.dtype != torch.float32 or known.shape != canvas.shape or not known.is_contiguous():
+        raise ValueError(f"pano_repaint_step: known must be contiguous fp32 {tuple(canvas.shape)}, got {known.dtype} "
+                         f"{tuple(known.shape)}")
+    if mask.dtype != torch.float32 or tuple(mask.shape) != (P, 1, g.Hc, g.Wc) or not mask.is_contiguous():
+        raise ValueError(f"pano_repaint_step: mask must be contiguous fp32 {(P, 1, g.Hc, g.Wc)}, got {mask.dtype} "
+                         f"{tuple(mask.shape)}")
+    noise_args = _noise_view(noise, canvas.shape, 3)
+    if out is None:
+        out = torch.empty_like(canvas)
+    if windows_out is None:
+        windows_out = torch.empty(P * g.nwin, C, g.S, g.S, dtype=torch.float32, device=canvas.device)
+    _dev(out, "out"); _dev(windows_out, "windows_out")
+    assert out.dtype == windows_out.dtype == torch.float32 and out.shape == canvas.shape
+    assert tuple(windows_out.shape) == (P * g.nwin, C, g.S, g.S)
+    check(lib.afldm_pano_repaint_step(ptr(canvas), ptr(eps_nhwc), ptr(known), ptr(mask), *noise_args, ptr(wt), ptr(out),
+                                      ptr(windows_out), ptr(coef), ptr(step_idx), int(advance), P, C, *_geom_args(g),
+                                      _code(eps_nhwc), stream_ptr()), "pano_repaint_step")
+    return out, windows_out
+
+
 def window_fuse(windows, wt, geometry, out=None):
     """windows NCHW fp32 / bf16 [P * nwin, C, S, S] -> the fp32 canvas [P, C, Hc, Wc] of their wt-weighted mean over the windows
     that cover each element (afldm_window_fuse); wt fp32 [S, S] > 0."""

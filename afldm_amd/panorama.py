@@ -7,7 +7,10 @@ Per axis, `window_origins(extent, S, stride, circular)`:
     not circular:  0, stride, 2 stride, ... while o + S < extent, then a last window flush at extent - S (the last gap may be
                    shorter than `stride`); extent == S gives (0,)
     circular:      k stride for k < ceil(extent / stride); the window covers (o + u) mod extent
-A 2-D grid is the product of the two lists, window k = iy * nx + ix.  At most MAX_ORIGINS windows per axis."""
+A 2-D grid is the product of the two lists, window k = iy * nx + ix.  At most MAX_ORIGINS windows per axis.
+
+`place(Hc, Wc, S, top, left, margin, wrap_x)` is where a window-sized block given to MyLDMPipeline.outpaint lies on the canvas: the
+rows and columns of the paste and of the kept rectangle, and the canvas mask."""
 from dataclasses import dataclass
 
 MAX_ORIGINS = 16
@@ -70,6 +73,49 @@ class Geometry:
     def corners(self):
         """(oy, ox) of window k = iy * nx + ix, in k order."""
         return [(y, x) for y in self.oy for x in self.ox]
+
+
+@dataclass(frozen=True)
+class Placement:
+    """Where an S x S block lies on a canvas (place): the canvas rows and columns of its S rows and columns, in block order, and
+    those of the kept rectangle - the block shrunk by `margin` on each side."""
+    top: int
+    left: int
+    rows: tuple
+    cols: tuple
+    keep_rows: tuple
+    keep_cols: tuple
+
+    def mask(self, Hc, Wc):
+        """The canvas mask as Hc lists of Wc floats: 1.0 on the kept rectangle, 0.0 elsewhere."""
+        rows, cols = set(self.keep_rows), set(self.keep_cols)
+        return [[1.0 if y in rows and x in cols else 0.0 for x in range(int(Wc))] for y in range(int(Hc))]
+
+
+def place(Hc, Wc, S, top=None, left=None, margin=0, wrap_x=False):
+    """The Placement of an S x S block with its corner at (top, left) on an Hc x Wc canvas, all in the canvas's units (the paste and
+    the mask of MyLDMPipeline.outpaint).  None centres the block on that axis.  On a wrapping x axis `left` may be anywhere in
+    [0, Wc) and the columns are taken modulo Wc; otherwise the block has to lie inside the canvas.  `margin`: the kept rectangle
+    is the block without its outer `margin` rows and columns.  Raises ValueError for a position off the grid (not an integer)
+    or outside the canvas, and for a margin that leaves nothing."""
+    Hc, Wc, S = int(Hc), int(Wc), int(S)
+    if S < 1 or S > Hc or S > Wc:
+        raise ValueError(f"place: a block of {S} on a {Hc} x {Wc} canvas")
+    top = (Hc - S) // 2 if top is None else top
+    left = (Wc - S) // 2 if left is None else left
+    for name, v in (("top", top), ("left", left), ("margin", margin)):
+        if int(v) != v:
+            raise ValueError(f"place: {name} = {v} is off the grid")
+    top, left, margin = int(top), int(left), int(margin)
+    if not 0 <= top <= Hc - S:
+        raise ValueError(f"place: rows {top} .. {top + S - 1} leave the canvas of {Hc} rows")
+    if not (0 <= left < Wc if wrap_x else 0 <= left <= Wc - S):
+        raise ValueError(f"place: columns {left} .. {left + S - 1} leave the {'wrapping ' if wrap_x else ''}canvas of {Wc} columns")
+    if margin < 0 or 2 * margin >= S:
+        raise ValueError(f"place: a margin of {margin} leaves nothing of a block of {S}")
+    rows = tuple(range(top, top + S))
+    cols = tuple((left + v) % Wc for v in range(S))
+    return Placement(top, left, rows, cols, rows[margin:S - margin], cols[margin:S - margin])
 
 
 def feather(n):

@@ -72,3 +72,11 @@ class I2SBLDMPipeline(MyLDMPipeline):
     def panorama(self, *args, **kwargs):
         raise NotImplementedError("I2SBLDMPipeline: MultiDiffusion panoramas are defined for the unconditional sampler "
                                   "(MyLDMPipeline.panorama); the bridge starts from an encoded image of the window's size")
+
+    def outpaint_latents(self, *args, **kwargs):
+        raise NotImplementedError("I2SBLDMPipeline: outpainting is defined for the unconditional sampler "
+                                  "(MyLDMPipeline.outpaint_latents); the bridge starts from an encoded image of the window's size")
+
+    def outpaint(self, *args, **kwargs):
+        raise NotImplementedError("I2SBLDMPipeline: outpainting is defined for the unconditional sampler "
+                                  "(MyLDMPipeline.outpaint); the bridge starts from an encoded image of the window's size")

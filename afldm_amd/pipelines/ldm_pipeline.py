@@ -552,3 +552,101 @@ class MyLDMPipeline(DiffusionPipeline):
             return canvas
         decoded = self.decode_panorama(canvas, self.panorama_geometry(int(height) // r, int(width) // r, lstride, circular))
         return self._images(decoded, output_type, return_dict)
+
+    # ------------------------------------------------------------------------------------------------ outpainting
+    @torch.no_grad()
+    def outpaint_latents(self, known_canvas, canvas_mask, stride=None, circular=False, num_inference_steps=50, eta=0.0,
+                         jump_length=10, jump_n_sample=10, generator=None, latents=None, use_graph=True):
+        """RePaint on a MultiDiffusion canvas, in latent space: sample canvases [P, C, Hc, Wc] that agree with `known_canvas` where
+        `canvas_mask` [P | 1, 1, Hc, Wc] is 1 and are generated where it is 0 (soft values blend) - a picture around a given crop,
+        or a strip of a given panorama repainted.  The canvas is known_canvas's; the windows are panorama_geometry's (`stride`,
+        `circular`).  Every evaluation runs the UNet on the windows as one batch, takes RePaint's reverse step per window, fuses
+        the steps by the plain mean over the windows that cover an element (panorama_latents), blends in the known content
+        noised to the same level and, where the schedule jumps, noises the canvas back up (inpaint_latents).  The schedule is
+        DDIMScheduler.outpaint_schedule: every evaluation ends in one afldm_pano_repaint_step, on replayed HIP graphs
+        (use_graph), or runs statement by statement in the eager loop below, which makes the same draws from `generator` in the
+        same order - the start canvas (unless `latents` [P, C, Hc, Wc] is given), then per evaluation canvas-shaped z_k, z_u, z_b
+        where the schedule draws them.  Needs no VAE.  Returns the fp32 canvas; with a hard mask the kept latents are
+        `known_canvas` exactly."""
+        from .. import ops
+        from ..engine import OutpaintEngine
+        self._refuse_dpm("outpaint_latents")
+        c, s, dev = self.unet.config.in_channels, self.unet.config.sample_size, self.unet.device
+        if known_canvas.dim() != 4 or known_canvas.shape[1] != c or known_canvas.shape[2] < s or known_canvas.shape[3] < s:
+            raise ValueError(f"outpaint_latents: known_canvas {tuple(known_canvas.shape)}, want [P, {c}, >= {s}, >= {s}]")
+        P, _, Hc, Wc = known_canvas.shape
+        if canvas_mask.dim() != 4 or tuple(canvas_mask.shape[1:]) != (1, Hc, Wc) or canvas_mask.shape[0] not in (1, P):
+            raise ValueError(f"outpaint_latents: canvas_mask {tuple(canvas_mask.shape)}, want [{P} or 1, 1, {Hc}, {Wc}]")
+        shape = (P, c, Hc, Wc)
+        if latents is not None and tuple(latents.shape) != shape:
+            raise ValueError(f"outpaint_latents: latents {tuple(latents.shape)}, want {shape}")
+        geom = self.panorama_geometry(Hc, Wc, stride, circular)
+        self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
+        sched = self.scheduler.outpaint_schedule(num_inference_steps, eta, jump_length, jump_n_sample)
+        known = known_canvas.to(device=dev, dtype=torch.float32).contiguous()
+        mask = canvas_mask.to(device=dev, dtype=torch.float32).contiguous()
+        ones = torch.ones(s, s, dtype=torch.float32, device=dev)
+
+        def eager(x, t, row, zs):
+            p, q, lo, hi, a, b, cz, k0, k1, u0, u1, _ = row
+            zk, zu, zb = zs
+            win = ops.window_crop(x, geom)                                    # [P * nwin, C, S, S]
+            eps = self.unet(win.to(self.unet.dtype), t).sample.float()
+            x0 = torch.clamp(p * win + q * eps, lo, hi)
+            unknown = a * ops.window_fuse(x0.contiguous(), ones, geom) + b * ops.window_fuse(eps.contiguous(), ones, geom)
+            if zu is not None:
+                unknown = unknown + cz * zu
+            knownp = k0 * known if zk is None else k0 * known + k1 * zk
+            y = mask * knownp + (1 - mask) * unknown
+            x = u0 * y if zb is None else u0 * y + u1 * zb
+            return x.contiguous()
+        return self._sample(sched, shape, generator, latents, use_graph, "_outpaint_engines", eager, OutpaintEngine, P * geom.nwin,
+                            known=(known, mask), geometry=geom)
+
+    @torch.no_grad()
+    def outpaint(self, image, height, width, top=None, left=None, keep_margin=0, stride=None, circular=False,
+                 num_inference_steps=50, eta=0.0, jump_length=10, jump_n_sample=10, generator=None, latents=None, use_graph=True,
+                 composite=True, output_type="pil", return_dict=True):
+        """Paint the height x width picture around `image` [B, 3, r S, r S] in [-1, 1] (the model's native size, as inpaint takes
+        it).  height, width, top, left and stride are PIXELS, multiples of the VAE's scale factor r; (top, left) is the image's
+        corner on the canvas, None centres it, and with `circular` the x axis wraps and so does the paste.  The image is encoded
+        with the posterior mode times scaling_factor and pasted into a zero canvas of height / r x width / r latents; the canvas
+        mask is 1 on that rectangle shrunk by `keep_margin` latents on each side (panorama.place) - the AF-VAE's filters are
+        global per plane, so the outermost latents of an encode see the image's opposite edge, and the margin hands them to the
+        sampler.  Sampling is outpaint_latents, decoding decode_panorama.  composite: the pixels under the mask are the input's
+        exactly, in fp32.  output_type as __call__; 'latent' returns the fp32 canvas."""
+        from ..panorama import place
+        self._refuse_dpm("outpaint")
+        if self.vae is None:
+            raise NotImplementedError("this pipeline was built without a VAE: use outpaint_latents")
+        r, s, dev = self._vae_ratio(), self.unet.config.sample_size, self.unet.device
+        if image.dim() != 4 or tuple(image.shape[1:]) != (3, s * r, s * r):
+            raise ValueError(f"outpaint: image {tuple(image.shape)}, want [B, 3, {s * r}, {s * r}]")
+        for name, v in (("height", height), ("width", width), ("stride", stride), ("top", top), ("left", left)):
+            if v is not None and (int(v) != v or int(v) % r or int(v) < (r if name in ("height", "width", "stride") else 0)):
+                raise ValueError(f"outpaint: {name} = {v} pixels must be a {'positive ' if name not in ('top', 'left') else ''}"
+                                 f"multiple of the VAE's scale factor {r}")
+        Hc, Wc = int(height) // r, int(width) // r
+        lstride = None if stride is None else int(stride) // r
+        at = place(Hc, Wc, s, None if top is None else int(top) // r, None if left is None else int(left) // r, keep_margin,
+                   bool(circular))
+        image = image.to(device=dev, dtype=torch.float32)
+        z = self._encode_mode(image).float()
+        B = image.shape[0]
+        rows, cols = torch.tensor(at.rows, device=dev), torch.tensor(at.cols, device=dev)
+        known = torch.zeros(B, z.shape[1], Hc, Wc, dtype=torch.float32, device=dev)
+        known[:, :, rows[:, None], cols[None, :]] = z
+        mask = torch.tensor(at.mask(Hc, Wc), dtype=torch.float32, device=dev)[None, None]
+        canvas = self.outpaint_latents(known, mask, lstride, circular, num_inference_steps, eta, jump_length, jump_n_sample,
+                                       generator, latents, use_graph)
+        if output_type == "latent":
+            return canvas
+        decoded = self.decode_panorama(canvas, self.panorama_geometry(Hc, Wc, lstride, circular))
+        if composite:
+            up = torch.arange(r, device=dev)
+            prow, pcol = (rows[:, None] * r + up).reshape(-1), (cols[:, None] * r + up).reshape(-1)      # the image's pixels
+            pasted = torch.zeros_like(decoded)
+            pasted[:, :, prow[:, None], pcol[None, :]] = image
+            pmask = mask.repeat_interleave(r, 2).repeat_interleave(r, 3)
+            decoded = torch.where(pmask == 1, pasted, decoded)
+        return self._images(decoded, output_type, return_dict)

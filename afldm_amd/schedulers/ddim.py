@@ -246,6 +246,16 @@ class DDIMScheduler:
         return Schedule.of(self, "repaint", [g[n - 1 - t] for t in ev], rows, draws, _repaint_steps=n, _repaint_eta=float(eta),
                            _repaint_jump_length=jl, _repaint_jump_n_sample=js)
 
+    def outpaint_schedule(self, num_inference_steps, eta=0.0, jump_length=10, jump_n_sample=10):
+        """Outpainting: RePaint on a MultiDiffusion canvas larger than the model's window, as the Schedule OutpaintEngine replays
+        with afldm_pano_repaint_step.  Timesteps, rows and draws are repaint_schedule(num_inference_steps, eta, jump_length,
+        jump_n_sample)'s, float for float (and it refuses what that refuses); a draw is one randn_tensor of the CANVAS's shape.
+        The kind is "outpaint" and the settings are its own, so that an engine of one kind never replays the other's schedule."""
+        rp = self.repaint_schedule(num_inference_steps, eta, jump_length, jump_n_sample)
+        return Schedule.of(self, "outpaint", rp.timesteps, rp.rows, rp.draws, _outpaint_steps=int(num_inference_steps),
+                           _outpaint_eta=float(eta), _outpaint_jump_length=int(jump_length),
+                           _outpaint_jump_n_sample=int(jump_n_sample))
+
     def ilvr_schedule(self, num_inference_steps, eta=1.0, range_t=0):
         """ILVR reference-guided sampling (Choi et al., ICCV 2021, Algorithm 1) over this scheduler's `num_inference_steps`
         timesteps g[0] > ... > g[N-1], as the Schedule DenoiseEngine replays with afldm_ilvr_step.  For evaluation i, with

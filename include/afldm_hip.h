@@ -610,6 +610,21 @@ int afldm_pano_step(const float* canvas, const void* eps, const float* noise, si
                     float* canvas_out, float* windows_out, const float* coef, int* step_idx, int advance, int P, int C, int Hc,
                     int Wc, int S, const int* oy, int ny, const int* ox, int nx, int wrap_y, int wrap_x, int dtype,
                     afldm_stream_t stream);
+/* Outpainting: RePaint (afldm_repaint_step) on a MultiDiffusion canvas, one launch per UNet evaluation.  Arguments as
+ * afldm_pano_step, plus known (NCHW fp32 [P,C,Hc,Wc]: the content to keep), mask (fp32 [P,1,Hc,Wc], 1 = keep) and three
+ * canvas-shaped noise slots per step as afldm_repaint_step lays them out (z_k, z_u, z_b at noise + s noise_step_stride +
+ * {0, 1, 2} noise_slot_stride).  coef float[12 nsteps], the "repaint" row (p, q, lo, hi, a, b, c, k0, k1, u0, u1, 0); per
+ * canvas element, over the windows k that cover it, in ascending k, every product and sum rounded on its own:
+ *   x0_k = clamp(p x + q e_k, lo, hi);  A = sum_k w x0_k;  E = sum_k w e_k;  W = sum_k w
+ *   unknown = a A / W + b E / W + c z_u;  knownp = k0 known + k1 z_k
+ *   out = u0 (m knownp + (1 - m) unknown) + u1 z_b          (1 - m == 0: the unknown side is left out, not added as 0)
+ * canvas_out and windows_out as afldm_pano_step.  A slot whose coefficient (k1, c, u1) is 0 is not read; noise itself must
+ * not be NULL.  canvas_out may alias canvas; step_idx / advance as the DDIM update above. */
+int afldm_pano_repaint_step(const float* canvas, const void* eps, const float* known, const float* mask, const float* noise,
+                            size_t noise_step_stride, size_t noise_slot_stride, const float* wt, float* canvas_out,
+                            float* windows_out, const float* coef, int* step_idx, int advance, int P, int C, int Hc, int Wc,
+                            int S, const int* oy, int ny, const int* ox, int nx, int wrap_y, int wrap_x, int dtype,
+                            afldm_stream_t stream);
 /* canvas[P][ch][Y][X] = sum_k w windows[P nwin + k][ch][u][v] / sum_k w: windows NCHW dtype [P nwin,C,S,S], canvas fp32.  S,
  * the origins and the extents are in the caller's units (the pixel-space blend of per-window decodes passes all of them
  * times the VAE's scale factor). */
