@@ -130,6 +130,9 @@ def _load():
                              ip, ip, vp], c_int),
         "afldm_pano_repaint_step": ([vp, vp, vp, vp, vp, c_size_t, c_size_t, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip,
                                      POINTER(c_int), ip, POINTER(c_int), ip, ip, ip, ip, vp], c_int),
+        "afldm_hires_step": ([vp, vp, vp, vp, vp, c_size_t, vp, vp, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, POINTER(c_int), ip,
+                              POINTER(c_int), ip, ip, ip, vp], c_int),
+        "afldm_hires_windows": ([vp, vp, vp, fp, vp, ip, ip, ip, ip, ip, POINTER(c_int), ip, POINTER(c_int), ip, ip, vp], c_int),
         "afldm_attn_identity_block_ok":([ip, ip, ip, ip, ip], c_int),
         "afldm_attn_identity_block": ([vp, vp, ip, vp, vp, ip, fp, vp, vp, vp, ip, ip, ip, ip, vp], c_int),
         "afldm_pag_step": ([vp, vp, vp, c_size_t, vp, vp, vp, ip, ip, ip, ip, ip, ip, vp], c_int),

@@ -13,7 +13,7 @@
 // arrived in.  All of a plane's global reads of x come before the first barrier and all stores after the last: x_out may alias x.
 // Uniform branches (the row is the same for every thread): a slot whose coefficient (k1, c) is exactly 0 is not loaded, and with
 // w = 0 neither are ref, z_k, Lh and Lw, and the two passes are skipped - the launch is then the plain stochastic step.
-#include "step_common.hpp"
+#include "plane_pass.hpp"
 
 namespace afldm {
 
@@ -23,59 +23,8 @@ struct ilvr_row {
   float p, q, lo, hi, a, b, c, k0, k1, w;
 };
 
-constexpr int ILVR_SMAX = 64;
-constexpr int ILVR_THREADS = 256;
-
-// global row-major [S][S] -> LDS tile of pitch P
-__device__ __forceinline__ void ilvr_load_matrix(const float* __restrict__ L, float* tile, int S, int P, int tid) {
-  for (int i = tid; i < S * S; i += ILVR_THREADS) {
-    const int r = i / S;
-    tile[r * P + (i - r * S)] = L[i];
-  }
-}
-
-// out[i][j] = sum_k m[i][k] * v(j, k), v(j, k) = vt[j * vsj + k * vsk], k ascending.  Thread (g = tid / S, j = tid % S) owns column
-// j of the rows g, g + G, g + 2 G, ... (G = 256 / S >= 4 row groups; the last 256 % S threads idle) and takes them R at a
-// time: one read of v and R broadcast reads of m per R fmaf.  Each output is one chain whatever R is.
-template <int R>
-__device__ __forceinline__ void ilvr_pass_rows(const float* m, const float* vt, int vsj, int vsk, float* out, int S, int P, int tid) {
-  const int G = ILVR_THREADS / S;
-  const int g = tid / S, j = tid - g * S;
-  if (g >= G) return;
-  const float* vp = vt + j * vsj;
-  for (int i0 = g; i0 < S; i0 += R * G) {
-    int row[R];
-    float acc[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int i = i0 + r * G;
-      row[r] = (i < S ? i : S - 1) * P;          // (clamped: read in bounds, not stored)
-      acc[r] = 0.0f;
-    }
-    for (int k = 0; k < S; ++k) {
-      const float v = vp[k * vsk];
-#pragma unroll
-      for (int r = 0; r < R; ++r) acc[r] = fmaf(m[row[r] + k], v, acc[r]);
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int i = i0 + r * G;
-      if (i < S) out[i * P + j] = acc[r];
-    }
-  }
-}
-
-// R = the rows a thread owns, ceil(S / G), up to 4: one for S <= 16 (a thread per output), two for S <= 22, four from there on
-__device__ __forceinline__ void ilvr_pass(const float* m, const float* vt, int vsj, int vsk, float* out, int S, int P, int tid) {
-  const int G = ILVR_THREADS / S;
-  const int rows = (S + G - 1) / G;
-  if (rows <= 1)
-    ilvr_pass_rows<1>(m, vt, vsj, vsk, out, S, P, tid);
-  else if (rows == 2)
-    ilvr_pass_rows<2>(m, vt, vsj, vsk, out, S, P, tid);
-  else
-    ilvr_pass_rows<4>(m, vt, vsj, vsk, out, S, P, tid);
-}
+constexpr int ILVR_SMAX = PLANE_SMAX;
+constexpr int ILVR_THREADS = PLANE_THREADS;
 
 // One plane.  xpl / rpl / zk / zu / opl: the plane's S * S floats of x / ref / the two noise slots / x_out; ep: the plane's first
 // eps element, es floats between pixels (NHWC: C; same layout as x: 1).  V = 4: S * S % 4 == 0 and 16-byte aligned planes.
@@ -114,15 +63,15 @@ __device__ __forceinline__ void ilvr_plane(const float* xpl, const T* __restrict
     }
   }
   if (guided) {
-    ilvr_load_matrix(Lw, tm, S, P, tid);
+    plane_load_matrix(Lw, tm, S, P, tid);
     __syncthreads();                                   // every read of x is behind us
-    ilvr_pass(td, tm, P, 1, tt, S, P, tid);            // t[i][j] = sum_k d[i][k] Lw[j][k]
+    plane_pass(td, tm, P, 1, tt, S, P, tid);           // t[i][j] = sum_k d[i][k] Lw[j][k]
     __syncthreads();
     if (Lh != Lw) {                                    // (uniform; the same matrix twice is already there)
-      ilvr_load_matrix(Lh, tm, S, P, tid);
+      plane_load_matrix(Lh, tm, S, P, tid);
       __syncthreads();
     }
-    ilvr_pass(tm, tt, 1, P, td, S, P, tid);            // res[i][j] = sum_k Lh[i][k] t[k][j]
+    plane_pass(tm, tt, 1, P, td, S, P, tid);           // res[i][j] = sum_k Lh[i][k] t[k][j]
     __syncthreads();
   }
 #pragma unroll

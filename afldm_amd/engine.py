@@ -40,6 +40,11 @@ afldm_pano_repaint_step as the last line: the "repaint" row per window, the same
 a canvas mask - run(canvas, draw=..., known=(known_canvas, canvas_mask)) - and RePaint's jump back up.  The noise buffer is
 [steps, 3, P, C, Hc, Wc].
 
+HiresEngine (kind "hires", DDIMScheduler.hires_schedule: a canvas of scale x the window that is ONE image, after DemoFusion) is
+PanoramaEngine with scale^2 dilated windows behind the local ones in `lat` and afldm_hires_step as the last line: it mixes the
+local means with the dilated window's prediction, pulls the canvas towards the noised upsampled base latents and low-passes the
+dilated views of the next input - run(canvas, draw=..., known=(ref, eps_ref)).  The noise buffer is [steps, P, C, Hc, Hc].
+
 PAGEngine (kind "pag", DDIMScheduler.pag_schedule: perturbed-attention guidance) samples B latents with a UNet batch of 2 B: both
 halves of `x_nhwc` hold the same latents, the attention blocks named by `sites` run PAGAttnProcessor (the plain block on the first
 half, the identity-attention block on the second), and the last line of a step is afldm_pag_step, which reads both halves of eps.
@@ -534,6 +539,70 @@ class OutpaintEngine(PanoramaEngine):
             raise ValueError(f"OutpaintEngine: known canvas {tuple(z0.shape)} / mask {tuple(mask.shape)}, want {want} / "
                              f"{tuple(self.mask.shape)} (or batch 1)")
         return z0, mask
+
+
+class HiresEngine(PanoramaEngine):
+    """High-resolution sampling on the replayed graphs (after DemoFusion): P square canvases of scale x the UNet's window, each
+    seen through NW = nwin + scale^2 windows - the nwin local windows of `geometry`, then the scale^2 dilated windows, which take
+    every scale-th latent of the whole canvas - batch_size = P * NW planes in `lat`.  A step is PanoramaEngine's with
+    afldm_hires_step as the last line: the local means mixed with the dilated prediction, the reverse step, the skip residual
+    towards the noised reference, and the next UNet input with its dilated views low-passed.  run(canvas, draw=...,
+    known=(ref, eps_ref)): the upsampled base latents and the run's noise tensor, both [P, C, Hc, Hc], are per-run static
+    buffers, so another base image replays the same graphs; the low-pass L = ilvr_filter(Hc, scale) and the window weight are
+    engine state.  reset(canvas) writes the canvas and makes the first UNet input with the schedule's f_0
+    (afldm_hires_windows).  Geometry and scale are baked into the captured graphs."""
+
+    def __init__(self, unet, scheduler, batch_size, num_inference_steps=50, use_graph=True, steps_per_graph=5, branches=1, *,
+                 geometry, scale):
+        if geometry is None or scale is None:
+            raise ValueError("HiresEngine needs a panorama.Geometry and the scale")
+        s, scale = unet.config.sample_size, int(scale)
+        per = geometry.nwin + scale * scale
+        if (geometry.S != s or scale < 1 or geometry.Hc != scale * s or geometry.Wc != scale * s or geometry.wrap_y or geometry.wrap_x
+                or batch_size % per):
+            raise ValueError(f"HiresEngine: windows of {geometry.S} on a {geometry.Hc} x {geometry.Wc} canvas for a UNet of sample_size "
+                             f"{s} at scale {scale} (want a square canvas of scale x sample_size that does not wrap), batch "
+                             f"{batch_size} for {geometry.nwin} + {scale * scale} windows per canvas")
+        self.geometry, self.scale, self.P = geometry, scale, batch_size // per
+        DenoiseEngine.__init__(self, unet, scheduler, batch_size, num_inference_steps, use_graph, steps_per_graph, 1)
+
+    def _hires_state(self):
+        """The fp32 canvas, the count average as the window weight, the run's reference and noise canvases, the ideal low-pass of
+        cut-off 1 / scale on the canvas's plane, and one canvas-shaped noise row per step, only when some step draws."""
+        from .af_libs.ideal_lpf import ilvr_filter
+        from .schedulers.ddim import hires_kappa
+        g, dev = self.geometry, self.unet.device
+        self.canvas = torch.zeros(self.P, self.lat.shape[1], g.Hc, g.Wc, dtype=torch.float32, device=dev)
+        self.wt = torch.ones(g.S, g.S, dtype=torch.float32, device=dev)
+        self.known = torch.zeros_like(self.canvas)
+        self.eps_ref = torch.zeros_like(self.canvas)
+        self.filter = ilvr_filter(g.Hc, self.scale).to(device=dev, dtype=torch.float32).contiguous()
+        self._static = ("eps_ref", self.eps_ref, False)
+        cfg = self.schedule.config          # f_0 of DDIMScheduler.hires_start: how far the FIRST input's dilated views are low-passed
+        self.f0 = hires_kappa(self.timesteps[0], cfg["num_train_timesteps"], cfg["_hires_cosine_scale_3"])
+        return [(self.known, self.eps_ref, self._noise(self.canvas.shape, only_if_drawn=True)[0], self.wt, self.filter, self.filter,
+                 g, self.scale)]
+
+    UPDATES = {"hires": (ops.hires_step, _hires_state)}
+
+    def _check_known(self, known):
+        if known is None:
+            raise ValueError("HiresEngine: run(canvas, draw=..., known=(ref, eps_ref)) needs the upsampled reference and its noise")
+        ref, eps_ref = known
+        want = tuple(self.canvas.shape)
+        if tuple(ref.shape) != want or tuple(eps_ref.shape) != want:
+            raise ValueError(f"HiresEngine: ref {tuple(ref.shape)} / eps_ref {tuple(eps_ref.shape)}, want {want} for both")
+        return ref, eps_ref
+
+    def reset(self, canvas):
+        """canvas: [P, C, Hc, Hc] (any device / float dtype), the noised upsampled reference; scaled by init_noise_sigma, written
+        to the canvas buffer and turned into the first UNet input."""
+        if tuple(canvas.shape) != tuple(self.canvas.shape):
+            raise ValueError(f"HiresEngine: canvas {tuple(canvas.shape)}, want {tuple(self.canvas.shape)}")
+        self.refresh_if_stale()
+        self.canvas.copy_(canvas.to(device=self.canvas.device, dtype=torch.float32) * self.schedule.init_noise_sigma)
+        ops.hires_windows(self.canvas, self.filter, self.filter, self.f0, self.geometry, self.scale, out=self.lat)
+        self.step_idx.fill_(-1)
 
 
 @contextlib.contextmanager

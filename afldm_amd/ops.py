@@ -1856,6 +1856,67 @@ def pano_repaint_step(canvas, eps_nhwc, known, mask, noise, wt, geometry, coef, 
     return out, windows_out
 
 
+# ----------------------------------------------------------------------------- high-resolution sampling: local + dilated windows
+def _hires_args(name, canvas, g, scale, Lh, Lw):
+    """The checks hires_step and hires_windows share: (P, C, windows per canvas, the C geometry arguments)."""
+    P, C = _pano_canvas(name, canvas, g)
+    if g.wrap_y or g.wrap_x:
+        raise ValueError(f"{name}: the canvas does not wrap")
+    if not canvas.is_contiguous():
+        raise ValueError(f"{name}: the canvas must be contiguous")
+    for m, n in ((Lh, "Lh"), (Lw, "Lw")):
+        if m is None:
+            continue
+        _dev(m, n)
+        if m.dtype != torch.float32 or tuple(m.shape) != (g.Hc, g.Wc) or not m.is_contiguous():
+            raise ValueError(f"{name}: {n} must be a contiguous fp32 [{g.Hc}, {g.Wc}] matrix, got {m.dtype} {tuple(m.shape)}")
+    return P, C, g.nwin + int(scale) ** 2, _geom_args(g)[:7] + (int(scale),)
+
+
+def hires_step(canvas, eps_nhwc, ref, eps_ref, noise, wt, Lh, Lw, geometry, scale, coef, step_idx, advance=False, out=None,
+               windows_out=None):
+    """The fused high-resolution update (afldm_hires_step): canvas, ref, eps_ref fp32 [P, C, Hc, Hc] with Hc = scale * S; eps NHWC
+    dtype [P * NW, S, S, C], NW = nwin + scale^2 - the UNet's output on the local windows of `geometry` (a panorama.Geometry, no
+    wrap) followed by the scale^2 dilated windows of each canvas; wt fp32 [S, S] > 0; Lh, Lw fp32 [Hc, Hc]; noise: fp32 view
+    [steps, P, C, Hc, Hc] whose last four dimensions are contiguous, or None when no row has c != 0; coef float[12*nsteps]
+    "hires" rows and step_idx int32[1] on device.  Returns (canvas_out, windows_out): the new canvas (out= may be the canvas
+    itself) and the next UNet input, NCHW fp32 [P * NW, C, S, S]."""
+    g = geometry
+    P, C, NW, geom = _hires_args("hires_step", canvas, g, scale, Lh, Lw)
+    _dev(eps_nhwc, "eps"); _dev(ref, "ref"); _dev(eps_ref, "eps_ref"); _pano_weights("hires_step", wt, g)
+    if tuple(eps_nhwc.shape) != (P * NW, g.S, g.S, C) or not eps_nhwc.is_contiguous():
+        raise ValueError(f"hires_step: eps {tuple(eps_nhwc.shape)}, want contiguous NHWC {(P * NW, g.S, g.S, C)}")
+    for t, n in ((ref, "ref"), (eps_ref, "eps_ref")):
+        if t.dtype != torch.float32 or t.shape != canvas.shape or not t.is_contiguous():
+            raise ValueError(f"hires_step: {n} must be contiguous fp32 {tuple(canvas.shape)}, got {t.dtype} {tuple(t.shape)}")
+    noise_args = (None, 0) if noise is None else _noise_view(noise, canvas.shape)
+    if out is None:
+        out = torch.empty_like(canvas)
+    if windows_out is None:
+        windows_out = torch.empty(P * NW, C, g.S, g.S, dtype=torch.float32, device=canvas.device)
+    _dev(out, "out"); _dev(windows_out, "windows_out")
+    assert out.dtype == windows_out.dtype == torch.float32 and out.shape == canvas.shape and out.is_contiguous()
+    assert tuple(windows_out.shape) == (P * NW, C, g.S, g.S) and windows_out.is_contiguous()
+    check(lib.afldm_hires_step(ptr(canvas), ptr(eps_nhwc), ptr(ref), ptr(eps_ref), *noise_args, ptr(wt), ptr(Lh), ptr(Lw), ptr(out),
+                               ptr(windows_out), ptr(coef), ptr(step_idx), int(advance), P, C, *geom, _code(eps_nhwc), stream_ptr()),
+          "hires_step")
+    return out, windows_out
+
+
+def hires_windows(canvas, Lh, Lw, f, geometry, scale, out=None):
+    """canvas fp32 [P, C, Hc, Hc] -> the UNet input of a high-resolution evaluation, NCHW fp32 [P * NW, C, S, S]: the local crops
+    and the dilated views of canvas + f (Lh canvas Lw^T - canvas) (afldm_hires_windows: the tail of hires_step, the same bits).
+    Lh / Lw may be None when f == 0."""
+    g = geometry
+    P, C, NW, geom = _hires_args("hires_windows", canvas, g, scale, Lh, Lw)
+    if out is None:
+        out = torch.empty(P * NW, C, g.S, g.S, dtype=torch.float32, device=canvas.device)
+    _dev(out, "out")
+    assert out.dtype == torch.float32 and tuple(out.shape) == (P * NW, C, g.S, g.S) and out.is_contiguous()
+    check(lib.afldm_hires_windows(ptr(canvas), ptr(Lh), ptr(Lw), float(f), ptr(out), P, C, *geom, stream_ptr()), "hires_windows")
+    return out
+
+
 def window_fuse(windows, wt, geometry, out=None):
     """windows NCHW fp32 / bf16 [P * nwin, C, S, S] -> the fp32 canvas [P, C, Hc, Wc] of their wt-weighted mean over the windows
     that cover each element (afldm_window_fuse); wt fp32 [S, S] > 0."""

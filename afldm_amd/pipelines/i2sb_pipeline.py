@@ -80,3 +80,11 @@ class I2SBLDMPipeline(MyLDMPipeline):
     def outpaint(self, *args, **kwargs):
         raise NotImplementedError("I2SBLDMPipeline: outpainting is defined for the unconditional sampler "
                                   "(MyLDMPipeline.outpaint); the bridge starts from an encoded image of the window's size")
+
+    def hires_latents(self, *args, **kwargs):
+        raise NotImplementedError("I2SBLDMPipeline: high-resolution sampling is defined for the unconditional sampler "
+                                  "(MyLDMPipeline.hires_latents); the bridge starts from an encoded image of the window's size")
+
+    def hires(self, *args, **kwargs):
+        raise NotImplementedError("I2SBLDMPipeline: high-resolution sampling is defined for the unconditional sampler "
+                                  "(MyLDMPipeline.hires); the bridge starts from an encoded image of the window's size")

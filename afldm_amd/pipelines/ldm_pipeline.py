@@ -650,3 +650,102 @@ class MyLDMPipeline(DiffusionPipeline):
             pmask = mask.repeat_interleave(r, 2).repeat_interleave(r, 3)
             decoded = torch.where(pmask == 1, pasted, decoded)
         return self._images(decoded, output_type, return_dict)
+
+    # ------------------------------------------------------------------------------------------------ high-resolution sampling
+    HIRES_MAX_CANVAS = 64           # afldm_hires_step holds a canvas plane in one workgroup's LDS
+
+    @torch.no_grad()
+    def hires_latents(self, base_latents, scale=2, stride=None, eta=0.0, num_inference_steps=50, cosine_scale_1=3.0,
+                      cosine_scale_2=1.0, cosine_scale_3=1.0, generator=None, use_graph=True):
+        """The same kind of image at `scale` times the resolution, in latent space (after DemoFusion, Du et al., CVPR 2024; one
+        phase, S -> scale S): `base_latents` [P, C, S, S] are clean latents sampled at the model's own size.  They are upsampled
+        (ref = U z0 U^T, the interpolating ideal upsampler afldm_filter_matrix(0, S, scale)), noised with ONE canvas-shaped tensor
+        eps_ref to the first level, and the canvas [P, C, scale S, scale S] is denoised through MultiDiffusion windows (the local
+        windows of panorama_geometry with `stride`, default S // 2) plus the two things that tie its far ends together: a skip
+        residual towards the reference noised with the same eps_ref (weight kappa^cosine_scale_1), and dilated sampling -
+        scale^2 more windows per canvas that take every scale-th latent of the whole canvas, whose prediction is mixed with the
+        local mean (weight kappa^cosine_scale_2) and whose input is the canvas behind the ideal low-pass of cut-off 1 / scale
+        (ilvr_filter; blended in by kappa^cosine_scale_3), under which the scale^2 views are sub-pixel shifts of one image.  A
+        cosine scale of None switches its term off; all three None is MultiDiffusion from the noised reference.  The schedule is
+        DDIMScheduler.hires_schedule: every evaluation runs the UNet on P (nwin + scale^2) windows and ends in one
+        afldm_hires_step, on replayed HIP graphs (use_graph), or runs statement by statement in the eager loop below, which makes
+        the same draws from `generator` in the same order - eps_ref in the model's dtype, then one canvas-shaped tensor per
+        evaluation whose sigma is not 0.  Needs no VAE.  Returns the fp32 canvas."""
+        from .. import ops
+        from ..af_libs.ideal_lpf import ilvr_filter
+        from ..engine import HiresEngine
+        self._refuse_dpm("hires_latents")
+        c, s, dev = self.unet.config.in_channels, self.unet.config.sample_size, self.unet.device
+        if int(scale) != scale or int(scale) < 2:
+            raise ValueError(f"hires_latents: scale = {scale} must be an integer >= 2")
+        scale = int(scale)
+        Hc = scale * s
+        if Hc > self.HIRES_MAX_CANVAS:
+            raise ValueError(f"hires_latents: scale {scale} of sample_size {s} is a canvas of {Hc} latents; the limit is "
+                             f"{self.HIRES_MAX_CANVAS} (one workgroup holds a canvas plane in LDS)")
+        if base_latents.dim() != 4 or tuple(base_latents.shape[1:]) != (c, s, s):
+            raise ValueError(f"hires_latents: base_latents {tuple(base_latents.shape)}, want [P, {c}, {s}, {s}]")
+        P = base_latents.shape[0]
+        shape = (P, c, Hc, Hc)
+        geom = self.panorama_geometry(Hc, Hc, s // 2 if stride is None else stride)
+        nwin, NW = geom.nwin, geom.nwin + scale * scale
+        self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
+        sched = self.scheduler.hires_schedule(num_inference_steps, eta, cosine_scale_1, cosine_scale_2, cosine_scale_3)
+        k0, k1, f0 = self.scheduler.hires_start(num_inference_steps, cosine_scale_3)
+        z0 = ops.to_nhwc(base_latents.to(device=dev, dtype=torch.float32).contiguous())
+        ref = ops.to_nchw(ops.af_resample(z0, ops.up_matrix(s, scale, dev)))
+        eps_ref = sched.drawer(generator, shape, dev, self.unet.dtype)().to(device=dev, dtype=torch.float32).contiguous()
+        start = k0 * ref + k1 * eps_ref
+        L = ilvr_filter(Hc, scale).to(device=dev, dtype=torch.float32).contiguous()
+        ones = torch.ones(s, s, dtype=torch.float32, device=dev)
+        f_in = [f0]                                                           # the low-pass weight of the NEXT evaluation's input
+
+        def eager(x, t, row, zs):
+            p, q, lo, hi, a, b, cz, r0, r1, r, g, f = row
+            win = ops.hires_windows(x, L, L, f_in[0], geom, scale)            # [P * NW, C, S, S]: local crops, then dilated views
+            eps = self.unet(win.to(self.unet.dtype), t).sample.float().reshape(P, NW, c, s, s)
+            loc = eps[:, :nwin].reshape(P * nwin, c, s, s).contiguous()
+            x0 = torch.clamp(p * win.reshape(P, NW, c, s, s)[:, :nwin].reshape(P * nwin, c, s, s) + q * loc, lo, hi)
+            x0m, em = ops.window_fuse(x0.contiguous(), ones, geom), ops.window_fuse(loc, ones, geom)
+            if g != 0.0:
+                eg = torch.empty_like(x)
+                for i in range(scale):
+                    for j in range(scale):
+                        eg[:, :, i::scale, j::scale] = eps[:, nwin + i * scale + j]
+                x0m = (1 - g) * x0m + g * torch.clamp(p * x + q * eg, lo, hi)
+                em = (1 - g) * em + g * eg
+            x = a * x0m + b * em
+            if zs[0] is not None:
+                x = x + cz * zs[0]
+            if r != 0.0:
+                x = r * (r0 * ref + r1 * eps_ref) + (1 - r) * x
+            f_in[0] = f
+            return x.contiguous()
+        return self._sample(sched, shape, generator, start, use_graph, "_hires_engines", eager, HiresEngine, P * NW,
+                            known=(ref, eps_ref), geometry=geom, scale=scale)
+
+    @torch.no_grad()
+    def hires(self, batch_size=1, scale=2, base_latents=None, stride=None, eta=0.0, num_inference_steps=50, cosine_scale_1=3.0,
+              cosine_scale_2=1.0, cosine_scale_3=1.0, generator=None, use_graph=True, output_type="pil", return_dict=True):
+        """Sample images at `scale` times the model's resolution: a base sample at the model's own size (this pipeline's
+        __call__ with the same eta, step count and generator, unless `base_latents` [P, C, S, S] is given), hires_latents on the
+        canvas of scale x sample_size latents, then decode_panorama over the local windows.  `stride` is in PIXELS, a multiple of
+        the VAE's scale factor.  output_type as __call__; 'latent' returns the fp32 canvas."""
+        self._refuse_dpm("hires")
+        if self.vae is None:
+            raise NotImplementedError("this pipeline was built without a VAE: use hires_latents")
+        r = self._vae_ratio()
+        if stride is not None and (int(stride) != stride or int(stride) % r or int(stride) < r):
+            raise ValueError(f"hires: stride = {stride} pixels must be a positive multiple of the VAE's scale factor {r}")
+        lstride = None if stride is None else int(stride) // r
+        if base_latents is None:
+            base_latents = self(batch_size=batch_size, generator=generator, eta=eta, num_inference_steps=num_inference_steps,
+                                output_type="latent", use_graph=use_graph)
+        canvas = self.hires_latents(base_latents, scale, lstride, eta, num_inference_steps, cosine_scale_1, cosine_scale_2,
+                                    cosine_scale_3, generator, use_graph)
+        if output_type == "latent":
+            return canvas
+        s = self.unet.config.sample_size
+        Hc = int(scale) * s
+        decoded = self.decode_panorama(canvas, self.panorama_geometry(Hc, Hc, s // 2 if lstride is None else lstride))
+        return self._images(decoded, output_type, return_dict)

@@ -18,6 +18,13 @@ from ..configs import FFHQ_DDIM_CONFIG, FrozenConfig
 from .schedule import Schedule
 
 
+def hires_kappa(t, num_train_timesteps, scale):
+    """DemoFusion's cosine factor of timestep t, (1 + cos(pi (T - t) / T)) / 2 - 1 at the noisiest end of the training schedule,
+    0 at t = 0 - to the power `scale`; 0 for a scale of None (the term is switched off).  hires_schedule's r, g and f."""
+    T = int(num_train_timesteps)
+    return 0.0 if scale is None else (0.5 * (1.0 + math.cos(math.pi * (T - int(t)) / T))) ** float(scale)
+
+
 @dataclass
 class DDIMSchedulerOutput:
     prev_sample: torch.Tensor
@@ -255,6 +262,52 @@ class DDIMScheduler:
         return Schedule.of(self, "outpaint", rp.timesteps, rp.rows, rp.draws, _outpaint_steps=int(num_inference_steps),
                            _outpaint_eta=float(eta), _outpaint_jump_length=int(jump_length),
                            _outpaint_jump_n_sample=int(jump_n_sample))
+
+    def _hires_kappa(self, t, scale):
+        return hires_kappa(t, self.config.num_train_timesteps, scale)
+
+    def hires_schedule(self, num_inference_steps, eta=0.0, cosine_scale_1=3.0, cosine_scale_2=1.0, cosine_scale_3=1.0):
+        """High-resolution sampling on a canvas of scale x the model's window (after DemoFusion, Du et al., CVPR 2024) over this
+        scheduler's `num_inference_steps` timesteps g[0] > ... > g[N-1], as the Schedule HiresEngine replays with
+        afldm_hires_step.  For evaluation i, with ab = alphas_cumprod[g[i]], ab' the next level (final_alpha_cumprod after the
+        last) and kappa(t) = (1 + cos(pi (T - t) / T)) / 2, T = num_train_timesteps, the row is
+          (p, q, lo, hi, a, b, c) = _reverse_row(ab, ab', eta)      the reverse step, applied to the mixed predictions
+          g = kappa(g[i]) ^ cosine_scale_2                          the weight of the dilated window's prediction against the local mean
+          k0, k1 = sqrt(ab'), sqrt(1 - ab')                         the upsampled reference noised to the next level ...
+          r = kappa(g[i+1]) ^ cosine_scale_1                        ... and the skip residual towards it
+          f = kappa(g[i+1]) ^ cosine_scale_3                        how far the NEXT evaluation's dilated views are low-passed
+        and the last evaluation has k0 = 1, k1 = 0, r = 0, f = 0: it returns the reverse step itself.  A cosine scale of None
+        switches its term off in every row (r = 0, g = 0 or f = 0).  A step draws - one randn_tensor of the CANVAS's shape in
+        the model's dtype - only where c is not 0.  hires_start gives the first evaluation's level and low-pass."""
+        if self.config.clip_sample or self.config.prediction_type != "epsilon":
+            raise NotImplementedError("afldm_amd.DDIMScheduler implements the reference's setting: "
+                                      "epsilon prediction, clip_sample=False")
+        n = int(num_inference_steps)
+        self.set_timesteps(n)
+        ts = self._timesteps_host
+        power = self._hires_kappa
+        rows = []
+        for i, t in enumerate(ts):
+            last = i == n - 1
+            ab = float(self.alphas_cumprod[t])
+            ab_prev = float(self.final_alpha_cumprod) if last else float(self.alphas_cumprod[ts[i + 1]])
+            tail = (1.0, 0.0, 0.0, power(t, cosine_scale_2), 0.0) if last else (
+                math.sqrt(ab_prev), math.sqrt(1 - ab_prev), power(ts[i + 1], cosine_scale_1), power(t, cosine_scale_2),
+                power(ts[i + 1], cosine_scale_3))
+            rows.append(self._reverse_row(ab, ab_prev, eta) + tail)
+        unit = {k: None if v is None else float(v) for k, v in (("_hires_cosine_scale_1", cosine_scale_1),
+                                                                ("_hires_cosine_scale_2", cosine_scale_2),
+                                                                ("_hires_cosine_scale_3", cosine_scale_3))}
+        return Schedule.of(self, "hires", ts, rows, [r[6] != 0.0 for r in rows], _hires_steps=n, _hires_eta=float(eta), **unit)
+
+    def hires_start(self, num_inference_steps, cosine_scale_3=1.0):
+        """(sqrt(ab_0), sqrt(1 - ab_0), f_0) of hires_schedule's first evaluation: the canvas starts as sqrt(ab_0) ref +
+        sqrt(1 - ab_0) eps_ref, and the first UNet input's dilated views are low-passed by f_0 = kappa(g[0]) ^ cosine_scale_3 (0
+        for None)."""
+        self.set_timesteps(int(num_inference_steps))
+        t0 = self._timesteps_host[0]
+        ab = float(self.alphas_cumprod[t0])
+        return math.sqrt(ab), math.sqrt(1 - ab), self._hires_kappa(t0, cosine_scale_3)
 
     def ilvr_schedule(self, num_inference_steps, eta=1.0, range_t=0):
         """ILVR reference-guided sampling (Choi et al., ICCV 2021, Algorithm 1) over this scheduler's `num_inference_steps`

@@ -13,6 +13,11 @@ UNet evaluation, fixed when it is made.  `kind` names the update kernel that rea
     "outpaint"  the "repaint" row, float for float, applied on a canvas: x0 per window, then RePaint's update with the means over the
             covering windows in x0's and eps's place, the known content, the mask and the three noise slots canvas-shaped:
             unknown = a mean_k x0_k + b mean_k eps_k + c z_u;  the rest as "repaint"                    afldm_pano_repaint_step
+    "hires" (p, q, lo, hi, a, b, c, k0, k1, r, g, f):  high-resolution sampling on a canvas of scale x the window (after DemoFusion):
+            the local windows' means as "pano", mixed by g with the prediction of the dilated window through the element, one
+            reverse step, the skip residual r towards the noised upsampled reference, and the dilated views of the next UNet input
+            low-passed by f:  x0m = (1 - g) mean_k x0_k + g x0_g;  em = (1 - g) mean_k eps_k + g eps_g;  xp = a x0m + b em + c z_u;
+            x_out = r (k0 ref + k1 eps_ref) + (1 - r) xp;  dilated input = x_out + f (L x_out L^T - x_out)       afldm_hires_step
     "pag"   (p, q, lo, hi, a, b, d, c, s, phi, 0, 0):  perturbed-attention guidance on a batch of 2 B, e the UNet's output and e_p
             the perturbed UNet's:  g = e + s (e - e_p);  phi != 0: g <- g (phi std(e) / std(g) + 1 - phi) per sample;  then the
             "sde" row applied to g:  x0 = clamp(p x + q g, lo, hi);  x_out = a x + b x0 + d g + c z          afldm_pag_step
@@ -21,13 +26,13 @@ UNet evaluation, fixed when it is made.  `kind` names the update kernel that rea
             row) - and the same guided update with e_d in e_p's place                                        afldm_pag_step
 
 The rows come from the scheduler that owns the update (DDIMScheduler.schedule / stochastic_schedule,
-DDIMScheduler.repaint_schedule / ilvr_schedule / panorama_schedule / pag_schedule / sag_schedule / outpaint_schedule, DPMSolverMultistepScheduler.schedule, I2SBScheduler.ode_schedule / bridge_schedule,
+DDIMScheduler.repaint_schedule / ilvr_schedule / panorama_schedule / pag_schedule / sag_schedule / outpaint_schedule / hires_schedule, DPMSolverMultistepScheduler.schedule, I2SBScheduler.ode_schedule / bridge_schedule,
 MyLDMPipeline.inversion_schedule) as Python floats and are rounded once to fp32 by `table`.  An "sde" schedule also states which
 steps draw noise and how: exactly the randn_tensor calls, in the same order, that the scheduler's eager `step()` makes, so that
 the engine can draw them from the caller's generator before the captured graphs need them.  A "repaint" schedule has up to
 three draws per step and states them per slot: `draws[k]` is (z_k, z_u, z_b), drawn in that order; an "ilvr" schedule has up
 to two, (z_k, z_u).  A "pano" schedule draws one canvas-shaped tensor per step, and only where the row's c is not 0; an "outpaint" schedule draws as
-"repaint" does, canvas-shaped.`key` identifies everything the rows were computed from; the engine
+"repaint" does, canvas-shaped; a "hires" schedule draws as "pano" does.  `key` identifies everything the rows were computed from; the engine
 cache (engine.cached_engine) compares it, so two schedules with equal keys must replay the same graph."""
 from dataclasses import dataclass
 
@@ -38,7 +43,8 @@ from ..utils import randn_tensor
 
 # kind -> (row width, noise slots per step, may a step draw): the one place that states them.  Several slots: `draws` is per slot
 KINDS = {"ddim": (4, 1, False), "dpm": (8, 1, False), "sde": (8, 1, True), "repaint": (12, 3, True), "ilvr": (12, 2, True),
-         "pano": (8, 1, True), "pag": (12, 1, True), "sag": (12, 1, True), "outpaint": (12, 3, True)}
+         "pano": (8, 1, True), "pag": (12, 1, True), "sag": (12, 1, True), "outpaint": (12, 3, True),
+         "hires": (12, 1, True)}
 ROW_WIDTH, NOISE_SLOTS = {k: v[0] for k, v in KINDS.items()}, {k: v[1] for k, v in KINDS.items() if v[2]}      # derived views
 _MADE = {}          # key -> Schedule: the rows are ~0.1 ms of scalar tensor arithmetic each, and a sampler asks per call
 

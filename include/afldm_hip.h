@@ -633,6 +633,34 @@ int afldm_window_fuse(const void* windows, const float* wt, float* canvas, int P
 /* windows[P nwin + k][ch][u][v] = canvas[P][ch][(oy + u) mod Hc][(ox + v) mod Wc], fp32 to fp32, exact. */
 int afldm_window_crop(const float* canvas, float* windows, int P, int C, int Hc, int Wc, int S, const int* oy, int ny,
                       const int* ox, int nx, int wrap_y, int wrap_x, afldm_stream_t stream);
+/* High-resolution sampling (after DemoFusion, Du et al., CVPR 2024), one launch per UNet evaluation.  The canvas is square,
+ * Hc = Wc = scale * S <= 64.  Per canvas the window batch holds NW = nwin + scale^2 windows: the nwin = ny * nx local windows of
+ * afldm_pano_step (no wrap), then the dilated ones - window nwin + i scale + j covers the canvas elements (i + scale u,
+ * j + scale v).  eps: NHWC dtype [P NW,S,S,C]; windows_out: NCHW fp32 [P NW,C,S,S]; ref, eps_ref: NCHW fp32 [P,C,Hc,Wc], the
+ * upsampled base latents and the run's one noise tensor; Lh, Lw: fp32 [Hc][Hc], the low-pass of the dilated views; wt and
+ * noise as afldm_pano_step (noise may be NULL when no row has c != 0).  coef float[12 nsteps], the "hires" row
+ * (p, q, lo, hi, a, b, c, k0, k1, r, g, f).  For the canvas element x at (P, ch, Y, X), every product and sum rounded on its
+ * own, the sums over the covering local windows k in ascending k:
+ *   x0_k = clamp(p x + q e_k, lo, hi);  A = sum_k w x0_k;  E = sum_k w e_k;  W = sum_k w
+ *   e_g  = eps[P NW + nwin + (Y mod scale) scale + X mod scale][Y div scale][X div scale][ch];  x0_g = clamp(p x + q e_g, lo, hi)
+ *   x0m  = (1 - g) A / W + g x0_g;  em = (1 - g) E / W + g e_g          (g == 0: x0m = A / W, em = E / W, e_g is not read)
+ *   xp   = a x0m + b em + c z                                           (c == 0: z is not read)
+ *   out  = r (k0 ref + k1 eps_ref) + (1 - r) xp                         (r == 0: out = xp, ref and eps_ref are not read)
+ *   canvas_out = out;  windows_out[local k] = the crops of out
+ *   windows_out[dilated] = the sub-lattices of out + f (Lh out Lw^T - out) per plane   (f == 0: of out; Lh, Lw are not read)
+ * One 256-thread workgroup per (P, ch) plane holds it in LDS (three Hc x (Hc | 1) fp32 tiles, under 50 KB); each output of the
+ * two passes (Lw first, then Lh) is one ascending-k fmaf chain: no atomics, a plane's bits depend neither on P nor on the grid.
+ * canvas_out may alias canvas; oy / ox are host arrays passed on by value; step_idx / advance as the DDIM update above.
+ * Before any launch AFLDM_ESHAPE refuses: Hc != Wc, Hc != scale * S, Hc < 2 or Hc > 64, scale < 1, more than 16 origins on
+ * an axis, a window that leaves the canvas, an uncovered coordinate. */
+int afldm_hires_step(const float* canvas, const void* eps, const float* ref, const float* eps_ref, const float* noise,
+                     size_t noise_step_stride, const float* wt, const float* Lh, const float* Lw, float* canvas_out,
+                     float* windows_out, const float* coef, int* step_idx, int advance, int P, int C, int Hc, int Wc, int S,
+                     const int* oy, int ny, const int* ox, int nx, int scale, int dtype, afldm_stream_t stream);
+/* The last two lines of afldm_hires_step alone, for a given canvas and f: the local crops and the dilated views of
+ * canvas + f (Lh canvas Lw^T - canvas).  The same device code, so the same bits.  Lh / Lw may be NULL when f == 0. */
+int afldm_hires_windows(const float* canvas, const float* Lh, const float* Lw, float f, float* windows_out, int P, int C, int Hc,
+                        int Wc, int S, const int* oy, int ny, const int* ox, int nx, int scale, afldm_stream_t stream);
 /* tvals[step] -> t_out[0] (device->device), so the timestep also follows step_idx.  pre_advance != 0:
  * step_idx is incremented first (a sampler loop then starts from step_idx = -1 and needs no `advance`
  * launch behind afldm_ddim_step). */
