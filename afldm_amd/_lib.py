@@ -155,6 +155,11 @@ def _load():
         "afldm_slot_select": ([vp, vp, vp, vp, vp, vp, vp, vp, ip, ip, ip, c_size_t, vp], c_int),
         "afldm_slot_step": ([vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, vp], c_int),
         "afldm_slot_exchange": ([vp, vp, vp, vp, vp, vp, ip, c_size_t, ip, ip, vp], c_int),
+        "afldm_picard_blocks": ([ip, ip, ip], c_int),
+        "afldm_picard_sweep": ([vp, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, ip, vp], c_int),
+        "afldm_picard_stride": ([vp, vp, vp, vp, vp, vp, ip, vp, vp, vp, vp, vp, vp, fp, ip, ip, ip, ip, ip, ip, ip, ip, c_size_t, vp],
+                                c_int),
+        "afldm_picard_slide": ([vp, vp, vp, ip, ip, ip, ip, ip, vp], c_int),
         "afldm_probe_mfma": ([vp, ip, ip, vp], c_int),
         "afldm_probe_mfma_random": ([vp, ip, ip, vp], c_int),
         "afldm_probe_copy": ([vp, vp, c_size_t, vp], c_int),

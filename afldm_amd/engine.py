@@ -59,6 +59,12 @@ its own, so "ddim" requests of different step counts share the graphs and a fini
 (afldm_slot_select in place of afldm_select_step_row, afldm_slot_step in place of afldm_ddim_step, afldm_slot_exchange at the
 boundary); afldm_amd/serving.py drives it.
 
+PicardEngine (parallel-in-time sampling, ParaDiGMS) walks ONE "ddim" schedule, but a window of its rows at a time: every image keeps
+window + 1 states, the UNet evaluates the first `window` of them as one batch with a timestep per row, and the step ends in
+afldm_picard_sweep (the recurrence along the window, and how far each estimate moved), afldm_picard_stride (how many states to
+accept: the image's cursor moves here and nowhere else, and the next evaluation's rows are gathered) and afldm_picard_slide.  The
+host replays until every cursor has reached the end of the schedule.
+
 Structure.  __init__ validates and stores its arguments; _allocate makes every device buffer and is what refresh_if_stale calls
 again after unet.to(dtype / device).  A kind is one entry of UPDATES - the update op of ops that ends a step, and a function that
 allocates what the kind keeps between steps and returns, per branch, the tensors the op takes between eps and the coefficient
@@ -913,3 +919,140 @@ class SlotEngine(DenoiseEngine):
     def take(self, idx):
         """out_host[idx] as a tensor of its own [1, C, H, W]; the caller has waited for the harvest's event."""
         return self.out_host[idx].clone().unsqueeze(0)
+
+
+class PicardEngine(DenoiseEngine):
+    """Parallel-in-time sampling (ParaDiGMS, Shih et al., NeurIPS 2023) on the replayed graphs: every image keeps window + 1
+    states X[0 .. window], estimates of window consecutive states of ONE "ddim" schedule, and an iteration evaluates the UNet on
+    X[0 .. window - 1] of all P images as one batch of P window rows, sweeps the sampler's recurrence along the window with
+    those outputs (afldm_picard_sweep), accepts the states whose predecessors moved by no more than `tolerance` in mean square
+    (afldm_picard_stride: the stride s >= 1, the only place an image's cursor `base` moves, and the gather of the next
+    evaluation's timesteps and time-embedding rows) and slides the window by s (afldm_picard_slide).  X[0] is always a state of
+    the sequential sampler up to `tolerance`; with tolerance 0 it is that state exactly and the run is the plain DDIM sampler at
+    batch P window, taking n iterations.  An image is finished when base == n; iterations replayed after that leave it alone.
+
+    The states are state-major, [window + 1, P, C, S, S], so `lat` - rows 0 .. window - 1 - is the contiguous NCHW batch the
+    plain step's layout conversion and UNet take unchanged (UNet row j P + p).  run() replays as many iterations as every
+    unfinished image needs at the least, ceil((n - base) / window), then reads the cursors back - one small non-blocking copy
+    into pinned memory and an event - and goes on until every image is finished.  stats: {"iterations", "evaluations"
+    (iterations P window), "strides" (per iteration, one per image)}."""
+    ONE_BRANCH = True           # one cursor table, one stride launch: no parallel branches
+
+    def __init__(self, unet, scheduler, batch_size, num_inference_steps=50, use_graph=True, steps_per_graph=5, branches=1, *,
+                 window=8, tolerance=0.1):
+        kind = (scheduler if isinstance(scheduler, Schedule) else scheduler.schedule(num_inference_steps)).kind
+        if kind not in self.UPDATES:
+            raise NotImplementedError(f"PicardEngine: update_kind {kind!r}: the window takes 'ddim' schedules only (a stochastic kind "
+                                      "needs a pre-drawn noise row per state, 'dpm' a history per state)")
+        if unet.device.type != "cuda":
+            raise RuntimeError("PicardEngine needs the UNet on an MI355X ('cuda') device; there is no CPU path")
+        odd = sorted({type(m.processor).__name__ for m in unet.modules() if hasattr(m, "processor")} - {"AttnProcessor2_0"})
+        if odd:
+            raise ValueError(f"PicardEngine: the UNet has attention processors {odd}; the window needs the plain one")
+        self.window, self.tolerance = self.check_window(window, tolerance)
+        self.stats = None
+        super().__init__(unet, scheduler, batch_size, num_inference_steps, use_graph, steps_per_graph, 1)
+
+    @staticmethod
+    def check_window(window, tolerance):
+        """(window, tolerance) as the engine stores them; ValueError for a window below 1 (or above the kernels' 256) or a
+        tolerance that is negative or NaN."""
+        if int(window) != window or not 1 <= int(window) <= 256:
+            raise ValueError(f"PicardEngine: window = {window} must be an integer in 1 .. 256")
+        if not float(tolerance) >= 0.0:
+            raise ValueError(f"PicardEngine: tolerance = {tolerance} must be >= 0")
+        return int(window), float(tolerance)
+
+    def _allocate(self):
+        """Every device buffer in the UNet's current dtype and on its device; drops the graphs."""
+        unet, dev, P, Wn, n = self.unet, self.unet.device, self.B, self.window, self.n
+        c, s = unet.config.in_channels, unet.config.sample_size
+        i32 = dict(dtype=torch.int32, device=dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.states = torch.zeros(Wn + 1, P, c, s, s, **f32)
+        self.lat = self.states[:Wn].view(Wn * P, c, s, s)          # what the UNet evaluates
+        self.swept = torch.zeros(Wn, P, c, s, s, **f32)             # Y[1 .. Wn]
+        self.partial = torch.zeros(P, Wn, ops.picard_blocks(c, s, s), **f32)
+        self.x_nhwc = torch.empty(Wn * P, s, s, c, dtype=unet.dtype, device=dev)
+        self.graph = self.graph_multi = None
+        # per image: (base, iter) and the last stride; per (image, row): the last errors; per iteration: every image's stride
+        self.cur, self.stride, self.err = torch.zeros(2, P, **i32), torch.zeros(P, **i32), torch.zeros(P, Wn, **f32)
+        self.log = torch.zeros(n + self.steps_per_graph + 1, P, **i32)
+        self.cur_host = torch.zeros(2, P, dtype=torch.int32, pin_memory=True)
+        self._polled = torch.cuda.Event()
+        # the row table, laid out as the slot sampler's: one time-embedding row per schedule row
+        self.row_coef = self.schedule.table(dev).contiguous()
+        self.row_t = torch.tensor(self.timesteps, dtype=torch.float32).to(dev)
+        self.row_temb = torch.arange(n, **i32)
+        self.temb_table = torch.cat([unet.temb_projection(t) for t in self.timesteps], 0).contiguous()
+        self.t_cur, self.active = torch.zeros(Wn * P, **f32), torch.zeros(Wn * P, **i32)
+        self.temb_rows = torch.zeros(Wn * P, self.temb_table.shape[1], dtype=unet.dtype, device=dev)   # (zeros: a row past the end evaluates finite)
+        self.temb_slices = unet.temb_slices(self.temb_rows, per_sample=True)
+        self._model_key = model_state_key(unet)
+        self._side, self._sync = [], [ops.new_sync_buffer(dev)]
+        self.hist = self.noise = self.known = self.mask = self.filter = self._static = None
+        self._update, self._state = self.UPDATES[self.schedule.kind][0], [()]
+
+    UPDATES = {"ddim": (ops.picard_sweep, DenoiseEngine._no_state)}
+
+    def _gather(self, decide):
+        ops.picard_stride(self.partial, self.cur, self.stride, self.err, self.log, self.row_t, self.row_temb, self.t_cur, self.active,
+                          self.temb_table, self.temb_rows, self.tolerance ** 2, self.states.shape[2:], gather_only=not decide)
+
+    def _step(self):
+        self._substep(self.lat, self.x_nhwc)
+
+    def _apply(self, lat, eps, branch):
+        self._update(self.states, eps, self.swept, self.partial, self.row_coef, self.cur[0])
+        self._gather(True)
+        ops.picard_slide(self.states, self.swept, self.stride)
+
+    def _carried(self):
+        return [self.states, self.cur, self.stride, self.err, self.log, self.t_cur, self.active, self.temb_rows]
+
+    def _rewind(self):
+        pass                        # (the cursors are carried: _capture puts them back)
+
+    def _result(self):
+        return self.states[0].clone()
+
+    def reset(self, latents):
+        """latents [P, C, S, S]: every state of the window starts as the start latents, every cursor at row 0."""
+        self.refresh_if_stale()
+        self.states.copy_((latents.to(device=self.lat.device, dtype=torch.float32) * self.schedule.init_noise_sigma).unsqueeze(0)
+                          .expand_as(self.states))
+        self.cur.zero_()
+        self.stride.zero_()
+        self.log.zero_()
+        self._gather(False)
+
+    def _poll(self):
+        """(base, iter) per image as they stand behind everything launched so far."""
+        self.cur_host.copy_(self.cur, non_blocking=True)
+        self._polled.record()
+        self._polled.synchronize()
+        return self.cur_host[0].tolist(), int(self.cur_host[1, 0])
+
+    @torch.no_grad()
+    def run(self, latents, draw=None, known=None):
+        """latents [P, C, S, S] -> the sampled latents (fp32); `stats` says what it took.  draw and known do not apply."""
+        if known is not None:
+            raise ValueError("PicardEngine: known= goes with a 'repaint' or 'ilvr' schedule; the window takes 'ddim' ones")
+        if tuple(latents.shape) != tuple(self.states.shape[1:]):
+            raise ValueError(f"PicardEngine: latents {tuple(latents.shape)}, want {tuple(self.states.shape[1:])}")
+        self.reset(latents)
+        base, done = [0] * self.B, 0
+        while min(base) < self.n:
+            if done >= self.n:
+                raise RuntimeError(f"PicardEngine: {done} iterations of a {self.n}-row schedule and the cursors stand at {base}: "
+                                   "every iteration advances an unfinished image by one row at the least")
+            # what every unfinished image needs at the least, within what is left of the n iterations that always suffice
+            self.step(min(max(-(-(self.n - b) // self.window) for b in base), self.n - done))
+            base, done = self._poll()
+        out = self._result()
+        strides = self.log[:done].tolist()
+        while strides and not any(strides[-1]):
+            strides.pop()           # (iterations of a replay group after the last image finished)
+        self.stats = {"iterations": len(strides), "evaluations": len(strides) * self.B * self.window, "strides": strides}
+        self.check_errors()
+        return out

@@ -2012,6 +2012,75 @@ def slot_exchange(cmd, lat, out, fresh, pos, end):
     return lat
 
 
+# ----------------------------------------------------------------------------- parallel-in-time sampling (Picard sweeps over a window)
+def picard_blocks(C, H, W):
+    """Blocks of an afldm_picard_sweep per image: the last dimension of its workspace `partial` [P, Wn, blocks]."""
+    n = lib.afldm_picard_blocks(int(C), int(H), int(W))
+    if n <= 0:
+        raise ValueError(f"picard_blocks: bad shape ({C}, {H}, {W})")
+    return n
+
+
+def _picard_states(x, y):
+    _dev(x, "x"); _dev(y, "y")
+    assert x.dtype == y.dtype == torch.float32 and x.dim() == 5 and x.shape[0] >= 2, "picard: x must be fp32 [Wn + 1, P, C, H, W]"
+    Wn, P, C, H, W = x.shape[0] - 1, *x.shape[1:]
+    assert tuple(y.shape) == (Wn, P, C, H, W), f"picard: y must be [{Wn}, {P}, {C}, {H}, {W}]"
+    return Wn, P, C, H, W
+
+
+def picard_sweep(x, eps_nhwc, y, partial, row_coef, base):
+    """afldm_picard_sweep: x fp32 [Wn + 1, P, C, H, W] (the states X[0 .. Wn] of every image), eps NHWC dtype [Wn P, H, W, C] (row
+    j P + p evaluated at X[j] of image p), y fp32 [Wn, P, C, H, W] <- Y[1 .. Wn], partial fp32 [P, Wn, picard_blocks(C, H, W)] <-
+    the blocks' sums of (Y[j + 1] - X[j + 1])^2; row_coef fp32 [n, 4], base int32 [P] (read only).  A finished image (base[p] == n)
+    is skipped."""
+    Wn, P, C, H, W = _picard_states(x, y)
+    _dev(eps_nhwc, "eps"); _dev(partial, "partial"); _dev(row_coef, "row_coef")
+    _slot_ints(P, base=base)
+    assert row_coef.dtype == partial.dtype == torch.float32 and row_coef.dim() == 2 and row_coef.shape[1] == 4
+    assert tuple(eps_nhwc.shape) == (Wn * P, H, W, C) and tuple(partial.shape) == (P, Wn, picard_blocks(C, H, W))
+    check(lib.afldm_picard_sweep(ptr(x), ptr(eps_nhwc), ptr(y), ptr(partial), ptr(row_coef), ptr(base), P, Wn, row_coef.shape[0],
+                                 C, H, W, _code(eps_nhwc), stream_ptr()), "picard_sweep")
+    return y
+
+
+def picard_stride(partial, cur, stride, err, log, row_t, row_temb, t_out, active, temb_table, temb_rows, tol2, shape,
+                  gather_only=False):
+    """afldm_picard_stride: per image p, err[p, j] = sum_b partial[p, j, b] / (C H W); s = min(first j + 1 with err[p, j] > tol2,
+    else Wn; n - base[p]); stride[p] = s; base[p] += s; log[iter[p], p] = s; iter[p] += 1 - cur int32 [2, P] holds (base, iter) -
+    then t_out / active / temb_rows [Wn P] are gathered for the rows base[p] + j (slot_select's tables: row_t fp32 [n], row_temb
+    int32 [n], temb_table [T, width]).  A finished image: s = 0 and nothing gathered.  shape = (C, H, W) of a state;
+    gather_only: no decision, no advance, the gather alone."""
+    _dev(partial, "partial"); _dev(cur, "cur"); _dev(err, "err"); _dev(log, "log")
+    P, Wn = partial.shape[0], partial.shape[1]
+    C, H, W = (int(v) for v in shape)
+    n, T = row_t.numel(), temb_table.shape[0]
+    _slot_ints(P, stride=stride)
+    _slot_ints(Wn * P, active=active)
+    for name, t in (("row_t", row_t), ("row_temb", row_temb), ("t_out", t_out), ("temb_table", temb_table), ("temb_rows", temb_rows)):
+        _dev(t, name)
+    assert partial.dtype == err.dtype == torch.float32 and tuple(partial.shape) == (P, Wn, picard_blocks(C, H, W))
+    assert cur.dtype == log.dtype == torch.int32 and tuple(cur.shape) == (2, P) and tuple(err.shape) == (P, Wn)
+    assert log.dim() == 2 and log.shape[1] == P
+    assert row_t.dtype == t_out.dtype == torch.float32 and row_temb.dtype == torch.int32 and row_temb.numel() == n
+    assert t_out.numel() == Wn * P and temb_table.dim() == 2 and tuple(temb_rows.shape) == (Wn * P, temb_table.shape[1])
+    assert temb_table.dtype == temb_rows.dtype
+    nbytes = temb_table.shape[1] * temb_table.element_size()
+    check(lib.afldm_picard_stride(ptr(partial), ptr(cur[0]), ptr(cur[1]), ptr(stride), ptr(err), ptr(log), log.shape[0], ptr(row_t),
+                                  ptr(row_temb), ptr(t_out), ptr(active), ptr(temb_table), ptr(temb_rows), float(tol2),
+                                  int(bool(gather_only)), P, Wn, n, C, H, W, T, nbytes, stream_ptr()), "picard_stride")
+    return stride
+
+
+def picard_slide(x, y, stride):
+    """afldm_picard_slide, in place: X[j] of image p <- Y[min(j + stride[p], Wn)], j = 0 .. Wn (x, y as picard_sweep); an image
+    whose stride is 0 is not touched."""
+    Wn, P, C, H, W = _picard_states(x, y)
+    _slot_ints(P, stride=stride)
+    check(lib.afldm_picard_slide(ptr(x), ptr(y), ptr(stride), P, Wn, C, H, W, stream_ptr()), "picard_slide")
+    return x
+
+
 FLOW_PICK, FLOW_POOL = 0, 1
 
 

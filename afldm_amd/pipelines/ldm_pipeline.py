@@ -103,6 +103,95 @@ class MyLDMPipeline(DiffusionPipeline):
             raise ValueError("sample_mixed: no requests")
         return server.decode(tickets, output_type, return_dict)
 
+    # ------------------------------------------------------------------------------------------------ parallel-in-time sampling
+    @torch.no_grad()
+    def sample_parallel_latents(self, batch_size=1, num_inference_steps=50, window=8, tolerance=0.1, generator=None, latents=None,
+                                use_graph=True, eta=0.0):
+        """Parallel-in-time DDIM sampling (ParaDiGMS, Shih et al., NeurIPS 2023; diffusers' DDIMParallelScheduler pipeline, whose
+        default `tolerance` this takes): `window` consecutive steps of every image are evaluated as one UNet batch of batch_size x
+        window rows and iterated to their fixed point - Picard iteration on the sampler's recurrence.  One iteration evaluates
+        eps at the window's current estimates, sweeps the DDIM update along the window with those outputs, accepts every state
+        up to the first whose estimate moved by more than tolerance^2 in mean square (at least one: the first state of a window
+        is always exact) and slides the window that far.  An image therefore costs `iterations` evaluations of batch `window`
+        instead of num_inference_steps evaluations of batch 1, and iterations <= num_inference_steps always.  tolerance = 0
+        accepts a state only when its predecessors did not move at all: the plain DDIM sampler, one state per iteration;
+        window = 1 is that sampler too.  tolerance > 0 trades accuracy for iterations.  How many iterations a trained model
+        takes at a given tolerance has not been measured here, and no claim about sample quality is made for any tolerance.
+
+        The start latents are drawn as __call__ draws them.  use_graph: PicardEngine on replayed HIP graphs (afldm_picard_sweep /
+        _stride / _slide behind the UNet); otherwise the statement-by-statement loop below: per-row timesteps into the UNet, the
+        recurrence and the errors in torch, the stride decided on the host.  Only the deterministic DDIM sampler has this form:
+        eta != 0 and a DPM scheduler raise NotImplementedError.  Needs no VAE.  Returns (fp32 latents [B, C, S, S], stats) with
+        stats = {"iterations", "evaluations" (iterations x batch_size x window), "strides" (per iteration, one per image)}."""
+        from ..engine import PicardEngine
+        self._refuse_dpm("sample_parallel_latents")
+        if not isinstance(self.scheduler, DDIMScheduler):
+            raise NotImplementedError(f"sample_parallel_latents needs a DDIMScheduler: it is not implemented with "
+                                      f"{type(self.scheduler).__name__} (PicardEngine takes any 'ddim' Schedule directly)")
+        if eta != 0.0:
+            raise NotImplementedError("sample_parallel_latents: eta != 0 (a stochastic schedule) needs a pre-drawn noise row per "
+                                      "state of the window, which is not implemented")
+        window, tolerance = PicardEngine.check_window(window, tolerance)
+        self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
+        c, s = self.unet.config.in_channels, self.unet.config.sample_size
+        if latents is None:
+            latents = randn_tensor((batch_size, c, s, s), generator=generator)
+        if latents.dim() != 4 or tuple(latents.shape[1:]) != (c, s, s):
+            raise ValueError(f"sample_parallel_latents: latents {tuple(latents.shape)}, want [B, {c}, {s}, {s}]")
+        sched = self.scheduler.schedule(num_inference_steps)
+        if use_graph:
+            eng = cached_engine(self, "_picard_engines", sched, latents.shape[0], True, self.unet, PicardEngine, window=window,
+                                tolerance=tolerance)
+            eng.scheduler = self.scheduler
+            return eng.run(latents), eng.stats
+        return self._picard_loop(sched, latents, window, tolerance)
+
+    def _picard_loop(self, sched, latents, window, tolerance):
+        """sample_parallel_latents(use_graph=False): the four steps of an iteration as torch statements."""
+        if self.unet.device.type != "cuda":
+            raise RuntimeError("sample_parallel_latents needs the UNet on an MI355X ('cuda') device; there is no CPU path")
+        dev, n, Wn, P = self.unet.device, len(sched.rows), window, latents.shape[0]
+        rows, ts = sched.table(dev), sched.timesteps
+        x = (latents.to(device=dev, dtype=torch.float32) * sched.init_noise_sigma).unsqueeze(0).repeat(Wn + 1, 1, 1, 1, 1)
+        base, strides = [0] * P, []
+        while min(base) < n:
+            if len(strides) >= n:
+                raise RuntimeError(f"sample_parallel_latents: {len(strides)} iterations of a {n}-row schedule, cursors at {base}")
+            # 1. evaluate: row j P + p at X[j] of image p with its own timestep (a row past the end: evaluated, not used)
+            t = torch.tensor([float(ts[min(base[p] + j, n - 1)]) for j in range(Wn) for p in range(P)], device=dev)
+            eps = self.unet(x[:Wn].reshape((Wn * P,) + tuple(x.shape[2:])).to(self.unet.dtype), t).sample.float().reshape(x[:Wn].shape)
+            # 2. sweep
+            y = [x[0]]
+            for j in range(Wn):
+                on = torch.tensor([base[p] + j < n for p in range(P)], device=dev).reshape(P, 1, 1, 1)
+                c0, c1, c2, c3 = (rows[[min(base[p] + j, n - 1) for p in range(P)], k].reshape(P, 1, 1, 1) for k in range(4))
+                y.append(torch.where(on, c2 * ((y[j] - c1 * eps[j]) / c0) + c3 * eps[j], y[j]))
+            y = torch.stack(y)
+            err = (y[1:] - x[1:]).pow(2).mean(dim=(2, 3, 4)).tolist()          # [Wn][P]
+            # 3. stride, 4. slide
+            took = []
+            for p in range(P):
+                if base[p] >= n:
+                    took.append(0)
+                    continue
+                over = [j + 1 for j in range(Wn) if base[p] + j < n and err[j][p] > tolerance ** 2]
+                sp = min(min(over + [Wn]), n - base[p])
+                x[:, p] = y[[min(j + sp, Wn) for j in range(Wn + 1)], p]
+                base[p] += sp
+                took.append(sp)
+            strides.append(took)
+        stats = {"iterations": len(strides), "evaluations": len(strides) * P * Wn, "strides": strides}
+        return x[0].clone(), stats
+
+    @torch.no_grad()
+    def sample_parallel(self, batch_size=1, num_inference_steps=50, window=8, tolerance=0.1, generator=None, latents=None,
+                        use_graph=True, eta=0.0, output_type="pil", return_dict=True):
+        """Sample images with parallel-in-time DDIM sampling: sample_parallel_latents, then decode.  output_type as __call__;
+        'latent' returns the latents in the UNet's dtype.  The statistics of the run stay in `pipe.parallel_stats`."""
+        out, self.__dict__["parallel_stats"] = self.sample_parallel_latents(batch_size, num_inference_steps, window, tolerance,
+                                                                            generator, latents, use_graph, eta)
+        return self._deliver(out.to(self.unet.dtype), output_type, return_dict)
+
     def _deliver(self, latents, output_type, return_dict):
         """'latent' -> the latents; 'pt' -> decoded tensor in [-1, 1]; 'np' / 'pil' -> [0, 1] NHWC arrays / PIL images
         (wrapped in ImagePipelineOutput unless return_dict is False)."""

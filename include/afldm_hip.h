@@ -702,6 +702,41 @@ int afldm_slot_step(float* x, const void* eps, const float* row_coef, const int*
 int afldm_slot_exchange(const int* cmd, float* lat, float* out, const float* fresh, int* pos, int* end, int B, size_t slot_elems,
                         int out_rows, int fresh_rows, afldm_stream_t stream);
 
+/* ---- parallel-in-time sampling: Picard sweeps over a window of steps (ParaDiGMS, Shih et al., NeurIPS 2023) ------------
+ * Every image p of P keeps Wn + 1 states X[0 .. Wn], estimates of x_{base[p]} .. x_{base[p] + Wn} of ONE "ddim" schedule of n
+ * rows; X[0] is exact.  x: fp32 [Wn + 1][P][C][H][W] (state-major: rows 0 .. Wn - 1 are the NCHW batch [Wn P] the UNet
+ * evaluates, UNet row j P + p); y: fp32 [Wn][P][C][H][W], row j holds Y[j + 1]; eps: NHWC dtype [Wn P][H][W][C].
+ *   base[p], iter[p]  device int32: the schedule row X[0] stands at (0 .. n, n = finished) and the iterations seen so far
+ *   row_coef [n][4], row_t [n], row_temb [n], temb_table [T][row_bytes]   the slot sampler's row table (above)
+ * One iteration is the UNet evaluation and then the three calls below, in this order.  All are stream-ordered, capturable and
+ * allocate nothing; they hold no atomics, and what they compute for an image depends neither on P nor on p.  An index read from
+ * device memory that falls outside its table skips what it indexes: nothing is read or written out of range.  A finished
+ * image is skipped by all three: of its states, errors, timesteps and time-embedding rows nothing is written.
+ *
+ * afldm_picard_blocks - the blocks B of a sweep per image, from the shape alone: ceil(C H W / (256 V)), V = 4 where
+ *   H W % 4 == 0 (then x and y must be 16-byte aligned: AFLDM_EALIGN otherwise), else 1.  partial is fp32 [P][Wn][B].
+ * afldm_picard_sweep - Y[0] = X[0]; for j = 0 .. Wn - 1 with r = base[p] + j:
+ *     r < n:   Y[j + 1] = c2 x0 + c3 e_j,  x0 = (Y[j] - c1 e_j) / c0,  (c0 .. c3) = row_coef[r], in afldm_ddim_step's float
+ *              operations and order (a swept row has afldm_ddim_step's bits for the same operands)
+ *     r >= n:  Y[j + 1] = Y[j]
+ *   and partial[p][j][b] = block b's sum of (Y[j + 1] - X[j + 1])^2 (0 for r >= n), summed in a fixed order.  Reads base only.
+ * afldm_picard_stride - ONE workgroup per image, and the only place base[p] moves:
+ *     err[p][j] = (sum_b partial[p][j][b], b ascending) / (C H W);  s = min({j + 1 : err[p][j] > tol2} U {Wn}, n - base[p]);
+ *     stride[p] = s;  base[p] += s;  log[iter[p]][p] = s (iter[p] < log_cap);  iter[p] += 1
+ *   (a finished image: s = 0), then, where s > 0, the gather for the next evaluation: for j = 0 .. Wn - 1 with r = base[p] + j
+ *   < n: t_out[j P + p] = row_t[r], active[j P + p] = 1, temb_rows[j P + p] <- temb_table[row_temb[r]] (row_bytes % 16 == 0);
+ *   r >= n: active[j P + p] = 0 and nothing else, so the row is evaluated with what it last held.  gather_only != 0: no
+ *   decision and no advance, only the gather for the cursors as they stand (before the first evaluation of a run).
+ * afldm_picard_slide - X[j] = Y[min(j + stride[p], Wn)], j = 0 .. Wn; stride[p] outside 1 .. Wn: the image is left alone. */
+int afldm_picard_blocks(int C, int H, int W);
+int afldm_picard_sweep(const float* x, const void* eps, float* y, float* partial, const float* row_coef, const int* base, int P,
+                       int Wn, int n, int C, int H, int W, int dtype, afldm_stream_t stream);
+int afldm_picard_stride(const float* partial, int* base, int* iter, int* stride, float* err, int* log, int log_cap,
+                        const float* row_t, const int* row_temb, float* t_out, int* active, const void* temb_table,
+                        void* temb_rows, float tol2, int gather_only, int P, int Wn, int n, int C, int H, int W, int T,
+                        size_t row_bytes, afldm_stream_t stream);
+int afldm_picard_slide(float* x, const float* y, const int* stride, int P, int Wn, int C, int H, int W, afldm_stream_t stream);
+
 /* ---- masked equivariance metrics (shift_utils/metrics.py:5-20) ------------------------------
  * One pass over a, b [B][n] (dtype) and mask [B][n] fp32: out[b] = { sum ((a - b) mask)^2, sum mask,
  * max(a mask), min(a mask), max(b mask), min(b mask) } (fp32 [B][6]).  mask_mse = mean_b out[b][0] / out[b][1];
