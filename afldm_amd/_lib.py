@@ -124,6 +124,8 @@ def _load():
         "afldm_repaint_step": ([vp, vp, vp, vp, vp, c_size_t, c_size_t, vp, vp, vp, ip, ip, ip, ip, ip, ip, vp], c_int),
         "afldm_repaint_step_flat": ([vp] * 8 + [fp] * 11 + [c_size_t, vp], c_int),
         "afldm_mask_pool": ([vp, vp, ip, ip, ip, ip, ip, vp], c_int),
+        "afldm_sdedit_step": ([vp, vp, vp, vp, vp, vp, c_size_t, vp, vp, vp, ip, ip, ip, ip, ip, ip, vp], c_int),
+        "afldm_sdedit_step_flat": ([vp] * 7 + [fp] * 10 + [c_size_t, vp], c_int),
         "afldm_ilvr_step": ([vp, vp, vp, vp, c_size_t, c_size_t, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, vp], c_int),
         "afldm_ilvr_step_flat": ([vp] * 8 + [fp] * 10 + [c_size_t, ip, ip, vp], c_int),
         "afldm_pano_step": ([vp, vp, vp, c_size_t, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, POINTER(c_int), ip, POINTER(c_int), ip, ip,

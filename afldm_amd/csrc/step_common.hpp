@@ -1,4 +1,4 @@
-// step_common.hpp — what the sampler-update kernels (dpm, sde, repaint, ilvr, pag, pano, hires .hip) share.  Everything here has internal
+// step_common.hpp — what the sampler-update kernels (dpm, sde, repaint, sdedit, ilvr, pag, pano, hires .hip) share.  Everything here has internal
 // linkage: every .hip file is its own translation unit and there is no relocatable device code, so each gets its own copy.
 #pragma once
 #include "common.hpp"

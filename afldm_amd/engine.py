@@ -30,6 +30,11 @@ one update that is not elementwise: it low-passes a whole (b, c) plane in LDS.  
 [steps, 2, B, C, H, W] and two static per-run tensors, the reference latents and the [S, S] filter matrix -
 run(latents, draw=..., known=(ref, L)); another reference or another cut-off replays the same graphs.
 
+SDEditEngine (kind "sdedit", DDIMScheduler.sdedit_schedule: image-to-image sampling, SDEdit with a change map) has [steps, 12]
+rows and afldm_sdedit_step as the last line, which selects per element between the reverse step and the original noised to the
+next level with the run's one fixed noise - run(x_start, draw=..., known=(orig, cmap, z)); three static per-run tensors and, only
+when eta != 0, a noise buffer [steps, B, C, H, W].
+
 PanoramaEngine (kind "pano", DDIMScheduler.panorama_schedule: MultiDiffusion) samples a canvas [P, C, Hc, Wc] larger than the UNet's
 window: `lat` holds the P * nwin windows of a panorama.Geometry, the canvas is a second fp32 buffer, and the last line of a step is
 afldm_pano_step, which applies the "sde" row per window, averages over the windows that cover each canvas element and writes both
@@ -434,6 +439,11 @@ class DenoiseEngine:
                              f"{tuple(self.lat.shape)} / {tuple(second.shape)}" + (" (or batch 1)" if broadcast else ""))
         return z0, extra
 
+    def _set_known(self, z0, extra):
+        """run()'s known=, as _check_known returned it, into the static buffers the captured graphs read."""
+        self.known.copy_(z0)
+        self._static[1].copy_(extra)
+
     @torch.no_grad()
     def run(self, latents, draw=None, known=None):
         """latents -> the sampled latents (fp32).  An "sde", "repaint" or "ilvr" schedule needs `draw`: a callable returning the next
@@ -446,8 +456,7 @@ class DenoiseEngine:
         z0, extra = self._check_known(known)
         self.reset(latents)
         if known is not None:          # (after reset: a dtype or device change re-allocates the static buffers)
-            self.known.copy_(z0)
-            self._static[1].copy_(extra)
+            self._set_known(z0, extra)
         if self.noise is None:
             self.step(self.n)
         else:
@@ -465,6 +474,46 @@ class DenoiseEngine:
         out = self._result()
         self.check_errors()                           # one 8-byte read per run: a run whose hand-over failed must not return latents
         return out
+
+
+class SDEditEngine(DenoiseEngine):
+    """Image-to-image sampling on the replayed graphs: SDEdit with a per-element change map (Differential Diffusion).  A step is
+    the plain sampler's launch list with afldm_sdedit_step as the last line: an element whose change value is <= the row's
+    threshold is held on the original's noised trajectory k0 orig + k1 z - z the run's ONE fixed noise - and every other element
+    takes the reverse step.  run(x_start, draw=..., known=(orig, cmap, z)): the original latents and the fixed noise [B, C, S, S]
+    and the change map [B | 1, 1, S, S] are per-run static buffers, so another image, map or noise replays the same graphs;
+    x_start is k0_start orig + k1_start z (DDIMScheduler.sdedit_start); `draw` returns latent-shaped tensors, one per evaluation
+    that draws (eta != 0).  The update is elementwise per sample, so parallel branches work as for the repaint kind."""
+
+    def _sdedit_state(self):
+        """The run's original latents, fixed noise and change map (a batch-1 map is broadcast) and one noise row per step, only
+        when some step draws (eta != 0).  Every branch takes its batch slice of all four."""
+        self.known = torch.zeros_like(self.lat)
+        self.zfix = torch.zeros_like(self.lat)
+        self.cmap = torch.zeros((self.B, 1) + tuple(self.lat.shape[2:]), dtype=torch.float32, device=self.lat.device)
+        self._static = ("cmap", self.cmap, True)
+        return [self._slice(b, self.known, self.cmap, self.zfix) + (z,)
+                for b, z in enumerate(self._noise(self.lat.shape, only_if_drawn=True))]
+
+    UPDATES = {"sdedit": (ops.sdedit_step, _sdedit_state)}
+
+    def _check_known(self, known):
+        if known is None or len(known) != 3:
+            raise ValueError("SDEditEngine: run(x_start, draw=..., known=(orig, cmap, z)) needs the original latents, the change map "
+                             "and the run's fixed noise")
+        orig, cmap, z = known
+        want = tuple(self.lat.shape)
+        if tuple(orig.shape) != want or tuple(z.shape) != want or tuple(cmap.shape) not in [tuple(self.cmap.shape),
+                                                                                           (1,) + tuple(self.cmap.shape[1:])]:
+            raise ValueError(f"SDEditEngine: orig {tuple(orig.shape)} / z {tuple(z.shape)} / change map {tuple(cmap.shape)}, want "
+                             f"{want} / {want} / {tuple(self.cmap.shape)} (or batch 1)")
+        return orig, (cmap, z)
+
+    def _set_known(self, orig, extra):
+        cmap, z = extra
+        self.known.copy_(orig)
+        self.cmap.copy_(cmap)
+        self.zfix.copy_(z)
 
 
 class PanoramaEngine(DenoiseEngine):

@@ -1565,6 +1565,47 @@ def mask_pool(mask, r, mode=MASK_MIN, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- image-to-image (SDEdit with a change map)
+def sdedit_step(x, eps_nhwc, orig, cmap, z, noise, coef, step_idx, advance=False, out=None):
+    """x, orig, z NCHW fp32 [B, C, H, W] (z: the run's one fixed noise), cmap fp32 [B, 1, H, W] (the change map: an element is held
+    on orig's noised trajectory while cmap <= the row's thr), eps NHWC dtype; noise: None (no row has c != 0) or an fp32 view
+    [steps, B, C, H, W] whose last four dimensions are contiguous (a batch slice of a larger buffer is fine: the row stride is
+    noise.stride(0)); coef float[12*nsteps] rows (p, q, lo, hi, a, b, c, k0, k1, thr, 0, 0) and step_idx int32[1] on device."""
+    _dev(x, "x"); _dev(eps_nhwc, "eps"); _dev(orig, "orig"); _dev(cmap, "cmap"); _dev(z, "z")
+    if x.dim() != 4:
+        raise ValueError(f"sdedit_step: x {tuple(x.shape)}, want [B, C, H, W]")
+    B, C, H, W = x.shape
+    assert x.dtype == orig.dtype == cmap.dtype == z.dtype == torch.float32
+    if orig.shape != x.shape or z.shape != x.shape or tuple(cmap.shape) != (B, 1, H, W) or tuple(eps_nhwc.shape) != (B, H, W, C):
+        raise ValueError(f"sdedit_step: x {tuple(x.shape)}, orig {tuple(orig.shape)}, z {tuple(z.shape)}, cmap {tuple(cmap.shape)} "
+                         f"(want {(B, 1, H, W)}: expand a batch-1 map first), eps {tuple(eps_nhwc.shape)} (want NHWC {(B, H, W, C)})")
+    assert x.is_contiguous() and orig.is_contiguous() and cmap.is_contiguous() and z.is_contiguous() and eps_nhwc.is_contiguous()
+    noise_args = (None, 0) if noise is None else _noise_view(noise, x.shape)
+    if out is None:
+        out = torch.empty_like(x)
+    check(lib.afldm_sdedit_step(ptr(x), ptr(eps_nhwc), ptr(orig), ptr(cmap), ptr(z), *noise_args, ptr(out), ptr(coef), ptr(step_idx),
+                                int(advance), B, C, H, W, _code(eps_nhwc), stream_ptr()), "sdedit_step")
+    return out
+
+
+def sdedit_step_flat(x, eps, orig, cmap, z, z_u, row, out=None):
+    """x, eps, orig, cmap: same-shape contiguous fp32 CUDA tensors (the change map expanded to x's shape); z, z_u: such a tensor, or
+    None where its coefficient (k1, c) is 0; row = the floats (p, q, lo, hi, a, b, c, k0, k1, thr)."""
+    _dev(x, "x"); _dev(eps, "eps"); _dev(orig, "orig"); _dev(cmap, "cmap")
+    assert x.dtype == eps.dtype == orig.dtype == cmap.dtype == torch.float32
+    if not (x.shape == eps.shape == orig.shape == cmap.shape):
+        raise ValueError(f"sdedit_step_flat: x {tuple(x.shape)}, eps {tuple(eps.shape)}, orig {tuple(orig.shape)}, cmap "
+                         f"{tuple(cmap.shape)} must have one shape (expand the change map first)")
+    assert x.is_contiguous() and eps.is_contiguous() and orig.is_contiguous() and cmap.is_contiguous()
+    row = [float(c) for c in row[:10]]
+    _slot_tensors("sdedit_step_flat", x, (z, z_u), (row[8], row[6]), ("z", "z_u"), contiguous=True)
+    if out is None:
+        out = torch.empty_like(x)
+    check(lib.afldm_sdedit_step_flat(ptr(x), ptr(eps), ptr(orig), ptr(cmap), ptr(z), ptr(z_u), ptr(out), *row, x.numel(),
+                                     stream_ptr()), "sdedit_step_flat")
+    return out
+
+
 # ----------------------------------------------------------------------------- ILVR reference-guided sampling
 def _ilvr_plane(name, x, Lh, Lw):
     """The checks ilvr_step and ilvr_step_flat share: fp32 [B, C, H, W] latents, Lh fp32 [H, H] and Lw fp32 [W, W] on the device.

@@ -88,3 +88,11 @@ class I2SBLDMPipeline(MyLDMPipeline):
     def hires(self, *args, **kwargs):
         raise NotImplementedError("I2SBLDMPipeline: high-resolution sampling is defined for the unconditional sampler "
                                   "(MyLDMPipeline.hires); the bridge starts from an encoded image of the window's size")
+
+    def img2img_latents(self, *args, **kwargs):
+        raise NotImplementedError("I2SBLDMPipeline: image-to-image sampling (SDEdit) is defined for the unconditional sampler "
+                                  "(MyLDMPipeline.img2img_latents); the bridge has its own start, the encoded low-resolution image")
+
+    def img2img(self, *args, **kwargs):
+        raise NotImplementedError("I2SBLDMPipeline: image-to-image sampling (SDEdit) is defined for the unconditional sampler "
+                                  "(MyLDMPipeline.img2img); the bridge has its own start, the encoded low-resolution image")

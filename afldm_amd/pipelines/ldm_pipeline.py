@@ -354,6 +354,91 @@ class MyLDMPipeline(DiffusionPipeline):
             decoded = mask * image + (1 - mask) * decoded.float()
         return self._images(decoded, output_type, return_dict)
 
+    # ------------------------------------------------------------------------------------------------ image-to-image (SDEdit)
+    @torch.no_grad()
+    def img2img_latents(self, orig_latents, strength=0.6, change_map=None, num_inference_steps=50, eta=0.0, generator=None,
+                        noise=None, use_graph=True):
+        """Image-to-image sampling in latent space: SDEdit (Meng et al., ICLR 2022; the reference's get_timesteps and
+        prepare_latents_sdedit, video_equiv_editing_pipeline.py:251-328) with a per-element change map (Differential Diffusion,
+        Levin & Fried 2023).  `orig_latents` [B, C, S, S] is noised to the first of the last n = int(num_inference_steps * strength)
+        timesteps and denoised from there.  `change_map` [B | 1, 1, S, S] in [0, 1] gives every element a strength of its own:
+        1 is regenerated from the first evaluation, 0 is never touched and comes back exactly, and a value between is held on the
+        original's noised trajectory until the schedule's threshold (n - 1 - k) / n falls below it; None: all ones, plain SDEdit.
+        Needs no VAE.  The schedule is DDIMScheduler.sdedit_schedule: every UNet evaluation ends in one afldm_sdedit_step, on
+        replayed HIP graphs (use_graph) or in the eager loop below, which makes the same draws from `generator` in the same
+        order - the run's one noise z in the model's dtype (unless `noise` is given), then per evaluation z_u where the schedule
+        draws it - and carries the latents in fp32 like the engine.  Returns latents in the UNet's dtype."""
+        from .. import ops
+        from ..engine import SDEditEngine
+        self._refuse_dpm("img2img_latents")
+        c, s = self.unet.config.in_channels, self.unet.config.sample_size
+        if orig_latents.dim() != 4 or tuple(orig_latents.shape[1:]) != (c, s, s):
+            raise ValueError(f"img2img_latents: orig_latents {tuple(orig_latents.shape)}, want [B, {c}, {s}, {s}]")
+        B = orig_latents.shape[0]
+        if change_map is not None and (change_map.dim() != 4 or tuple(change_map.shape[1:]) != (1, s, s)
+                                       or change_map.shape[0] not in (1, B)):
+            raise ValueError(f"img2img_latents: change_map {tuple(change_map.shape)}, want [{B} or 1, 1, {s}, {s}]")
+        if noise is not None and tuple(noise.shape) != (B, c, s, s):
+            raise ValueError(f"img2img_latents: noise {tuple(noise.shape)}, want {(B, c, s, s)}")
+        self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
+        sched = self.scheduler.sdedit_schedule(num_inference_steps, strength, eta)
+        k0s, k1s = self.scheduler.sdedit_start(num_inference_steps, strength)
+        dev = self.unet.device
+        shape = (B, c, s, s)
+        orig = orig_latents.to(device=dev, dtype=torch.float32).contiguous()
+        cmap = (torch.ones(1, 1, s, s, device=dev) if change_map is None else change_map).to(device=dev, dtype=torch.float32)
+        if noise is None:
+            noise = sched.drawer(generator, shape, dev, self.unet.dtype)()
+        z = noise.to(device=dev, dtype=torch.float32).contiguous()
+        # the start, by the formula every held element follows: the row (p = q = 0, no clip, a = b = c = 0, k0_start, k1_start,
+        # thr = +inf) holds everything at k0_start orig + k1_start z
+        zero = torch.zeros_like(orig)
+        start = ops.sdedit_step_flat(zero, zero, orig, zero, z, None,
+                                     (0.0, 0.0, -float("inf"), float("inf"), 0.0, 0.0, 0.0, k0s, k1s, float("inf")))
+        full = None if use_graph else cmap.expand(B, c, s, s).contiguous()
+
+        def eager(x, t, row, zs):
+            eps = self.unet(x.to(self.unet.dtype), t).sample
+            return ops.sdedit_step_flat(x, eps.float().contiguous(), orig, full, z, zs[0], row)
+        return self._sample(sched, shape, generator, start, use_graph, "_sdedit_engines", eager, cls=SDEditEngine,
+                            known=(orig, cmap, z)).to(self.unet.dtype)
+
+    @torch.no_grad()
+    def img2img(self, image, strength=0.6, change_map=None, num_inference_steps=50, eta=0.0, generator=None, noise=None,
+                use_graph=True, composite=True, output_type="pil", return_dict=True):
+        """Change `image` [B, 3, H, W] in [-1, 1] by `strength`; `change_map` [B | 1, 1, H, W] in [0, 1] says per pixel how much
+        (0 = keep, 1 = regenerate; None: everywhere).  The image is encoded with the posterior mode times scaling_factor
+        (harness.vae_encode_mode), the map pooled to the latent grid by its mean over the VAE's down-sampling blocks
+        (afldm_mask_pool), the latents sampled by img2img_latents and decoded.  composite: pixels whose change value is exactly 0
+        are the input's, in fp32; nothing is blended elsewhere.  output_type as __call__; 'latent' returns the sampled latents."""
+        from .. import ops
+        self._refuse_dpm("img2img")
+        if self.vae is None:
+            raise NotImplementedError("this pipeline was built without a VAE: use img2img_latents")
+        r = self._vae_ratio()
+        s = self.unet.config.sample_size
+        if image.dim() != 4 or tuple(image.shape[1:]) != (3, s * r, s * r):
+            raise ValueError(f"img2img: image {tuple(image.shape)}, want [B, 3, {s * r}, {s * r}]")
+        if change_map is not None and (change_map.dim() != 4 or tuple(change_map.shape[1:]) != (1, s * r, s * r)
+                                       or change_map.shape[0] not in (1, image.shape[0])):
+            raise ValueError(f"img2img: change_map {tuple(change_map.shape)}, want [{image.shape[0]} or 1, 1, {s * r}, {s * r}]")
+        if not 0.0 <= float(strength) <= 1.0:
+            raise ValueError(f"img2img: strength = {strength} must be in [0, 1]")
+        dev = self.unet.device
+        image = image.to(device=dev, dtype=torch.float32)
+        latent_map = None
+        if change_map is not None:
+            change_map = change_map.to(device=dev, dtype=torch.float32).contiguous()
+            latent_map = ops.mask_pool(change_map, r, ops.MASK_MEAN)
+        out = self.img2img_latents(self._encode_mode(image), strength, latent_map, num_inference_steps, eta, generator, noise,
+                                   use_graph)
+        if output_type == "latent":
+            return out
+        decoded = self.vae.decode(out.to(self.vae.dtype) / self.vae.config.scaling_factor).sample
+        if composite and change_map is not None:
+            decoded = torch.where(change_map == 0, image, decoded.float())
+        return self._images(decoded, output_type, return_dict)
+
     # ------------------------------------------------------------------------------------------------ ILVR reference guidance
     @torch.no_grad()
     def ilvr_latents(self, ref_latents, down_factor=4, range_t=0, num_inference_steps=50, eta=1.0, phi=None, generator=None,

@@ -309,6 +309,51 @@ class DDIMScheduler:
         ab = float(self.alphas_cumprod[t0])
         return math.sqrt(ab), math.sqrt(1 - ab), self._hires_kappa(t0, cosine_scale_3)
 
+    def _sdedit_timesteps(self, num_inference_steps, strength):
+        """The reference's get_timesteps (video_equiv_editing_pipeline.py:320-328): the last min(int(N strength), N) of the N
+        timesteps.  Raises ValueError for a strength outside [0, 1] or one that leaves no evaluation."""
+        n_all, strength = int(num_inference_steps), float(strength)
+        if not 0.0 <= strength <= 1.0:
+            raise ValueError(f"sdedit_schedule: strength = {strength} must be in [0, 1]")
+        init = min(int(n_all * strength), n_all)
+        t_start = max(n_all - init, 0)
+        self.set_timesteps(n_all)
+        ts = self._timesteps_host[t_start:]
+        if not ts:
+            raise ValueError(f"sdedit_schedule: strength = {strength} leaves none of the {n_all} steps (int({n_all} * {strength}) = 0)")
+        return ts
+
+    def sdedit_schedule(self, num_inference_steps, strength, eta=0.0):
+        """Image-to-image sampling: SDEdit (Meng et al., ICLR 2022) with a per-element change map (Differential Diffusion, Levin &
+        Fried 2023), as the Schedule SDEditEngine replays with afldm_sdedit_step.  The timesteps are the reference's
+        get_timesteps: the last n = min(int(N strength), N) of this scheduler's N = `num_inference_steps`, g[0] > ... > g[n-1].
+        For evaluation k, with ab = alphas_cumprod[g[k]] and ab' the next level (final_alpha_cumprod after the last):
+          (p, q, lo, hi, a, b, c) = _reverse_row(ab, ab', eta)      the reverse step of a released element
+          k0, k1 = sqrt(ab'), sqrt(1 - ab')                         the original noised to the next level with the run's ONE noise z
+          thr = (n - 1 - k) / n                                     an element of change value <= thr is held on that trajectory
+        and the last evaluation has k0 = 1, k1 = 0 and thr = 0: what is still held then (change value <= 0) is the original
+        exactly, and a change value of 1 is never held (thr_0 = 1 - 1 / n).  A step draws z_u - one randn_tensor of the latent
+        shape in the model's dtype - only where c is not 0.  sdedit_start gives the level the run starts from."""
+        if self.config.prediction_type != "epsilon":
+            raise NotImplementedError("afldm_amd.DDIMScheduler.sdedit_schedule implements epsilon prediction")
+        ts = self._sdedit_timesteps(num_inference_steps, strength)
+        n = len(ts)
+        rows = []
+        for k, t in enumerate(ts):
+            last = k == n - 1
+            ab = float(self.alphas_cumprod[t])
+            ab_prev = float(self.final_alpha_cumprod) if last else float(self.alphas_cumprod[ts[k + 1]])
+            k0, k1 = (1.0, 0.0) if last else (math.sqrt(ab_prev), math.sqrt(1 - ab_prev))
+            rows.append(self._reverse_row(ab, ab_prev, eta) + (k0, k1, (n - 1 - k) / n, 0.0, 0.0))
+        return Schedule.of(self, "sdedit", ts, rows, [r[6] != 0.0 for r in rows], _sdedit_steps=int(num_inference_steps),
+                           _sdedit_strength=n, _sdedit_eta=float(eta))
+
+    def sdedit_start(self, num_inference_steps, strength):
+        """(k0_start, k1_start) = (sqrt(ab_0), sqrt(1 - ab_0)) of sdedit_schedule's first timestep: the run starts from
+        k0_start orig + k1_start z (the reference's add_noise at the truncated schedule's first timestep)."""
+        ab = float(self.alphas_cumprod[self._sdedit_timesteps(num_inference_steps, strength)[0]])
+        return math.sqrt(ab), math.sqrt(1 - ab)
+
     def ilvr_schedule(self, num_inference_steps, eta=1.0, range_t=0):
         """ILVR reference-guided sampling (Choi et al., ICCV 2021, Algorithm 1) over this scheduler's `num_inference_steps`
         timesteps g[0] > ... > g[N-1], as the Schedule DenoiseEngine replays with afldm_ilvr_step.  For evaluation i, with

@@ -24,15 +24,19 @@ UNet evaluation, fixed when it is made.  `kind` names the update kernel that rea
     "sag"   the "pag" row, float for float (s = sag_scale): self-attention guidance, two DEPENDENT evaluations per step - e, then
             e_d on the input degraded where the attention mass of one site exceeds 1 (afldm_sag_degrade reads p and q of the
             row) - and the same guided update with e_d in e_p's place                                        afldm_pag_step
+    "sdedit" (p, q, lo, hi, a, b, c, k0, k1, thr, 0, 0):  image-to-image sampling (SDEdit) with a per-element change map
+            (Differential Diffusion):  x0 = clamp(p x + q eps, lo, hi);  xp = a x0 + b eps + c z_u;  held = k0 orig + k1 z, z the
+            run's ONE fixed noise;  x_out = (cmap <= thr) ? held : xp - a select, not a blend         afldm_sdedit_step
 
 The rows come from the scheduler that owns the update (DDIMScheduler.schedule / stochastic_schedule,
-DDIMScheduler.repaint_schedule / ilvr_schedule / panorama_schedule / pag_schedule / sag_schedule / outpaint_schedule / hires_schedule, DPMSolverMultistepScheduler.schedule, I2SBScheduler.ode_schedule / bridge_schedule,
+DDIMScheduler.repaint_schedule / ilvr_schedule / panorama_schedule / pag_schedule / sag_schedule / outpaint_schedule / hires_schedule / sdedit_schedule, DPMSolverMultistepScheduler.schedule, I2SBScheduler.ode_schedule / bridge_schedule,
 MyLDMPipeline.inversion_schedule) as Python floats and are rounded once to fp32 by `table`.  An "sde" schedule also states which
 steps draw noise and how: exactly the randn_tensor calls, in the same order, that the scheduler's eager `step()` makes, so that
 the engine can draw them from the caller's generator before the captured graphs need them.  A "repaint" schedule has up to
 three draws per step and states them per slot: `draws[k]` is (z_k, z_u, z_b), drawn in that order; an "ilvr" schedule has up
 to two, (z_k, z_u).  A "pano" schedule draws one canvas-shaped tensor per step, and only where the row's c is not 0; an "outpaint" schedule draws as
-"repaint" does, canvas-shaped; a "hires" schedule draws as "pano" does.  `key` identifies everything the rows were computed from; the engine
+"repaint" does, canvas-shaped; a "hires" schedule draws as "pano" does; an "sdedit" schedule draws one latent-shaped z_u per step, only where
+the row's c is not 0 (its fixed noise z is a per-run tensor like the original, not a draw of a step).  `key` identifies everything the rows were computed from; the engine
 cache (engine.cached_engine) compares it, so two schedules with equal keys must replay the same graph."""
 from dataclasses import dataclass
 
@@ -44,7 +48,7 @@ from ..utils import randn_tensor
 # kind -> (row width, noise slots per step, may a step draw): the one place that states them.  Several slots: `draws` is per slot
 KINDS = {"ddim": (4, 1, False), "dpm": (8, 1, False), "sde": (8, 1, True), "repaint": (12, 3, True), "ilvr": (12, 2, True),
          "pano": (8, 1, True), "pag": (12, 1, True), "sag": (12, 1, True), "outpaint": (12, 3, True),
-         "hires": (12, 1, True)}
+         "hires": (12, 1, True), "sdedit": (12, 1, True)}
 ROW_WIDTH, NOISE_SLOTS = {k: v[0] for k, v in KINDS.items()}, {k: v[1] for k, v in KINDS.items() if v[2]}      # derived views
 _MADE = {}          # key -> Schedule: the rows are ~0.1 ms of scalar tensor arithmetic each, and a sampler asks per call
 

@@ -490,6 +490,28 @@ int afldm_repaint_step_flat(const float* x, const float* eps, const float* known
  * mean (summed in fp64, rounded once). */
 enum { AFLDM_MASK_MIN = 0, AFLDM_MASK_MEAN = 1 };
 int afldm_mask_pool(const float* mask, float* out, int B, int H, int W, int r, int mode, afldm_stream_t stream);
+/* ---- Image-to-image update: SDEdit (Meng et al., ICLR 2022) with a change map (Differential Diffusion, Levin & Fried 2023)
+ * Step s = *step_idx applies the row coef[12 s .. 12 s + 12) = (p, q, lo, hi, a, b, c, k0, k1, thr, 0, 0), the run's one fixed
+ * noise z and the step's noise z_u = noise[s * noise_step_stride + i]:
+ *   x0    = clamp(p x + q eps, lo, hi)                lo = -inf, hi = +inf: no clip; a NaN passes through
+ *   xp    = a x0 + b eps + c z_u                      the DDIM reverse step of a released element
+ *   held  = k0 orig + k1 z                            the original, noised to the next level
+ *   x_out = (m <= thr) ? held : xp                    m = cmap[b, 0, h, w], the change map: 0 = keep, 1 = regenerate
+ * The last line is a select, not a blend: at a held element nothing of x, eps or z_u reaches x_out (not even a NaN or Inf),
+ * and a NaN in cmap compares false, so that element is generated.  z is not read where k1 = 0 and z_u not where c = 0: an
+ * unused buffer may hold anything.  noise may be NULL for a schedule none of whose rows has c != 0 (no z_u is added then).
+ * x, orig, z, x_out: NCHW fp32 [B,C,H,W], x_out may alias x; cmap: fp32 [B,1,H,W]; eps: NHWC dtype; noise: fp32 rows of
+ * [B,C,H,W] NCHW, noise_step_stride floats apart (>= B*C*H*W: a branch passes its batch slice of a larger buffer), drawn by
+ * the caller's generator outside any captured graph; step_idx / advance as the DDIM update above. */
+int afldm_sdedit_step(const float* x, const void* eps, const float* orig, const float* cmap, const float* z, const float* noise,
+                      size_t noise_step_stride, float* x_out, const float* coef, int* step_idx, int advance, int B, int C,
+                      int H, int W, int dtype, afldm_stream_t stream);
+/* Same update on flat same-layout fp32 tensors of n elements (the change map expanded to that layout too), the row by value,
+ * for an eager loop - and for the start of a run: the row (0, 0, -inf, inf, 0, 0, 0, k0, k1, +inf) gives k0 orig + k1 z, the
+ * formula every held element follows.  z / z_u may be NULL where k1 / c is 0. */
+int afldm_sdedit_step_flat(const float* x, const float* eps, const float* orig, const float* cmap, const float* z,
+                           const float* z_u, float* x_out, float p, float q, float lo, float hi, float a, float b, float c,
+                           float k0, float k1, float thr, size_t n, afldm_stream_t stream);
 /* ---- ILVR reference-guided update (Choi et al., ICCV 2021, Algorithm 1) with a linear low-pass phi -----------------
  * Step s = *step_idx applies the row coef[12 s .. 12 s + 12) = (p, q, lo, hi, a, b, c, k0, k1, w, 0, 0) and the two noise
  * slots z_k, z_u = noise[s * noise_step_stride + slot * noise_slot_stride + i], slot = 0, 1:
