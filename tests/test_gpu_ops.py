@@ -183,6 +183,15 @@ def test_af_resample(dtype, N, C):
         yv = y.float()
         assert (st.sum(1)[..., 0] - yv.sum((1, 2))).abs().max() <= 1e-3 * (1 + yv.sum((1, 2)).abs().max())
         assert (st.sum(1)[..., 1] - (yv * yv).sum((1, 2))).abs().max() <= 1e-3 * (1 + (yv * yv).sum((1, 2)).max())
+        # every emitted split on its own: af_lpf_down2 writes one per output row, af_resample_plane one per plane; each is a
+        # sum of n stored values (or their squares) in fp32, whatever the order: |err| <= n 2^-24 sum |v|
+        S = st.shape[1]
+        assert S in (1, N // 2)
+        rows = yv.double().view(2, S, -1, C)
+        n = rows.shape[2]
+        for j, v in ((0, rows), (1, rows * rows)):
+            err, bound = (st[..., j].double() - v.sum(2)).abs(), n * 2.0 ** -24 * v.abs().sum(2)
+            assert (err <= bound).all(), f"af_lpf_down2 N={N} statistic {j}: split off by {float((err / bound.clamp_min(1e-30)).max()):.2f} bounds"
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
