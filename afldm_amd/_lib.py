@@ -112,6 +112,9 @@ def _load():
         "afldm_attn_block_fused_supported": ([ip, ip, ip, ip], c_int),
         "afldm_attn_block_fused_trace": ([vp], c_int),
         "afldm_af_act_trace": ([vp], c_int),
+        "afldm_af_act_route": ([ip] * 8 + [POINTER(c_int)], c_int),
+        "afldm_af_resample_route": ([ip, ip, ip, POINTER(c_int)], c_int),
+        "afldm_af_tune": ([ip, ip], c_int),
         "afldm_attn_block_fused": ([vp, vp, ip, vp, vp, ip, fp, vp, vp, vp, ip, ip, ip, ip, fp, ip, vp], c_int),
         "afldm_attn_block_fused_out_supported": ([ip, ip, ip, ip, ip], c_int),
         "afldm_attn_block_fused_out": ([vp, vp, ip, vp, vp, ip, fp, vp, vp, vp, vp, vp, vp, vp, vp, c_longlong, ip, ip, ip, ip, fp, ip,

@@ -1257,23 +1257,42 @@ static int af_plane_wgs_per_cu() {
   const int by_regs = N == 32 ? (CH == 8 && sizeof(T) == 2 ? 3 : 2) : 4;
   return by_lds < 1 ? 1 : (by_lds < by_regs ? by_lds : by_regs);
 }
-template <typename T, int N, int CH>
-static int launch_af_plane(const AfP<T>& p, int cus, hipStream_t st) {
-  typedef PlaneCfg<T, N, CH> CF;
-  static unsigned long long attr_set = 0;
-  if (first_on_device(attr_set)) {
-    (void)hipFuncSetAttribute((const void*)k_af_act_plane<T, N, CH>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              CF::LDS_BYTES);
-  }
-  const int nitems = p.B * ((p.C1 + p.C2) / CH);
-  int grid = cus * af_plane_wgs_per_cu<T, N, CH>();
-  if (grid > nitems) grid = nitems;
-  k_af_act_plane<T, N, CH><<<grid, CF::NW * 64, CF::LDS_BYTES, st>>>(p);
-  return check_launch("afldm_af_act(plane)");
+// ---- tuning state of the two planners below (afldm_af_tune).  One struct, filled from the environment on first use: a
+// process that never calls afldm_af_tune runs what the variables say.
+struct AfTune {
+  int ch;                 // AFLDM_AF_CH: the plane kernel's item size, 8 / 16 (0 = by makespan; A/B)
+  int small_n;            // AFLDM_AF_SMALL_N: bit mask 4 / 8 of the plane sizes that run on the VALU kernel instead of the
+                          // Kronecker MFMA kernel.  N = 4 (default): one thread per plane with the loop over the upsampled rows
+                          // fully unrolled (all 64 coefficients in SGPRs) beats the MFMA form, whose workgroups each stage a
+                          // 64 KB constant image: 5.251 -> 5.229 ms/step (same box).  N = 8 needs 256 coefficients per row
+                          // step and stays on MFMA (VALU: 5.25 -> 5.51).
+  int p8;                 // AFLDM_AF_P8: bf16 8 x 8 planes on the separable two-planes-per-tile kernel (0 -> Kronecker; A/B)
+  int stagger;            // AFLDM_AF_STAGGER: see k_af_act_plane
+  int no_resample_small;  // AFLDM_NO_RESAMPLE_SMALL: the small resampling sites in two passes (A/B)
+  int resample_split;     // AFLDM_RESAMPLE_SPLIT: threads per plane at 8 -> 16 (1 / 2 / 4; A/B)
+  int max_grid;           // (no variable) cap on the plane kernel's grid, 0 = none: a few items then make several per workgroup
+};
+static int env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
+static AfTune af_tune_env() {
+  AfTune t;
+  t.ch = env_int("AFLDM_AF_CH", 0);
+  t.small_n = env_int("AFLDM_AF_SMALL_N", 4);
+  t.p8 = env_int("AFLDM_AF_P8", 1) != 0;
+  t.stagger = env_int("AFLDM_AF_STAGGER", 0);
+  t.no_resample_small = env_int("AFLDM_NO_RESAMPLE_SMALL", 0) != 0;
+  t.resample_split = env_int("AFLDM_RESAMPLE_SPLIT", 4);
+  t.max_grid = 0;
+  return t;
+}
+static AfTune& af_tune() {
+  static AfTune t = af_tune_env();
+  return t;
 }
 
-template <typename T, int N>
-static int launch_af_mfma(const AfP<T>& p, hipStream_t st) {
+static int af_device_cus() {
   static int cus = 0;
   if (!cus) {
     hipDeviceProp_t prop;
@@ -1281,47 +1300,116 @@ static int launch_af_mfma(const AfP<T>& p, hipStream_t st) {
     (void)hipGetDevice(&dev);
     cus = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
   }
-  // Items are indivisible, so a launch takes ceil(items / resident workgroups) item times: pick the
-  // item size (16 or 8 channels) with the smaller makespan (an 8-channel item measured 0.62-0.82 of a 16-channel one).
-  const int Ct = p.C1 + p.C2;
-  const long long slots16 = (long long)cus * af_plane_wgs_per_cu<T, N, 16>(), slots8 = (long long)cus * af_plane_wgs_per_cu<T, N, 8>();
-  const long long items16 = (long long)p.B * (Ct / 16), items8 = 2 * items16;
-  const double t16 = (double)((items16 + slots16 - 1) / slots16), t8 = 0.65 * (double)((items8 + slots8 - 1) / slots8);
-  // (8-channel items read 16-byte pieces of every pixel: only worth it while the tensor stays
-  //  cache-resident between the two item passes over a line - measured 1.15x slower per round at 75 MB)
-  const size_t bytes = (size_t)p.B * N * N * Ct * sizeof(T);
-  static const int s_ch = getenv("AFLDM_AF_CH") ? atoi(getenv("AFLDM_AF_CH")) : 0;      // A/B: force the item size (8 / 16)
-  if (s_ch == 8 && p.C1 % 8 == 0) return launch_af_plane<T, N, 8>(p, cus, st);
-  if (s_ch == 16) return launch_af_plane<T, N, 16>(p, cus, st);
-  if (t8 < t16 && p.C1 % 8 == 0 && bytes <= (40u << 20)) return launch_af_plane<T, N, 8>(p, cus, st);
-  return launch_af_plane<T, N, 16>(p, cus, st);
+  return cus;
+}
+
+// ---- the activation's plan: which kernel a call runs, and how.  af_act_dispatch launches exactly this; afldm_af_act_route
+// reports it.  ipw = the most items one workgroup handles (plane: items of CH channels of a sample; kron / p8: of 16 channels,
+// one per wave; small: planes, one per thread).
+struct AfRoute {
+  int kernel;             // AFLDM_AF_ROUTE_PLANE / _KRON / _P8 / _SMALL
+  int ch;                 // plane: channels per item (8 / 16); else 0
+  int grid;
+  int ipw;
+};
+
+template <typename T>
+static bool af_act_plan(int N, int C1, int C2, int B, int cus, bool has_packed, bool has_UD, AfRoute& r) {
+  const AfTune& t = af_tune();
+  const int Ct = C1 + C2;
+  const bool c16 = C1 % 16 == 0 && C2 % 16 == 0;
+  const int nitems = B * (Ct / 16);
+  auto small = [&]() {
+    const int total = B * Ct;
+    r = AfRoute{AFLDM_AF_ROUTE_SMALL, 0, (total + 255) / 256, total < 256 ? total : 256};
+    return true;
+  };
+  auto kron = [&](int lds_bytes) {
+    const int ngroups = (nitems + 3) / 4;
+    const int per_cu = (160 * 1024) / lds_bytes >= 2 ? 2 : 1;
+    int grid = 256 * per_cu;
+    if (grid > ngroups) grid = ngroups;
+    const int ipw = 4 * ((ngroups + grid - 1) / grid);
+    r = AfRoute{AFLDM_AF_ROUTE_KRON, 0, grid, ipw < nitems ? ipw : nitems};
+    return true;
+  };
+  switch (N) {
+    case 2: return small();
+    case 4:
+      if (has_packed && c16 && !(t.small_n & 4)) return kron(KronCfg<T, 4>::LDS_BYTES);
+      return small();
+    case 8:
+      // bf16: the separable two-planes-per-tile kernel (no constant image)
+      if (sizeof(T) == 2 && t.p8 && has_UD && c16 && !(t.small_n & 8)) {
+        r = AfRoute{AFLDM_AF_ROUTE_P8, 0, (nitems + 3) / 4, nitems < 4 ? nitems : 4};
+        return true;
+      }
+      if (has_packed && c16 && !(t.small_n & 8)) return kron(KronCfg<T, 8>::LDS_BYTES);
+      return small();
+    case 16:
+    case 32: {
+      if (cus <= 0) cus = af_device_cus();
+      const int w16 = N == 16 ? af_plane_wgs_per_cu<T, 16, 16>() : af_plane_wgs_per_cu<T, 32, 16>();
+      const int w8 = N == 16 ? af_plane_wgs_per_cu<T, 16, 8>() : af_plane_wgs_per_cu<T, 32, 8>();
+      // Items are indivisible, so a launch takes ceil(items / resident workgroups) item times: pick the
+      // item size (16 or 8 channels) with the smaller makespan (an 8-channel item measured 0.62-0.82 of a 16-channel one).
+      const long long slots16 = (long long)cus * w16, slots8 = (long long)cus * w8;
+      const long long items16 = (long long)B * (Ct / 16), items8 = 2 * items16;
+      const double t16 = (double)((items16 + slots16 - 1) / slots16), t8 = 0.65 * (double)((items8 + slots8 - 1) / slots8);
+      // (8-channel items read 16-byte pieces of every pixel: only worth it while the tensor stays
+      //  cache-resident between the two item passes over a line - measured 1.15x slower per round at 75 MB)
+      const size_t bytes = (size_t)B * N * N * Ct * sizeof(T);
+      int ch = 16;
+      if (t.ch == 8 && C1 % 8 == 0) ch = 8;
+      else if (t.ch == 16) ch = 16;
+      else if (t8 < t16 && C1 % 8 == 0 && bytes <= (40u << 20)) ch = 8;
+      const long long items = ch == 8 ? items8 : items16;
+      long long grid = ch == 8 ? slots8 : slots16;
+      if (grid > items) grid = items;
+      if (t.max_grid > 0 && grid > t.max_grid) grid = t.max_grid;
+      if (grid < 1) grid = 1;
+      r = AfRoute{AFLDM_AF_ROUTE_PLANE, ch, (int)grid, (int)((items + grid - 1) / grid)};
+      return true;
+    }
+  }
+  return false;
+}
+
+template <typename T, int N, int CH>
+static int launch_af_plane(const AfP<T>& p, int grid, hipStream_t st) {
+  typedef PlaneCfg<T, N, CH> CF;
+  static unsigned long long attr_set = 0;
+  if (first_on_device(attr_set)) {
+    (void)hipFuncSetAttribute((const void*)k_af_act_plane<T, N, CH>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              CF::LDS_BYTES);
+  }
+  k_af_act_plane<T, N, CH><<<grid, CF::NW * 64, CF::LDS_BYTES, st>>>(p);
+  return check_launch("afldm_af_act(plane)");
+}
+
+template <typename T, int N>
+static int launch_af_mfma(const AfP<T>& p, const AfRoute& r, hipStream_t st) {
+  if (r.ch == 8) return launch_af_plane<T, N, 8>(p, r.grid, st);
+  return launch_af_plane<T, N, 16>(p, r.grid, st);
 }
 template <typename T, int N>
-static int launch_af_kron(const AfP<T>& p, hipStream_t st) {
+static int launch_af_kron(const AfP<T>& p, int grid, hipStream_t st) {
   typedef KronCfg<T, N> CF;
   static unsigned long long attr_set = 0;
   if (first_on_device(attr_set)) {
     (void)hipFuncSetAttribute((const void*)k_af_act_kron<T, N>, hipFuncAttributeMaxDynamicSharedMemorySize, CF::LDS_BYTES);
   }
-  const int nitems = p.B * ((p.C1 + p.C2) / 16);
-  const int ngroups = (nitems + 3) / 4;
-  const int per_cu = (160 * 1024) / CF::LDS_BYTES >= 2 ? 2 : 1;
-  int grid = 256 * per_cu;
-  if (grid > ngroups) grid = ngroups;
   k_af_act_kron<T, N><<<grid, 256, CF::LDS_BYTES, st>>>(p);
   return check_launch("afldm_af_act(kron)");
 }
 
-static int launch_af_p8(const AfP<bf16>& p, hipStream_t st) {
-  const int nitems = p.B * ((p.C1 + p.C2) / 16);
-  k_af_act_p8<<<(nitems + 3) / 4, 256, 0, st>>>(p);
+static int launch_af_p8(const AfP<bf16>& p, int grid, hipStream_t st) {
+  k_af_act_p8<<<grid, 256, 0, st>>>(p);
   return check_launch("afldm_af_act(p8)");
 }
 
 template <typename T, int N>
-static int launch_af_small(const AfP<T>& p, hipStream_t st) {
-  const int total = p.B * (p.C1 + p.C2);
-  const int grid = (total + 255) / 256;
+static int launch_af_small(const AfP<T>& p, int grid, hipStream_t st) {
   k_af_act_small<T, N><<<grid, 256, 0, st>>>(p);
   return check_launch("afldm_af_act(small)");
 }
@@ -1336,32 +1424,30 @@ static int af_act_dispatch(const void* x1, int C1, const void* x2, int C2, const
   p.x1 = (const T*)x1; p.x2 = (const T*)x2; p.gs = gs; p.gamma = gamma; p.beta = beta;
   p.U = U; p.D = D; p.y = (T*)y; p.C1 = C1; p.C2 = C2; p.G = G; p.B = B;
   p.trace = g_af_trace;
-  static const int s_stagger = getenv("AFLDM_AF_STAGGER") ? atoi(getenv("AFLDM_AF_STAGGER")) : 0;
-  p.stagger = s_stagger;
+  p.stagger = af_tune().stagger;
   p.y_blocked = y_layout == 1 ? 1 : (y_layout == 2 && N == 2 ? 2 : 0);      // 2: plane-constant output of the 2 x 2 kernel
   p.x_blocked = x_layout == 1 ? 1 : 0;
-  // bit mask 4 / 8: plane sizes run on the VALU kernel instead of the Kronecker MFMA kernel.  N = 4 (default): one thread
-  // per plane with the loop over the upsampled rows fully unrolled (all 64 coefficients in SGPRs) beats the MFMA form,
-  // whose workgroups each stage a 64 KB constant image: 5.251 -> 5.229 ms/step (same box).  N = 8 needs 256 coefficients
-  // per row step and stays on MFMA (VALU: 5.25 -> 5.51).
-  static const int s_small = getenv("AFLDM_AF_SMALL_N") ? atoi(getenv("AFLDM_AF_SMALL_N")) : 4;
-  switch (N) {
-    case 2: return launch_af_small<T, 2>(p, st);
-    case 4:
-      if (packed && p.C1 % 16 == 0 && p.C2 % 16 == 0 && !(s_small & 4)) return launch_af_kron<T, 4>(p, st);
-      return launch_af_small<T, 4>(p, st);
-    case 8:
-      if constexpr (sizeof(T) == 2) {
-        // bf16: the separable two-planes-per-tile kernel (no constant image); AFLDM_AF_P8=0 -> the Kronecker kernel (A/B)
-        static const bool p8 = !(getenv("AFLDM_AF_P8") && atoi(getenv("AFLDM_AF_P8")) == 0);
-        if (p8 && p.U && p.D && p.C1 % 16 == 0 && p.C2 % 16 == 0 && !(s_small & 8)) return launch_af_p8(p, st);
-      }
-      if (packed && p.C1 % 16 == 0 && p.C2 % 16 == 0 && !(s_small & 8)) return launch_af_kron<T, 8>(p, st);
-      return launch_af_small<T, 8>(p, st);
-    case 16: return launch_af_mfma<T, 16>(p, st);
-    case 32: return launch_af_mfma<T, 32>(p, st);
+  AfRoute r;
+  if (!af_act_plan<T>(N, C1, C2, B, 0, packed != nullptr, U && D, r)) {
+    set_error("afldm_af_act: plane size N=%d not in {2,4,8,16,32}", N);
+    return AFLDM_ESHAPE;
   }
-  set_error("afldm_af_act: plane size N=%d not in {2,4,8,16,32}", N);
+  switch (r.kernel) {
+    case AFLDM_AF_ROUTE_SMALL:
+      if (N == 2) return launch_af_small<T, 2>(p, r.grid, st);
+      if (N == 4) return launch_af_small<T, 4>(p, r.grid, st);
+      return launch_af_small<T, 8>(p, r.grid, st);
+    case AFLDM_AF_ROUTE_KRON:
+      if (N == 4) return launch_af_kron<T, 4>(p, r.grid, st);
+      return launch_af_kron<T, 8>(p, r.grid, st);
+    case AFLDM_AF_ROUTE_P8:
+      if constexpr (sizeof(T) == 2) return launch_af_p8(p, r.grid, st);
+      break;
+    case AFLDM_AF_ROUTE_PLANE:
+      if (N == 16) return launch_af_mfma<T, 16>(p, r, st);
+      return launch_af_mfma<T, 32>(p, r, st);
+  }
+  set_error("afldm_af_act: no kernel for the planned route %d (N=%d)", r.kernel, N);
   return AFLDM_ESHAPE;
 }
 
@@ -1369,7 +1455,7 @@ static int af_act_dispatch(const void* x1, int C1, const void* x2, int C2, const
 // one thread per plane, lanes = channels (the coefficients are wave-uniform scalar operands).  Exactly the two passes of
 // k_axis_contract_reg - H first into an fp32 intermediate, then W, every sum an fmaf chain over ascending k from 0 - with
 // the intermediate in registers instead of an fp32 tensor in memory and a second launch: bit-identical results and
-// statistics (one split per output row).  A <= 8: the plane lives in registers, output row by output row; A = 16 (-> 8): the
+// statistics (one split per output row; tests/test_gpu_af_routes.py holds both to that).  A <= 8: the plane lives in registers, output row by output row; A = 16 (-> 8): the
 // output accumulates column by column (64 accumulators) - correct but 3x slower than the two passes (128 coefficients do not fit the
 // scalar registers), not dispatched.
 // SPLIT: threads per plane (A <= 8 form): thread `part` of a plane computes the output rows [part R / SPLIT, (part + 1) R / SPLIT) -
@@ -1452,29 +1538,40 @@ __global__ void __launch_bounds__(256) k_resample_small(const T* __restrict__ in
   }
 }
 
+// ---- the resampler's plan (y = M x M^T, [B,N,N,C] -> [B,R,R,C]): resample_dispatch launches exactly this;
+// afldm_af_resample_route reports it.
+struct RsRoute {
+  int kind;               // AFLDM_RESAMPLE_ROUTE_SMALL (one launch, k_resample_small) / _REG (two register-blocked passes) / _GENERIC
+  int split;              // small: threads per plane (1 / 2 / 4); else 0
+};
+
+static RsRoute resample_plan(int N, int C, int Rout) {
+  const AfTune& t = af_tune();
+  const bool twice = Rout == 2 * N, half = 2 * Rout == N;
+  // the small sites in one launch (16 -> 8 measured 3x SLOWER this way: 47.6 vs 14.7 us)
+  if (!t.no_resample_small && ((twice && (N == 2 || N == 4 || N == 8)) || (half && (N == 4 || N == 8))))
+    return RsRoute{AFLDM_RESAMPLE_ROUTE_SMALL, N == 8 && Rout == 16 && t.resample_split > 1 ? (t.resample_split == 2 ? 2 : 4) : 1};
+  if (C % 4 == 0 && ((twice && N >= 2 && N <= 16) || (half && N >= 4 && N <= 32)) && (N & (N - 1)) == 0)
+    return RsRoute{AFLDM_RESAMPLE_ROUTE_REG, 0};
+  return RsRoute{AFLDM_RESAMPLE_ROUTE_GENERIC, 0};
+}
+
 template <typename T>
 static int resample_dispatch(const void* x, const float* M, void* y, float* ws, int B, int N, int C, int Rout,
                              hipStream_t st, float* stats = nullptr) {
-  // pass 1 contracts H into the fp32 workspace [B][Rout][N][C]; pass 2 contracts W
-  {
-    // the small sites in one launch (k_resample_small; AFLDM_NO_RESAMPLE_SMALL=1: the two-pass form, for A/B)
-    static const bool s_off = getenv("AFLDM_NO_RESAMPLE_SMALL") && atoi(getenv("AFLDM_NO_RESAMPLE_SMALL")) != 0;
-    const int grid = (int)(((size_t)B * C + 255) / 256);
-    static const int s_split = getenv("AFLDM_RESAMPLE_SPLIT") ? atoi(getenv("AFLDM_RESAMPLE_SPLIT")) : 4;      // threads per plane at 8 -> 16 (1 / 2 / 4; A/B)
-    if (!s_off && N == 8 && Rout == 16 && s_split > 1) {
-      if (s_split == 2) k_resample_small<T, 8, 16, 2><<<(int)(((size_t)B * C * 2 + 255) / 256), 256, 0, st>>>((const T*)x, (T*)y, M, B, C, stats);
-      else k_resample_small<T, 8, 16, 4><<<(int)(((size_t)B * C * 4 + 255) / 256), 256, 0, st>>>((const T*)x, (T*)y, M, B, C, stats);
-      return check_launch("afldm_af_resample(small)");
-    }
+  const RsRoute route = resample_plan(N, C, Rout);
+  if (route.kind == AFLDM_RESAMPLE_ROUTE_SMALL) {
+    const int grid = (int)(((size_t)B * C * route.split + 255) / 256);
+    if (route.split == 2) k_resample_small<T, 8, 16, 2><<<grid, 256, 0, st>>>((const T*)x, (T*)y, M, B, C, stats);
+    else if (route.split == 4) k_resample_small<T, 8, 16, 4><<<grid, 256, 0, st>>>((const T*)x, (T*)y, M, B, C, stats);
 #define AFLDM_RSS(A_, R_)                                                                                     \
-  if (!s_off && N == A_ && Rout == R_) {                                                                      \
-    k_resample_small<T, A_, R_><<<grid, 256, 0, st>>>((const T*)x, (T*)y, M, B, C, stats);                    \
-    return check_launch("afldm_af_resample(small)");                                                          \
-  }
-    AFLDM_RSS(2, 4) AFLDM_RSS(4, 8) AFLDM_RSS(8, 16) AFLDM_RSS(4, 2) AFLDM_RSS(8, 4)      // (16 -> 8 measured 3x SLOWER this way: 47.6 vs 14.7 us)
+    else if (N == A_ && Rout == R_) k_resample_small<T, A_, R_><<<grid, 256, 0, st>>>((const T*)x, (T*)y, M, B, C, stats);
+    AFLDM_RSS(2, 4) AFLDM_RSS(4, 8) AFLDM_RSS(8, 16) AFLDM_RSS(4, 2) AFLDM_RSS(8, 4)
 #undef AFLDM_RSS
+    return check_launch("afldm_af_resample(small)");
   }
-  if (C % 4 == 0 && (Rout == 2 * N || 2 * Rout == N) && N >= 2 && N <= 32 && (N & (N - 1)) == 0) {
+  // pass 1 contracts H into the fp32 workspace [B][Rout][N][C]; pass 2 contracts W
+  if (route.kind == AFLDM_RESAMPLE_ROUTE_REG) {
     const size_t t1 = (size_t)B * N * (C / 4), t2 = (size_t)B * Rout * (C / 4);
     const int g1 = (int)((t1 + 255) / 256 < 8192 ? (t1 + 255) / 256 : 8192);
     const int g2 = (int)((t2 + 255) / 256 < 8192 ? (t2 + 255) / 256 : 8192);
@@ -1546,6 +1643,59 @@ extern "C" int afldm_af_act_slabs(const float* slabs, int nslab, const float* bi
 
 extern "C" int afldm_af_act_trace(void* buf) {
   g_af_trace = (unsigned long long*)buf;
+  return AFLDM_OK;
+}
+
+extern "C" int afldm_af_tune(int field, int value) {
+  AfTune& t = af_tune();
+  switch (field) {
+    case AFLDM_AF_TUNE_RESET: t = af_tune_env(); return AFLDM_OK;
+    case AFLDM_AF_TUNE_CH:
+      AFLDM_REQUIRE(value == 0 || value == 8 || value == 16, AFLDM_ESHAPE, "afldm_af_tune: ch=%d not in {0, 8, 16}", value);
+      t.ch = value;
+      return AFLDM_OK;
+    case AFLDM_AF_TUNE_SMALL_N:
+      AFLDM_REQUIRE((value & ~12) == 0, AFLDM_ESHAPE, "afldm_af_tune: small_n=%d is a mask of 4 | 8", value);
+      t.small_n = value;
+      return AFLDM_OK;
+    case AFLDM_AF_TUNE_P8: t.p8 = value != 0; return AFLDM_OK;
+    case AFLDM_AF_TUNE_STAGGER:
+      AFLDM_REQUIRE(value >= 0 && value <= 64, AFLDM_ESHAPE, "afldm_af_tune: stagger=%d not in 0 .. 64", value);
+      t.stagger = value;
+      return AFLDM_OK;
+    case AFLDM_AF_TUNE_NO_RESAMPLE_SMALL: t.no_resample_small = value != 0; return AFLDM_OK;
+    case AFLDM_AF_TUNE_RESAMPLE_SPLIT:
+      AFLDM_REQUIRE(value == 1 || value == 2 || value == 4, AFLDM_ESHAPE, "afldm_af_tune: resample_split=%d not in {1, 2, 4}", value);
+      t.resample_split = value;
+      return AFLDM_OK;
+    case AFLDM_AF_TUNE_MAX_GRID:
+      AFLDM_REQUIRE(value >= 0, AFLDM_ESHAPE, "afldm_af_tune: max_grid=%d (0 = no cap, else >= 1)", value);
+      t.max_grid = value;
+      return AFLDM_OK;
+  }
+  set_error("afldm_af_tune: unknown field %d", field);
+  return AFLDM_ESHAPE;
+}
+
+extern "C" int afldm_af_act_route(int dtype, int N, int C1, int C2, int B, int cus, int has_packed, int has_UD, int* route) {
+  AFLDM_REQUIRE(route, AFLDM_ENULL, "afldm_af_act_route: NULL pointer");
+  AFLDM_REQUIRE(C1 > 0 && C2 >= 0 && B > 0 && cus >= 0, AFLDM_ESHAPE, "afldm_af_act_route: bad C1=%d C2=%d B=%d cus=%d", C1, C2, B, cus);
+  AFLDM_REQUIRE(N < 16 || (C1 % 16 == 0 && C2 % 16 == 0), AFLDM_ESHAPE,
+                "afldm_af_act_route: C1=%d / C2=%d must be multiples of 16 for N=%d", C1, C2, N);
+  AFLDM_REQUIRE(dtype == AFLDM_F32 || dtype == AFLDM_BF16, AFLDM_EDTYPE, "afldm_af_act_route: unknown dtype %d", dtype);
+  AfRoute r;
+  const bool ok = dtype == AFLDM_F32 ? af_act_plan<float>(N, C1, C2, B, cus, has_packed != 0, has_UD != 0, r)
+                                     : af_act_plan<bf16>(N, C1, C2, B, cus, has_packed != 0, has_UD != 0, r);
+  AFLDM_REQUIRE(ok, AFLDM_ESHAPE, "afldm_af_act_route: plane size N=%d not in {2,4,8,16,32}", N);
+  route[0] = r.kernel; route[1] = r.ch; route[2] = r.grid; route[3] = r.ipw;
+  return AFLDM_OK;
+}
+
+extern "C" int afldm_af_resample_route(int N, int C, int R, int* route) {
+  AFLDM_REQUIRE(route, AFLDM_ENULL, "afldm_af_resample_route: NULL pointer");
+  AFLDM_REQUIRE(N > 0 && C > 0 && R > 0, AFLDM_ESHAPE, "afldm_af_resample_route: bad shape");
+  const RsRoute r = resample_plan(N, C, R);
+  route[0] = r.kind; route[1] = r.split;
   return AFLDM_OK;
 }
 

@@ -2,6 +2,8 @@
 of device memory and streams; every op below is one or two HIP kernel launches from
 libafldm_hip.so on torch's current stream.  All activations are NHWC ([B, H, W, C]) or
 token-major ([B, T, C]) contiguous CUDA tensors in fp32 or bf16.  CPU tensors raise."""
+import collections
+import contextlib
 import ctypes
 import math
 import os
@@ -389,6 +391,45 @@ def af_act(x1, x2=None, stats=None, gamma=None, beta=None, G=0, eps=0.0, out=Non
     # dense separable form: 24 N^3 flop per plane; one read + one write of the tensor
     _end(tok, f"af_act_N{N}", 24.0 * N ** 3 * B * (C1 + C2), 2 * B * N * N * (C1 + C2) * x1.element_size())
     return out
+
+
+AF_KERNELS = ("plane", "kron", "p8", "small")                  # AFLDM_AF_ROUTE_*
+RESAMPLE_KINDS = ("small", "reg", "generic")                   # AFLDM_RESAMPLE_ROUTE_*
+AfRoute = collections.namedtuple("AfRoute", "kernel ch grid items_per_wg")
+ResampleRoute = collections.namedtuple("ResampleRoute", "kind split")
+_AF_TUNE_FIELDS = {"ch": 1, "small_n": 2, "p8": 3, "stagger": 4, "no_resample_small": 5, "resample_split": 6, "max_grid": 7}
+
+
+def af_act_route(dtype, N, C1, C2, B, cus=0, has_packed=None, has_UD=True):
+    """The kernel af_act runs for such a call (afldm_af_act_route: the plan the launch itself follows).  cus = 0 asks the
+    device; any other value plans for that many compute units and needs no GPU.  has_packed: as af_act passes it (N >= 4)."""
+    out = (ctypes.c_int * 4)()
+    has_packed = N >= 4 if has_packed is None else has_packed
+    check(_lib.lib.afldm_af_act_route(DTYPE_CODE[dtype], N, C1, C2, B, cus, int(has_packed), int(has_UD), out), "af_act_route")
+    return AfRoute(AF_KERNELS[out[0]], out[1], out[2], out[3])
+
+
+def af_resample_route(N, C, R):
+    """The route of af_up2 / af_lpf_down2 / af_resample inside afldm_af_resample (not the MFMA plane kernel that af_up2 /
+    af_lpf_down2 pick themselves at 16 -> 32 / 32 -> 16)."""
+    out = (ctypes.c_int * 2)()
+    check(_lib.lib.afldm_af_resample_route(N, C, R, out), "af_resample_route")
+    return ResampleRoute(RESAMPLE_KINDS[out[0]], out[1])
+
+
+@contextlib.contextmanager
+def af_tune(**fields):
+    """Set fields of the activation / resampling planners (afldm_af_tune: ch, small_n, p8, stagger, no_resample_small,
+    resample_split, max_grid) for the block; on exit every field is back at its environment default."""
+    unknown = set(fields) - set(_AF_TUNE_FIELDS)
+    if unknown:
+        raise TypeError(f"af_tune: unknown field(s) {sorted(unknown)}")
+    try:
+        for name, value in fields.items():
+            check(_lib.lib.afldm_af_tune(_AF_TUNE_FIELDS[name], int(value)), "af_tune")
+        yield
+    finally:
+        check(_lib.lib.afldm_af_tune(0, 0), "af_tune")
 
 
 def _resample_plane(x, M, R, out, want_stats):

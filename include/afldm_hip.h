@@ -113,6 +113,36 @@ int afldm_gn_fold(const float* stats_in, int S_in, float* stats_out, int S_out, 
  * launches on the plane kernel (N = 16 / 32) fill (phase boundaries of a workgroup's first two items; csrc/af.hip),
  * NULL = off (the default). */
 int afldm_af_act_trace(void* buf);
+/* Which kernel afldm_af_act / afldm_af_act_c8 run for a call, and how (the function the launch itself goes through):
+ * route[0] = AFLDM_AF_ROUTE_*, route[1] = channels per item of the plane kernel (8 / 16, else 0), route[2] = grid,
+ * route[3] = the most items one workgroup handles (plane: CH channels of a sample; kron / p8: 16 channels, one item per wave;
+ * small: planes, one per thread).  cus = compute units to plan for, 0 = the current device's (only N = 16 / 32 ask);
+ * has_packed / has_UD = whether the call passes the packed image / U and D.  Needs no GPU when cus > 0. */
+#define AFLDM_AF_ROUTE_PLANE 0
+#define AFLDM_AF_ROUTE_KRON 1
+#define AFLDM_AF_ROUTE_P8 2
+#define AFLDM_AF_ROUTE_SMALL 3
+int afldm_af_act_route(int dtype, int N, int C1, int C2, int B, int cus, int has_packed, int has_UD, int* route);
+/* The same for afldm_af_up2 / afldm_af_lpf_down2 / afldm_af_resample ([B,N,N,C] -> [B,R,R,C]): route[0] = AFLDM_RESAMPLE_ROUTE_*,
+ * route[1] = threads per plane of the one-launch kernel (1 / 2 / 4, else 0). */
+#define AFLDM_RESAMPLE_ROUTE_SMALL 0
+#define AFLDM_RESAMPLE_ROUTE_REG 1
+#define AFLDM_RESAMPLE_ROUTE_GENERIC 2
+int afldm_af_resample_route(int N, int C, int R, int* route);
+/* Tuning state of both planners, one field per call (tests, A/B timing).  Every field starts from its environment variable,
+ * read once: AFLDM_AF_CH (0), AFLDM_AF_SMALL_N (4), AFLDM_AF_P8 (1), AFLDM_AF_STAGGER (0), AFLDM_NO_RESAMPLE_SMALL (0),
+ * AFLDM_RESAMPLE_SPLIT (4); max_grid (0 = no cap) limits the plane kernel's grid so that a tensor of a few items gives
+ * several items per workgroup.  AFLDM_AF_TUNE_RESET puts every field back to those defaults.  Not synchronised with
+ * launches on other threads. */
+#define AFLDM_AF_TUNE_RESET 0
+#define AFLDM_AF_TUNE_CH 1
+#define AFLDM_AF_TUNE_SMALL_N 2
+#define AFLDM_AF_TUNE_P8 3
+#define AFLDM_AF_TUNE_STAGGER 4
+#define AFLDM_AF_TUNE_NO_RESAMPLE_SMALL 5
+#define AFLDM_AF_TUNE_RESAMPLE_SPLIT 6
+#define AFLDM_AF_TUNE_MAX_GRID 7
+int afldm_af_tune(int field, int value);
 /* ---- alias-free operators -----------------------------------------------------------------
  * afldm_af_act: [GroupNorm-apply ->] WarpedNonlinearity(SiLU) (af_blocks.py:19-28):
  *   y = D silu(U xn U^T) D^T per (b, c) plane,  xn = GN-applied x when stats1 != NULL

@@ -208,16 +208,16 @@ AF_SHAPES = [
     # N, C1, C2, G
     (2, 48, 96, 8),          # cpg = 18, seam inside group 2: gn_wave_keys, a wave spans 3 - 4 keys
     (2, 64, 0, 64),          # cpg = 1: 64 keys per wave, 16 rounds
-    (4, 96, 48, 8),          # Kronecker MFMA kernel; cpg = 18, seam inside group 5
+    (4, 96, 48, 8),          # the VALU kernel (the default at N = 4; Kronecker MFMA: test_gpu_af_routes); cpg = 18, seam inside group 5
     (4, 36, 0, 6),           # C % 16 != 0: the VALU kernel; cpg = 6
     (8, 96, 48, 8),          # bf16: k_af_act_p8; fp32: Kronecker; cpg = 18
     (8, 64, 0, 32),          # cpg = 2
     (16, 16, 32, 8),         # plane kernel; cpg = 6, seam inside group 2; cpg * smax = 6 .. 192: both sides of 128
     (16, 64, 32, 4),         # cpg = 24, seam inside group 2; 24 * 4 = 96 (fast), 24 * 8 = 192 (in line)
-    (16, 64, 0, 64),         # cpg = 1: an item touches 16 groups (> 4 waves: `fast` / `n_piped` off)
+    (16, 64, 0, 64),         # cpg = 1: an item (8 channels at B = 3) touches 8 groups (> 4 waves: `fast` / `n_piped` off)
     (16, 144, 0, 8),         # cpg = 18: an item touches 2 groups
     (32, 32, 16, 8),         # cpg = 6, seam inside group 5
-    (32, 64, 0, 32),         # cpg = 2: 8 groups per item
+    (32, 64, 0, 32),         # cpg = 2: 4 groups per 8-channel item (16-channel items, 8 groups: test_gpu_af_routes)
     (32, 192, 0, 8),         # cpg = 24
 ]
 
