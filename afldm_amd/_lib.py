@@ -109,6 +109,7 @@ def _load():
         "afldm_pack_weight_up2": ([vp, vp, ip, ip, ip, vp], c_int),
         "afldm_attention": ([vp, ip, vp, ip, vp, vp, ip, ip, ip, ip, ip, ip, ip, fp, ip, vp], c_int),
         "afldm_attention_interp": ([vp, ip, vp, vp, ip, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, ip, fp, ip, vp], c_int),
+        "afldm_attention_bank": ([vp, ip, vp, ip, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, ip, fp, ip, vp], c_int),
         "afldm_attn_block_fused_supported": ([ip, ip, ip, ip], c_int),
         "afldm_attn_block_fused_trace": ([vp], c_int),
         "afldm_af_act_trace": ([vp], c_int),

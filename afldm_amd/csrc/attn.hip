@@ -30,6 +30,11 @@
 // last); at the source boundary the normalised O of source 0, weighted by 1 - alpha, moves to a second set of
 // accumulators and the running max / row sums restart exactly as at chunk 0 (source 1 alone is then the same
 // arithmetic as a single-source launch on it); the epilogue adds alpha times source 1's normalised O in fp32 and rounds once.
+//
+// BANK (afldm_attention_bank): INTERP whose two sources are slots of ONE bank k [S,Tk,ldk] / vt [S,C,Tk], named per sample by
+// src[b] = (s0, s1) (device memory, clamped into [0, S) here).  A workgroup belongs to one sample, so alpha[b] == 0 is a
+// workgroup-uniform condition: the stream then ends after source 0's nchunks chunks (source 1 is neither staged nor read) and
+// the epilogue is the single-source one.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -57,8 +62,14 @@ struct AttnIP : AttnP<T> {
   const float* alpha;    // [B] blend weights, read when the kernel runs (a replayed graph sees the values of its replay)
 };
 
-template <typename T, bool INTERP>
-using AttnArg = typename std::conditional<INTERP, AttnIP<T>, AttnP<T>>::type;
+template <typename T>
+struct AttnBP : AttnIP<T> {
+  const int* src;        // [B,2] bank slots of the two sources (k1 / vt1 are unused: both sources live in k / vt); read when the kernel runs
+  int S;                 // bank slots
+};
+
+template <typename T, bool INTERP, bool BANK>
+using AttnArg = typename std::conditional<BANK, AttnBP<T>, typename std::conditional<INTERP, AttnIP<T>, AttnP<T>>::type>::type;
 
 __device__ __forceinline__ int aswz(int row) { return (4 - ((row >> 2) & 3)) & 3; }
 
@@ -70,8 +81,10 @@ template <typename T, int ND /* 16-row tiles of V^T: head_dim rows + the row of 
           bool RAGGED /* Tk % 64 != 0: clamped / element-wise staging and key masking */,
           int DBG = 0 /* timing decomposition (AFLDM_ATTN_DBG): 1 no exp2, 2 no P V MFMA, 4 no S MFMA, 8 no max,
                          16 no per-chunk staging, 32 no per-chunk barrier; results are garbage */,
-          bool INTERP = false /* two sources blended by alpha[b] (afldm_attention_interp) */>
-__global__ void __launch_bounds__(NW * 64) k_attn(AttnArg<T, INTERP> p) {
+          bool INTERP = false /* two sources blended by alpha[b] (afldm_attention_interp) */,
+          bool BANK = false /* INTERP with both sources picked from one bank by src[b] (afldm_attention_bank) */>
+__global__ void __launch_bounds__(NW * 64) k_attn(AttnArg<T, INTERP, BANK> p) {
+  static_assert(INTERP || !BANK, "BANK is a mode of INTERP");
   typedef Mma<T> MM;
   typedef typename MM::Chunk Chunk;
   constexpr int EPC = MM::EPC, KPF = MM::KPF;
@@ -95,7 +108,12 @@ __global__ void __launch_bounds__(NW * 64) k_attn(AttnArg<T, INTERP> p) {
   bid /= p.qblocks;
   const int h = bid % p.heads;
   const int b = bid / p.heads;
-  const int kb = b / (p.B / p.Bk);
+  int kb = b / (p.B / p.Bk);
+  [[maybe_unused]] int kb1 = kb;
+  if constexpr (BANK) {   // the sample's two bank slots, clamped (the host cannot check a device tensor without a sync)
+    kb = min(max(__builtin_amdgcn_readfirstlane(p.src[2 * b]), 0), p.S - 1);
+    kb1 = min(max(__builtin_amdgcn_readfirstlane(p.src[2 * b + 1]), 0), p.S - 1);
+  }
   const int q0 = (qb * NW + wave) * 32;
   const int C = p.heads * p.d;
 
@@ -352,15 +370,22 @@ __global__ void __launch_bounds__(NW * 64) k_attn(AttnArg<T, INTERP> p) {
   const T* kbase1 = kbase;
   const T* vbase1 = vbase;
   float blend = 0.f;
-  if constexpr (INTERP) {
+  if constexpr (BANK) {
+    kbase1 = p.k + (size_t)kb1 * p.Tk * p.ldk + h * p.d;
+    vbase1 = p.vt + ((size_t)kb1 * C + h * p.d) * p.Tk;
+    blend = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p.alpha[b])));
+  } else if constexpr (INTERP) {
     kbase1 = p.k1 + (size_t)kb * p.Tk * p.ldk + h * p.d;
     vbase1 = p.vt1 + ((size_t)kb * C + h * p.d) * p.Tk;
     blend = p.alpha[b];
   }
+  // BANK: alpha == 0 ends the stream after source 0 (workgroup-uniform: a workgroup belongs to one sample)
+  const bool skip = BANK && blend == 0.0f;
+  const int nstream = skip ? nchunks : 2 * nchunks;
   auto load_chunk2 = [&](int c, Chunk (&rk)[KPT], Chunk (&rv)[VPT]) {
-    if (c >= 2 * nchunks) {
+    if (c >= nstream) {
       if constexpr (RAGGED) return;
-      c = 2 * nchunks - 1;
+      c = nstream - 1;
     }
     const bool s1 = c >= nchunks;
     const int key0 = (s1 ? c - nchunks : c) * KC;
@@ -437,6 +462,12 @@ __global__ void __launch_bounds__(NW * 64) k_attn(AttnArg<T, INTERP> p) {
   store_chunk(0, rkA, rvA);
   __syncthreads();
   [[maybe_unused]] f32x4 ob[2][ND];    // INTERP: (1 - alpha) x the normalised O of source 0
+  if constexpr (BANK) {                // (a skipped source 1 never reaches the boundary: source 0's O is still in oacc then)
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int td = 0; td < ND; ++td) ob[u][td] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
   if constexpr (INTERP) {
     // the same two-stage pipeline over both sources' chunks; at the boundary (chunk nchunks, wave-uniform) source 0's O is
     // normalised, weighted by 1 - alpha and parked in ob, and the accumulators, m_run and Q's -m_run channel restart as at
@@ -464,12 +495,13 @@ __global__ void __launch_bounds__(NW * 64) k_attn(AttnArg<T, INTERP> p) {
       }
       compute((c < nchunks ? c : c - nchunks) * KC, buf);
     };
-    const int nall = 2 * nchunks;        // even: every pair of steps is whole
+    const int nall = nstream;            // even (every pair of steps is whole) unless BANK skips source 1
     for (int c = 0; c < nall; c += 2) {
       load_chunk2(c + 2, rkA, rvA);
       step(c, 0);
-      store_chunk(1, rkB, rvB);
+      if (!BANK || c + 1 < nall) store_chunk(1, rkB, rvB);
       __syncthreads();
+      if (BANK && c + 1 >= nall) break;
       load_chunk2(c + 3, rkB, rvB);
       step(c + 1, 1);
       if (c + 2 < nall) store_chunk(0, rkA, rvA);
@@ -502,7 +534,7 @@ __global__ void __launch_bounds__(NW * 64) k_attn(AttnArg<T, INTERP> p) {
     for (int td = 0; td < ND; ++td)
       if (td == ltile) lsel = oacc[u][td][0];
     const float l = __shfl(lsel, lsrc, 64);
-    const float inv = (INTERP ? blend : 1.0f) / l;
+    const float inv = (INTERP && !skip ? blend : 1.0f) / l;     // skip: oacc is source 0's, ob is zero
     const int qrow = q0 + 16 * u + li;
     if (qrow < p.Tq) {
       T* op = p.o + ((size_t)b * p.Tq + qrow) * p.ldo + h * p.d;
@@ -560,6 +592,17 @@ static bool attn_interp_launch_nw(const AttnIP<T>& p, int nd, int grid, hipStrea
   return true;
 }
 
+// afldm_attention_bank's kernels (the same table)
+template <typename T, int NW, bool RAGGED>
+static bool attn_bank_launch_nw(const AttnBP<T>& p, int nd, int grid, hipStream_t st) {
+  constexpr bool BF = sizeof(T) == 2;
+  if (nd == 1) k_attn<T, 1, 1, NW, RAGGED, 0, true, true><<<grid, NW * 64, 0, st>>>(p);
+  else if (nd == 2) k_attn<T, 2, BF ? 1 : 2, NW, RAGGED, 0, true, true><<<grid, NW * 64, 0, st>>>(p);
+  else if (nd == 3) k_attn<T, 3, BF ? 2 : 3, NW, RAGGED, 0, true, true><<<grid, NW * 64, 0, st>>>(p);
+  else return false;
+  return true;
+}
+
 template <typename T>
 static void attn_params(AttnP<T>& p, const void* q, int ldq, const void* k, int ldk, const void* vt, void* o, int ldo, int B,
                         int Bk, int heads, int Tq, int Tk, int d, float scale) {
@@ -602,6 +645,28 @@ static int attn_interp_launch(const void* q, int ldq, const void* k0, const void
     return AFLDM_ESHAPE;
   }
   return check_launch("afldm_attention_interp");
+}
+
+template <typename T>
+static int attn_bank_launch(const void* q, int ldq, const void* k, int ldk, const void* vt, const int* src, const float* alpha,
+                            void* o, int ldo, int B, int S, int heads, int Tq, int Tk, int d, float scale, hipStream_t st) {
+  AttnBP<T> p;
+  attn_params<T>(p, q, ldq, k, ldk, vt, o, ldo, B, B, heads, Tq, Tk, d, scale);
+  p.k1 = (const T*)k; p.vt1 = (const T*)vt; p.alpha = alpha; p.src = src; p.S = S;
+  const int waves = attn_waves(B, heads, Tq);
+  p.qblocks = (Tq + 32 * waves - 1) / (32 * waves);
+  const int grid = B * heads * p.qblocks;
+  const int nd = d / 16 + 1;
+  const bool ragged = Tk % KC != 0;
+  const bool ok = waves == 8 ? (ragged ? attn_bank_launch_nw<T, 8, true>(p, nd, grid, st) : attn_bank_launch_nw<T, 8, false>(p, nd, grid, st))
+                  : waves == 4 ? (ragged ? attn_bank_launch_nw<T, 4, true>(p, nd, grid, st) : attn_bank_launch_nw<T, 4, false>(p, nd, grid, st))
+                  : waves == 2 ? (ragged ? attn_bank_launch_nw<T, 2, true>(p, nd, grid, st) : attn_bank_launch_nw<T, 2, false>(p, nd, grid, st))
+                               : (ragged ? attn_bank_launch_nw<T, 1, true>(p, nd, grid, st) : attn_bank_launch_nw<T, 1, false>(p, nd, grid, st));
+  if (!ok) {
+    set_error("afldm_attention_bank: unsupported head_dim %d", d);
+    return AFLDM_ESHAPE;
+  }
+  return check_launch("afldm_attention_bank");
 }
 
 template <typename T>
@@ -659,6 +724,22 @@ extern "C" int afldm_attention_interp(const void* q, int ldq, const void* k0, co
     return attn_interp_launch<float>(q, ldq, k0, k1, ldk, vt0, vt1, alpha, o, ldo, B, Bk, heads, Tq, Tk, d, scale, st);
   if (dtype == AFLDM_BF16)
     return attn_interp_launch<bf16>(q, ldq, k0, k1, ldk, vt0, vt1, alpha, o, ldo, B, Bk, heads, Tq, Tk, d, scale, st);
+  set_error("%s: unknown dtype %d", name, dtype);
+  return AFLDM_EDTYPE;
+}
+
+extern "C" int afldm_attention_bank(const void* q, int ldq, const void* k, int ldk, const void* vt, const int* src,
+                                    const float* alpha, void* o, int ldo, int B, int S, int heads, int Tq, int Tk, int d,
+                                    float scale, int dtype, afldm_stream_t stream) {
+  const char* name = "afldm_attention_bank";
+  AFLDM_REQUIRE(S >= 1, AFLDM_ESHAPE, "%s: a bank of S=%d sources", name, S);
+  const int rc = attn_check(name, q, ldq, k, ldk, vt, o, ldo, B, 1, heads, Tq, Tk, d, dtype);
+  if (rc != AFLDM_OK) return rc;
+  AFLDM_REQUIRE(src && alpha, AFLDM_ENULL, "%s: NULL src / alpha", name);
+  AFLDM_REQUIRE(((size_t)src & 3) == 0 && ((size_t)alpha & 3) == 0, AFLDM_EALIGN, "%s: src / alpha must be 4-byte aligned", name);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == AFLDM_F32) return attn_bank_launch<float>(q, ldq, k, ldk, vt, src, alpha, o, ldo, B, S, heads, Tq, Tk, d, scale, st);
+  if (dtype == AFLDM_BF16) return attn_bank_launch<bf16>(q, ldq, k, ldk, vt, src, alpha, o, ldo, B, S, heads, Tq, Tk, d, scale, st);
   set_error("%s: unknown dtype %d", name, dtype);
   return AFLDM_EDTYPE;
 }

@@ -56,16 +56,24 @@ class CrossFrameSampler:
     interp=True (image interpolation, LDMInterpolationPipeline): the processors blend two stored passes (enable_interp); the
     STORE pass is ONE batch-2 graph of both endpoints (AttnState.PAIR: sample s fills slot s), and a LOAD engine owns a
     persistent [B] blend-weight buffer that its captured graph reads by address - run(..., alpha=...) fills it before the
-    replay.  Its engines are keyed ('interp', load, batch)."""
+    replay.  Its engines are keyed ('interp', load, batch).
 
-    def __init__(self, unet, scheduler, steps, interp=False):
+    bank=True (frame sequences, LDMVideoPipeline): a STORE pass at any batch S keeps its S samples as one bank per step
+    (AttnState.BANK), and a LOAD engine owns persistent [B, 2] source and [B] blend-weight buffers that its captured graph reads
+    by address (each attention = one afldm_attention_bank launch) - run(..., src=..., alpha=...) fills them before the replay.
+    Its engines are keyed ('bank', load, batch, S)."""
+
+    def __init__(self, unet, scheduler, steps, interp=False, bank=False):
         """scheduler: a Schedule of `steps` evaluations, or a scheduler with .schedule(steps) (as DenoiseEngine takes)."""
-        self.unet, self.scheduler, self.steps, self.interp = unet, scheduler, steps, bool(interp)
+        self.unet, self.scheduler, self.steps, self.interp, self.bank = unet, scheduler, steps, bool(interp), bool(bank)
         self.attn_state = AttnState()
         self.names = list(get_unet_attn_processors(unet))
-        self.procs = {k: CrossFrameAttnProcessor(self.attn_state, enable_interp=self.interp, cache_kv=True) for k in self.names}
+        self.procs = {k: CrossFrameAttnProcessor(self.attn_state, enable_interp=self.interp, cache_kv=True, enable_bank=self.bank)
+                      for k in self.names}
         self.engines = {}
-        self.alphas = {}                              # interp: LOAD batch -> the blend-weight buffer its graph reads
+        self.alphas = {}                              # interp / bank: LOAD batch -> the blend-weight buffer its graph reads
+        self.sources = {}                             # bank: LOAD batch -> the [B, 2] int32 source buffer its graph reads
+        self.bank_size = 0                            # bank: S of the stored pass
         self.model_key, self.stored = None, False
 
     def install(self):
@@ -73,9 +81,10 @@ class CrossFrameSampler:
         set_unet_attn_processor(self.unet, dict(self.procs))
         return previous
 
-    def run(self, latents, load, alpha=None):
+    def run(self, latents, load, alpha=None, src=None):
         """One pass over the schedule (processors installed by the caller): STORE (load=False; attn_state is reset) or LOAD.
-        interp: a STORE pass takes the two endpoints as one batch of 2; a LOAD pass needs `alpha`, one blend weight per sample."""
+        interp: a STORE pass takes the two endpoints as one batch of 2; a LOAD pass needs `alpha`, one blend weight per sample.
+        bank: a STORE pass takes the S sources as one batch; a LOAD pass needs `src` (per sample, its two bank slots) and `alpha`."""
         from .models.blocks import invalidate_stale_packed
         B = latents.shape[0]
         fp = model_state_key(self.unet)
@@ -102,29 +111,48 @@ class CrossFrameSampler:
                     buf = self.alphas[B] = torch.zeros(B, dtype=torch.float32, device=self.unet.device)
                 buf.copy_(torch.as_tensor(alpha, dtype=torch.float32))        # stream-ordered before the replay that reads it
                 self.attn_state.set_alpha(buf)
+            if self.bank:
+                if alpha is None or src is None or len(alpha) != B or len(src) != B:
+                    raise ValueError(f"CrossFrameSampler(bank): a LOAD pass of {B} samples needs {B} source pairs and blend weights")
+                if B not in self.alphas:
+                    self.alphas[B] = torch.zeros(B, dtype=torch.float32, device=self.unet.device)
+                    self.sources[B] = torch.zeros(B, 2, dtype=torch.int32, device=self.unet.device)
+                # stream-ordered before the replay that reads them
+                self.alphas[B].copy_(torch.as_tensor(alpha, dtype=torch.float32))
+                self.sources[B].copy_(torch.as_tensor(src, dtype=torch.int32).reshape(B, 2))
+                self.attn_state.set_alpha(self.alphas[B])
+                self.attn_state.set_sources(self.sources[B])
         else:
             self.attn_state.reset()
+            if self.bank:
+                self.attn_state.set_store_id(AttnState.BANK)
+                self.bank_size = B
             if self.interp:
                 if B != 2:
                     raise ValueError(f"CrossFrameSampler(interp): the STORE pass is one batch of the two endpoints, got {B}")
                 self.attn_state.set_store_id(AttnState.PAIR)
-        key = ("interp", bool(load), B) if self.interp else (bool(load), B)
+        key = ("interp", bool(load), B) if self.interp else ("bank", bool(load), B, self.bank_size) if self.bank else (bool(load), B)
         if key not in self.engines:
             if not load:                          # a new STORE capture moves the stored tensors: the LOAD graphs read the old ones
                 self.engines.clear()
+            elif self.bank:                       # ONE LOAD graph: a sequence passes through it in chunks, whatever its length
+                for other in [k for k in self.engines if k[1]]:
+                    del self.engines[other]
             self.engines[key] = _UnrolledEngine(self.unet, self.scheduler, B, self.steps, self.attn_state)
         out = self.engines[key].run(latents)
         self.stored = self.stored or not load
         return out
 
 
-def _sampler(pipeline, schedule, interp=False):
+def _sampler(pipeline, schedule, interp=False, bank=None):
     """The pipeline's cached CrossFrameSampler over `schedule` (a "ddim"-kind Schedule: DDIM, or the SR harness's I2SB ODE
-    bridge).  interp: the interpolation sampler, cached apart.  A sampler is bound to the UNet object and to the attention
-    modules it found there, so both are part of its key."""
+    bridge).  interp: the interpolation sampler, cached apart; bank: the name of a banked sampler's slot (the video pipeline keeps
+    two, one per schedule).  A sampler is bound to the UNet object and to the attention modules it found there, so both are
+    part of its key."""
     unet = pipeline.unet
-    return cached_engine(pipeline, "_xframe_interp_sampler" if interp else "_xframe_sampler", schedule, None, True, unet,
-                         build=lambda: CrossFrameSampler(unet, schedule, len(schedule.timesteps), interp=interp),
+    slot = f"_xframe_bank_sampler_{bank}" if bank else "_xframe_interp_sampler" if interp else "_xframe_sampler"
+    return cached_engine(pipeline, slot, schedule, None, True, unet,
+                         build=lambda: CrossFrameSampler(unet, schedule, len(schedule.timesteps), interp=interp, bank=bool(bank)),
                          extra=(unet, tuple(get_unet_attn_processors(unet))))
 
 

@@ -712,7 +712,7 @@ class AttnProcessor2_0:
     (the protocol CrossFrameAttnProcessor uses, reference cross_frame_attn.py:125)."""
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None, kv=None, kv_sink=None,
-                 kv1=None, alpha=None, qk_sink=None):
+                 kv1=None, alpha=None, qk_sink=None, src=None):
         """kv / kv_sink (CrossFrameAttnProcessor with cache_kv): `kv_sink(k, vt)` receives this call's projected keys
         [B, T, C] (a view) and channel-major values [B, C, T] - the self-attention then runs on the three-launch path, where
         they exist in memory; `kv = (k, vt)` runs the attention against such a stored pair (Bk divides B) instead of projecting
@@ -720,10 +720,13 @@ class AttnProcessor2_0:
         kv1 + alpha (the interpolating processor): a second stored pair, and the output is
         to_out((1 - alpha) attn(q, kv) + alpha attn(q, kv1)) + residual with alpha [B] fp32 on the device - one
         afldm_attention_interp launch and one to_out GEMM (to_out is affine and the residual is common to both terms).
+        src + alpha (the banked processor): `kv = (k, vt)` is a bank of S stored sources and src [B, 2] int32 on the device names
+        every sample's two (ops.attention_bank: one launch, then the one to_out + residual as on the interp path).
         qk_sink (SAGAttnProcessor): `qk_sink(q, k)` receives this call's projected queries and keys [B, T, C] (views of the
         q | k buffer) in front of the attention launch; like kv_sink it sends the block to the three-launch path."""
         assert attention_mask is None
         assert kv1 is None or (kv is not None and alpha is not None)
+        assert src is None or (kv is not None and alpha is not None and kv1 is None)
         B, H, W, C = hidden_states.shape
         gamma, beta = packed_norm(attn.group_norm)
         gn = attn.group_norm
@@ -782,7 +785,9 @@ class AttnProcessor2_0:
             q = linear_forward(attn.to_q, tokens)
             w, b = packed_qkv(attn, tokens.dtype, ("k", "v"))
             k, vt = ops.linear_split(encoder_hidden_states, w, b, C)
-        if kv1 is not None:
+        if src is not None:
+            o = ops.attention_bank(q, k, vt, src, alpha, attn.heads, scale=attn.scale)
+        elif kv1 is not None:
             o = ops.attention_interp(q, k, vt, kv1[0], kv1[1], alpha, attn.heads, scale=attn.scale)
         else:
             o = ops.attention(q, k, vt, attn.heads, scale=attn.scale)

@@ -1328,6 +1328,39 @@ def attention_interp(q, k0, vt0, k1, vt1, alpha, heads, scale=None, out=None):
     return out
 
 
+def attention_bank(q, k_bank, vt_bank, src, alpha, heads, scale=None, out=None):
+    """attention_interp() with every sample naming its own two sources in a bank: k_bank [S,Tk,C] / vt_bank [S,C,Tk] (layouts as
+    attention(); what a STORE pass at batch S leaves), src int32 [B,2] bank slots (clamped into [0, S) by the kernel), alpha
+    fp32 [B]; both device tensors, read when the kernel runs - a captured graph picks up the values they hold at each replay.
+    A sample with alpha == 0 never reads its second source (afldm_attention_bank: one launch)."""
+    _dev(vt_bank, "vt_bank")
+    _dev(src, "src")
+    _dev(alpha, "alpha")
+    if not (q.is_cuda and k_bank.is_cuda):
+        raise RuntimeError("afldm_amd: attention inputs must live on an MI355X (cuda) device; there is no CPU path")
+    B, Tq, C = q.shape
+    S, Tk, _ = k_bank.shape
+    if tuple(vt_bank.shape) != (S, C, Tk) or not vt_bank.is_contiguous() or k_bank.dtype != q.dtype or vt_bank.dtype != q.dtype:
+        raise ValueError(f"attention_bank: bank k {tuple(k_bank.shape)} {k_bank.dtype} / vt {tuple(vt_bank.shape)} {vt_bank.dtype} "
+                         f"(contiguous: {vt_bank.is_contiguous()}) does not match q {tuple(q.shape)} {q.dtype}")
+    if src.dtype != torch.int32 or tuple(src.shape) != (B, 2) or not src.is_contiguous():
+        raise ValueError(f"attention_bank: src must be contiguous int32 [{B}, 2], got {src.dtype} {tuple(src.shape)}")
+    if alpha.dtype != torch.float32 or tuple(alpha.shape) != (B,):
+        raise ValueError(f"attention_bank: alpha must be fp32 [{B}], got {alpha.dtype} {tuple(alpha.shape)}")
+    ldq, ldk = q.stride(1), k_bank.stride(1)
+    assert q.stride(2) == 1 and k_bank.stride(2) == 1 and q.stride(0) == Tq * ldq and k_bank.stride(0) == Tk * ldk
+    d = C // heads
+    if scale is None:
+        scale = d ** -0.5
+    if out is None:
+        out = torch.empty((B, Tq, C), dtype=q.dtype, device=q.device)
+    tok = _begin()
+    check(lib.afldm_attention_bank(ptr(q), ldq, ptr(k_bank), ldk, ptr(vt_bank), ptr(src), ptr(alpha), ptr(out), C, B, S, heads, Tq,
+                                   Tk, d, float(scale), _code(q), stream_ptr()), "attention_bank")
+    _end(tok, "attention_bank", 8.0 * B * heads * Tq * Tk * d, (2 * B * Tq * C + 4 * S * Tk * C) * q.element_size())
+    return out
+
+
 _FUSED_ATTN = os.environ.get("AFLDM_NO_FUSED_ATTN", "0") != "1"
 # below this many (sample, head) workgroups the chip is too empty with one workgroup per pair: the three-launch path wins.
 # In-step A/B (profiles/r04/small_batch_tiles_ab.txt): 128 against 256: batch 8 2.385 -> 2.362 (the 16^2 level fuses), batch 12

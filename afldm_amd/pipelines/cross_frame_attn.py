@@ -20,17 +20,21 @@ class AttnState:
 
     Beyond the reference: `set_store_id(AttnState.PAIR)` makes ONE batch-2 STORE pass fill both slots (sample 0 -> slot 0, sample
     1 -> slot 1: the samples are independent, so this is the reference's two batch-1 passes at half the launches), and
-    `set_alpha` also takes a 1-D fp32 device tensor, one blend weight per sample of the LOAD batch."""
+    `set_alpha` also takes a 1-D fp32 device tensor, one blend weight per sample of the LOAD batch.
+    `set_store_id(AttnState.BANK)` makes a STORE pass at ANY batch S keep the whole batch as one bank of S sources per timestep,
+    and `set_sources(t)` - t an int32 [B, 2] tensor - names, per sample of a LOAD batch, the two bank slots it attends to (the
+    banked processor, enable_bank; blended by that sample's alpha)."""
     STORE, LOAD, IDLE = 0, 1, 2
     PAIR = -1
-    _FIELDS = ("state", "timestep", "store_id", "alpha")
+    BANK = -2
+    _FIELDS = ("state", "timestep", "store_id", "alpha", "sources")
 
     def __init__(self):
         self._v = {}
         self.reset()
 
     def reset(self):
-        self._v.update(state=self.STORE, timestep=0, store_id=0, alpha=0)
+        self._v.update(state=self.STORE, timestep=0, store_id=0, alpha=0, sources=None)
 
     def __getattr__(self, name):                      # only reached for names that are not real attributes
         if name in AttnState._FIELDS:
@@ -54,6 +58,15 @@ class AttnState:
                              f"{alpha.dtype} {tuple(alpha.shape)}")
         self._v["alpha"] = alpha
 
+    def set_sources(self, sources):
+        """int32 [B, 2]: sample b of the LOAD batch attends to bank slots sources[b] = (s0, s1).  On the device for the cached
+        path (afldm_attention_bank reads it when the kernel runs, and clamps it into the bank); None clears it."""
+        if sources is not None and not (torch.is_tensor(sources) and sources.ndim == 2 and sources.shape[1] == 2
+                                        and sources.dtype == torch.int32):
+            what = f"{sources.dtype} {tuple(sources.shape)}" if torch.is_tensor(sources) else type(sources).__name__
+            raise ValueError(f"AttnState.set_sources: sources must be an int32 tensor [B, 2], got {what}")
+        self._v["sources"] = sources
+
     def set_store_id(self, store_id):
         self._v["store_id"] = store_id
 
@@ -70,15 +83,51 @@ class CrossFrameAttnProcessor(AttnProcessor2_0):
     stored map again every step (reference cross_frame_attn.py:88-125 recomputes them: same layer, same input, same numbers).
     `maps` is still filled as the reference does.  With enable_interp, a LOAD pass that finds both slots cached runs
     to_q -> ONE afldm_attention_interp launch over both stored pairs (per-sample alpha) -> ONE to_out + residual, instead of
-    two GroupNorms, two K / V projections, two attentions, two to_out GEMMs and a torch blend."""
+    two GroupNorms, two K / V projections, two attentions, two to_out GEMMs and a torch blend.
+    enable_bank (frame sequences, LDMVideoPipeline): a STORE pass with store_id BANK keeps its whole batch of S samples in slot
+    0 as one bank, and a LOAD pass lets sample b attend to bank slots attn_state.sources[b] = (s0, s1), blended by its alpha.
+    With cached K / V that is to_q -> ONE afldm_attention_bank launch -> ONE to_out + residual; without, the eager yardstick:
+    per sample and named source one GroupNorm + K / V projection of that slot's stored map and one afldm_attention, then the
+    torch blend (a sample whose alpha is 0 runs its first source only, like the kernel)."""
 
-    def __init__(self, attn_state: AttnState, enable_interp=False, cache_kv=False):
+    def __init__(self, attn_state: AttnState, enable_interp=False, cache_kv=False, enable_bank=False):
         super().__init__()
         self.attn_state = attn_state
         self.maps = [dict(), dict()]
         self.kv = [dict(), dict()]
         self.enable_interp = enable_interp
         self.cache_kv = bool(cache_kv)
+        self.enable_bank = bool(enable_bank)
+        if self.enable_bank and self.enable_interp:
+            raise ValueError("CrossFrameAttnProcessor: enable_bank and enable_interp are two different LOAD modes")
+
+    def _load_bank(self, attn, hidden_states, attention_mask, temb, t):
+        """LOAD of the banked processor (see the class docstring)."""
+        B = hidden_states.shape[0]
+        src = self.attn_state.sources
+        if src is None or src.shape[0] != B:
+            raise ValueError(f"a banked LOAD pass of {B} samples needs AttnState.set_sources with an int32 [{B}, 2] tensor, got "
+                             f"{None if src is None else tuple(src.shape)}")
+        if self.cache_kv and t in self.kv[0]:
+            if src.device != hidden_states.device:
+                raise ValueError(f"sources on {src.device} do not match the LOAD batch on {hidden_states.device}")
+            return AttnProcessor2_0.__call__(self, attn, hidden_states, None, attention_mask, temb, kv=self.kv[0][t], src=src,
+                                             alpha=self._alpha_vector(B, hidden_states.device))
+        bank = self.maps[0][t]
+        S = bank.shape[0]
+        alpha = self.attn_state.alpha
+        alphas = [float(a) for a in alpha.tolist()] if torch.is_tensor(alpha) else [float(alpha)] * B
+        if len(alphas) != B:
+            raise ValueError(f"per-sample alpha of {len(alphas)} weights does not match the LOAD batch {B}")
+        rows = []
+        for b, (s0, s1) in enumerate(src.tolist()):
+            x = hidden_states[b:b + 1]
+            per = []
+            for s in (s0, s1) if alphas[b] != 0.0 else (s0,):
+                s = min(max(s, 0), S - 1)
+                per.append(AttnProcessor2_0.__call__(self, attn, x, self._kv_source(attn, bank[s:s + 1], 1), attention_mask, temb))
+            rows.append(per[0] if len(per) == 1 else (1 - alphas[b]) * per[0] + alphas[b] * per[1])
+        return torch.cat(rows) if B > 1 else rows[0]
 
     def _alpha_vector(self, batch, device):
         """The LOAD pass's blend weights as the fp32 device vector [batch] the interpolating kernel reads."""
@@ -116,11 +165,15 @@ class CrossFrameAttnProcessor(AttnProcessor2_0):
             capturing = torch.cuda.is_current_stream_capturing()
             if sid == AttnState.PAIR:
                 return self._store_pair(attn, hidden_states, attention_mask, temb, t, capturing)
+            if sid == AttnState.BANK:             # the whole batch, as one bank of S sources, in slot 0
+                sid = 0
             self.maps[sid][t] = hidden_states.detach() if capturing else hidden_states.detach().clone()
             if not self.cache_kv:
                 return super().__call__(attn, hidden_states, None, attention_mask, temb)
             return super().__call__(attn, hidden_states, None, attention_mask, temb,
                                     kv_sink=lambda k, vt: self.kv[sid].__setitem__(t, (k, vt)))
+        if self.enable_bank:
+            return self._load_bank(attn, hidden_states, attention_mask, temb, t)
         B = hidden_states.shape[0]
         if self.cache_kv and t in self.kv[0] and B % self.kv[0][t][0].shape[0] == 0:
             if not self.enable_interp:

@@ -419,6 +419,17 @@ int afldm_attention(const void* q, int ldq, const void* k, int ldk, const void* 
 int afldm_attention_interp(const void* q, int ldq, const void* k0, const void* k1, int ldk, const void* vt0,
                            const void* vt1, const float* alpha, void* o, int ldo, int B, int Bk, int heads, int Tq,
                            int Tk, int d, float scale, int dtype, afldm_stream_t stream);
+/* The same blended attention over a BANK of S stored sources, every sample naming its own two: k [S,Tk,ldk] and
+ * vt [S,heads*d,Tk] in afldm_attention's layouts (a STORE pass at batch S leaves exactly this), src int32 [B,2] and
+ * alpha fp32 [B] in DEVICE memory, both read when the kernel runs (a replayed graph sees the values of its replay).
+ * With s0 = clamp(src[b][0]), s1 = clamp(src[b][1]) (clamped into [0, S) in the kernel),
+ *   o[b] = (1 - alpha[b]) softmax(q_b k[s0]^T scale) vt[s0] + alpha[b] softmax(q_b k[s1]^T scale) vt[s1]
+ * in afldm_attention_interp's arithmetic.  alpha[b] == 0.0f skips source 1 altogether (neither staged nor read): the
+ * sample costs, and equals, the single-source attention on k[s0].  Limits are afldm_attention's, S >= 1, src and alpha
+ * non-NULL and 4-byte aligned. */
+int afldm_attention_bank(const void* q, int ldq, const void* k, int ldk, const void* vt, const int* src,
+                         const float* alpha, void* o, int ldo, int B, int S, int heads, int Tq, int Tk, int d,
+                         float scale, int dtype, afldm_stream_t stream);
 
 /* ---- attention block front end, fused ------------------------------------------------------
  * group_norm -> to_q | to_k | to_v -> scaled_dot_product_attention of diffusers' AttnProcessor2_0 on the deprecated
