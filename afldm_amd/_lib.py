@@ -130,6 +130,9 @@ def _load():
         "afldm_mask_pool": ([vp, vp, ip, ip, ip, ip, ip, vp], c_int),
         "afldm_sdedit_step": ([vp, vp, vp, vp, vp, vp, c_size_t, vp, vp, vp, ip, ip, ip, ip, ip, ip, vp], c_int),
         "afldm_sdedit_step_flat": ([vp] * 7 + [fp] * 10 + [c_size_t, vp], c_int),
+        "afldm_rev_step": ([vp, vp, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, vp], c_int),
+        "afldm_rev_step_flat": ([vp, vp, vp, vp, vp, fp, fp, ip, ip, c_size_t, c_size_t, vp], c_int),
+        "afldm_rev_encode": ([vp, vp, vp, c_size_t, c_size_t, vp], c_int),
         "afldm_ilvr_step": ([vp, vp, vp, vp, c_size_t, c_size_t, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, vp], c_int),
         "afldm_ilvr_step_flat": ([vp] * 8 + [fp] * 10 + [c_size_t, ip, ip, vp], c_int),
         "afldm_pano_step": ([vp, vp, vp, c_size_t, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, POINTER(c_int), ip, POINTER(c_int), ip, ip,
@@ -184,6 +187,19 @@ lib, EXPORTS = _load()
 
 class AfldmError(RuntimeError):
     pass
+
+
+_HASH = []
+
+
+def library_hash():
+    """sha256 of the loaded library file, read once: what identifies the build (a ReversibleCode records it, because another
+    build's kernels may round differently)."""
+    if not _HASH:
+        import hashlib
+        with open(LIB_PATH, "rb") as f:
+            _HASH.append(hashlib.sha256(f.read()).hexdigest())
+    return _HASH[0]
 
 
 def check(rc, what=""):

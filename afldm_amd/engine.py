@@ -35,6 +35,11 @@ rows and afldm_sdedit_step as the last line, which selects per element between t
 next level with the run's one fixed noise - run(x_start, draw=..., known=(orig, cmap, z)); three static per-run tensors and, only
 when eta != 0, a noise buffer [steps, B, C, H, W].
 
+ReversibleEngine (kind "rev", DDIMScheduler.reversible_schedule: the bit-reversible sampler, a two-step DDIM on integers) has
+[steps, 4] rows (cx, ce, sign, boot) and afldm_rev_step as the last line.  Its state is a pair of int64 tensors on the grid 2^-32,
+rotated in place; `lat` is the fp32 view of the newer one and feeds the next evaluation.  run(start) takes latents or a
+ReversibleCode and returns a ReversibleCode; inverting and then sampling (or the reverse) returns the integers it started from.
+
 PanoramaEngine (kind "pano", DDIMScheduler.panorama_schedule: MultiDiffusion) samples a canvas [P, C, Hc, Wc] larger than the UNet's
 window: `lat` holds the P * nwin windows of a panorama.Geometry, the canvas is a second fp32 buffer, and the last line of a step is
 afldm_pano_step, which applies the "sde" row per window, averages over the windows that cover each canvas element and writes both
@@ -514,6 +519,89 @@ class SDEditEngine(DenoiseEngine):
         self.known.copy_(orig)
         self.cmap.copy_(cmap)
         self.zfix.copy_(z)
+
+
+class ReversibleEngine(DenoiseEngine):
+    """The bit-reversible sampler on the replayed graphs (kind "rev", DDIMScheduler.reversible_schedule): a step is the plain
+    sampler's launch list with afldm_rev_step as the last line.  The state is a pair of int64 tensors on the grid 2^-32 - `near`,
+    the level the UNet is evaluated at, and `far`, the level before it - which the update rotates in place at fixed addresses:
+    far <- near, near <- far + sign q, with `lat` <- the fp32 view of the new near, the next evaluation's input.  Integer adds of
+    the same q undo each other, so a run of the "invert" schedule followed by one of the "sample" schedule (or the reverse)
+    returns the integers it started from - provided every evaluation reproduces its bits, which holds for one batch size, dtype,
+    set of weights and build of the library (ReversibleCode records them).  run(start) takes fp32 latents - encoded to the grid, one
+    state, so the schedule must start with its boot row - or a ReversibleCode - two states, a from_code schedule - and returns a
+    ReversibleCode.  `bad` [B] collects, per sample, whether an element was non-finite or left the int64 range; check_errors
+    reads it once after the run and raises FloatingPointError naming the samples."""
+    ONE_BRANCH = True           # one `bad` word per sample of the whole batch, one pair of state buffers
+
+    def _rev_state(self):
+        """The int64 pair and the per-sample trouble flags."""
+        self.far = torch.zeros(tuple(self.lat.shape), dtype=torch.int64, device=self.lat.device)
+        self.near = torch.zeros_like(self.far)
+        self.bad = torch.zeros(self.B, dtype=torch.int32, device=self.lat.device)
+        self._capturing = False
+        return [(self.bad,)]
+
+    UPDATES = {"rev": (ops.rev_step, _rev_state)}
+
+    def _apply(self, lat, eps, branch):
+        self._update(self.far, self.near, eps, *self._state[branch], self.coef, self.step_idx, advance=False, out=lat)
+
+    def _carried(self):
+        return [self.lat, self.far, self.near, self.bad]
+
+    def _capture(self, counts, before_step=None):
+        self._capturing = True          # (the flags of the warm-up step are put back with the state: they are the run's to report)
+        try:
+            return super()._capture(counts, before_step)
+        finally:
+            self._capturing = False
+
+    def reset(self, start):
+        """start: fp32-able latents [B, C, H, W] for a schedule with a boot row, or a ReversibleCode for a from_code schedule -
+        (X_N, X_N-1) to sample from, (X_1, X_0) to invert."""
+        from .reversible import ReversibleCode, decode
+        cfg = self.schedule.config
+        sampling, from_code = cfg["_rev_direction"] == "sample", cfg["_rev_from_code"]
+        if isinstance(start, ReversibleCode) != from_code:
+            raise ValueError("ReversibleEngine: a from_code schedule starts from a ReversibleCode, and only such a schedule does")
+        self.refresh_if_stale()
+        self.bad.zero_()
+        if from_code:
+            levels = len(self.timesteps) + 1
+            if tuple(start.hi.shape) != tuple(self.lat.shape) or start.k != (levels if sampling else 1):
+                raise ValueError(f"ReversibleEngine: a code of {tuple(start.hi.shape)} at level {start.k}, want {tuple(self.lat.shape)} "
+                                 f"at level {levels if sampling else 1}")
+            far, near = (start.hi, start.lo) if sampling else (start.lo, start.hi)
+            self.far.copy_(far)
+            self.near.copy_(near)
+        else:
+            x = start.to(device=self.lat.device, dtype=torch.float32) * self.schedule.init_noise_sigma
+            ops.rev_encode(x.contiguous(), self.bad, out=self.near)
+            self.far.copy_(self.near)          # (the boot row does not read it)
+        self.lat.copy_(decode(self.near))
+        self.step_idx.fill_(-1)
+
+    def _result(self):
+        from . import _lib
+        from .reversible import ReversibleCode
+        cfg = self.schedule.config
+        sampling = cfg["_rev_direction"] == "sample"
+        levels = len(self.timesteps) + (1 if cfg["_rev_from_code"] else 0)
+        hi, lo = (self.far, self.near) if sampling else (self.near, self.far)
+        return ReversibleCode(hi.clone(), lo.clone(), 1 if sampling else levels, cfg["_rev_steps"], None, self.B, self.unet.dtype,
+                              self._model_key, _lib.library_hash())
+
+    def check_errors(self):
+        """The base class's check, then `bad`: one read per run.  A flagged sample had q = 0 at some element, so its states are not
+        on the trajectory: FloatingPointError names the samples; the others are valid, and so is the next run."""
+        super().check_errors()
+        if self._capturing:
+            return
+        rows = self.bad.nonzero().flatten().tolist()
+        if rows:
+            raise FloatingPointError(f"ReversibleEngine: non-finite values or int64 overflow in the latents of batch rows {rows} "
+                                     "(their update was skipped at those elements): the states of these rows are INVALID")
 
 
 class PanoramaEngine(DenoiseEngine):

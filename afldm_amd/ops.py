@@ -1680,6 +1680,75 @@ def sdedit_step_flat(x, eps, orig, cmap, z, z_u, row, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- bit-reversible sampler (int64 latents)
+def _rev_pair(name, far, near, lat, bad):
+    """The checks rev_step and rev_step_flat share: far / near contiguous int64 device tensors of one shape, lat fp32 of that
+    shape, bad int32 on the device."""
+    _dev(far, "far"); _dev(near, "near"); _dev(lat, "lat"); _dev(bad, "bad")
+    if far.dtype != torch.int64 or near.dtype != torch.int64 or far.shape != near.shape:
+        raise ValueError(f"{name}: far {far.dtype} {tuple(far.shape)} / near {near.dtype} {tuple(near.shape)}, want two int64 tensors "
+                         "of one shape")
+    if lat.dtype != torch.float32 or lat.shape != near.shape or bad.dtype != torch.int32 or bad.dim() != 1:
+        raise ValueError(f"{name}: lat {lat.dtype} {tuple(lat.shape)} (want fp32 {tuple(near.shape)}), bad {bad.dtype} "
+                         f"{tuple(bad.shape)} (want int32 [B])")
+
+
+def rev_step(far, near, eps_nhwc, bad, coef, step_idx, advance=False, out=None):
+    """The reversible update on the pair (far, near), int64 NCHW [B, C, H, W] on the grid 2^-32, rotated IN PLACE: far <- near,
+    near <- far + sign q (boot: near + sign q), q the integer the row makes of near and eps (afldm_rev_step in afldm_hip.h).  eps
+    NHWC dtype; bad int32 [B], set to 1 for a sample with trouble and never cleared here; coef float[4*nsteps] rows (cx, ce, sign,
+    boot) and step_idx int32[1] on device.  Returns `out`, the fp32 view of the new near."""
+    if out is None:
+        out = torch.empty(near.shape, dtype=torch.float32, device=near.device)
+    _rev_pair("rev_step", far, near, out, bad)
+    _dev(eps_nhwc, "eps")
+    if near.dim() != 4:
+        raise ValueError(f"rev_step: near {tuple(near.shape)}, want [B, C, H, W]")
+    B, C, H, W = near.shape
+    if tuple(eps_nhwc.shape) != (B, H, W, C) or bad.shape[0] != B:
+        raise ValueError(f"rev_step: eps {tuple(eps_nhwc.shape)} (want NHWC {(B, H, W, C)}), bad {tuple(bad.shape)} (want [{B}])")
+    check(lib.afldm_rev_step(ptr(far), ptr(near), ptr(eps_nhwc), ptr(out), ptr(bad), ptr(coef), ptr(step_idx), int(advance),
+                             B, C, H, W, _code(eps_nhwc), stream_ptr()), "rev_step")
+    return out
+
+
+def rev_step_flat(far, near, eps, bad, row, out=None):
+    """The same update with the row by value, row = (cx, ce, sign, boot): far, near same-shape contiguous int64 CUDA tensors
+    [B, ...] rotated in place, eps fp32 of that shape, bad int32 [B].  far may be `near` itself for a boot row (which does not
+    read far).  Returns `out`, the fp32 view of the new near."""
+    if out is None:
+        out = torch.empty(near.shape, dtype=torch.float32, device=near.device)
+    _rev_pair("rev_step_flat", far, near, out, bad)
+    _dev(eps, "eps")
+    if eps.dtype != torch.float32 or eps.shape != near.shape or near.dim() < 1 or bad.shape[0] != near.shape[0]:
+        raise ValueError(f"rev_step_flat: eps {eps.dtype} {tuple(eps.shape)} (want fp32 {tuple(near.shape)}), bad {tuple(bad.shape)} "
+                         f"(want [{near.shape[0] if near.dim() else '?'}])")
+    cx, ce, sign, boot = float(row[0]), float(row[1]), int(row[2]), int(bool(row[3]))
+    if sign not in (1, -1) or float(row[2]) != sign:
+        raise ValueError(f"rev_step_flat: sign = {row[2]} (want +1 or -1)")
+    n = near.numel()
+    check(lib.afldm_rev_step_flat(ptr(far), ptr(near), ptr(eps), ptr(out), ptr(bad), cx, ce, sign, boot, n,
+                                  max(n // near.shape[0], 1) if n else 1, stream_ptr()), "rev_step_flat")
+    return out
+
+
+def rev_encode(x, bad, out=None):
+    """x fp32 [B, ...] -> int64 rn(x 2^32) (ties to even; the product is exact).  bad int32 [B]: 1 is stored for a sample with a
+    non-finite value or one of magnitude >= 2^31 (its integer is 0); never cleared here."""
+    _dev(x, "x"); _dev(bad, "bad")
+    if x.dtype != torch.float32 or x.dim() < 1 or bad.dtype != torch.int32 or tuple(bad.shape) != (x.shape[0],):
+        raise ValueError(f"rev_encode: x {x.dtype} {tuple(x.shape)} (want fp32 [B, ...]), bad {bad.dtype} {tuple(bad.shape)} "
+                         "(want int32 [B])")
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.int64, device=x.device)
+    _dev(out, "out")
+    if out.dtype != torch.int64 or out.shape != x.shape:
+        raise ValueError(f"rev_encode: out {out.dtype} {tuple(out.shape)}, want int64 {tuple(x.shape)}")
+    n = x.numel()
+    check(lib.afldm_rev_encode(ptr(x), ptr(out), ptr(bad), n, max(n // x.shape[0], 1) if n else 1, stream_ptr()), "rev_encode")
+    return out
+
+
 # ----------------------------------------------------------------------------- ILVR reference-guided sampling
 def _ilvr_plane(name, x, Lh, Lw):
     """The checks ilvr_step and ilvr_step_flat share: fp32 [B, C, H, W] latents, Lh fp32 [H, H] and Lw fp32 [W, W] on the device.

@@ -96,3 +96,9 @@ class I2SBLDMPipeline(MyLDMPipeline):
     def img2img(self, *args, **kwargs):
         raise NotImplementedError("I2SBLDMPipeline: image-to-image sampling (SDEdit) is defined for the unconditional sampler "
                                   "(MyLDMPipeline.img2img); the bridge has its own start, the encoded low-resolution image")
+
+    def _no_reversible(self, *args, **kwargs):
+        raise NotImplementedError("I2SBLDMPipeline: the bit-reversible sampler is defined for the unconditional DDIM sampler "
+                                  "(MyLDMPipeline.sample_reversible / invert_reversible); a reversible bridge is not implemented")
+
+    sample_reversible = sample_reversible_latents = invert_reversible = _no_reversible

@@ -6,6 +6,7 @@ replayed HIP graph (afldm_amd.engine.DenoiseEngine); other output types decode t
 import inspect
 import json
 import os
+from dataclasses import replace
 
 import torch
 
@@ -438,6 +439,151 @@ class MyLDMPipeline(DiffusionPipeline):
         if composite and change_map is not None:
             decoded = torch.where(change_map == 0, image, decoded.float())
         return self._images(decoded, output_type, return_dict)
+
+    # ------------------------------------------------------------------------------------------------ bit-reversible sampling
+    @staticmethod
+    def _rev_is_code(what, code):
+        from ..reversible import ReversibleCode
+        if not isinstance(code, ReversibleCode):
+            raise TypeError(f"{what}: code must be a ReversibleCode, got {type(code).__name__}")
+
+    def _rev_code_check(self, what, code, k, num_inference_steps, exact):
+        """A ReversibleCode against the call that takes it: the level it sits at always; with `exact` also everything its bits
+        depend on."""
+        from .. import _lib
+        from ..engine import model_state_key
+        self._rev_is_code(what, code)
+        c, s = self.unet.config.in_channels, self.unet.config.sample_size
+        if code.hi.dim() != 4 or tuple(code.hi.shape[1:]) != (c, s, s) or code.lo.shape != code.hi.shape:
+            raise ValueError(f"{what}: a code of {tuple(code.hi.shape)} / {tuple(code.lo.shape)}, want [B, {c}, {s}, {s}] twice")
+        if code.k != k:
+            raise ValueError(f"{what}: the code sits at level {code.k}, and this call starts from level {k}")
+        if not exact:
+            return
+        diff = code.mismatches(batch=code.hi.shape[0], dtype=self.unet.dtype, model_key=model_state_key(self.unet),
+                               library=_lib.library_hash(), num_inference_steps=int(num_inference_steps))
+        if diff:
+            raise ValueError(f"{what}: the code was made with " + ", ".join(f"{n} = {a!r} (now {b!r})" for n, a, b in diff) +
+                             ": the steps would not be undone bit for bit.  exact=False runs it anyway, with no such guarantee")
+
+    def _rev_run(self, sched, start, use_graph):
+        """A "rev" schedule from `start` (latents or a ReversibleCode) to a ReversibleCode: ReversibleEngine on replayed graphs, or
+        the eager loop over ops.rev_step_flat, which carries the same int64 pair."""
+        from .. import _lib, ops
+        from ..engine import ReversibleEngine, model_state_key
+        from ..reversible import ReversibleCode, decode
+        cfg = sched.config
+        sampling, from_code = cfg["_rev_direction"] == "sample", cfg["_rev_from_code"]
+        B = (start.hi if from_code else start).shape[0]
+        if use_graph:
+            slot = f"_rev_{cfg['_rev_direction']}_{'code' if from_code else 'start'}_engines"
+            eng = cached_engine(self, slot, sched, B, True, self.unet, ReversibleEngine)
+            eng.scheduler = self.scheduler
+            return eng.run(start)
+        dev = self.unet.device
+        if dev.type != "cuda":
+            raise RuntimeError("the reversible sampler needs the UNet on an MI355X ('cuda') device; there is no CPU path")
+        bad = torch.zeros(B, dtype=torch.int32, device=dev)
+        if from_code:
+            far, near = ((start.hi, start.lo) if sampling else (start.lo, start.hi))
+            far, near = far.to(dev).clone(), near.to(dev).clone()
+        else:
+            near = ops.rev_encode((start.to(device=dev, dtype=torch.float32) * sched.init_noise_sigma).contiguous(), bad)
+            far = near.clone()
+        x = decode(near)
+        for t, row in self.progress_bar(list(zip(sched.timesteps, sched.rows))):
+            eps = self.unet(x.to(self.unet.dtype), t).sample
+            x = ops.rev_step_flat(far, near, eps.float().contiguous(), bad, row)
+        rows = bad.nonzero().flatten().tolist()
+        if rows:
+            raise FloatingPointError(f"the reversible sampler met non-finite values or int64 overflow in the latents of batch rows "
+                                     f"{rows}: the states of these rows are INVALID")
+        levels = len(sched.timesteps) + (1 if from_code else 0)
+        hi, lo = (far, near) if sampling else (near, far)
+        return ReversibleCode(hi, lo, 1 if sampling else levels, cfg["_rev_steps"], None, B, self.unet.dtype,
+                              model_state_key(self.unet), _lib.library_hash())
+
+    @torch.no_grad()
+    def sample_reversible_latents(self, batch_size=1, num_inference_steps=50, generator=None, latents=None, code=None,
+                                  use_graph=True, return_code=False, exact=True):
+        """Sample with the bit-reversible sampler: a two-step (leapfrog) form of deterministic DDIM, after BDIA (Zhang et al., ECCV
+        2024) at gamma = 1, with the latents carried as int64 fixed point on the grid 2^-32 (DDIMScheduler.reversible_schedule,
+        afldm_rev_step).  It costs one UNet evaluation per step like DDIM and is NOT the DDIM sampler: its samples differ, and no
+        claim about their quality is made.  What it gives is algebraic: invert_reversible(code=...) of the returned code walks the
+        same integers back and returns the start noise's integers exactly, and sampling from a code invert_reversible returned
+        gives back the inverted latents' integers exactly.
+
+        From noise - `latents`, or drawn as __call__ draws them - N evaluations; from `code` = the (X_N, X_N-1) invert_reversible
+        returned, N - 1 (its strength, if any, applies).  The guarantee holds when the code's batch size, model dtype, weights,
+        library build and step count are the call's: a code that differs raises ValueError, and exact=False runs it anyway
+        WITHOUT any bit guarantee.  use_graph: ReversibleEngine on replayed HIP graphs; otherwise the eager loop over
+        afldm_rev_step_flat, which carries the same int64 pair.  Only deterministic epsilon-prediction DDIM has this form.
+        Returns the fp32 latents, with return_code (latents, ReversibleCode at level 1)."""
+        self._refuse_dpm("sample_reversible_latents")
+        self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
+        c, s = self.unet.config.in_channels, self.unet.config.sample_size
+        if code is not None:
+            if latents is not None:
+                raise ValueError("sample_reversible_latents: give latents or a code, not both")
+            self._rev_is_code("sample_reversible_latents", code)
+            levels = len(self.scheduler.reversible_levels(num_inference_steps, code.strength)[0]) - 1
+            self._rev_code_check("sample_reversible_latents", code, levels, num_inference_steps, exact)
+            sched, start = self.scheduler.reversible_schedule(num_inference_steps, "sample", True, code.strength), code
+        else:
+            sched = self.scheduler.reversible_schedule(num_inference_steps, "sample", False)
+            if latents is None:
+                latents = sched.drawer(generator, (batch_size, c, s, s), self.unet.device, self.unet.dtype)()
+            if latents.dim() != 4 or tuple(latents.shape[1:]) != (c, s, s):
+                raise ValueError(f"sample_reversible_latents: latents {tuple(latents.shape)}, want [B, {c}, {s}, {s}]")
+            start = latents
+        out = self._rev_run(sched, start, use_graph)
+        if code is not None:
+            out = replace(out, strength=code.strength)
+        return (out.latents(), out) if return_code else out.latents()
+
+    @torch.no_grad()
+    def sample_reversible(self, batch_size=1, num_inference_steps=50, generator=None, latents=None, code=None, output_type="pil",
+                          return_dict=True, use_graph=True, return_code=False, exact=True):
+        """Sample images with the bit-reversible sampler: sample_reversible_latents, then decode.  output_type as __call__;
+        'latent' returns the latents in the UNet's dtype.  With return_code: (that, the ReversibleCode at level 1, whose
+        .latents() are the unrounded fp32 latents)."""
+        lat, out = self.sample_reversible_latents(batch_size, num_inference_steps, generator, latents, code, use_graph, True, exact)
+        got = self._deliver(lat.to(self.unet.dtype), output_type, return_dict)
+        return (got, out) if return_code else got
+
+    @torch.no_grad()
+    def invert_reversible(self, image_or_latents=None, code=None, num_inference_steps=50, strength=None, use_graph=True, exact=True):
+        """Invert with the bit-reversible sampler (sample_reversible_latents): returns the ReversibleCode (X_N, X_N-1) at the noise
+        end, from which sample_reversible(code=...) returns to where this started, integer for integer.
+
+        From `code` = the (X_1, X_0) a sampling run returned: N - 1 evaluations, and the result's `hi` is the integers of the noise
+        that run started from.  From an image [B, 3, H, W] in [-1, 1] (encoded with the posterior mode times scaling_factor) or
+        latents [B, C, S, S]: N evaluations, the first of them a plain DDIM inversion step from level 0 to level 1 with eps
+        evaluated at the image (the reference's inversion starts the same way).  The true eps at level 0 is unknowable, so what
+        comes back is a code - a noise-like pair that samples back to the image exactly - not "the" noise that made the image.
+        strength: invert up the first int(N strength) levels only, as img2img counts them.  exact as sample_reversible_latents."""
+        self._refuse_dpm("invert_reversible")
+        self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
+        c, s = self.unet.config.in_channels, self.unet.config.sample_size
+        if (code is None) == (image_or_latents is None):
+            raise ValueError("invert_reversible: give an image (or latents) or a code, and not both")
+        if code is not None:
+            self._rev_code_check("invert_reversible", code, 1, num_inference_steps, exact)
+            sched, start = self.scheduler.reversible_schedule(num_inference_steps, "invert", True, strength), code
+        else:
+            x = image_or_latents
+            if x.dim() != 4:
+                raise ValueError(f"invert_reversible: {tuple(x.shape)}, want an image [B, 3, H, W] or latents [B, {c}, {s}, {s}]")
+            if tuple(x.shape[1:]) != (c, s, s):
+                if self.vae is None:
+                    raise NotImplementedError("this pipeline was built without a VAE: give invert_reversible latents "
+                                              f"[B, {c}, {s}, {s}]")
+                r = self._vae_ratio()
+                if tuple(x.shape[1:]) != (3, s * r, s * r):
+                    raise ValueError(f"invert_reversible: image {tuple(x.shape)}, want [B, 3, {s * r}, {s * r}]")
+                x = self._encode_mode(x)
+            sched, start = self.scheduler.reversible_schedule(num_inference_steps, "invert", False, strength), x
+        return replace(self._rev_run(sched, start, use_graph), strength=strength)
 
     # ------------------------------------------------------------------------------------------------ ILVR reference guidance
     @torch.no_grad()

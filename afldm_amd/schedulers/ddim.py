@@ -354,6 +354,67 @@ class DDIMScheduler:
         ab = float(self.alphas_cumprod[self._sdedit_timesteps(num_inference_steps, strength)[0]])
         return math.sqrt(ab), math.sqrt(1 - ab)
 
+    def reversible_levels(self, num_inference_steps, strength=None):
+        """(tau, ab) of the bit-reversible sampler: tau[1] < ... < tau[N] this scheduler's timesteps in ascending order (with
+        `strength`, those of _sdedit_timesteps), tau[0] = None, and ab[0] = final_alpha_cumprod, ab[k] = alphas_cumprod[tau[k]],
+        as Python floats."""
+        if strength is None:
+            self.set_timesteps(int(num_inference_steps))
+            ts = self._timesteps_host
+        else:
+            ts = self._sdedit_timesteps(num_inference_steps, strength)
+        tau = [None] + sorted(int(t) for t in ts)
+        return tau, [float(self.final_alpha_cumprod)] + [float(self.alphas_cumprod[t]) for t in tau[1:]]
+
+    @staticmethod
+    def ddim_map(ab, k, j):
+        """(A, B) of the deterministic DDIM map from level k to level j given eps, x_j = A x_k + B eps, in float64:
+        A = sqrt(ab_j / ab_k), B = sqrt(1 - ab_j) - A sqrt(1 - ab_k)."""
+        A = math.sqrt(ab[j] / ab[k])
+        return A, math.sqrt(1 - ab[j]) - A * math.sqrt(1 - ab[k])
+
+    def reversible_schedule(self, num_inference_steps, direction, from_code, strength=None, eta=None):
+        """The bit-reversible sampler - a two-step (leapfrog) form of DDIM, after BDIA (Zhang et al., ECCV 2024) at gamma = 1 - as
+        the Schedule ReversibleEngine replays with afldm_rev_step on a pair (far, near) of int64 latents.  Levels as
+        reversible_levels; (A, B)(k -> j) as ddim_map.  The interior row of level k is
+          cx_k = A(k -> k-1) - A(k -> k+1),  ce_k = B(k -> k-1) - B(k -> k+1)       X_{k-1} = X_{k+1} + Q_k(X_k)
+        formed in float64 and rounded once to fp32 by Schedule.table.  Rows (timestep; cx, ce, sign, boot):
+          direction "sample", from noise X_N:         (tau_N; A(N -> N-1) - 1, B(N -> N-1), +1, 1), then k = N-1 .. 1: (tau_k; cx_k, ce_k, +1, 0)
+          direction "sample", from_code (X_N, X_N-1): the interior rows only, N - 1 evaluations
+          direction "invert", from an image X_0:      (tau_1; A(0 -> 1) - 1, B(0 -> 1), +1, 1), then k = 1 .. N-1: (tau_k; cx_k, ce_k, -1, 0)
+          direction "invert", from_code (X_1, X_0):   the interior rows only
+        The evaluation at level 0 uses tau_1, as the reference's inversion does.  Sampling ends with near = X_0, far = X_1;
+        inverting with near = X_N, far = X_N-1.  Only the deterministic epsilon-prediction sampler without clipping has this
+        form: anything else raises NotImplementedError."""
+        if self.config.clip_sample or self.config.prediction_type != "epsilon":
+            raise NotImplementedError("afldm_amd.DDIMScheduler.reversible_schedule implements the reference's setting: "
+                                      "epsilon prediction, clip_sample=False")
+        if eta is not None and float(eta) != 0.0:
+            raise NotImplementedError("afldm_amd.DDIMScheduler.reversible_schedule: eta != 0 adds noise, which the inverse cannot "
+                                      "take away again")
+        if direction not in ("sample", "invert"):
+            raise ValueError(f"reversible_schedule: direction {direction!r} (want 'sample' or 'invert')")
+        tau, ab = self.reversible_levels(num_inference_steps, strength)
+        N = len(tau) - 1
+        if from_code and N < 2:
+            raise ValueError(f"reversible_schedule: a code holds two levels, and this schedule has {N}")
+
+        def interior(k, sign):
+            (Ad, Bd), (Au, Bu) = self.ddim_map(ab, k, k - 1), self.ddim_map(ab, k, k + 1)
+            return tau[k], (Ad - Au, Bd - Bu, float(sign), 0.0)
+
+        if direction == "sample":
+            A, B = self.ddim_map(ab, N, N - 1)
+            rows = [(tau[N], (A - 1.0, B, 1.0, 1.0))] + [interior(k, +1) for k in range(N - 1, 0, -1)]
+        else:
+            A, B = self.ddim_map(ab, 0, 1)
+            rows = [(tau[1], (A - 1.0, B, 1.0, 1.0))] + [interior(k, -1) for k in range(1, N)]
+        if from_code:
+            rows = rows[1:]
+        return Schedule.of(self, "rev", [t for t, _ in rows], [r for _, r in rows], _rev_steps=int(num_inference_steps),
+                           _rev_direction=direction, _rev_from_code=bool(from_code),
+                           _rev_strength=None if strength is None else N)
+
     def ilvr_schedule(self, num_inference_steps, eta=1.0, range_t=0):
         """ILVR reference-guided sampling (Choi et al., ICCV 2021, Algorithm 1) over this scheduler's `num_inference_steps`
         timesteps g[0] > ... > g[N-1], as the Schedule DenoiseEngine replays with afldm_ilvr_step.  For evaluation i, with

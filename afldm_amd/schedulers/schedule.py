@@ -27,9 +27,12 @@ UNet evaluation, fixed when it is made.  `kind` names the update kernel that rea
     "sdedit" (p, q, lo, hi, a, b, c, k0, k1, thr, 0, 0):  image-to-image sampling (SDEdit) with a per-element change map
             (Differential Diffusion):  x0 = clamp(p x + q eps, lo, hi);  xp = a x0 + b eps + c z_u;  held = k0 orig + k1 z, z the
             run's ONE fixed noise;  x_out = (cmap <= thr) ? held : xp - a select, not a blend         afldm_sdedit_step
+    "rev"   (cx, ce, sign, boot):  the bit-reversible sampler (two-step DDIM after BDIA, gamma = 1) on a pair (far, near) of int64
+            latents on the grid 2^-32:  f = boot ? near : far;  x = rn_f32(near) 2^-32;  q = rn_i64(fl32(fl32(cx x) + fl32(ce eps)) 2^32);
+            far <- near;  near <- f + sign q - integer arithmetic, so the same row with the other sign undoes it    afldm_rev_step
 
 The rows come from the scheduler that owns the update (DDIMScheduler.schedule / stochastic_schedule,
-DDIMScheduler.repaint_schedule / ilvr_schedule / panorama_schedule / pag_schedule / sag_schedule / outpaint_schedule / hires_schedule / sdedit_schedule, DPMSolverMultistepScheduler.schedule, I2SBScheduler.ode_schedule / bridge_schedule,
+DDIMScheduler.repaint_schedule / ilvr_schedule / panorama_schedule / pag_schedule / sag_schedule / outpaint_schedule / hires_schedule / sdedit_schedule / reversible_schedule, DPMSolverMultistepScheduler.schedule, I2SBScheduler.ode_schedule / bridge_schedule,
 MyLDMPipeline.inversion_schedule) as Python floats and are rounded once to fp32 by `table`.  An "sde" schedule also states which
 steps draw noise and how: exactly the randn_tensor calls, in the same order, that the scheduler's eager `step()` makes, so that
 the engine can draw them from the caller's generator before the captured graphs need them.  A "repaint" schedule has up to
@@ -48,7 +51,7 @@ from ..utils import randn_tensor
 # kind -> (row width, noise slots per step, may a step draw): the one place that states them.  Several slots: `draws` is per slot
 KINDS = {"ddim": (4, 1, False), "dpm": (8, 1, False), "sde": (8, 1, True), "repaint": (12, 3, True), "ilvr": (12, 2, True),
          "pano": (8, 1, True), "pag": (12, 1, True), "sag": (12, 1, True), "outpaint": (12, 3, True),
-         "hires": (12, 1, True), "sdedit": (12, 1, True)}
+         "hires": (12, 1, True), "sdedit": (12, 1, True), "rev": (4, 1, False)}
 ROW_WIDTH, NOISE_SLOTS = {k: v[0] for k, v in KINDS.items()}, {k: v[1] for k, v in KINDS.items() if v[2]}      # derived views
 _MADE = {}          # key -> Schedule: the rows are ~0.1 ms of scalar tensor arithmetic each, and a sampler asks per call
 

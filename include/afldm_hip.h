@@ -553,6 +553,30 @@ int afldm_sdedit_step(const float* x, const void* eps, const float* orig, const 
 int afldm_sdedit_step_flat(const float* x, const float* eps, const float* orig, const float* cmap, const float* z,
                            const float* z_u, float* x_out, float p, float q, float lo, float hi, float a, float b, float c,
                            float k0, float k1, float thr, size_t n, afldm_stream_t stream);
+/* ---- Bit-reversible update: two-step (leapfrog) DDIM after BDIA (Zhang et al., ECCV 2024, gamma = 1) on int64 latents ----
+ * Every latent element is an int64 X on the grid 2^-32 (Q31.32).  Step s = *step_idx applies the row
+ * coef[4 s .. 4 s + 4) = (cx, ce, sign, boot) - sign +1 or -1, boot 0 or 1, as floats - to the pair (far, near):
+ *   f = boot ? near : far;  n = near;  e = (float)eps
+ *   x = rn_f32(n) * 2^-32                               one int64 -> fp32 rounding to nearest even, then an exact scale
+ *   d = fl32(fl32(cx * x) + fl32(ce * e))               two products and one sum, no fma
+ *   q = rn_i64(d * 2^32)                                the product is exact; ties to even
+ *   new = f + sign * q;   far <- n;   near <- new;   lat_out <- rn_f32(new) * 2^-32
+ * q depends on near and eps alone, so the same row with the opposite sign, applied to the rotated pair, restores both tensors
+ * bit for bit.  Trouble - a non-finite d, |d * 2^32| >= 2^63, signed overflow of the add - makes q = 0 for that element and
+ * stores 1 into bad[b] (never a 0: the caller zeroes bad before a run and reads it once after).
+ * far, near: int64 NCHW [B,C,H,W], 8-byte aligned (AFLDM_EALIGN), two different buffers (AFLDM_ESHAPE); lat_out: fp32 NCHW;
+ * bad: int32 [B]; eps: NHWC dtype; step_idx / advance as the DDIM update above.  16-byte accesses where C*H*W is even and
+ * far / near are 16-byte, lat_out 8-byte aligned; element by element otherwise. */
+int afldm_rev_step(long long* far, long long* near, const void* eps, float* lat_out, int* bad, const float* coef, int* step_idx,
+                   int advance, int B, int C, int H, int W, int dtype, afldm_stream_t stream);
+/* Same update on flat same-layout tensors of n elements (eps fp32), the row by value (sign +1 or -1: AFLDM_ESHAPE otherwise),
+ * for an eager loop.  bad has one word per rows_per_sample consecutive elements (> 0).  far == near is accepted with boot != 0
+ * only (a boot step does not read far; the buffer then ends up holding new). */
+int afldm_rev_step_flat(long long* far, long long* near, const float* eps, float* lat_out, int* bad, float cx, float ce, int sign,
+                        int boot, size_t n, size_t rows_per_sample, afldm_stream_t stream);
+/* The entry conversion X = rn_i64(x * 2^32) of n fp32 values (the product is exact; ties to even).  A non-finite x or
+ * |x| >= 2^31 gives X = 0 and stores 1 into bad[i / per_sample] (per_sample > 0).  X 8-byte aligned. */
+int afldm_rev_encode(const float* x, long long* X, int* bad, size_t n, size_t per_sample, afldm_stream_t stream);
 /* ---- ILVR reference-guided update (Choi et al., ICCV 2021, Algorithm 1) with a linear low-pass phi -----------------
  * Step s = *step_idx applies the row coef[12 s .. 12 s + 12) = (p, q, lo, hi, a, b, c, k0, k1, w, 0, 0) and the two noise
  * slots z_k, z_u = noise[s * noise_step_stride + slot * noise_slot_stride + i], slot = 0, 1:
