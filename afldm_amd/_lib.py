@@ -161,6 +161,8 @@ def _load():
         "afldm_flowest_smooth": ([vp, vp, ip, ip, ip, vp], c_int),
         "afldm_select_timestep": ([vp, vp, vp, ip, vp], c_int),
         "afldm_select_step_row": ([vp, vp, vp, ip, vp, vp, c_size_t, vp], c_int),
+        "afldm_cond_embed": ([vp, ip, vp, vp, vp, ip, ip, ip, vp], c_int),
+        "afldm_cond_embed_flat": ([vp, ip, vp, vp, ip, ip, ip, vp], c_int),
         "afldm_slot_select": ([vp, vp, vp, vp, vp, vp, vp, vp, ip, ip, ip, c_size_t, vp], c_int),
         "afldm_slot_step": ([vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, vp], c_int),
         "afldm_slot_exchange": ([vp, vp, vp, vp, vp, vp, ip, c_size_t, ip, ip, vp], c_int),

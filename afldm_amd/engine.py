@@ -64,6 +64,11 @@ of batch B per step: the first with SAGAttnProcessor at one site, which also wri
 afldm_sag_degrade turns x, e and the mass into the second evaluation's input; both outputs land in `eps2` [2 B] and the step ends
 in afldm_pag_step, unchanged.
 
+CFGEngine (kind "cfg", DDIMScheduler.cfg_schedule: classifier-free guidance over class labels) is the one engine that takes a
+class-conditional UNet: the class embedding enters before the SiLU of the time embedding, so instead of copying a tabulated row a
+step computes afldm_cond_embed and the projection GEMM per batch row inside the graph, from class rows that are per-run data; the
+UNet batch is 2 B (conditional rows, then unconditional rows) and the step ends in afldm_pag_step, unchanged.
+
 SlotEngine has no schedule of its own: every batch row ("slot") walks its own stretch of one device row table with a cursor of
 its own, so "ddim" requests of different step counts share the graphs and a finished slot is harvested and refilled between replays
 (afldm_slot_select in place of afldm_select_step_row, afldm_slot_step in place of afldm_ddim_step, afldm_slot_exchange at the
@@ -142,12 +147,23 @@ def cached_engine(owner, slot, schedule, batch, use_graph, unet, cls=None, build
     return owner.__dict__[slot][key]
 
 
+def refuse_class_conditional(unet, who):
+    """Every engine but CFGEngine hands the UNet a projection of the timestep alone: on a class-conditional UNet that would
+    ignore the labels silently, so it is an error."""
+    if getattr(unet, "class_embedding", None) is not None:
+        raise ValueError(f"{who}: the UNet is class-conditional (class_embedding); only CFGEngine (MyLDMPipeline.cfg_latents) "
+                         "carries class labels")
+
+
 class DenoiseEngine:
     ONE_BRANCH = False          # an update that needs the whole batch in one launch (PanoramaEngine) takes no parallel branches
+    CLASS_CONDITIONAL = False   # CFGEngine: the one engine that takes a class-conditional UNet (and only such a UNet)
 
     def __init__(self, unet, scheduler, batch_size, num_inference_steps=50, use_graph=True, steps_per_graph=5, branches=1):
         if unet.device.type != "cuda":
             raise RuntimeError("DenoiseEngine needs the UNet on an MI355X ('cuda') device; there is no CPU path")
+        if not self.CLASS_CONDITIONAL:
+            refuse_class_conditional(unet, type(self).__name__)
         self.unet, self.scheduler = unet, scheduler
         self.schedule = scheduler if isinstance(scheduler, Schedule) else scheduler.schedule(num_inference_steps)
         if len(self.schedule.timesteps) != num_inference_steps:
@@ -176,13 +192,9 @@ class DenoiseEngine:
         self.step_idx = torch.full((1,), -1, dtype=torch.int32, device=dev)
         self.t_cur = torch.zeros(1, dtype=torch.float32, device=dev)
         self.lat = torch.zeros(self.B, c, s, s, dtype=torch.float32, device=dev)
-        self.x_nhwc = torch.empty(self.B, s, s, c, dtype=unet.dtype, device=dev)
+        self.x_nhwc = torch.empty(self._unet_rows(), s, s, c, dtype=unet.dtype, device=dev)
         self.graph = self.graph_multi = None
-        # everything of the UNet that depends on the timestep only (time_proj -> time_embedding -> SiLU -> the 27
-        # time_emb_proj layers) is tabulated once for the schedule: [steps, sum Cout]; a step copies its row
-        self.temb_table = torch.cat([unet.temb_projection(t) for t in self.timesteps], 0).contiguous()
-        self.temb_row = torch.empty_like(self.temb_table[:1])
-        self.temb_slices = unet.temb_slices(self.temb_row)
+        self._tabulate()
         self._model_key = model_state_key(unet)
         self._side = [torch.cuda.Stream() for _ in range(self.branches - 1)]
         # counters of in-kernel reductions / cluster hand-overs: private to this engine (one per branch), so that its
@@ -191,6 +203,18 @@ class DenoiseEngine:
         self.hist = self.noise = self.known = self.mask = self.filter = self._static = None
         self._update, state = self.UPDATES[self.schedule.kind]
         self._state = state(self)
+
+    def _unet_rows(self):
+        """Rows of the UNet's batch per step: B, unless an engine evaluates several rows per sample (CFGEngine)."""
+        return self.B
+
+    def _tabulate(self):
+        """Everything of the UNet that depends on the timestep only (time_proj -> time_embedding -> SiLU -> the 27 time_emb_proj
+        layers), tabulated once for the schedule: [steps, sum Cout]; a step copies its row."""
+        unet = self.unet
+        self.temb_table = torch.cat([unet.temb_projection(t) for t in self.timesteps], 0).contiguous()
+        self.temb_row = torch.empty_like(self.temb_table[:1])
+        self.temb_slices = unet.temb_slices(self.temb_row)
 
     def _slice(self, b, *tensors, dim=0):
         """Branch b's batch slice (the batch at `dim`) of each of `tensors`; with one branch, the tensors themselves."""
@@ -804,6 +828,99 @@ class PAGEngine(DenoiseEngine):
             super().step(k)
 
 
+class CFGEngine(DenoiseEngine):
+    """Class-conditional sampling with classifier-free guidance on the replayed graphs - the one engine that takes a
+    class-conditional UNet.  diffusers adds the class embedding to the time embedding BEFORE the SiLU in front of the time_emb_proj
+    layers, so the projection is neither a per-step row nor a sum of a step part and a class part: the engine tabulates
+    `emb_table` [n, D], time_embedding's output per step before the SiLU, holds the run's class rows as DATA in `class_rows`
+    [R, D], and a step is
+
+        afldm_select_timestep (the one place the counter moves); afldm_cond_embed -> `act` [R, D]; the projection GEMM over all
+        time_emb_proj layers -> `temb_rows` [R, sum Cout], read by the resnets with a row stride; to_nhwc; forward_nhwc; the update
+
+    all inside the captured graphs, which hold the class rows' address only: other labels replay the same graphs.
+    guided (kind "cfg", DDIMScheduler.cfg_schedule): R = 2 B - rows 0 .. B-1 conditional, rows B .. 2B-1 unconditional, both
+    halves of `x_nhwc` the same latents - and the update is afldm_pag_step with s = guidance_scale - 1, so sigma(e) of
+    guidance_rescale is the conditional prediction's.  Not guided (a plain "ddim" or "sde" schedule: guidance_scale = 1): R = B
+    and the scheduler's own update.  run(latents, draw=..., known=class_rows): the rows [R, D] (any float dtype, as
+    UNet2DModel.class_embed returns them, the unconditional half behind the conditional one) are copied in before the first
+    replay; known=None reuses the rows of the previous run (set_class_rows)."""
+    ONE_BRANCH = True           # the update reads both halves of eps; one projection GEMM for the whole batch
+    CLASS_CONDITIONAL = True
+
+    def __init__(self, unet, scheduler, batch_size, num_inference_steps=50, use_graph=True, steps_per_graph=5, branches=1, *, guided):
+        if getattr(unet, "class_embedding", None) is None:
+            raise ValueError("CFGEngine needs a class-conditional UNet (num_class_embeds, or class_embed_type='identity')")
+        kind = (scheduler if isinstance(scheduler, Schedule) else scheduler.schedule(num_inference_steps)).kind
+        if guided is None or bool(guided) != (kind == "cfg"):
+            raise ValueError(f"CFGEngine: guided = {guided} with a schedule of kind {kind!r}: a 'cfg' schedule is guided (2 B UNet rows), "
+                             "a plain one is not")
+        self.guided, self.R = bool(guided), (2 if guided else 1) * int(batch_size)
+        self._rows_given = None
+        super().__init__(unet, scheduler, batch_size, num_inference_steps, use_graph, steps_per_graph, 1)
+
+    UPDATES = {"cfg": (ops.pag_step, DenoiseEngine._guided_state), "ddim": DenoiseEngine.UPDATES["ddim"],
+               "sde": DenoiseEngine.UPDATES["sde"]}
+
+    def _tabulate(self):
+        """The time embeddings per step BEFORE the SiLU, and the per-row buffers of a step."""
+        unet, dev = self.unet, self.unet.device
+        self.emb_table = torch.cat([unet.time_embedding_row(t) for t in self.timesteps], 0).contiguous()
+        D, width = self.emb_table.shape[1], unet._temb_weights(unet.dtype)[3]
+        self.class_rows = torch.zeros(self.R, D, dtype=unet.dtype, device=dev)
+        self.act = torch.zeros(self.R, D, dtype=unet.dtype, device=dev)
+        self.temb_rows = torch.zeros(self.R, width, dtype=unet.dtype, device=dev)
+        self.temb_slices = unet.temb_slices(self.temb_rows, per_sample=True)
+
+    def _retabulate(self):
+        self.emb_table.copy_(torch.cat([self.unet.time_embedding_row(t) for t in self.timesteps], 0))
+
+    def _unet_rows(self):
+        return self.R
+
+    def _allocate(self):
+        super()._allocate()
+        self._static = ("class_rows", self.class_rows, False)
+
+    def _step(self):
+        ops.select_timestep(self.t_table, self.step_idx, self.t_cur, pre_advance=True)
+        ops.cond_embed(self.emb_table, self.step_idx, self.class_rows, out=self.act)
+        w, b, _, _ = self.unet._temb_weights(self.unet.dtype)
+        with ops.sync_scope(self._sync[0]):
+            ops.conv2d(self.act, w, b, out=self.temb_rows)
+        self._substep(self.lat, self.x_nhwc)
+
+    def _eps(self, lat, x_nhwc):
+        ops.to_nhwc(lat, self.unet.dtype, out=x_nhwc[:self.B])
+        if self.guided:
+            ops.to_nhwc(lat, self.unet.dtype, out=x_nhwc[self.B:])
+        return self.unet.forward_nhwc(x_nhwc, self.t_cur, temb_slices=self.temb_slices)
+
+    def set_class_rows(self, rows):
+        """The class rows [R, D] of the next runs: a copy is kept (the caller's tensor may change afterwards) and written into the
+        static buffer by run, after its reset."""
+        if not torch.is_tensor(rows) or tuple(rows.shape) != tuple(self.class_rows.shape) or not rows.is_floating_point():
+            got = f"{rows.dtype} {tuple(rows.shape)}" if torch.is_tensor(rows) else type(rows).__name__
+            raise ValueError(f"CFGEngine: class rows {got}, want a float tensor {tuple(self.class_rows.shape)} "
+                             + ("(conditional rows, then unconditional rows)" if self.guided else "(one row per sample)"))
+        self._rows_given = rows.detach().clone()
+
+    def _check_known(self, known):
+        if known is not None:
+            self.set_class_rows(known)
+        if self._rows_given is None:
+            raise ValueError("CFGEngine: run(latents, draw=..., known=class_rows) needs the class rows (UNet2DModel.class_embed)")
+        return self._rows_given, None
+
+    def _set_known(self, rows, extra):
+        self.class_rows.copy_(rows)
+
+    @torch.no_grad()
+    def run(self, latents, draw=None, known=None):
+        """As DenoiseEngine.run; known = the class rows [R, D], or None to keep the previous run's."""
+        return super().run(latents, draw, known if known is not None else self._rows_given)
+
+
 @contextlib.contextmanager
 def sag_processor(unet, site, mass=None):
     """SAGAttnProcessor on the attention module `site` names (a module path), writing into `mass` (or into a tensor of its own
@@ -918,6 +1035,7 @@ class SlotEngine(DenoiseEngine):
                  out_capacity=None):
         if unet.device.type != "cuda":
             raise RuntimeError("SlotEngine needs the UNet on an MI355X ('cuda') device; there is no CPU path")
+        refuse_class_conditional(unet, "SlotEngine")
         odd = sorted({type(m.processor).__name__ for m in unet.modules() if hasattr(m, "processor")} - {"AttnProcessor2_0"})
         if odd:
             raise ValueError(f"SlotEngine: the UNet has attention processors {odd}; slots need the plain one")

@@ -50,16 +50,25 @@ class UNet2DModel(nn.Module):
         cfg.update({k: v for k, v in extra.items()})       # unknown keys are kept on .config, like diffusers
         object.__setattr__(self, "config", FrozenConfig(cfg))
         if (time_embedding_type != "positional" or act_fn != "silu" or downsample_type != "conv"
-                or upsample_type != "conv" or resnet_time_scale_shift != "default" or class_embed_type is not None
+                or upsample_type != "conv" or resnet_time_scale_shift != "default" or class_embed_type not in (None, "identity")
                 or mid_block_scale_factor != 1 or center_input_sample):
             raise NotImplementedError("afldm_amd.UNet2DModel covers the configuration family of the AF-LDM "
-                                      "checkpoints (positional time embedding, conv resampling, SiLU)")
+                                      "checkpoints (positional time embedding, conv resampling, SiLU; class embeddings: "
+                                      "an nn.Embedding table or 'identity', not 'timestep')")
         assert len(down_block_types) == len(up_block_types) == len(block_out_channels)
         boc = list(block_out_channels)
         temb_dim = time_embedding_dim or boc[0] * 4
         self.conv_in = nn.Conv2d(in_channels, boc[0], kernel_size=3, padding=(1, 1))
         self.time_proj = B.Timesteps(boc[0], flip_sin_to_cos, freq_shift)
         self.time_embedding = B.TimestepEmbedding(boc[0], temb_dim)
+        # class conditioning as diffusers builds it: a table of num_class_embeds rows (state-dict key class_embedding.weight), or
+        # the identity on rows the caller provides; a config without either gains no module and no key
+        if class_embed_type is None and num_class_embeds is not None:
+            self.class_embedding = nn.Embedding(int(num_class_embeds), temb_dim)
+        elif class_embed_type == "identity":
+            self.class_embedding = nn.Identity()
+        else:
+            self.class_embedding = None
 
         self.down_blocks = nn.ModuleList()
         out_c = boc[0]
@@ -160,9 +169,34 @@ class UNet2DModel(nn.Module):
             cache[key] = (ops.pack_weight(w, dtype), b, offs, o)
         return cache[key]
 
-    def time_embed(self, timestep, batch):
+    def class_embed(self, class_labels):
+        """-> the class rows [B, temb_dim] in the model dtype, on the model's device: class_embedding.weight[class_labels] for
+        integer labels [B] (a table of num_class_embeds rows), the rows themselves for class_embed_type 'identity' (a float
+        [B, temb_dim] tensor).  Integer labels outside [0, num_class_embeds) raise ValueError on the host, before any launch."""
+        if self.class_embedding is None:
+            raise ValueError("class_embedding needs to be initialized in order to use class conditioning")
+        if class_labels is None:
+            raise ValueError("class_labels should be provided when doing class conditioning")
+        dev, dtype, D = self.device, self.dtype, self.time_embedding.linear_2.out_features
+        if isinstance(self.class_embedding, nn.Identity):
+            rows = torch.as_tensor(class_labels)
+            if not rows.is_floating_point() or rows.dim() != 2 or rows.shape[1] != D:
+                raise ValueError(f"class_labels of an 'identity' class embedding are float rows [B, {D}], got {rows.dtype} "
+                                 f"{tuple(rows.shape)}")
+            return rows.to(device=dev, dtype=dtype).contiguous()
+        labels = torch.as_tensor(class_labels)
+        if labels.is_floating_point() or labels.dtype == torch.bool or labels.dim() > 1:
+            raise ValueError(f"class_labels must be integers [B], got {labels.dtype} {tuple(labels.shape)}")
+        labels = labels.reshape(-1).to(device="cpu", dtype=torch.int64)          # (the host check: B integers)
+        K = self.class_embedding.num_embeddings
+        if labels.numel() and (int(labels.min()) < 0 or int(labels.max()) >= K):
+            raise ValueError(f"class_labels {labels.tolist()} outside [0, {K}) (num_class_embeds = {K})")
+        return self.class_embedding.weight.detach()[labels.to(dev)].to(dtype).contiguous()
+
+    def time_embed(self, timestep, batch, class_rows=None):
         """-> (per-resnet list of (temb slice view, stride)), emb.  `timestep`: python number,
-        0-dim / 1-elem tensor (shared by the batch -> 1 row, broadcast) or a [B] tensor."""
+        0-dim / 1-elem tensor (shared by the batch -> 1 row, broadcast) or a [B] tensor.  class_rows [B, temb_dim]
+        (class_embed): added to emb before the SiLU, as diffusers does - one projection row per sample."""
         dev, dtype = self.device, self.dtype
         if torch.is_tensor(timestep):
             t = timestep.to(device=dev, dtype=torch.float32).reshape(-1)
@@ -172,6 +206,11 @@ class UNet2DModel(nn.Module):
         t_emb = self.time_proj(t, dtype)
         emb = self.time_embedding(t_emb)                                   # [rows, temb_dim]
         w, b, offs, total = self._temb_weights(dtype)
+        if class_rows is not None:
+            if tuple(class_rows.shape) != (batch, emb.shape[1]) or class_rows.dtype != dtype:
+                raise ValueError(f"class rows {class_rows.dtype} {tuple(class_rows.shape)}, want {dtype} [{batch}, {emb.shape[1]}]")
+            proj = ops.conv2d(ops.cond_embed_flat(emb, class_rows), w, b)  # [B, sum Cout]
+            return self.temb_slices(proj, True), emb
         proj = ops.conv2d(ops.silu(emb), w, b)                            # [rows, sum Cout]
         return self.temb_slices(proj, t.numel() > 1), emb
 
@@ -180,6 +219,12 @@ class UNet2DModel(nn.Module):
         _, _, offs, total = self._temb_weights(self.dtype)
         stride = total if per_sample else 0
         return [(proj.view(-1)[o:] if stride == 0 else proj[:, o:], stride) for o in offs]
+
+    def time_embedding_row(self, timestep):
+        """[1, temb_dim] output of time_embedding for one shared timestep, BEFORE the SiLU (what CFGEngine tabulates per step: the
+        class rows are added to it)."""
+        t = torch.full((1,), float(timestep), dtype=torch.float32, device=self.device)
+        return self.time_embedding(self.time_proj(t, self.dtype))
 
     def temb_projection(self, timestep):
         """[1, sum Cout] time_emb_proj outputs of one shared timestep (what DenoiseEngine tabulates per step)."""
@@ -191,10 +236,15 @@ class UNet2DModel(nn.Module):
 
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
-    def forward_nhwc(self, x, timestep, temb_slices=None):
+    def forward_nhwc(self, x, timestep, temb_slices=None, class_rows=None):
         """x: NHWC [B, H, W, in_channels] in the model dtype -> NHWC [B, H, W, out_channels].
-        temb_slices: the per-resnet time_emb_proj slices when the caller already has them (DenoiseEngine's table)."""
-        slices = temb_slices if temb_slices is not None else self.time_embed(timestep, x.shape[0])[0]
+        temb_slices: the per-resnet time_emb_proj slices when the caller already has them (DenoiseEngine's table; CFGEngine's
+        per-row projection, which has the class rows in it).  class_rows [B, temb_dim] (class_embed) otherwise, on a
+        class-conditional model."""
+        if temb_slices is None and (class_rows is None) != (self.class_embedding is None):
+            raise ValueError("class_labels should be provided when doing class conditioning" if class_rows is None else
+                             "class_embedding needs to be initialized in order to use class conditioning")
+        slices = temb_slices if temb_slices is not None else self.time_embed(timestep, x.shape[0], class_rows)[0]
         it = iter(slices)
 
         def take(n):
@@ -236,13 +286,19 @@ class UNet2DModel(nn.Module):
 
     @torch.no_grad()
     def forward(self, sample, timestep, class_labels=None, return_dict=True):
+        # diffusers UNet2DModel.forward: emb = time_embedding(t) + class_embedding(class_labels), then the resnets
+        # (the labels are checked first, on the host)
+        if self.class_embedding is None and class_labels is not None:
+            raise ValueError("class_embedding needs to be initialized in order to use class conditioning")
+        class_rows = None if self.class_embedding is None else self.class_embed(class_labels)
+        if class_rows is not None and class_rows.shape[0] != sample.shape[0]:
+            raise ValueError(f"{class_rows.shape[0]} class labels for a batch of {sample.shape[0]}")
         if not sample.is_cuda:
             raise RuntimeError("afldm_amd.UNet2DModel runs on MI355X only (hand-written HIP kernels); "
                                "move the model and inputs to 'cuda'.  The CPU restatement lives in oracle/ "
                                "and is test infrastructure, not a fallback.")
-        assert class_labels is None
         x = ops.to_nhwc(sample.to(torch.float32).contiguous(), self.dtype)
-        y = self.forward_nhwc(x, timestep)
+        y = self.forward_nhwc(x, timestep, class_rows=class_rows)
         out = ops.to_nchw(y).to(sample.dtype if sample.dtype in (torch.float32, torch.bfloat16) else torch.float32)
         if not return_dict:
             return (out,)

@@ -2144,6 +2144,43 @@ def select_step_row(tvals, step_idx, t_out, table, row_out, pre_advance=False):
     return t_out
 
 
+# ----------------------------------------------------------------------------- class conditioning (classifier-free guidance)
+def _cond_rows(name, class_rows, out):
+    _dev(class_rows, "class_rows")
+    if class_rows.dim() != 2 or class_rows.dtype not in DTYPE_CODE:
+        raise ValueError(f"{name}: class_rows must be [rows, D] in fp32 or bf16, got {class_rows.dtype} {tuple(class_rows.shape)}")
+    if out is None:
+        out = torch.empty_like(class_rows)
+    _dev(out, "out")
+    assert out.shape == class_rows.shape and out.dtype == class_rows.dtype
+    return out
+
+
+def cond_embed(emb_table, step_idx, class_rows, out=None):
+    """afldm_cond_embed: out[r] = silu(rnd(emb_table[*step_idx] + class_rows[r])) - emb_table [n, D] the time embeddings per step
+    BEFORE the SiLU, class_rows / out [rows, D], all in one dtype; step_idx int32 [1] on the device, read only.  A counter outside
+    [0, n) leaves `out` untouched."""
+    out = _cond_rows("cond_embed", class_rows, out)
+    _dev(emb_table, "emb_table"); _dev(step_idx, "step_idx")
+    assert emb_table.dim() == 2 and emb_table.dtype == class_rows.dtype and emb_table.shape[1] == class_rows.shape[1]
+    assert step_idx.dtype == torch.int32 and step_idx.numel() == 1
+    rows, D = class_rows.shape
+    check(lib.afldm_cond_embed(ptr(emb_table), emb_table.shape[0], ptr(step_idx), ptr(class_rows), ptr(out), rows, D,
+                               _code(class_rows), stream_ptr()), "cond_embed")
+    return out
+
+
+def cond_embed_flat(emb, class_rows, out=None):
+    """afldm_cond_embed_flat: out[r] = silu(rnd(emb[r or 0] + class_rows[r])) - emb [1 | rows, D] (one row is broadcast)."""
+    out = _cond_rows("cond_embed_flat", class_rows, out)
+    _dev(emb, "emb")
+    assert emb.dim() == 2 and emb.dtype == class_rows.dtype and emb.shape[1] == class_rows.shape[1]
+    rows, D = class_rows.shape
+    check(lib.afldm_cond_embed_flat(ptr(emb), emb.shape[0], ptr(class_rows), ptr(out), rows, D, _code(class_rows), stream_ptr()),
+          "cond_embed_flat")
+    return out
+
+
 # ----------------------------------------------------------------------------- slot sampler (a step counter per batch row)
 def _slot_ints(B, **tensors):
     for name, t in tensors.items():

@@ -97,6 +97,14 @@ class I2SBLDMPipeline(MyLDMPipeline):
         raise NotImplementedError("I2SBLDMPipeline: image-to-image sampling (SDEdit) is defined for the unconditional sampler "
                                   "(MyLDMPipeline.img2img); the bridge has its own start, the encoded low-resolution image")
 
+    def cfg_latents(self, *args, **kwargs):
+        raise NotImplementedError("I2SBLDMPipeline: classifier-free guidance is defined for the class-conditional DDIM sampler "
+                                  "(MyLDMPipeline.cfg_latents); the bridge's UNet is conditioned on its start image, not on a label")
+
+    def cfg(self, *args, **kwargs):
+        raise NotImplementedError("I2SBLDMPipeline: classifier-free guidance is defined for the class-conditional DDIM sampler "
+                                  "(MyLDMPipeline.cfg); the bridge's UNet is conditioned on its start image, not on a label")
+
     def _no_reversible(self, *args, **kwargs):
         raise NotImplementedError("I2SBLDMPipeline: the bit-reversible sampler is defined for the unconditional DDIM sampler "
                                   "(MyLDMPipeline.sample_reversible / invert_reversible); a reversible bridge is not implemented")

@@ -697,6 +697,92 @@ class MyLDMPipeline(DiffusionPipeline):
                                latents, use_graph)
         return self._deliver(out, output_type, return_dict)
 
+    # ------------------------------------------------------------------------------------------------ classifier-free guidance
+    def _cfg_rows(self, class_labels, null_label, null_embedding, guided):
+        """(labels for unet.forward on the evaluated batch, the class rows [R, D] CFGEngine takes, B): the conditional rows, and
+        behind them - when guided - the unconditional rows: the row of `null_label` (default num_class_embeds - 1) of an
+        nn.Embedding table, `null_embedding` [D] or [B, D] (default zeros) of an 'identity' class embedding."""
+        unet = self.unet
+        if getattr(unet, "class_embedding", None) is None:
+            raise ValueError("classifier-free guidance needs a class-conditional UNet (num_class_embeds, or class_embed_type='identity')")
+        cond = unet.class_embed(class_labels)
+        B, D = cond.shape
+        if B == 0:
+            raise ValueError("cfg_latents: no class labels")
+        table = hasattr(unet.class_embedding, "num_embeddings")
+        if table and null_embedding is not None:
+            raise ValueError("null_embedding goes with class_embed_type='identity'; an embedding table takes null_label")
+        if not table and null_label is not None:
+            raise ValueError("null_label goes with an embedding table (num_class_embeds); class_embed_type='identity' takes null_embedding")
+        labels = torch.as_tensor(class_labels)
+        if not guided:
+            return (labels.reshape(-1) if table else labels), cond, B
+        if table:
+            null = unet.class_embedding.num_embeddings - 1 if null_label is None else int(null_label)
+            both = torch.cat([labels.reshape(-1).to("cpu", torch.int64), torch.full((B,), null, dtype=torch.int64)])
+            return both, unet.class_embed(both), B
+        null = torch.zeros(B, D) if null_embedding is None else torch.as_tensor(null_embedding).float().cpu()
+        if null.dim() == 1:
+            null = null.unsqueeze(0).expand(B, -1)
+        if tuple(null.shape) != (B, D):
+            raise ValueError(f"null_embedding {tuple(null.shape)}, want [{D}] or [{B}, {D}]")
+        both = torch.cat([labels.float().cpu(), null])
+        return both, unet.class_embed(both), B
+
+    @torch.no_grad()
+    def cfg_latents(self, class_labels, guidance_scale=3.0, guidance_rescale=0.0, null_label=None, null_embedding=None, eta=0.0,
+                    num_inference_steps=50, generator=None, latents=None, use_graph=True):
+        """Class-conditional sampling with classifier-free guidance (Ho & Salimans 2022) in latent space, one sample per entry of
+        `class_labels` - integer labels [B] for a UNet with an embedding table (num_class_embeds), float rows [B, temb_dim] for
+        class_embed_type 'identity'.  Every evaluation runs the UNet on 2 B rows, the B conditional ones and behind them the B
+        unconditional ones, e_c and e_u, and steps with g = e_c + (guidance_scale - 1) (e_c - e_u) - diffusers'
+        e_u + guidance_scale (e_c - e_u) in another order, so not bit-identical to it; `guidance_rescale` in [0, 1] pulls the
+        standard deviation of g back towards e_c's per sample (diffusers rescale_noise_cfg).  The unconditional rows: with an
+        embedding table the row of `null_label`, default num_class_embeds - 1 - the convention of training with the LAST class
+        as the dropped-label ("null") class; a checkpoint trained otherwise must say which row it is - and with 'identity'
+        `null_embedding`, default zeros.  guidance_scale = 1 evaluates the B conditional rows only and applies the scheduler's own
+        update.  The schedule is DDIMScheduler.cfg_schedule: replayed HIP graphs (use_graph, CFGEngine: the class rows are data,
+        other labels replay the same graphs) or the eager loop below over unet.forward and afldm_pag_step_flat, which makes the
+        same draws from `generator` in the same order - the start latents (unless `latents` is given), then with eta != 0 one
+        tensor per evaluation - and carries the latents in fp32 like the engine.  Needs no VAE.  Returns latents in the UNet's
+        dtype."""
+        from .. import ops
+        from ..engine import CFGEngine
+        self._refuse_dpm("classifier-free guidance")
+        w = float(guidance_scale)
+        self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
+        sched = self.scheduler.cfg_schedule(num_inference_steps, eta, w, guidance_rescale)      # (also checks the two settings)
+        guided = w != 1.0
+        if not guided:
+            sched = (self.scheduler.stochastic_schedule(num_inference_steps, eta) if float(eta) != 0.0
+                     else self.scheduler.schedule(num_inference_steps))
+        labels, rows, B = self._cfg_rows(class_labels, null_label, null_embedding, guided)
+        c, s = self.unet.config.in_channels, self.unet.config.sample_size
+        shape = (B, c, s, s)
+        if latents is not None and tuple(latents.shape) != shape:
+            raise ValueError(f"cfg_latents: latents {tuple(latents.shape)}, want [{B}, {c}, {s}, {s}] for {B} class labels")
+
+        def eager(x, t, row, zs):
+            if guided:
+                eps2 = self.unet(torch.cat([x, x]).to(self.unet.dtype), t, labels).sample.float()
+                return ops.pag_step_flat(x, eps2[:B].contiguous(), eps2[B:].contiguous(), zs[0], row)
+            e = self.unet(x.to(self.unet.dtype), t, labels).sample.float().contiguous()
+            if sched.kind == "ddim":
+                return ops.ddim_step_flat(x, e, row)
+            return ops.pag_step_flat(x, e, e, zs[0], row + (0.0, 0.0, 0.0, 0.0))        # the "sde" row: s = 0, phi = 0
+        return self._sample(sched, shape, generator, latents, use_graph, "_cfg_engines", eager, CFGEngine, known=rows,
+                            guided=guided).to(self.unet.dtype)
+
+    @torch.no_grad()
+    def cfg(self, class_labels, guidance_scale=3.0, guidance_rescale=0.0, null_label=None, null_embedding=None, eta=0.0,
+            num_inference_steps=50, generator=None, latents=None, use_graph=True, output_type="pil", return_dict=True):
+        """Sample images of the classes `class_labels` with classifier-free guidance: cfg_latents, then decode.  output_type as
+        __call__; 'latent' returns the sampled latents."""
+        self._refuse_dpm("classifier-free guidance")
+        out = self.cfg_latents(class_labels, guidance_scale, guidance_rescale, null_label, null_embedding, eta, num_inference_steps,
+                               generator, latents, use_graph)
+        return self._deliver(out, output_type, return_dict)
+
     # ------------------------------------------------------------------------------------------------ self-attention guidance
     def sag_site_of(self, sag_site):
         """The ONE attention module `sag_site` names, as a module path: a key of get_unet_attn_processors without its

@@ -169,6 +169,24 @@ class DDIMScheduler:
         return Schedule.of(self, "pag", sde.timesteps, rows, draws, _pag_steps=int(num_inference_steps), _pag_eta=float(eta),
                            _pag_scale=s, _pag_rescale=phi)
 
+    def cfg_schedule(self, num_inference_steps, eta=0.0, guidance_scale=3.0, guidance_rescale=0.0):
+        """Classifier-free guidance (Ho & Salimans 2022) over class labels on this scheduler's `num_inference_steps` timesteps, as
+        the Schedule CFGEngine replays with afldm_pag_step: every evaluation runs the UNet on the conditional and the
+        unconditional rows as one batch, e_c and e_u, forms g = e_c + (guidance_scale - 1) (e_c - e_u) - diffusers'
+        e_u + guidance_scale (e_c - e_u) in another order of operations - rescales it per sample towards std(e_c) by
+        `guidance_rescale` (diffusers rescale_noise_cfg) and applies the row of stochastic_schedule(num_inference_steps, eta)
+        to g.  The first eight fields of a row are that schedule's, float for float; then guidance_scale - 1,
+        guidance_rescale, 0, 0.  The draws are as in pag_schedule.  guidance_scale = 1 is the conditional sampler."""
+        w, phi = float(guidance_scale), float(guidance_rescale)
+        if not w >= 1.0 or not 0.0 <= phi <= 1.0:
+            raise ValueError(f"cfg_schedule: guidance_scale = {guidance_scale} must be >= 1 and guidance_rescale = "
+                             f"{guidance_rescale} in [0, 1]")
+        sde = self.stochastic_schedule(num_inference_steps, eta)
+        rows = [r + (w - 1.0, phi, 0.0, 0.0) for r in sde.rows]
+        draws = sde.draws if float(eta) != 0.0 else [False] * len(rows)
+        return Schedule.of(self, "cfg", sde.timesteps, rows, draws, _cfg_steps=int(num_inference_steps), _cfg_eta=float(eta),
+                           _cfg_scale=w, _cfg_rescale=phi)
+
     def sag_schedule(self, num_inference_steps, eta=0.0, sag_scale=0.75, guidance_rescale=0.0):
         """Self-attention guidance (Hong et al., ICCV 2023; diffusers StableDiffusionSAGPipeline) over this scheduler's
         `num_inference_steps` timesteps, as the Schedule SAGEngine replays: every step evaluates the UNet, degrades its input where

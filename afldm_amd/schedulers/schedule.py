@@ -24,6 +24,8 @@ UNet evaluation, fixed when it is made.  `kind` names the update kernel that rea
     "sag"   the "pag" row, float for float (s = sag_scale): self-attention guidance, two DEPENDENT evaluations per step - e, then
             e_d on the input degraded where the attention mass of one site exceeds 1 (afldm_sag_degrade reads p and q of the
             row) - and the same guided update with e_d in e_p's place                                        afldm_pag_step
+    "cfg"   the "pag" row with s = guidance_scale - 1: classifier-free guidance over class labels on a batch of 2 B, e the output on
+            the conditional rows and e_p the output on the unconditional rows (CFGEngine)                  afldm_pag_step
     "sdedit" (p, q, lo, hi, a, b, c, k0, k1, thr, 0, 0):  image-to-image sampling (SDEdit) with a per-element change map
             (Differential Diffusion):  x0 = clamp(p x + q eps, lo, hi);  xp = a x0 + b eps + c z_u;  held = k0 orig + k1 z, z the
             run's ONE fixed noise;  x_out = (cmap <= thr) ? held : xp - a select, not a blend         afldm_sdedit_step
@@ -51,7 +53,7 @@ from ..utils import randn_tensor
 # kind -> (row width, noise slots per step, may a step draw): the one place that states them.  Several slots: `draws` is per slot
 KINDS = {"ddim": (4, 1, False), "dpm": (8, 1, False), "sde": (8, 1, True), "repaint": (12, 3, True), "ilvr": (12, 2, True),
          "pano": (8, 1, True), "pag": (12, 1, True), "sag": (12, 1, True), "outpaint": (12, 3, True),
-         "hires": (12, 1, True), "sdedit": (12, 1, True), "rev": (4, 1, False)}
+         "hires": (12, 1, True), "sdedit": (12, 1, True), "rev": (4, 1, False), "cfg": (12, 1, True)}
 ROW_WIDTH, NOISE_SLOTS = {k: v[0] for k, v in KINDS.items()}, {k: v[1] for k, v in KINDS.items() if v[2]}      # derived views
 _MADE = {}          # key -> Schedule: the rows are ~0.1 ms of scalar tensor arithmetic each, and a sampler asks per call
 

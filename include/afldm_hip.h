@@ -759,6 +759,24 @@ int afldm_select_timestep(const float* tvals, int* step_idx, float* t_out, int p
  * one row per step; the step then starts with this launch instead of seven. */
 int afldm_select_step_row(const float* tvals, int* step_idx, float* t_out, int pre_advance, const void* table,
                           void* row_out, size_t row_bytes, afldm_stream_t stream);
+/* ---- class conditioning (classifier-free guidance) ---------------------------------------------------------------------
+ * diffusers' UNet2DModel adds the class embedding to the time embedding BEFORE the SiLU in front of the time_emb_proj layers,
+ * so a class-conditional step has no per-step row to copy: it tabulates time_embedding's output per step and runs
+ *   act[r][j] = silu( rnd( emb_table[s][j] + class_rows[r][j] ) ),  s = *step_idx (read only, never advanced)
+ * in front of the GEMM over all time_emb_proj layers (afldm_conv2d on act).
+ * emb_table  [n][D] dtype: time_embedding's output per step, BEFORE the SiLU
+ * class_rows [rows][D], act [rows][D], in dtype; all three 16-byte aligned (AFLDM_EALIGN)
+ * rnd = one rounding to dtype: in bf16 this is diffusers' bf16 `emb + class_emb`
+ * silu = x sigmoid(x) as afldm_silu evaluates it, the result rounded once: the bits of afldm_silu on the rounded sum
+ * D % 8 == 0 (16-byte chunks in bf16), else AFLDM_ESHAPE before any launch
+ * s outside [0, n): nothing is read or written (the rule of the slot calls)
+ * The kernel only reads step_idx (many workgroups do): afldm_select_timestep in front of it is the one place the counter moves.
+ * stream-ordered, capturable, allocates nothing */
+int afldm_cond_embed(const void* emb_table, int n, const int* step_idx, const void* class_rows, void* act, int rows, int D,
+                     int dtype, afldm_stream_t stream);
+/* the same for an eager forward: emb [emb_rows][D] with emb_rows in {1, rows} (1 = broadcast), no step index */
+int afldm_cond_embed_flat(const void* emb, int emb_rows, const void* class_rows, void* act, int rows, int D, int dtype,
+                          afldm_stream_t stream);
 
 /* ---- slot sampler: a step counter per batch row (continuous batching) ------------------------------------------------
  * Every batch row b of B (a "slot") walks its own stretch [begin, end) of one shared row table of capacity R:
