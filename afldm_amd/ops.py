@@ -393,11 +393,12 @@ def af_act(x1, x2=None, stats=None, gamma=None, beta=None, G=0, eps=0.0, out=Non
     return out
 
 
-AF_KERNELS = ("plane", "kron", "p8", "small")                  # AFLDM_AF_ROUTE_*
-RESAMPLE_KINDS = ("small", "reg", "generic")                   # AFLDM_RESAMPLE_ROUTE_*
+AF_KERNELS = tuple(_lib.ABI.names("AFLDM_AF_ROUTE_"))           # ("plane", "kron", ...): the header's names, by value
+RESAMPLE_KINDS = tuple(_lib.ABI.names("AFLDM_RESAMPLE_ROUTE_"))
 AfRoute = collections.namedtuple("AfRoute", "kernel ch grid items_per_wg")
 ResampleRoute = collections.namedtuple("ResampleRoute", "kind split")
-_AF_TUNE_FIELDS = {"ch": 1, "small_n": 2, "p8": 3, "stagger": 4, "no_resample_small": 5, "resample_split": 6, "max_grid": 7}
+_AF_TUNE_FIELDS = _lib.ABI.names("AFLDM_AF_TUNE_")               # {"ch": 1, "small_n": 2, ...}
+_AF_TUNE_RESET = _AF_TUNE_FIELDS.pop("reset")
 
 
 def af_act_route(dtype, N, C1, C2, B, cus=0, has_packed=None, has_UD=True):
@@ -429,7 +430,7 @@ def af_tune(**fields):
             check(_lib.lib.afldm_af_tune(_AF_TUNE_FIELDS[name], int(value)), "af_tune")
         yield
     finally:
-        check(_lib.lib.afldm_af_tune(0, 0), "af_tune")
+        check(_lib.lib.afldm_af_tune(_AF_TUNE_RESET, 0), "af_tune")
 
 
 def _resample_plane(x, M, R, out, want_stats):
@@ -1620,7 +1621,7 @@ def repaint_step_flat(x, eps, known, mask, noises, row, out=None):
     return out
 
 
-MASK_MIN, MASK_MEAN = 0, 1
+MASK_MIN, MASK_MEAN = _lib.ABI.constants["AFLDM_MASK_MIN"], _lib.ABI.constants["AFLDM_MASK_MEAN"]
 
 
 def mask_pool(mask, r, mode=MASK_MIN, out=None):
@@ -2302,7 +2303,7 @@ def picard_slide(x, y, stride):
     return x
 
 
-FLOW_PICK, FLOW_POOL = 0, 1
+FLOW_PICK, FLOW_POOL = _lib.ABI.constants["AFLDM_FLOW_PICK"], _lib.ABI.constants["AFLDM_FLOW_POOL"]
 
 
 def flow_splat_workspace(B, C, H, W, ds, mode):
