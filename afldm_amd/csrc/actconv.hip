@@ -66,7 +66,7 @@ struct ActConvLds {
 // PRE: the activation IN FRONT of the convolution (pa: raw input -> p.x1);  POST: the activation BEHIND it (pb: p.y -> pb.y,
 // statistics = the partial sums the convolution's epilogue has just written).  The phases are lambdas so that the
 // convolution tile's own `return`s (conv3h_body.inc) leave its phase, not the kernel.
-template <typename T, int BM, int W_, int BN, int WGM, int WGN, int NPROD, int STAGES, int MINW, int MF, int TPS, int CH, bool PRE, bool POST>
+template <typename T, int BM, int W_, int BN, int WGM, int WGN, int NPROD, int MINW, int TPS, int CH, bool PRE, bool POST>
 __global__ void __launch_bounds__((WGM * WGN + NPROD) * 64, MINW) k_act_conv3h(ConvP p, AfP<T> pa, AfP<T> pb, ClusterP xx) {
   constexpr bool SUB = false;
   constexpr int N = W_;
@@ -402,7 +402,7 @@ __global__ void __launch_bounds__((WGM * WGN + NPROD) * 64, MINW) k_act_conv3h(C
 template <int BM, int W_, int BN, int WGM, int WGN, int MINW, int CH, bool PRE, bool POST>
 static int launch_actconv(ConvP p, const AfP<bf16>& pa, const AfP<bf16>& pb, unsigned* sync, size_t sync_bytes, hipStream_t st) {
   typedef bf16 T;
-  constexpr int NPROD = 4, STAGES = 3, MF = 16, TPS = 1;
+  constexpr int NPROD = 4, STAGES = kH3Stages, TPS = 1;
   constexpr int NWALL = WGM * WGN + NPROD, NG = NWALL / 4;
   constexpr int ROWS = BM / W_, NPI = ((ROWS + 2) * (W_ + 2) + 7) / 8;
   constexpr int lds_conv = 2 * NPI * 1024 + STAGES * BN * 128;
@@ -421,7 +421,7 @@ static int launch_actconv(ConvP p, const AfP<bf16>& pa, const AfP<bf16>& pb, uns
   xx.flags = (tiles % (8 * xx.cs) != 0 || s_mode == 1 || g_actconv_general) ? 1 : 0;
   xx.trace = g_actconv_trace;
   AFLDM_REQUIRE(sync_bytes >= (size_t)(16384 + 2 * 32 * p.B) * 4, AFLDM_ESHAPE, "afldm_af_act_conv2d: sync buffer too small for %d samples", p.B);
-  auto kern = k_act_conv3h<T, BM, W_, BN, WGM, WGN, NPROD, STAGES, MINW, MF, TPS, CH, PRE, POST>;
+  auto kern = k_act_conv3h<T, BM, W_, BN, WGM, WGN, NPROD, MINW, TPS, CH, PRE, POST>;
   static unsigned long long attr_set = 0;
   if (first_on_device(attr_set)) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   kern<<<dim3(tiles, 1, 1), NWALL * 64, lds, st>>>(p, pa, pb, xx);
@@ -436,7 +436,7 @@ static int actconv_kernel_for(const afldm_af_act_args* pre, const afldm_conv_arg
   if (conv->H != conv->W || (N != 32 && N != 16) || conv->x2 || conv->C2 || conv->Cout % 192) return 0;
   int vid = 0;
   if (!conv3h_plan(conv, p, &vid)) return 0;
-  if (!((N == 32 && vid == kConv3hFirst + 0) || (N == 16 && vid == kConv3hFirst + 2))) return 0;
+  if (!((N == 32 && vid == 41) || (N == 16 && vid == 43))) return 0;      // the 256 x 192 / 128 x 192 tiles instantiated above
   const int bm = N == 32 ? 256 : 128;
   const int cs = (N * N / bm) * (conv->Cout / 192);
   if (conv->sync_bytes < (size_t)(16384 + 2 * 32 * conv->B) * 4) return 0;

@@ -377,20 +377,20 @@ __device__ __forceinline__ void splitk_fused_reduce(const ConvP& p, int m0, int 
 // wave-instruction costs ~60-185 issue cycles (MI355X_MICROARCH.md); at 10 of them per wave per
 // K step that is as long as the 48 MFMAs, and an in-order wave cannot overlap the two.  Split
 // across waves that share a SIMD, the DMA issue runs under the other wave's MFMAs.
-// R128 (KCH = 2 only): an LDS row holds the whole 128-byte K step of one pixel / cout row, so every
-// LDS-DMA wave-instruction fetches 8 full 128-byte lines (8 lanes x 16 B per row) instead of 16
-// half lines.  Measured with AFLDM_CONV_DBG (profiles/r01/conv_dma_mfma_decomposition.log): with
-// 64-byte pieces the DMA stream ALONE took 93 % of the kernel time at ~13 TB/s of requested bytes
-// (each line requested twice, by the kc = 0 and kc = 1 instructions).  Row r keeps source chunk c
-// at position c ^ ((r >> 1) & 7): conflict-free for the 16-lane groups of ds_read_b128.
+// A K step is one 128-byte row (two MFMA K chunks): an LDS row holds the whole K step of one pixel / cout
+// row, so every LDS-DMA wave-instruction fetches 8 full 128-byte lines (8 lanes x 16 B per row).  Measured
+// with AFLDM_CONV_DBG (profiles/r01/conv_dma_mfma_decomposition.log): with 64-byte pieces (16 half lines per
+// instruction, removed) the DMA stream ALONE took 93 % of the kernel time at ~13 TB/s of requested bytes.
+// Row r keeps source chunk c at position c ^ ((r >> 1) & 7): conflict-free for the 16-lane groups of
+// ds_read_b128.
 // MINW: waves per SIMD the register allocator must leave room for (the 128x192 tile needs 151 + 96
 // registers in its main loop = 2 waves per SIMD = 2 workgroups per CU; left alone the allocator
 // spends 30 more on the epilogue and halves the occupancy).
-template <typename T, int BM, int BN, int WGM, int WGN, int KCH, int STAGES, int NPROD = 0, bool R128 = false, int MINW = 1>
+template <typename T, int BM, int BN, int WGM, int WGN, int STAGES, int NPROD = 0, int MINW = 1>
 __global__ void __launch_bounds__((WGM * WGN + NPROD) * 64, MINW) k_igemm2(ConvP p) {
   typedef Mma<T> MM;
   typedef typename MM::Chunk Chunk;
-  static_assert(!R128 || KCH == 2, "128-byte rows hold exactly two MFMA K chunks");
+  constexpr int KCH = 2;                            // MFMA K chunks of a K step (one 128-byte row)
   constexpr int NWC = WGM * WGN;                    // consumer (compute) waves
   constexpr int NW = NPROD > 0 ? NPROD : NWC;       // waves that issue the LDS-DMA
   constexpr int EPC = MM::EPC, EPR = 4 * EPC, KSTEP = KCH * EPR;
@@ -441,21 +441,18 @@ __global__ void __launch_bounds__((WGM * WGN + NPROD) * 64, MINW) k_igemm2(ConvP
   __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)((const T*)p.w + (size_t)(p.w_bstride ? m0 / HW : 0) * p.w_bstride), 0, (int)w_bytes, 0x00020000);
 
   // per-lane source coordinates.  Instruction j (0..XI-1) of a stage covers plane kc = j / XG, row
-  // group g = j % XG; this wave issues j = wave + NW * i.  Lane l: row 16 g + (l >> 2), source
-  // chunk (l & 3) ^ swz(row)  [swz(row) depends only on (l >> 4)].
-  // R128: instruction j covers rows 8 j .. 8 j + 7; lane l: row 8 j + (l >> 3), position l & 7 holds
+  // group g = j % XG; this wave issues j = wave + NW * i.
+  // Instruction j covers rows 8 j .. 8 j + 7; lane l: row 8 j + (l >> 3), position l & 7 holds
   // source chunk (l & 7) ^ ((row >> 1) & 7) = (l & 7) ^ ((4 j + (l >> 4)) & 7).
-  const int lrow = R128 ? lane >> 3 : lane >> 2;
-  const int lchunk = (lane & 3) ^ ((4 - (lane >> 4)) & 3);
+  const int lrow = lane >> 3;
   int xoh[XPW], xow[XPW], xcin[XPW];   // xcin: element offset of this lane's chunk inside the K step
   unsigned xbase[XPW];  // byte offset of pixel (b, oh, ow) channel 0 in a tensor with C channels = 1 (scaled later)
   bool xok[XPW];
 #pragma unroll
   for (int i = 0; i < XPW; ++i) {
     const int j = wave + NW * i;
-    const int g = j % XG;
-    xcin[i] = R128 ? (((lane & 7) ^ ((4 * j + (lane >> 4)) & 7)) * EPC) : ((j / XG) * EPR + lchunk * EPC);
-    const int m = R128 ? m0 + 8 * j + lrow : m0 + 16 * g + lrow;
+    xcin[i] = ((lane & 7) ^ ((4 * j + (lane >> 4)) & 7)) * EPC;
+    const int m = m0 + 8 * j + lrow;
     xok[i] = m < p.M;
     const int mm = xok[i] ? m : 0;
     const int b = mm / HW, pix = mm - b * HW;
@@ -469,9 +466,8 @@ __global__ void __launch_bounds__((WGM * WGN + NPROD) * 64, MINW) k_igemm2(ConvP
 #pragma unroll
   for (int i = 0; i < WPW; ++i) {
     const int j = wave + NW * i;
-    const int g = j % WG_;
-    wcin[i] = R128 ? (((lane & 7) ^ ((4 * j + (lane >> 4)) & 7)) * EPC) : ((j / WG_) * EPR + lchunk * EPC);
-    const int n = R128 ? n0 + 8 * j + lrow : n0 + 16 * g + lrow;
+    wcin[i] = ((lane & 7) ^ ((4 * j + (lane >> 4)) & 7)) * EPC;
+    const int n = n0 + 8 * j + lrow;
     wok[i] = n < p.Cout;
     wrow[i] = (unsigned)(wok[i] ? n : 0) * (unsigned)(p.KS * p.KS);
   }
@@ -577,14 +573,12 @@ __global__ void __launch_bounds__((WGM * WGN + NPROD) * 64, MINW) k_igemm2(ConvP
 #pragma unroll
       for (int t = 0; t < TN; ++t) {
         const int row = wn * WNS + t * 16 + li;
-        a[t] = R128 ? ld16<Chunk>(sW + row * 128 + (((kc * 4 + lg) ^ ((row >> 1) & 7)) << 4))
-                    : ld16<Chunk>(sW + (kc * BN + row) * 64 + ((lg ^ swz(row)) << 4));
+        a[t] = ld16<Chunk>(sW + row * 128 + (((kc * 4 + lg) ^ ((row >> 1) & 7)) << 4));
       }
 #pragma unroll
       for (int t = 0; t < TM; ++t) {
         const int row = wm * WMS + t * 16 + li;
-        b[t] = R128 ? ld16<Chunk>(sX + row * 128 + (((kc * 4 + lg) ^ ((row >> 1) & 7)) << 4))
-                    : ld16<Chunk>(sX + (kc * BM + row) * 64 + ((lg ^ swz(row)) << 4));
+        b[t] = ld16<Chunk>(sX + row * 128 + (((kc * 4 + lg) ^ ((row >> 1) & 7)) << 4));
       }
 #pragma unroll
       for (int tn = 0; tn < TN; ++tn)
@@ -927,260 +921,6 @@ __global__ void __launch_bounds__((WGM * WGN + NPROD) * 64, MINW) k_igemm2(ConvP
         const int b = m0 / HW, sp = (m0 - b * HW) / BM;
         *reinterpret_cast<f32x2*>(p.stats_out + (((size_t)b * p.stats_S + sp) * p.Cout + n0 + c) * 2) = f32x2{a1, a2};
       }
-    }
-  }
-}
-
-// ----------------------------------------------------------------------------- v5: persistent tiles
-// 128x192 tiles, 4 MFMA-only consumer waves + 4 LDS-DMA producer waves (as variant 33), but a workgroup
-// walks SEVERAL tiles and the producers never stop at a tile boundary: while the consumers run the epilogue
-// of tile i the ring already holds the first STAGES-1 K steps of tile i+1, and the epilogue's stores drain
-// under the next tile's MFMAs.  (With one tile per workgroup slot nothing overlaps the fixed part: 14 of
-// the 52 us of a 192->192 3x3 conv at 32x32 remain with both the DMA and the MFMA phase switched off.)
-// The epilogue is wave-private - a consumer wave owns 64 rows x 96 couts, adds bias / time embedding /
-// residual in fp32 in registers, rounds, stages 32 rows at a time through its own LDS patch and stores
-// 192-byte row pieces; GroupNorm partial sums are written per (32-row pass) split, so no workgroup
-// barrier exists outside the K loop and the producers may run ahead.  bf16, H*W % 128 == 0, Cout % 192 == 0,
-// token-major output, no split-K.  Same K order and rounding as k_igemm2: bit-identical results.
-template <typename T, int STAGES>
-__global__ void __launch_bounds__(512, 1) k_igemm3(ConvP p) {
-  typedef Mma<T> MM;
-  typedef typename MM::Chunk Chunk;
-  constexpr int BM = 128, BN = 192, WGN = 2, NWC = 4, NW = 4;
-  constexpr int EPC = MM::EPC, KSTEP = 8 * EPC, ESZ = (int)sizeof(T);
-  constexpr int WMS = 64, WNS = 96, TM = 4, TN = 6;
-  constexpr int XI = BM / 8, WI = BN / 8, XPW = XI / NW, WPW = WI / NW, LPS = XPW + WPW;
-  constexpr int X_STAGE = BM * 128, W_STAGE = BN * 128, STAGE = X_STAGE + W_STAGE;
-  constexpr int SROW = WNS + 8, WSTG = 32 * SROW * ESZ;
-  constexpr unsigned OOB = 0x80000000u;
-  static_assert(sizeof(T) == 2, "bf16 only");
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave_all = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const bool is_producer = wave_all >= NWC;
-  const int li = lane & 15, lg = lane >> 4;
-  const int G = gridDim.x;
-  const int tiles_m_ = p.M / BM, ntiles = tiles_m_ * p.tiles_n;
-  const int first = xcd_remap(blockIdx.x, G);
-  const int nmine = first < ntiles ? (ntiles - first + G - 1) / G : 0;
-  const int Ct = p.C1 + p.C2, cblocks = Ct / KSTEP, HW = p.H * p.W, pad = p.KS >> 1;
-  const int ksteps = p.ksteps;
-  auto tile_origin = [&](int ti, int& m0, int& n0) {
-    const int tile = first + ti * G;
-    const int tm = p.m_fast ? tile % tiles_m_ : tile / p.tiles_n;
-    const int tn = p.m_fast ? tile / tiles_m_ : tile % p.tiles_n;
-    m0 = tm * BM;
-    n0 = tn * BN;
-  };
-
-  if (is_producer) {
-    const int wave = wave_all - NWC;
-    const long long x1_bytes = (long long)p.M * p.C1 * ESZ, x2_bytes = (long long)p.M * p.C2 * ESZ;
-    const long long w_bytes = (long long)p.Cout * p.KS * p.KS * Ct * ESZ;
-    __amdgpu_buffer_rsrc_t rx1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.x1, 0, (int)x1_bytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t rx2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x2 ? p.x2 : p.x1), 0, (int)x2_bytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, (int)w_bytes, 0x00020000);
-    const int lrow = lane >> 3;
-    int xoh[XPW], xow[XPW], xcin[XPW];
-    unsigned xbase[XPW];
-    unsigned xoff1[XPW], xoff2[XPW], woff[WPW];
-    int cur = 0;                       // tile of the NEXT step to issue
-    int is_kt = 0, is_tap = 0, is_ci0 = 0, is_kh = 0, is_kw = 0;
-    auto retap = [&]() {
-      const int dh = is_kh - pad, dw = is_kw - pad;
-      const int dpix = dh * p.W + dw;
-#pragma unroll
-      for (int i = 0; i < XPW; ++i) {
-        const int ih = xoh[i] + dh, iw = xow[i] + dw;
-        const bool ok = (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
-        const unsigned pixel = (unsigned)((int)xbase[i] + dpix);
-        const unsigned cin = (unsigned)xcin[i];
-        xoff1[i] = ok ? (pixel * (unsigned)p.C1 + cin) * ESZ : OOB;
-        xoff2[i] = ok ? (pixel * (unsigned)p.C2 + cin) * ESZ : OOB;
-      }
-    };
-    auto setup_tile = [&]() {
-      int m0, n0;
-      tile_origin(cur, m0, n0);
-#pragma unroll
-      for (int i = 0; i < XPW; ++i) {
-        const int j = wave + NW * i;
-        xcin[i] = ((lane & 7) ^ ((4 * j + (lane >> 4)) & 7)) * EPC;
-        const int m = m0 + 8 * j + lrow;
-        const int b = m / HW, pix = m - b * HW;
-        xoh[i] = pix / p.W;
-        xow[i] = pix - xoh[i] * p.W;
-        xbase[i] = (unsigned)m;
-      }
-#pragma unroll
-      for (int i = 0; i < WPW; ++i) {
-        const int j = wave + NW * i;
-        const int wc = ((lane & 7) ^ ((4 * j + (lane >> 4)) & 7)) * EPC;
-        const int n = n0 + 8 * j + lrow;
-        woff[i] = ((unsigned)n * (unsigned)(p.KS * p.KS) * (unsigned)Ct + (unsigned)wc) * ESZ;
-      }
-      is_kt = is_tap = is_ci0 = is_kh = is_kw = 0;
-      retap();
-    };
-    if (nmine > 0) setup_tile();
-    auto issue = [&](int slot) {
-      char* sbase = smem + slot * STAGE;
-      const bool live = cur < nmine;
-      const bool second = is_ci0 >= p.C1;
-      const unsigned xs = live ? (unsigned)((second ? is_ci0 - p.C1 : is_ci0) * ESZ) : OOB;
-      const unsigned wsoff = live ? (unsigned)((is_tap * Ct + is_ci0) * ESZ) : OOB;
-#pragma unroll
-      for (int i = 0; i < XPW; ++i) {
-        const int j = wave + NW * i;
-        lds_ptr_t dst = (lds_ptr_t)(sbase + j * 1024);
-        if (second) __builtin_amdgcn_raw_ptr_buffer_load_lds(rx2, dst, 16, (int)xoff2[i], (int)xs, 0, 0);
-        else __builtin_amdgcn_raw_ptr_buffer_load_lds(rx1, dst, 16, (int)xoff1[i], (int)xs, 0, 0);
-      }
-#pragma unroll
-      for (int i = 0; i < WPW; ++i) {
-        const int j = wave + NW * i;
-        lds_ptr_t dst = (lds_ptr_t)(sbase + X_STAGE + j * 1024);
-        if (p.w_nt) __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, dst, 16, (int)woff[i], (int)wsoff, 0, 2);
-        else __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, dst, 16, (int)woff[i], (int)wsoff, 0, 0);
-      }
-      if (!live) return;
-      ++is_kt;
-      is_ci0 += KSTEP;
-      if (is_ci0 >= Ct) {
-        is_ci0 = 0;
-        ++is_tap;
-        if (++is_kw == p.KS) {
-          is_kw = 0;
-          ++is_kh;
-        }
-        if (is_kt < ksteps) retap();
-      }
-      if (is_kt == ksteps) {          // next tile: its first K steps follow immediately (no drain)
-        ++cur;
-        if (cur < nmine) setup_tile();
-      }
-    };
-#pragma unroll
-    for (int q = 0; q < STAGES - 1; ++q) issue(q);
-    int slot = 0;
-    const int total = nmine * ksteps;
-    for (int g = 0; g < total; ++g) {
-      wait_vmcnt<(STAGES - 2) * LPS>();
-      __builtin_amdgcn_s_barrier();
-      int nslot = slot + STAGES - 1;
-      if (nslot >= STAGES) nslot -= STAGES;
-      issue(nslot);
-      slot = slot + 1 == STAGES ? 0 : slot + 1;
-    }
-    wait_vmcnt<0>();
-    return;
-  }
-
-  // ---------------- consumers
-  const int cw = wave_all, wm = cw / WGN, wn = cw % WGN;
-  T* ws = reinterpret_cast<T*>(smem + STAGES * STAGE + cw * WSTG);
-  const T* temb = (const T*)p.temb;
-  const T* res = (const T*)p.residual;
-  int slot = 0;
-  for (int ti = 0; ti < nmine; ++ti) {
-    int m0, n0;
-    tile_origin(ti, m0, n0);
-    f32x4 acc[TN][TM];
-#pragma unroll
-    for (int a = 0; a < TN; ++a)
-#pragma unroll
-      for (int b = 0; b < TM; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int kt = 0; kt < ksteps; ++kt) {
-      __builtin_amdgcn_s_barrier();
-      const char* sX = smem + slot * STAGE;
-      const char* sW = sX + X_STAGE;
-#pragma unroll
-      for (int kc = 0; kc < 2; ++kc) {
-        Chunk a[TN], b[TM];
-#pragma unroll
-        for (int t = 0; t < TN; ++t) {
-          const int row = wn * WNS + t * 16 + li;
-          a[t] = ld16<Chunk>(sW + row * 128 + (((kc * 4 + lg) ^ ((row >> 1) & 7)) << 4));
-        }
-#pragma unroll
-        for (int t = 0; t < TM; ++t) {
-          const int row = wm * WMS + t * 16 + li;
-          b[t] = ld16<Chunk>(sX + row * 128 + (((kc * 4 + lg) ^ ((row >> 1) & 7)) << 4));
-        }
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-          for (int tm = 0; tm < TM; ++tm) MM::mma(acc[tn][tm], a[tn], b[tm]);
-      }
-      slot = slot + 1 == STAGES ? 0 : slot + 1;
-    }
-    // ---- wave-private epilogue: 2 passes of 32 rows
-    const int bsm = m0 / HW;
-    const int split0 = ((m0 - bsm * HW) / BM) * 4 + wm * 2;
-#pragma unroll
-    for (int ps = 0; ps < 2; ++ps) {
-#pragma unroll
-      for (int tn = 0; tn < TN; ++tn) {
-        const int n = n0 + wn * WNS + 16 * tn + 4 * lg;
-        f32x4 bv = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
-        f32x4 tv = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (temb) {
-          const bf16x4 t4 = *reinterpret_cast<const bf16x4*>(temb + (size_t)bsm * p.temb_stride + n % p.temb_mod);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) tv[r] = (float)t4[r];
-        }
-        float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int tmi = 0; tmi < 2; ++tmi) {
-          const int tm = 2 * ps + tmi;
-          const int m = m0 + wm * WMS + 16 * tm + li;
-          float v[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            v[r] = acc[tn][tm][r] + bv[r];
-            if (temb) v[r] += tv[r];
-          }
-          if (res) {
-            const bf16x4 rr = *reinterpret_cast<const bf16x4*>(res + (size_t)m * p.res_ld + n);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] += (float)rr[r];
-          }
-          bf16x4 o;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            o[r] = (bf16)v[r];
-            const float q = (float)o[r];
-            s1[r] += q;
-            s2[r] = fmaf(q, q, s2[r]);
-          }
-          *reinterpret_cast<bf16x4*>(ws + (16 * tmi + li) * SROW + 16 * tn + 4 * lg) = o;
-        }
-        if (p.stats_out) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-#pragma unroll
-            for (int o = 1; o < 16; o <<= 1) {
-              s1[r] += __shfl_xor(s1[r], o, 64);
-              s2[r] += __shfl_xor(s2[r], o, 64);
-            }
-          }
-          if (li == 0) {
-            float* so = p.stats_out + (((size_t)bsm * p.stats_S + split0 + ps) * p.Cout + n) * 2;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) *reinterpret_cast<f32x2*>(so + 2 * r) = f32x2{s1[r], s2[r]};
-          }
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-      constexpr int CPR = WNS / 8;     // 16-byte pieces per staged row
-#pragma unroll 2
-      for (int it = 0; it < 32 * CPR / 64; ++it) {
-        const int idx = lane + 64 * it, row = idx / CPR, c = idx - row * CPR;
-        st16<Chunk>((T*)p.y + (size_t)(m0 + wm * WMS + 32 * ps + row) * p.y_ld + n0 + wn * WNS + c * 8,
-                    ld16<Chunk>(ws + row * SROW + c * 8));
-      }
-      __builtin_amdgcn_wave_barrier();
     }
   }
 }
@@ -1537,84 +1277,68 @@ struct Plan {
   int cfg_auto, splitk_auto;   // the automatic choice (fallback when a forced / preferred variant cannot run the shape)
 };
 
-constexpr int KCH_DEFAULT = 2;
+constexpr int KCH_DEFAULT = 2;     // MFMA K chunks per K step: one 128-byte row of channels
 
-struct Variant {
-  int bm, bn, ver, stages;
+template <typename T, int BM, int BN, int WGM, int WGN>
+static void launch_igemm(const ConvP& p0, hipStream_t st) {
+  ConvP p = p0;
+  constexpr int KCH = KCH_DEFAULT;
+  p.tiles_n = (p.Cout + BN - 1) / BN;
+  const int tiles_m = (p.M + BM - 1) / BM;
+  dim3 grid(tiles_m * p.tiles_n, 1, p.splitk);
+  constexpr int lds = 2 * KCH * (BM + BN) * 64;
+  static unsigned long long attr_set = 0;
+  if (first_on_device(attr_set)) {
+    (void)hipFuncSetAttribute((const void*)k_igemm<T, BM, BN, WGM, WGN, KCH>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  }
+  k_igemm<T, BM, BN, WGM, WGN, KCH><<<grid, WGM * WGN * 64, lds, st>>>(p);
+}
+
+template <typename T, int BM, int BN, int WGM, int WGN, int STAGES, int NPROD, int MINW>
+static void launch_igemm2(const ConvP& p0, hipStream_t st) {
+  ConvP p = p0;
+  p.tiles_n = (p.Cout + BN - 1) / BN;
+  const int tiles_m = (p.M + BM - 1) / BM;
+  dim3 grid(tiles_m * p.tiles_n, 1, p.splitk);
+  constexpr int lds = STAGES * (BM + BN) * 128;
+  static unsigned long long attr_set = 0;
+  if (first_on_device(attr_set)) {
+    (void)hipFuncSetAttribute((const void*)k_igemm2<T, BM, BN, WGM, WGN, STAGES, NPROD, MINW>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  }
+  k_igemm2<T, BM, BN, WGM, WGN, STAGES, NPROD, MINW><<<grid, (WGM * WGN + NPROD) * 64, lds, st>>>(p);
+}
+
+// The GEMM rows of the variant table (ConvVariant, conv_common.hpp), each made from the arguments that instantiate its
+// launchers; the halo-patch rows (41 and up) are conv3h.hip's.
+template <int BM, int BN, int WGM, int WGN>
+static constexpr ConvVariant conv_row_igemm(int id) {
+  return {id, CONV_IGEMM, BM, BN, launch_igemm<float, BM, BN, WGM, WGN>, launch_igemm<bf16, BM, BN, WGM, WGN>};
+}
+template <int BM, int BN, int WGM, int WGN, int STAGES, int NPROD, int MINW>
+static constexpr ConvVariant conv_row_igemm2(int id) {
+  return {id, CONV_IGEMM_DMA, BM, BN, launch_igemm2<float, BM, BN, WGM, WGN, STAGES, NPROD, MINW>,
+          launch_igemm2<bf16, BM, BN, WGM, WGN, STAGES, NPROD, MINW>, NPROD > 0};
+}
+static constexpr ConvVariant kGemmVariants[] = {
+    // register-staged (k_igemm): where an operand exceeds what a buffer descriptor addresses (resolve_exec)
+    conv_row_igemm<128, 128, 2, 2>(0),
+    conv_row_igemm<128, 64, 2, 2>(1),
+    conv_row_igemm<64, 64, 2, 2>(3),
+    // LDS-DMA (k_igemm2); MINW: 2 workgroups per CU for the 128x192 / 128x128 tiles, 3 for 128x64
+    conv_row_igemm2<128, 192, 2, 2, 2, 0, 2>(29),
+    conv_row_igemm2<128, 128, 2, 2, 2, 0, 2>(30),
+    conv_row_igemm2<128, 64, 2, 2, 2, 0, 3>(31),
+    conv_row_igemm2<64, 64, 2, 2, 4, 0, 1>(32),
+    conv_row_igemm2<128, 192, 2, 2, 3, 4, 1>(33),      // + 4 producer waves, 3 stages, one workgroup per CU
 };
-// index = variant id used by afldm_conv2d_tune / the automatic chooser
-static const Variant kVariants[] = {
-    {128, 128, 1, 2},  // 0
-    {128, 64, 1, 2},   // 1
-    {64, 128, 1, 2},   // 2
-    {64, 64, 1, 2},    // 3
-    {128, 128, 2, 2},  // 4
-    {128, 128, 2, 3},  // 5
-    {128, 64, 2, 2},   // 6
-    {128, 64, 2, 3},   // 7
-    {128, 64, 2, 4},   // 8
-    {64, 128, 2, 3},   // 9
-    {64, 128, 2, 4},   // 10
-    {64, 64, 2, 4},    // 11
-    {128, 192, 2, 2},  // 12
-    {256, 64, 2, 2},   // 13
-    {256, 64, 2, 3},   // 14
-    {64, 64, 2, 6},    // 15
-    {128, 192, 2, 4},  // 16  (K step = one 64-byte row piece: KCH = 1)
-    {128, 128, 2, 4},  // 17  (KCH = 1)
-    {128, 192, 2, 3},  // 18  (KCH = 1)
-    {128, 192, 2, 2},  // 19  (KCH = 1: 40 KB LDS -> 4 workgroups per CU)
-    {128, 128, 2, 2},  // 20  (KCH = 1: 32 KB LDS)
-    {128, 192, 3, 2},  // 21  wave-specialised: 4 consumer + 4 producer waves
-    {128, 192, 3, 3},  // 22
-    {128, 128, 3, 2},  // 23
-    {128, 128, 3, 3},  // 24
-    {128, 192, 3, 2},  // 25  4 consumers + 2 producers
-    {256, 192, 3, 2},  // 26  8 consumers (4x2) + 4 producers, 112 KB LDS
-    {256, 128, 3, 2},  // 27  8 consumers (4x2) + 4 producers, 96 KB LDS
-    {128, 64, 3, 3},   // 28  4 consumers + 2 producers
-    {128, 192, 4, 2},  // 29  ver 4 = 128-byte LDS rows (full-line LDS-DMA)
-    {128, 128, 4, 2},  // 30
-    {128, 64, 4, 2},   // 31
-    {64, 64, 4, 4},    // 32
-    {128, 192, 4, 3},  // 33  + 4 producer waves
-    {128, 128, 4, 2},  // 34  + 4 producer waves
-    {128, 128, 4, 3},  // 35
-    {256, 64, 4, 2},   // 36
-    {64, 192, 4, 2},   // 37  short-K GEMMs: twice the tiles of 128x192 (epilogues of one round overlap the next)
-    {64, 128, 4, 2},   // 38
-    {64, 192, 4, 3},   // 39
-    {128, 192, 5, 3},  // 40  ver 5 = persistent tiles (k_igemm3): producers run ahead across tile boundaries
-    {256, 192, 6, 3},  // 41  ver 6 = halo-patch 3x3 (conv3h.hip): 32x32 planes, 8 image rows per tile, 8 + 4 waves
-    {128, 192, 6, 3},  // 42  16x16 planes, 8 rows per tile, 8 consumers (64x48) + 4 producers
-    {128, 192, 6, 3},  // 43  16x16 planes, 4 consumers (64x96) + 4 producers
-    {256, 192, 6, 3},  // 44  16x16 planes, one whole sample per tile
-    {128, 192, 6, 3},  // 45  32x32 planes, 4 rows per tile, 8 + 4 waves
-    {128, 192, 6, 3},  // 46  32x32 planes, 4 rows per tile, 4 + 4 waves
-    {256, 192, 6, 3},  // 47  = 41 on 32x32x16 MFMAs
-    {128, 192, 6, 3},  // 48  = 43 on 32x32x16 MFMAs
-    {256, 192, 6, 3},  // 49  = 44 on 32x32x16 MFMAs
-    {128, 192, 6, 3},  // 50  = 46 on 32x32x16 MFMAs
-    {64, 96, 6, 3},    // 51  halo-patch, 8x8 planes: one sample x 96 couts per tile, 3 taps per K step, no split-K
-    {64, 96, 6, 3},    // 52  4x4 planes: four samples x 96 couts per tile, split-K over the channel blocks
-    {64, 96, 6, 3},    // 53  = 51
-    {128, 96, 6, 3},   // 54  16x16 planes, 8 rows x 96 couts (small batches)
-    {128, 96, 6, 3},   // 55  32x32 planes, 4 rows x 96 couts (small batches)
-    {64, 32, 4, 12},   // 56  64x32 tiles, 12 stages (a skinny GEMM's K step costs DMA latency / ring depth): dense layers over <= 64 rows (the 2x2 level at batch 64) WITHOUT split-K
-    {256, 192, 6, 2},  // 57  = 41 with a 2-deep weight ring (lookahead experiment)
-    {256, 128, 6, 3},  // 58  halo-patch on planes of 64^2 and up (AF-VAE): 8 x 32 pixel blocks x 128 couts
-    {256, 128, 6, 3},  // 59  = 58 with 4 consumer waves (128 x 64 each)
-    {256, 128, 6, 3},  // 60  = 58 on 32x32x16 MFMAs
-    {128, 96, 6, 2},   // 61  halo-patch, 32x32 planes, 128 x 96 tiles sized for TWO workgroups per CU (4 + 2 waves, 2-deep ring)
-    {128, 96, 6, 2},   // 62  the same for 16x16 planes
-    {256, 128, 6, 3},  // 63  = 58 with persistent workgroups (k_conv3h_pers: one workgroup per CU walks its tiles)
-    {128, 192, 6, 3},  // 64  32x32 planes, 4 rows x 192 couts per tile, persistent workgroups (two tiles per CU at batch 64)
-    {64, 96, 6, 3},    // 65  32x32 planes, 2 rows x 96 couts per tile (small batches)
-    {64, 96, 6, 3},    // 66  16x16 planes, 4 rows x 96 couts per tile (small batches)
-    {128, 48, 6, 3},   // 67  8x8 planes: TWO samples x 48 couts per tile (half the weight bytes per workgroup of 51; round 5)
-    {128, 48, 6, 3},   // 68  4x4 planes: EIGHT samples x 48 couts per tile
-};
-constexpr int kNumVariants = (int)(sizeof(kVariants) / sizeof(kVariants[0]));
+
+const ConvVariant* conv_variant(int id) {
+  for (const ConvVariant& v : kGemmVariants)
+    if (v.id == id) return &v;
+  return conv3h_variant(id);
+}
 
 template <typename T>
 static int epr() { return 4 * Mma<T>::EPC; }
@@ -1638,31 +1362,30 @@ static Plan make_plan(const afldm_conv_args* a, int elems_per_row) {
   //   M >= 4096, Cout % 128 == 0                           : 128x128
   //   M >= 1024                                            : 128x64
   // and split-K so that tiles * splitk ~ one resident set of workgroups.
-  int vid, bm, bn;
+  int vid;
   const int ksteps_all = a->KS * a->KS * (Ct / kstep);
   const long long tiles64 = ((M + 63) / 64) * ((a->Cout + 63) / 64);
   if (M <= 4096 && ((ksteps_all <= 64 && tiles64 >= 256 && !(a->Cout % 192 == 0 && ksteps_all >= 27 && M >= 4096)) ||
                     (ksteps_all <= 16 && tiles64 >= 128))) {
-    vid = 32; bm = 64; bn = 64;
+    vid = 32;
     // more than two resident rounds of 64x64 tiles (the q|k|v projection of the 4x4 level at batch 64: 576): 128x64
     // tiles halve the rounds (in situ 5.180 -> 5.159 ms/step; 128x128 / 128x192 with K slices measured slower)
-    if (a->KS == 1 && tiles64 >= 512 && M % 128 == 0) { vid = 31; bm = 128; bn = 64; }
+    if (a->KS == 1 && tiles64 >= 512 && M % 128 == 0) vid = 31;
   }
-  else if (M >= 32768 && a->Cout % 192 == 0) { vid = 29; bm = 128; bn = 192; }
-  else if (a->Cout % 192 == 0 && ((M >= 4096 && ksteps_all >= 27) || (M >= 1024 && ksteps_all >= 100))) { vid = 33; bm = 128; bn = 192; }
-  else if (M >= 4096 && a->Cout % 128 == 0 && a->KS > 1) { vid = 30; bm = 128; bn = 128; }
-  else if (M >= 1024) { vid = 31; bm = 128; bn = 64; }
-  else { vid = 32; bm = 64; bn = 64; }
+  else if (M >= 32768 && a->Cout % 192 == 0) vid = 29;
+  else if (a->Cout % 192 == 0 && ((M >= 4096 && ksteps_all >= 27) || (M >= 1024 && ksteps_all >= 100))) vid = 33;
+  else if (M >= 4096 && a->Cout % 128 == 0 && a->KS > 1) vid = 30;
+  else if (M >= 1024) vid = 31;
+  else vid = 32;
   const int ksteps = a->KS * a->KS * (Ct / kstep);
-  auto splitk_for = [&](int v) {
-    const int bm_ = kVariants[v].bm, bn_ = kVariants[v].bn;
-    const long long tiles = ((M + bm_ - 1) / bm_) * ((a->Cout + bn_ - 1) / bn_);
+  auto splitk_for = [&](int id) {
+    const ConvVariant& v = *conv_variant(id);
+    const long long tiles = ((M + v.bm - 1) / v.bm) * ((a->Cout + v.bn - 1) / v.bn);
     int sk = 1;
-    if (v == 56) return 1;
-    if (kVariants[v].ver == 6) {
-      // halo-patch kernel: the small-tile variants (51+) may split the CHANNEL BLOCKS over up to 4 slices when the
+    if (v.family == CONV_HALO) {
+      // halo-patch kernel: the small-tile variants may split the CHANNEL BLOCKS over up to 8 slices when the
       // tiles alone leave most CUs idle; the slice count must divide the number of 128-byte channel blocks
-      if (v < 51 || (v >= 57 && v != 65 && v != 66 && v != 67 && v != 68)) return 1;
+      if (!v.may_split) return 1;
       const int ncb = Ct / (2 * elems_per_row);
       int z = 1;
       static const int s_zmax = getenv("AFLDM_CONV3H_ZMAX") ? atoi(getenv("AFLDM_CONV3H_ZMAX")) : 8;      // (4 -> 8: batch 8 2.410 -> 2.378, batch 1 2.158 -> 2.134 ms/step, same box)
@@ -1676,7 +1399,7 @@ static Plan make_plan(const afldm_conv_args* a, int elems_per_row) {
       if (s_z1 && tiles >= 128 && elems_per_row == 32) z = 1;
       return z;
     }
-    if (kVariants[v].ver == 4 && kVariants[v].stages == 3 && bn_ == 192) {
+    if (v.producers) {
       // one 8-wave workgroup per CU: aim at 256 workgroups (measured best: 64 tiles -> 4, 128 tiles -> 2)
       sk = (int)((256 + tiles / 2) / tiles);
       int maxsk = ksteps / 8;
@@ -1698,18 +1421,14 @@ static Plan make_plan(const afldm_conv_args* a, int elems_per_row) {
   pl.splitk_auto = splitk_for(vid);
   // halo-patch kernel for the 3x3 convolutions of the 32x32 / 16x16 levels (conv3h.hip); support is checked by resolve_exec
   {
-    static const int s_h3 = getenv("AFLDM_CONV3H") ? atoi(getenv("AFLDM_CONV3H")) : 4;      // 0: off, 1: 32x32 / 16x16 only, 2: + variant 42 at 16x16, 3: + 8x8 / 4x4, 4: + small batches
+    static const int s_h3 = getenv("AFLDM_CONV3H") ? atoi(getenv("AFLDM_CONV3H")) : 4;      // 0: off, 1 / 2: 32x32 / 16x16 only, 3: + 8x8 / 4x4, 4: + small batches
     if (s_h3 && a->KS == 3 && a->C2 == 0 && a->H == a->W && a->Cout % 192 == 0) {
       // tile by plane size; the large tiles only while they still give every CU a workgroup
       const long long t256 = (M / 256) * (a->Cout / 192), t128 = (M / 128) * (a->Cout / 192);
       const bool bf = elems_per_row == 32;      // (64-byte row pieces: 32 bf16 / 16 fp32)
-      static const int s_co = getenv("AFLDM_CONV3H_CO") ? atoi(getenv("AFLDM_CONV3H_CO")) : 0;      // bit 0: 32x32 planes, bit 1: 16x16 planes on the two-per-CU tiles (A/B)
-      const long long t96 = (M / 128) * (a->Cout / 96);
-      if (bf && (s_co & 1) && a->W == 32 && t96 >= 512 && a->Cout % 96 == 0) vid = 61;
-      else if (bf && (s_co & 2) && a->W == 16 && t96 >= 512 && a->Cout % 96 == 0) vid = 62;
-      else if (a->W == 32 && t256 >= 192) vid = 41;
+      if (a->W == 32 && t256 >= 192) vid = 41;
       else if (a->W == 32 && t128 >= 192 && s_h3 >= 4 && bf) vid = 46;
-      else if (a->W == 16 && t128 >= 192) vid = s_h3 == 2 ? 42 : 43;      // 4 consumer waves (64x96) measured best at 16x16
+      else if (a->W == 16 && t128 >= 192) vid = 43;      // 4 consumer waves (64x96) measured best at 16x16
       else if (s_h3 >= 3 && a->W == 8 && M >= 2048 && a->Cout % 96 == 0) vid = 51;
       else if (s_h3 >= 3 && a->W == 4 && M >= 1024 && a->Cout % 96 == 0) vid = 52;
       else if (s_h3 >= 4 && bf && a->Cout % 96 == 0) {      // small batches (bf16; fp32 measured slower: 4.99 vs 4.38 ms/step at batch 1): the 96-cout tiles with split channel blocks
@@ -1737,18 +1456,8 @@ static Plan make_plan(const afldm_conv_args* a, int elems_per_row) {
     static const bool off = getenv("AFLDM_NO_CONV3H_SUB") != nullptr;
     if (!off && a->KS == 3 && a->C2 == 0 && a->W >= 64 && a->W % 32 == 0 && a->H % 8 == 0 && a->Cout % 128 == 0 &&
         Ct % (2 * elems_per_row) == 0 && M >= 256 * 192) {
-      static const int s_subv = getenv("AFLDM_CONV3H_SUBV") ? atoi(getenv("AFLDM_CONV3H_SUBV")) : 63;     // 58 / 59 / 60 / 63 (A/B)
-      vid = (s_subv >= 58 && s_subv <= 60) || s_subv == 63 ? s_subv : 58;
-      if (vid == 63 && !(elems_per_row == 32 && M / 256 * (a->Cout / 128) >= 512)) vid = 58;      // bf16; persistent tiles pay from two tiles per CU
+      vid = elems_per_row == 32 && M / 256 * (a->Cout / 128) >= 512 ? 63 : 58;      // bf16: persistent workgroups pay from two tiles per CU
     }
-  }
-  {
-    // a dense layer over <= 64 rows (the 3x3 convolutions of the 2x2 level in their flattened form at batch 64) on 96+
-    // 64x32 tiles that walk the whole K themselves (no slabs, no reduction launch): MEASURED SLOWER - 28.7 us kernel-only
-    // against 11.1 + 4.3 us for four slices of 64x64 tiles (a K step of this skinny tile costs ~0.6 us whatever the
-    // ring depth: 4 and 12 stages measure the same), 5.39 vs 5.26 ms/step.  Off unless AFLDM_DENSE_NOSPLIT is set.
-    static const bool off = getenv("AFLDM_DENSE_NOSPLIT") == nullptr;
-    if (!off && a->KS == 1 && a->H * a->W == 1 && M <= 64 && a->Cout >= 2048 && a->Cout % 32 == 0) vid = 56;
   }
   // in-situ tuning hook (tools/tune_insitu.py): AFLDM_CONV_OVERRIDE="M:Cout:KS:Ct=variant/splitk;..."
   int ov_sk = -1;
@@ -1758,7 +1467,7 @@ static Plan make_plan(const afldm_conv_args* a, int elems_per_row) {
       for (const char* q = ov; q && *q;) {
         long long m_ = 0; int co = 0, ks = 0, ct = 0, v = -1, sk_ = -1;
         if (sscanf(q, "%lld:%d:%d:%d=%d/%d", &m_, &co, &ks, &ct, &v, &sk_) == 6 && m_ == M && co == a->Cout && ks == a->KS &&
-            ct == Ct && v >= 0 && v < kNumVariants) {
+            ct == Ct && conv_variant(v)) {
           vid = v; ov_sk = sk_;
         }
         q = strchr(q, ';');
@@ -1766,7 +1475,7 @@ static Plan make_plan(const afldm_conv_args* a, int elems_per_row) {
       }
     }
   }
-  if (g_force_variant >= 0 && g_force_variant < kNumVariants) vid = g_force_variant;
+  if (g_force_variant >= 0) vid = g_force_variant;      // (afldm_conv2d_tune accepts live ids only)
   pl.cfg = vid;
   pl.splitk = splitk_for(vid);
   if (ov_sk >= 1) pl.splitk = ov_sk;
@@ -1774,128 +1483,13 @@ static Plan make_plan(const afldm_conv_args* a, int elems_per_row) {
   return pl;
 }
 
-template <typename T, int BM, int BN, int WGM, int WGN>
-static void launch_igemm(const ConvP& p0, hipStream_t st) {
-  ConvP p = p0;
-  constexpr int KCH = KCH_DEFAULT;
-  p.tiles_n = (p.Cout + BN - 1) / BN;
-  const int tiles_m = (p.M + BM - 1) / BM;
-  dim3 grid(tiles_m * p.tiles_n, 1, p.splitk);
-  constexpr int lds = 2 * KCH * (BM + BN) * 64;
-  static unsigned long long attr_set = 0;
-  if (first_on_device(attr_set)) {
-    (void)hipFuncSetAttribute((const void*)k_igemm<T, BM, BN, WGM, WGN, KCH>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  }
-  k_igemm<T, BM, BN, WGM, WGN, KCH><<<grid, WGM * WGN * 64, lds, st>>>(p);
-}
-
-template <typename T, int BM, int BN, int WGM, int WGN, int STAGES, int KCH = KCH_DEFAULT, int NPROD = 0, bool R128 = false, int MINW = 1>
-static void launch_igemm2(const ConvP& p0, hipStream_t st) {
-  ConvP p = p0;
-  p.ksteps = p0.ksteps * KCH_DEFAULT / KCH;     // p0.ksteps counts KCH_DEFAULT-wide steps
-  p.tiles_n = (p.Cout + BN - 1) / BN;
-  const int tiles_m = (p.M + BM - 1) / BM;
-  dim3 grid(tiles_m * p.tiles_n, 1, p.splitk);
-  constexpr int lds = STAGES * KCH * (BM + BN) * 64;
-  static unsigned long long attr_set = 0;
-  if (first_on_device(attr_set)) {
-    (void)hipFuncSetAttribute((const void*)k_igemm2<T, BM, BN, WGM, WGN, KCH, STAGES, NPROD, R128, MINW>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  }
-  k_igemm2<T, BM, BN, WGM, WGN, KCH, STAGES, NPROD, R128, MINW><<<grid, (WGM * WGN + NPROD) * 64, lds, st>>>(p);
-}
-
-
-template <typename T>
-static void launch_igemm3(const ConvP& p0, hipStream_t st) {
-  if constexpr (sizeof(T) == 2) {
-    constexpr int STAGES = 3;
-    ConvP p = p0;
-    p.tiles_n = p.Cout / 192;
-    const int tiles = (p.M / 128) * p.tiles_n;
-    constexpr int lds = STAGES * (128 + 192) * 128 + 4 * 32 * (96 + 8) * 2;
-    static unsigned long long attr_set = 0;
-    if (first_on_device(attr_set)) {
-      (void)hipFuncSetAttribute((const void*)k_igemm3<T, STAGES>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    }
-    k_igemm3<T, STAGES><<<tiles < 256 ? tiles : 256, 512, lds, st>>>(p);
-  }
-}
-
-// shapes the persistent-tile kernel covers
-template <typename T>
-static bool igemm3_ok(const afldm_conv_args* a) {
-  const int HW = a->H * a->W;
-  const int Ct = a->C1 + a->C2;
-  return sizeof(T) == 2 && a->out_mode == 0 && !a->y2 && HW % 128 == 0 && a->Cout % 192 == 0 && Ct % 64 == 0 &&
-         (a->C2 == 0 || a->C1 % 64 == 0) && a->y_ld % 8 == 0 && (!a->residual || a->res_ld % 4 == 0) &&
-         (!a->temb || (a->temb_stride % 4 == 0 && (a->temb_mod <= 0 || a->temb_mod % 4 == 0))) && aligned16(a->y) &&
-         (!a->bias || aligned16(a->bias));
-}
-
-template <typename T>
-static bool launch_variant(int id, const ConvP& p, hipStream_t st) {
-  if (id == 56) {
-    launch_igemm2<T, 64, 32, 2, 2, 12, 2, 0, true>(p, st);
-    return true;
-  }
-  if (id >= kConv3hFirst) {
-    conv3h_launch(id, (int)sizeof(T), p, st);
-    return true;
-  }
-  switch (id) {
-    case 40: launch_igemm3<T>(p, st); return true;
-    case 0: launch_igemm<T, 128, 128, 2, 2>(p, st); return true;
-    case 1: launch_igemm<T, 128, 64, 2, 2>(p, st); return true;
-    case 2: launch_igemm<T, 64, 128, 2, 2>(p, st); return true;
-    case 3: launch_igemm<T, 64, 64, 2, 2>(p, st); return true;
-    case 4: launch_igemm2<T, 128, 128, 2, 2, 2>(p, st); return true;
-    case 5: launch_igemm2<T, 128, 128, 2, 2, 3>(p, st); return true;
-    case 6: launch_igemm2<T, 128, 64, 2, 2, 2>(p, st); return true;
-    case 7: launch_igemm2<T, 128, 64, 2, 2, 3>(p, st); return true;
-    case 8: launch_igemm2<T, 128, 64, 2, 2, 4>(p, st); return true;
-    case 9: launch_igemm2<T, 64, 128, 2, 2, 3>(p, st); return true;
-    case 10: launch_igemm2<T, 64, 128, 2, 2, 4>(p, st); return true;
-    case 11: launch_igemm2<T, 64, 64, 2, 2, 4>(p, st); return true;
-    case 12: launch_igemm2<T, 128, 192, 2, 2, 2, KCH_DEFAULT, 0, false, 2>(p, st); return true;
-    case 13: launch_igemm2<T, 256, 64, 4, 1, 2>(p, st); return true;
-    case 14: launch_igemm2<T, 256, 64, 4, 1, 3>(p, st); return true;
-    case 15: launch_igemm2<T, 64, 64, 2, 2, 6>(p, st); return true;
-    case 16: launch_igemm2<T, 128, 192, 2, 2, 4, 1>(p, st); return true;
-    case 17: launch_igemm2<T, 128, 128, 2, 2, 4, 1>(p, st); return true;
-    case 18: launch_igemm2<T, 128, 192, 2, 2, 3, 1>(p, st); return true;
-    case 19: launch_igemm2<T, 128, 192, 2, 2, 2, 1>(p, st); return true;
-    case 20: launch_igemm2<T, 128, 128, 2, 2, 2, 1>(p, st); return true;
-    case 21: launch_igemm2<T, 128, 192, 2, 2, 2, 2, 4>(p, st); return true;
-    case 22: launch_igemm2<T, 128, 192, 2, 2, 3, 2, 4>(p, st); return true;
-    case 23: launch_igemm2<T, 128, 128, 2, 2, 2, 2, 4>(p, st); return true;
-    case 24: launch_igemm2<T, 128, 128, 2, 2, 3, 2, 4>(p, st); return true;
-    case 25: launch_igemm2<T, 128, 192, 2, 2, 2, 2, 2>(p, st); return true;
-    case 26: launch_igemm2<T, 256, 192, 4, 2, 2, 2, 4, true, 3>(p, st); return true;
-    case 27: launch_igemm2<T, 256, 128, 4, 2, 2, 2, 4>(p, st); return true;
-    case 28: launch_igemm2<T, 128, 64, 2, 2, 3, 2, 2>(p, st); return true;
-    case 29: launch_igemm2<T, 128, 192, 2, 2, 2, 2, 0, true, 2>(p, st); return true;
-    case 30: launch_igemm2<T, 128, 128, 2, 2, 2, 2, 0, true, 2>(p, st); return true;
-    case 31: launch_igemm2<T, 128, 64, 2, 2, 2, 2, 0, true, 3>(p, st); return true;
-    case 32: launch_igemm2<T, 64, 64, 2, 2, 4, 2, 0, true>(p, st); return true;
-    case 33: launch_igemm2<T, 128, 192, 2, 2, 3, 2, 4, true>(p, st); return true;
-    case 34: launch_igemm2<T, 128, 128, 2, 2, 2, 2, 4, true>(p, st); return true;
-    case 35: launch_igemm2<T, 128, 128, 2, 2, 3, 2, 0, true>(p, st); return true;
-    case 36: launch_igemm2<T, 256, 64, 4, 1, 2, 2, 0, true>(p, st); return true;
-    case 37: launch_igemm2<T, 64, 192, 2, 2, 2, 2, 0, true, 2>(p, st); return true;
-    case 38: launch_igemm2<T, 64, 128, 2, 2, 2, 2, 0, true, 2>(p, st); return true;
-    case 39: launch_igemm2<T, 64, 192, 2, 2, 3, 2, 0, true, 2>(p, st); return true;
-  }
-  return false;
-}
-
 // How afldm_conv2d will run a problem (shared by the dispatch and the host-side queries).
 struct Exec {
   Plan pl;
-  int vid;       // igemm variant actually launched
+  int vid;       // variant actually launched (a live id)
   int splitk;    // after the workspace check
   int fused;     // split-K slices reduced inside the GEMM launch (splitk_fused_reduce)
+  const ConvVariant& row() const { return *conv_variant(vid); }
 };
 
 static int device_cus() {
@@ -1923,14 +1517,7 @@ static Exec resolve_exec(const afldm_conv_args* a) {
   }
   const bool v2_ok = M * (a->C1 > a->C2 ? a->C1 : a->C2) * (long long)sizeof(T) < (1ll << 31) &&
                      (long long)a->Cout * a->KS * a->KS * Ct * (long long)sizeof(T) < (1ll << 31);
-  {
-    // persistent tiles (variant 40) where the 128x192 one-tile-per-slot kernel would run >= 2 rounds of tiles
-    static const int s_persist = getenv("AFLDM_PERSIST") ? atoi(getenv("AFLDM_PERSIST")) : 0;
-    const long long tiles = (M / 128) * (a->Cout / 192);
-    if (s_persist && e.vid == 29 && e.splitk == 1 && tiles >= 512 && igemm3_ok<T>(a)) e.vid = 40;
-    if (e.vid == 40 && (e.splitk != 1 || !igemm3_ok<T>(a))) e.vid = 29;
-  }
-  if (kVariants[e.vid].ver == 6) {
+  if (conv_variant(e.vid)->family == CONV_HALO) {
     ConvP q;
     memset(&q, 0, sizeof(q));
     q.x1 = a->x1; q.w = a->w; q.y = a->y; q.y2 = a->y2; q.residual = a->residual; q.temb = a->temb;
@@ -1938,7 +1525,7 @@ static Exec resolve_exec(const afldm_conv_args* a) {
     q.out_mode = a->out_mode; q.y_ld = a->y_ld; q.res_ld = a->res_ld; q.temb_stride = a->temb_stride;
     q.temb_mod = a->temb_mod > 0 ? a->temb_mod : a->Cout;
     q.splitk = e.splitk;               // (after the workspace check: a shape that needs its slices cannot run without them)
-    if (!conv3h_supported(e.vid, (int)sizeof(T), q)) {       // not this kernel's shape: the automatic choice
+    if (!conv3h_supported(*conv_variant(e.vid), (int)sizeof(T), q)) {       // not this kernel's shape: the automatic choice
       e.vid = e.pl.cfg_auto;
       e.splitk = e.pl.splitk_auto;
       if (e.splitk > 1) {
@@ -1947,7 +1534,7 @@ static Exec resolve_exec(const afldm_conv_args* a) {
       }
     }
   }
-  if (kVariants[e.vid].ver >= 2 && kVariants[e.vid].ver != 6 && !v2_ok) e.vid = kVariants[e.vid].bm == 128 ? (kVariants[e.vid].bn >= 128 ? 0 : 1) : 3;
+  if (const ConvVariant& v = *conv_variant(e.vid); v.family == CONV_IGEMM_DMA && !v2_ok) e.vid = v.bm == 128 ? (v.bn >= 128 ? 0 : 1) : 3;
   e.fused = 0;
   {
     // in-kernel split-K reduction: every workgroup of the launch must be resident (tiles * splitk <= CUs), the slice
@@ -1958,9 +1545,9 @@ static Exec resolve_exec(const afldm_conv_args* a) {
     // write-through stores are slower than plain ones, and every slice waits for the slowest.  The guide's verdict
     // for this seam (cut it) holds here; afldm_conv2d_fused_splitk(1) / AFLDM_FUSED_SPLITK=1 re-enable it.
     static const bool env_on = getenv("AFLDM_FUSED_SPLITK") && atoi(getenv("AFLDM_FUSED_SPLITK")) != 0;
-    const Variant& v = kVariants[e.vid];
+    const ConvVariant& v = *conv_variant(e.vid);
     const int HW = a->H * a->W, z = e.splitk;
-    if ((env_on || g_fused_splitk) && z > 1 && v.ver >= 2 && v.ver <= 4 && a->sync && a->sync_bytes >= 40960 && (z == 2 || z == 4 || z == 8) &&
+    if ((env_on || g_fused_splitk) && z > 1 && v.family == CONV_IGEMM_DMA && a->sync && a->sync_bytes >= 40960 && (z == 2 || z == 4 || z == 8) &&
         v.bm % z == 0 && a->out_mode == 0 && !a->y2 && a->Cout % 4 == 0 && a->y_ld % 4 == 0 &&
         (!a->residual || a->res_ld % 4 == 0) && (!a->temb || a->temb_stride % 4 == 0) &&
         (size_t)z * M * a->Cout * 4 < ((size_t)1 << 31)) {
@@ -2004,7 +1591,7 @@ static int stats_mode(const afldm_conv_args* a, const Exec& e, int* S) {
     return ST_EPILOGUE;
   }
   if (e.pl.kind == 0 && e.splitk > 1 && e.fused) {
-    const int rw = kVariants[e.vid].bm / e.splitk;
+    const int rw = e.row().bm / e.splitk;
     *S = rw >= HW ? 1 : HW / rw;
     return ST_FUSED;
   }
@@ -2012,20 +1599,16 @@ static int stats_mode(const afldm_conv_args* a, const Exec& e, int* S) {
     *S = reduce_stats_splits(HW);
     return ST_REDUCE;
   }
-  if (e.pl.kind == 0 && e.splitk == 1 && e.vid == 40) {
-    *S = (HW / 128) * 4;      // one split per (consumer row half, 32-row pass)
-    return ST_EPILOGUE;
-  }
-  if (e.pl.kind == 0 && e.splitk == 1 && kVariants[e.vid].ver >= 2 && HW % kVariants[e.vid].bm == 0 && vec16 &&
+  if (e.pl.kind == 0 && e.splitk == 1 && e.row().family != CONV_IGEMM && HW % e.row().bm == 0 && vec16 &&
       !getenv("AFLDM_CONV_NOSTAGE")) {
-    *S = HW / kVariants[e.vid].bm;
+    *S = HW / e.row().bm;
     return ST_EPILOGUE;
   }
-  if (sizeof(T) == 2 && e.pl.kind == 0 && e.splitk == 1 && kVariants[e.vid].ver == 6 && kVariants[e.vid].bm % HW == 0 && vec16) {
+  if (sizeof(T) == 2 && e.pl.kind == 0 && e.splitk == 1 && e.row().family == CONV_HALO && e.row().bm % HW == 0 && vec16) {
     *S = 1;           // halo-patch tiles of several whole samples (4x4 planes): one record per sample from the epilogue
     return ST_EPILOGUE;
   }
-  if (e.pl.kind == 0 && e.splitk == 1 && kVariants[e.vid].ver >= 2 && kVariants[e.vid].ver <= 4 && HW == 1 && vec16 &&
+  if (e.pl.kind == 0 && e.splitk == 1 && e.row().family == CONV_IGEMM_DMA && HW == 1 && vec16 &&
       !getenv("AFLDM_CONV_NOSTAGE")) {
     *S = 1;           // H * W == 1: a row is a sample, written straight from the epilogue (stats_multi 2)
     return ST_EPILOGUE;
@@ -2052,7 +1635,7 @@ extern "C" int afldm_gn_stats(const void* x, int C, float* stats, int B, int HW,
 template <typename T>
 static bool norm_fusable(const afldm_conv_args* a, const Exec& e, int smode) {
   if (sizeof(T) != 2 || e.pl.kind != 0 || e.splitk != 1 || smode != ST_EPILOGUE || !a->stats_out) return false;
-  if (e.vid != 51 && e.vid != 53) return false;
+  if (e.vid != 51) return false;
   if (a->H != 8 || a->W != 8 || a->out_mode != 0 || a->y2 || a->y_ld != a->Cout) return false;
   if (a->norm_groups <= 0 || a->Cout % a->norm_groups || !a->norm_gamma || !a->norm_beta) return false;
   const int cpg = a->Cout / a->norm_groups;
@@ -2119,8 +1702,8 @@ static int shortcut_ok(const afldm_conv_args* a) {
   if (M >= (1ll << 28) || M * cmax * (long long)sizeof(T) >= (1ll << 31) || (long long)a->Cout * Csc * (long long)sizeof(T) >= (1ll << 31)) return 0;
   if (lin_wreg_bm(a) || skinny_stats_splits(a)) return 0;
   const Exec ex = resolve_exec<T>(a);
-  if (ex.pl.kind != 0 || kVariants[ex.vid].ver != 6 || ex.fused || !conv3h_shortcut_ok(ex.vid)) return 0;
-  if (conv3h_taps_per_step(ex.vid) == 3) return (a->defer_reduce && ex.splitk == 1) ? 0 : 2;     // (deferred: there must be slabs to hand over)
+  if (ex.pl.kind != 0 || ex.fused || !ex.row().folds_shortcut) return 0;
+  if (ex.row().tps == 3) return (a->defer_reduce && ex.splitk == 1) ? 0 : 2;     // (deferred: there must be slabs to hand over)
   return (ex.splitk == 1 && !a->defer_reduce && !a->y_norm) ? 1 : 0;
 }
 
@@ -2133,12 +1716,12 @@ static bool c8_ok(const afldm_conv_args* a) {
   //  afldm_conv2d_c8_ok checks the batch chunking)
   if (a->w_batch_stride || a->defer_reduce || a->KS != 3 || lin_wreg_bm(a) || skinny_stats_splits(a)) return false;
   const Exec ex = resolve_exec<T>(a);
-  if (ex.pl.kind != 0 || kVariants[ex.vid].ver != 6 || ex.splitk != 1 || ex.fused) return false;
+  if (ex.pl.kind != 0 || ex.row().family != CONV_HALO || ex.splitk != 1 || ex.fused) return false;
   if (a->stats_out) {
     int S = 0;
     if (stats_mode<T>(a, ex, &S) != ST_EPILOGUE) return false;
   }
-  return a->H == a->W && a->W <= 32 && a->H * a->W >= kVariants[ex.vid].bm;
+  return a->H == a->W && a->W <= 32 && a->H * a->W >= ex.row().bm;
 }
 
 template <typename T>
@@ -2194,7 +1777,7 @@ static int conv_dispatch(const afldm_conv_args* a, hipStream_t st) {
     p.splitk = ex.splitk;
     if (smode == ST_EPILOGUE) {
       p.stats_out = a->stats_out;
-      p.stats_multi = (a->H * a->W) == 1 ? 2 : (a->H * a->W) < kVariants[ex.vid].bm ? 1 : 0;
+      p.stats_multi = (a->H * a->W) == 1 ? 2 : (a->H * a->W) < ex.row().bm ? 1 : 0;
     }
     p.sync = ex.fused ? a->sync : nullptr;
     if (ex.fused && smode == ST_FUSED) p.stats_out = a->stats_out;
@@ -2204,17 +1787,16 @@ static int conv_dispatch(const afldm_conv_args* a, hipStream_t st) {
       p.ncpg = a->Cout / a->norm_groups; p.neps = a->norm_eps;
     }
     if (a->w_batch_stride) {      // per-sample weights: the LDS-DMA GEMM only, whole tiles inside a sample, K not split
-      const int ver = kVariants[ex.vid].ver;
-      AFLDM_REQUIRE(ver >= 2 && ver <= 4 && p.splitk == 1 && (a->H * a->W) % kVariants[ex.vid].bm == 0, AFLDM_ESHAPE,
+      AFLDM_REQUIRE(ex.row().family == CONV_IGEMM_DMA && p.splitk == 1 && (a->H * a->W) % ex.row().bm == 0, AFLDM_ESHAPE,
                     "afldm_conv2d: w_batch_stride needs H*W a multiple of the %d-row tile of variant %d and no split-K",
-                    kVariants[ex.vid].bm, ex.vid);
+                    ex.row().bm, ex.vid);
     }
     {
       // weights that exactly one workgroup per (cout tile, K slice) reads - a single row tile - stream non-temporally
       static const bool s_nt = !(getenv("AFLDM_NT_WEIGHTS") && atoi(getenv("AFLDM_NT_WEIGHTS")) == 0);
-      p.w_nt = (s_nt && !a->w_batch_stride && p.M <= kVariants[ex.vid].bm) ? 1 : 0;
+      p.w_nt = (s_nt && !a->w_batch_stride && p.M <= ex.row().bm) ? 1 : 0;
     }
-    launch_variant<T>(ex.vid, p, st);
+    (sizeof(T) == 2 ? ex.row().bf16 : ex.row().f32)(p, st);
     rc = check_launch("afldm_conv2d(igemm)");
     if (rc) return rc;
     if (p.splitk > 1 && !ex.fused && a->defer_reduce) return AFLDM_OK;      // the caller's consumer finishes the slabs (afldm_af_act_slabs)
@@ -2277,7 +1859,7 @@ static int conv_validate(const afldm_conv_args* a) {
 using namespace afldm;
 
 extern "C" int afldm_conv2d_tune(int variant, int splitk) {
-  AFLDM_REQUIRE(variant < kNumVariants, AFLDM_ESHAPE, "afldm_conv2d_tune: variant %d out of range (%d)", variant, kNumVariants);
+  AFLDM_REQUIRE(variant < 0 || conv_variant(variant), AFLDM_ESHAPE, "afldm_conv2d_tune: no variant %d (ids are sparse: see the variant rows in conv.hip and conv3h.hip)", variant);
   g_force_variant = variant;
   g_force_splitk = splitk;
   return AFLDM_OK;
@@ -2318,14 +1900,14 @@ static bool plan_h3(const afldm_conv_args* a, ConvP& p, int& vid) {
   if (lin_wreg_bm(a) || skinny_stats_splits(a)) return false;
   fill_convp<T>(a, p);
   const Exec ex = resolve_exec<T>(a);
-  if (ex.pl.kind != 0 || kVariants[ex.vid].ver != 6 || ex.splitk != 1 || ex.fused) return false;
+  if (ex.pl.kind != 0 || ex.row().family != CONV_HALO || ex.splitk != 1 || ex.fused) return false;
   p.stats_out = nullptr;
   p.stats_S = 1;
   p.stats_multi = 0;
   if (a->stats_out) {
     if (stats_mode<T>(a, ex, &p.stats_S) != ST_EPILOGUE) return false;
     p.stats_out = a->stats_out;
-    p.stats_multi = (a->H * a->W) == 1 ? 2 : (a->H * a->W) < kVariants[ex.vid].bm ? 1 : 0;
+    p.stats_multi = (a->H * a->W) == 1 ? 2 : (a->H * a->W) < ex.row().bm ? 1 : 0;
   }
   p.ksteps = 9 * ((a->C1 + a->C2) / (KCH_DEFAULT * epr<T>()));
   p.splitk = 1;

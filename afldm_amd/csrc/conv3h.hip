@@ -22,10 +22,8 @@
 // A ds_read_b128 is served in 16-lane groups made of 8 rows of lane group lg and 8 rows of lg ^ 1: bit 2 of the
 // position separates the two halves, and 4 rows of equal parity inside ANY run of 16 consecutive rows differ in
 // (q >> 1) & 3 - so the fragment reads are bank-conflict free for every tap shift of the patch (the swizzle of
-// k_igemm2, (q >> 1) & 7 on all three bits, is only conflict free for 16-aligned runs).  With 32x32x16 MFMAs a 16-lane
-// read group lies inside one 32-row fragment half (rows {0-3, 12-15, 20-27} + base, one chunk): there the plain
-// position c ^ ((q >> 1) & 7) is conflict free for every shift.  An LDS-DMA writes lane-linearly, so the permutation
-// is applied to the per-lane SOURCE chunk (guide rule 21).
+// k_igemm2, (q >> 1) & 7 on all three bits, is only conflict free for 16-aligned runs).  An LDS-DMA writes lane-linearly,
+// so the permutation is applied to the per-lane SOURCE chunk (guide rule 21).
 //
 // The residual enters through the ACCUMULATORS during the first K steps (fragment layout: its load latency runs under
 // MFMA work).  Epilogue: (residual + sum) + (bias + temb) in fp32, one rounding; bf16 tiles are staged ONCE in bf16
@@ -37,8 +35,8 @@
 
 namespace afldm {
 
-template <typename T, int BM, int W_, int BN, int WGM, int WGN, int NPROD, int STAGES, int MINW, int MF, int TPS, bool SUB = false>
-__global__ void __launch_bounds__((WGM * WGN + NPROD) * 64, MINW) k_conv3h(ConvP p) {
+template <typename T, int BM, int W_, int BN, int WGM, int WGN, int NPROD, int TPS, bool SUB>
+__global__ void __launch_bounds__((WGM * WGN + NPROD) * 64, (WGM * WGN + NPROD + 3) / 4) k_conv3h(ConvP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
 #define H3_BX blockIdx.x
 #define H3_NBX gridDim.x
@@ -54,7 +52,7 @@ __global__ void __launch_bounds__((WGM * WGN + NPROD) * 64, MINW) k_conv3h(ConvP
 }
 
 // ----------------------------------------------------------------------------------------------- persistent tiles
-// k_conv3h_pers (round 4): the halo-patch kernel with PERSISTENT workgroups for layers that give a CU several tiles (the
+// k_conv3h_pers (round 4): the halo-patch kernel on blocks of a larger plane (k_conv3h's SUB form) with PERSISTENT workgroups for layers that give a CU several tiles (the
 // AF-VAE's 64^2 .. 256^2 planes: 4 .. 64 tiles of 256 x 128 per CU; 128 -> 128 channels are only 18 K steps per tile, next
 // to ~16 us of launch + first-patch latency + epilogue per one-tile workgroup).  One workgroup per CU walks tiles
 // l, l + grid, ...; the LDS-DMA producers never stop at a tile boundary:
@@ -66,12 +64,12 @@ __global__ void __launch_bounds__((WGM * WGN + NPROD) * 64, MINW) k_conv3h(ConvP
 // The consumers therefore find their operands waiting when they come out of an epilogue, and an epilogue's stores drain
 // under the next tile's K loop.  bf16, 16x16x32 MFMAs, one tap per step, whole K per workgroup (no split-K); same
 // rounding points, statistics records and tile shapes as k_conv3h.
-template <int BM, int W_, int BN, int WGM, int WGN, bool SUB>
+template <int BM, int W_, int BN, int WGM, int WGN>
 __global__ void __launch_bounds__((WGM * WGN + 4) * 64, (WGM * WGN + 4 + 3) / 4) k_conv3h_pers(ConvP p) {
   typedef bf16 T;
   typedef Mma<T> MM;
   typedef typename MM::Chunk Chunk;
-  constexpr int MF = 16, NPROD = 4, STAGES = 3;
+  constexpr int MF = kH3MF, NPROD = 4, STAGES = kH3Stages;
   constexpr int NWC = WGM * WGN;
   constexpr int EPC = MM::EPC, KSTEP = 8 * EPC, ESZ = 2;
   constexpr int WMS = BM / WGM, WNS = BN / WGN, TM = WMS / MF, TN = WNS / MF;
@@ -103,8 +101,8 @@ __global__ void __launch_bounds__((WGM * WGN + 4) * 64, (WGM * WGN + 4 + 3) / 4)
   const int nmine = l < tiles ? (tiles - l + (int)gridDim.x - 1) / (int)gridDim.x : 0;
   const int tile_n = l % p.tiles_n;                             // (gridDim.x is a multiple of tiles_n: constant per workgroup)
   const int n0 = tile_n * BN;
-  const int Ct = p.C1, HW = SUB ? p.H * p.W : W_ * W_;
-  const int ncb = Ct / KSTEP, G = ncb * SPC;
+  const int Ct = p.C1, HW = p.H * p.W;
+  const int ncb = Ct / KSTEP;
   const bool has_stats = p.stats_out != nullptr;
   const int nepb = 1 + 2 * PASSES + (has_stats ? 2 : 0);        // workgroup barriers of one epilogue (both roles count them)
 
@@ -112,21 +110,13 @@ __global__ void __launch_bounds__((WGM * WGN + 4) * 64, (WGM * WGN + 4 + 3) / 4)
   auto geo = [&](int i) {                                        // i-th tile of this workgroup
     const int tile = l + i * (int)gridDim.x, tm = tile / p.tiles_n;
     TileGeo g;
-    if constexpr (SUB) {
-      const int tw = p.W / W_, tps = (p.H / ROWS) * tw;
-      g.b = tm / tps;
-      g.sp = tm - g.b * tps;
-      const int ty = g.sp / tw;
-      g.oh0 = ty * ROWS;
-      g.ow0 = (g.sp - ty * tw) * W_;
-      g.m0 = g.b * HW + g.oh0 * p.W + g.ow0;
-    } else {
-      g.m0 = tm * BM;
-      g.b = g.m0 / HW;
-      g.oh0 = (g.m0 - g.b * HW) / W_;
-      g.ow0 = 0;
-      g.sp = (g.m0 - g.b * HW) / BM;
-    }
+    const int tw = p.W / W_, tps = (p.H / ROWS) * tw;
+    g.b = tm / tps;
+    g.sp = tm - g.b * tps;
+    const int ty = g.sp / tw;
+    g.oh0 = ty * ROWS;
+    g.ow0 = (g.sp - ty * tw) * W_;
+    g.m0 = g.b * HW + g.oh0 * p.W + g.ow0;
     return g;
   };
 
@@ -139,7 +129,7 @@ __global__ void __launch_bounds__((WGM * WGN + 4) * 64, (WGM * WGN + 4 + 3) / 4)
     for (int i = 0; i < WPW; ++i) {
       const int j = wave + NPROD * i;
       const int r = 8 * j + (lane >> 3);
-      const int c = h_chunk_at<MF>(lane & 7, h_sw_rows<MF>(r));
+      const int c = h_chunk_at(lane & 7, h_sw_rows(r));
       woff[i] = ((unsigned)(n0 + r) * 9u * (unsigned)Ct + (unsigned)(c * EPC)) * ESZ;
     }
     // patch DMA of the i-th tile's channel block cb into patch buffer `buf`
@@ -152,19 +142,11 @@ __global__ void __launch_bounds__((WGM * WGN + 4) * 64, (WGM * WGN + 4 + 3) / 4)
         int j = wave + NPROD * k;
         if (j > NPI - 1) j = NPI - 1;                              // (short shares re-issue the last instruction: uniform vmcnt counts)
         const int q = 8 * j + (lane >> 3);
-        const int c = h_chunk_at<MF>(lane & 7, h_sw_patch<MF, W_>(q));
+        const int c = h_chunk_at(lane & 7, h_sw_patch<W_>(q));
         const int pr = q / PW, pc = q - pr * PW;
-        const int ih = g.oh0 + pr - 1;
-        bool ok;
-        int pixel;
-        if constexpr (SUB) {
-          const int iw = g.ow0 + pc - 1;
-          ok = q < NPQ && iw >= 0 && iw < p.W && ih >= 0 && ih < p.H;
-          pixel = g.b * HW + ih * p.W + iw;
-        } else {
-          ok = q < NPQ && pc >= 1 && pc <= W_ && ih >= 0 && ih < W_;
-          pixel = g.m0 + (pr - 1) * W_ + (pc - 1);
-        }
+        const int ih = g.oh0 + pr - 1, iw = g.ow0 + pc - 1;
+        const bool ok = q < NPQ && iw >= 0 && iw < p.W && ih >= 0 && ih < p.H;
+        const int pixel = g.b * HW + ih * p.W + iw;
         const unsigned off = ok ? ((unsigned)pixel * (unsigned)Ct + (unsigned)(c * EPC)) * ESZ : OOB;
         lds_ptr_t dst = (lds_ptr_t)(sbase + j * 1024);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, dst, 16, (int)off, (int)so, 0, 0);
@@ -228,8 +210,8 @@ __global__ void __launch_bounds__((WGM * WGN + 4) * 64, (WGM * WGN + 4 + 3) / 4)
     const int r = pix / W_, c = pix - r * W_;
     qb[t] = r * PW + c;
   }
-  auto frag_off = [&](int q) { return q * 128 + (h_pos<MF>(lg, h_sw_patch<MF, W_>(q)) << 4); };
-  const int a_off0 = (wn * WNS + li) * 128 + (h_pos<MF>(lg, h_sw_rows<MF>(wn * WNS + li)) << 4);
+  auto frag_off = [&](int q) { return q * 128 + (h_pos(lg, h_sw_patch<W_>(q)) << 4); };
+  const int a_off0 = (wn * WNS + li) * 128 + (h_pos(lg, h_sw_rows(wn * WNS + li)) << 4);
   auto cout_of = [&](int tn) { return n0 + wn * WNS + tn * MF + 4 * lg; };
   typedef __attribute__((ext_vector_type(4))) T Quad;
   const T* temb = (const T*)p.temb;
@@ -238,10 +220,7 @@ __global__ void __launch_bounds__((WGM * WGN + 4) * 64, (WGM * WGN + 4 + 3) / 4)
 
   for (int i = 0; i < nmine; ++i) {
     const TileGeo tg = geo(i);
-    auto gpix = [&](int tp) -> int {
-      if constexpr (SUB) return tg.m0 + (tp / W_) * p.W + (tp % W_);
-      else return tg.m0 + tp;
-    };
+    auto gpix = [&](int tp) -> int { return tg.m0 + (tp / W_) * p.W + (tp % W_); };
     f32x4 acc[TN][TM];
 #pragma unroll
     for (int a = 0; a < TN; ++a)
@@ -412,97 +391,9 @@ __global__ void __launch_bounds__((WGM * WGN + 4) * 64, (WGM * WGN + 4 + 3) / 4)
 }
 
 // ----------------------------------------------------------------------------------------------- host side
-struct H3Variant {
-  int bm, w, bn, wgm, wgn, mf, tps;
-  int sub;     // 1: a tile is a (bm / w) x w block of a LARGER plane (p.W % w == 0, p.H % (bm / w) == 0)
-};
-// ids kConv3hFirst + index
-static const H3Variant kH3[] = {
-    {256, 32, 192, 4, 2, 16, 1},   // 41: 32x32 planes, 8 rows per tile; 8 consumer waves (64 x 96 each) + 4 producers
-    {128, 16, 192, 2, 4, 16, 1},   // 42: 16x16 planes, 8 rows per tile; 8 consumers (64 x 48) + 4 producers
-    {128, 16, 192, 2, 2, 16, 1},   // 43: 16x16 planes; 4 consumers (64 x 96) + 4 producers
-    {256, 16, 192, 4, 2, 16, 1},   // 44: 16x16 planes, whole sample per tile
-    {128, 32, 192, 2, 4, 16, 1},   // 45: 32x32 planes, 4 rows per tile
-    {128, 32, 192, 2, 2, 16, 1},   // 46
-    {256, 32, 192, 4, 2, 32, 1},   // 47: as 41 on 32x32x16 MFMAs
-    {128, 16, 192, 2, 2, 32, 1},   // 48: as 43 on 32x32x16 MFMAs
-    {256, 16, 192, 4, 2, 32, 1},   // 49: as 44 on 32x32x16 MFMAs
-    {128, 32, 192, 2, 2, 32, 1},   // 50: as 46 on 32x32x16 MFMAs
-    {64, 8, 96, 2, 2, 16, 3},      // 51: 8x8 planes, one sample x 96 couts per tile, 3 taps per step, no split-K
-    {64, 4, 96, 2, 2, 16, 3},      // 52: 4x4 planes, four samples x 96 couts per tile, 3 taps per step, split-K 2
-    {64, 8, 96, 2, 2, 16, 3},      // 53: (= 51; a 192-cout tile with 3 taps per step does not fit the LDS)
-    {128, 16, 96, 2, 2, 16, 3},    // 54: 16x16 planes, 8 rows x 96 couts, 3 taps per step (small batches)
-    {128, 32, 96, 2, 2, 16, 3},    // 55: 32x32 planes, 4 rows x 96 couts (small batches)
-    {0, 0, 0, 0, 0, 0, 0},         // 56: (implicit-GEMM variant, conv.hip)
-    {256, 32, 192, 4, 2, 16, 1},   // 57: as 41 with a 2-deep weight ring (lookahead experiment)
-    {256, 32, 128, 4, 2, 16, 1, 1},   // 58: planes of 64^2 and up (AF-VAE): 8 x 32 pixel blocks x 128 couts, 8 + 4 waves
-    {256, 32, 128, 2, 2, 16, 1, 1},   // 59: as 58 with 4 consumer waves (128 x 64 each) + 4 producers
-    {256, 32, 128, 4, 2, 32, 1, 1},   // 60: as 58 on 32x32x16 MFMAs
-    // Two workgroups in flight per CU: 128 x 96 tiles, 4 consumer waves (64 x 48) + 2 producers, 2-deep
-    // weight ring: 72 - 78 KB of LDS and <= 168 VGPRs, so that one workgroup's prologue / epilogue runs under the other's K loop
-    {128, 32, 96, 2, 2, 16, 1},       // 61: 32x32 planes, 4 rows x 96 couts
-    {128, 16, 96, 2, 2, 16, 1},       // 62: 16x16 planes, 8 rows x 96 couts
-    // Persistent workgroups (k_conv3h_pers, round 4): one workgroup per CU walks several tiles, the LDS-DMA producers run on
-    // across tile boundaries (bf16, whole K per workgroup)
-    {256, 32, 128, 4, 2, 16, 1, 1},   // 63: as 58 (AF-VAE planes of 64^2 and up)
-    {128, 32, 192, 2, 2, 16, 1},      // 64: 32x32 planes, 4 rows per tile: two tiles per CU at batch 64
-    // Small batches (round 4): 64-pixel tiles, so that batch 8 still gives every CU a workgroup at the 32^2 / 16^2 levels
-    {64, 32, 96, 2, 2, 16, 3},        // 65: 32x32 planes, 2 rows x 96 couts, 3 taps per step
-    {64, 16, 96, 2, 2, 16, 3},        // 66: 16x16 planes, 4 rows x 96 couts
-    // Fewer weight bytes per workgroup at the low levels (round 5): the 8^2 / 4^2 convolutions are bound by the ~100 GB/s a CU pulls
-    // through LDS-DMA (741 KB per workgroup and launch, profiles/r02/small_tile_step_decomposition.txt); 128-pixel x 48-cout tiles
-    // stream half the weights and twice the (small) patch: 91 instead of 128 KB per channel block
-    {128, 8, 48, 4, 1, 16, 3},        // 67: 8x8 planes, two samples x 48 couts
-    {128, 4, 48, 4, 1, 16, 3},        // 68: 4x4 planes, eight samples x 48 couts
-};
-constexpr int kNumH3 = (int)(sizeof(kH3) / sizeof(kH3[0]));
-
-int conv3h_tile(int variant, int* bm, int* bn) {
-  const int k = variant - kConv3hFirst;
-  if (k < 0 || k >= kNumH3) return 0;
-  *bm = kH3[k].bm;
-  *bn = kH3[k].bn;
-  return 1;
-}
-
-bool conv3h_supported(int variant, int dtype_size, const ConvP& p) {
-  const int k = variant - kConv3hFirst;
-  if (k < 0 || k >= kNumH3) return false;
-  const H3Variant& v = kH3[k];
-  if (v.bm == 0) return false;
-  const int kstep = 128 / dtype_size;
-  const int eo = 16 / dtype_size;
-  const int HW = p.H * p.W;
-  const int z = p.splitk > 0 ? p.splitk : 1;
-  const bool tile_ok = HW % v.bm == 0 || (v.bm % HW == 0 && (z > 1 || dtype_size == 2));    // several samples per tile: as split-K slabs, or (bf16) through the per-sample epilogue
-  const bool plane_ok = v.sub ? (p.W > v.w && p.W % v.w == 0 && p.H % (v.bm / v.w) == 0 && z == 1) : (p.W == v.w && p.H == p.W && tile_ok);
-  if ((k == 22 || k == 23) && !(dtype_size == 2 && z == 1 && HW % v.bm == 0 && p.C1 / kstep >= 2 && (!p.temb || p.temb_mod > 0))) return false;   // persistent variants
-  if (k >= 24 && dtype_size != 2) return false;                                      // 65 / 66: bf16 instantiations only
-  return p.KS == 3 && p.C2 == 0 && plane_ok && p.M % v.bm == 0 && p.Cout % v.bn == 0 &&
-         p.C1 % kstep == 0 && (p.C1 / kstep) % z == 0 && p.out_mode == 0 && !p.y2 && p.y_ld % eo == 0 &&
-         (!p.residual || p.res_ld % eo == 0) && (!p.temb || (p.temb_stride % eo == 0 && p.temb_mod % eo == 0)) &&
-         (long long)p.M * p.C1 * dtype_size < (1ll << 31) && (long long)p.Cout * 9 * p.C1 * dtype_size < (1ll << 31) &&
-         p.Cout % 4 == 0 && aligned16(p.y) && aligned16(p.x1) && aligned16(p.w);
-}
-
-// the folded 1x1 shortcut (ConvP.sc_*) runs as centre-tap K steps of one channel block each: k_conv3h variants over whole planes,
-// with one tap per step (whole K per workgroup) or three (split-K allowed: a slice takes its share of the shortcut blocks)
-bool conv3h_shortcut_ok(int variant) {
-  const int k = variant - kConv3hFirst;
-  if (k < 0 || k >= kNumH3 || k == 22 || k == 23) return false;       // (22 / 23: k_conv3h_pers)
-  const H3Variant& v = kH3[k];
-  return v.bm != 0 && !v.sub && !(v.bm == 256 && v.w == 16) && !(v.tps == 3 && v.bn == 48);      // (the HAS_SC condition of conv3h_body.inc)
-}
-
-int conv3h_taps_per_step(int variant) {
-  const int k = variant - kConv3hFirst;
-  return (k < 0 || k >= kNumH3) ? 0 : kH3[k].tps;
-}
-
-template <typename T, int BM, int W_, int BN, int WGM, int WGN, int MF, int TPS, int STAGES = 3, bool SUB = false, int NPROD = 4, int MINW_ = 0>
+template <typename T, int BM, int W_, int BN, int WGM, int WGN, int TPS, bool SUB, int NPROD>
 static void launch_h3(const ConvP& p0, hipStream_t st) {
-  constexpr int NWC = WGM * WGN;
-  constexpr int MINW = MINW_ > 0 ? MINW_ : (NWC + NPROD + 3) / 4;
+  constexpr int NWC = WGM * WGN, STAGES = kH3Stages;
   constexpr int ROWS = BM / W_, SEG = ROWS < W_ ? ROWS : W_, NSEG = ROWS / SEG;
   constexpr int NPI = (NSEG * (SEG + 2) * (W_ + 2) + 7) / 8;
   constexpr int lds = 2 * NPI * 1024 + STAGES * TPS * BN * 128;
@@ -525,7 +416,7 @@ static void launch_h3(const ConvP& p0, hipStream_t st) {
     if (s_gn >= 0) best = (s_gn == 0 || (tiles % 8 == 0 && p.tiles_n % s_gn == 0 && 8 % s_gn == 0 && tiles_m % (8 / s_gn) == 0)) ? s_gn : 0;
     p.xcd_gn = best;
   }
-  auto kern = k_conv3h<T, BM, W_, BN, WGM, WGN, NPROD, STAGES, MINW, MF, TPS, SUB>;
+  auto kern = k_conv3h<T, BM, W_, BN, WGM, WGN, NPROD, TPS, SUB>;
   static unsigned long long attr_set = 0;
   if (first_on_device(attr_set)) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -533,35 +424,7 @@ static void launch_h3(const ConvP& p0, hipStream_t st) {
   kern<<<dim3(tiles, 1, p.splitk), (NWC + NPROD) * 64, lds, st>>>(p);
 }
 
-template <typename T>
-static void launch_h3_variant(int k, const ConvP& p, hipStream_t st) {
-  switch (k) {
-    case 0: launch_h3<T, 256, 32, 192, 4, 2, 16, 1>(p, st); break;
-    case 1: launch_h3<T, 128, 16, 192, 2, 4, 16, 1>(p, st); break;
-    case 2: launch_h3<T, 128, 16, 192, 2, 2, 16, 1>(p, st); break;
-    case 3: launch_h3<T, 256, 16, 192, 4, 2, 16, 1>(p, st); break;
-    case 4: launch_h3<T, 128, 32, 192, 2, 4, 16, 1>(p, st); break;
-    case 5: launch_h3<T, 128, 32, 192, 2, 2, 16, 1>(p, st); break;
-    case 6: launch_h3<T, 256, 32, 192, 4, 2, 32, 1>(p, st); break;
-    case 7: launch_h3<T, 128, 16, 192, 2, 2, 32, 1>(p, st); break;
-    case 8: launch_h3<T, 256, 16, 192, 4, 2, 32, 1>(p, st); break;
-    case 9: launch_h3<T, 128, 32, 192, 2, 2, 32, 1>(p, st); break;
-    case 10: launch_h3<T, 64, 8, 96, 2, 2, 16, 3>(p, st); break;
-    case 11: launch_h3<T, 64, 4, 96, 2, 2, 16, 3>(p, st); break;
-    case 12: launch_h3<T, 64, 8, 96, 2, 2, 16, 3>(p, st); break;
-    case 13: launch_h3<T, 128, 16, 96, 2, 2, 16, 3>(p, st); break;
-    case 14: launch_h3<T, 128, 32, 96, 2, 2, 16, 3>(p, st); break;
-    case 15: break;                                                   // (id 56 is an implicit-GEMM variant, conv.hip)
-    case 16: launch_h3<T, 256, 32, 192, 4, 2, 16, 1, 2>(p, st); break;  // 57: as 41 with a 2-deep weight ring (lookahead experiment)
-    case 17: launch_h3<T, 256, 32, 128, 4, 2, 16, 1, 3, true>(p, st); break;   // 58: sub-tiled large planes
-    case 18: launch_h3<T, 256, 32, 128, 2, 2, 16, 1, 3, true>(p, st); break;   // 59
-    case 19: launch_h3<T, 256, 32, 128, 4, 2, 32, 1, 3, true>(p, st); break;   // 60
-    case 20: launch_h3<T, 128, 32, 96, 2, 2, 16, 1, 2, false, 2, 3>(p, st); break;   // 61: two workgroups per CU
-    case 21: launch_h3<T, 128, 16, 96, 2, 2, 16, 1, 2, false, 2, 3>(p, st); break;   // 62
-  }
-}
-
-template <int BM, int W_, int BN, int WGM, int WGN, bool SUB>
+template <int BM, int W_, int BN, int WGM, int WGN>
 static void launch_h3_pers(const ConvP& p0, hipStream_t st) {
   constexpr int ROWS = BM / W_, NPI = ((ROWS + 2) * (W_ + 2) + 7) / 8;
   constexpr int lds = 2 * NPI * 1024 + 3 * BN * 128;
@@ -580,7 +443,7 @@ static void launch_h3_pers(const ConvP& p0, hipStream_t st) {
   int grid = tiles < cus ? tiles : cus;
   grid -= grid % p.tiles_n;                                    // a workgroup keeps its n tile (constant weight offsets)
   if (grid < p.tiles_n) grid = p.tiles_n;
-  auto kern = k_conv3h_pers<BM, W_, BN, WGM, WGN, SUB>;
+  auto kern = k_conv3h_pers<BM, W_, BN, WGM, WGN>;
   static unsigned long long attr_set = 0;
   if (first_on_device(attr_set)) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -588,16 +451,62 @@ static void launch_h3_pers(const ConvP& p0, hipStream_t st) {
   kern<<<dim3(grid, 1, 1), (WGM * WGN + 4) * 64, lds, st>>>(p);
 }
 
-void conv3h_launch(int variant, int dtype_size, const ConvP& p, hipStream_t st) {
-  const int k = variant - kConv3hFirst;
-  if (k == 22) { launch_h3_pers<256, 32, 128, 4, 2, true>(p, st); return; }
-  if (k == 23) { launch_h3_pers<128, 32, 192, 2, 2, false>(p, st); return; }
-  if (k == 24) { launch_h3<bf16, 64, 32, 96, 2, 2, 16, 3>(p, st); return; }
-  if (k == 25) { launch_h3<bf16, 64, 16, 96, 2, 2, 16, 3>(p, st); return; }
-  if (k == 26) { launch_h3<bf16, 128, 8, 48, 4, 1, 16, 3, 3, false, 2>(p, st); return; }
-  if (k == 27) { launch_h3<bf16, 128, 4, 48, 4, 1, 16, 3, 3, false, 2>(p, st); return; }
-  if (dtype_size == 2) launch_h3_variant<bf16>(k, p, st);
-  else launch_h3_variant<float>(k, p, st);
+// A row from the arguments that instantiate its launchers (F32 = false: bf16 instantiation only).  The small tiles with three
+// taps per step are the ones the planner may split over the channel blocks when the tiles alone leave most CUs idle.
+template <int BM, int W_, int BN, int WGM, int WGN, int TPS, bool SUB = false, int NPROD = 4, bool F32 = true>
+static constexpr ConvVariant h3_row(int id) {
+  ConvLaunch f32 = nullptr;
+  if constexpr (F32) f32 = launch_h3<float, BM, W_, BN, WGM, WGN, TPS, SUB, NPROD>;
+  return {id, CONV_HALO, BM, BN, f32, launch_h3<bf16, BM, W_, BN, WGM, WGN, TPS, SUB, NPROD>, false,
+          W_, TPS, SUB, false, TPS == 3, h3_has_shortcut(BN, TPS, SUB)};
+}
+template <int BM, int W_, int BN, int WGM, int WGN>
+static constexpr ConvVariant h3_row_pers(int id) {      // (bf16, blocks of a larger plane)
+  return {id, CONV_HALO, BM, BN, nullptr, launch_h3_pers<BM, W_, BN, WGM, WGN>, false, W_, 1, true, true, false, false};
+}
+
+static constexpr ConvVariant kH3[] = {
+    h3_row<256, 32, 192, 4, 2, 1>(41),                     // 32x32 planes, 8 rows per tile; 8 consumer waves (64 x 96 each) + 4 producers
+    h3_row<128, 16, 192, 2, 2, 1>(43),                     // 16x16 planes, 8 rows per tile; 4 consumers (64 x 96) + 4 producers
+    h3_row<128, 32, 192, 2, 2, 1>(46),                     // 32x32 planes, 4 rows per tile
+    h3_row<64, 8, 96, 2, 2, 3>(51),                        // 8x8 planes, one sample x 96 couts per tile, 3 taps per step
+    h3_row<64, 4, 96, 2, 2, 3>(52),                        // 4x4 planes, four samples x 96 couts per tile
+    h3_row<128, 16, 96, 2, 2, 3>(54),                      // 16x16 planes, 8 rows x 96 couts (small batches)
+    h3_row<128, 32, 96, 2, 2, 3>(55),                      // 32x32 planes, 4 rows x 96 couts (small batches)
+    h3_row<256, 32, 128, 4, 2, 1, true>(58),               // planes of 64^2 and up (AF-VAE): 8 x 32 pixel blocks x 128 couts, 8 + 4 waves
+    // Persistent workgroups (k_conv3h_pers, round 4): one workgroup per CU walks several tiles, the LDS-DMA producers run on
+    // across tile boundaries
+    h3_row_pers<256, 32, 128, 4, 2>(63),                   // as 58
+    // Small batches (round 4): 64-pixel tiles, so that batch 8 still gives every CU a workgroup at the 32^2 / 16^2 levels
+    h3_row<64, 32, 96, 2, 2, 3, false, 4, false>(65),      // 32x32 planes, 2 rows x 96 couts
+    h3_row<64, 16, 96, 2, 2, 3, false, 4, false>(66),      // 16x16 planes, 4 rows x 96 couts
+    // Fewer weight bytes per workgroup at the low levels (round 5): the 8^2 / 4^2 convolutions are bound by the ~100 GB/s a CU pulls
+    // through LDS-DMA (741 KB per workgroup and launch, profiles/r02/small_tile_step_decomposition.txt); 128-pixel x 48-cout tiles
+    // stream half the weights and twice the (small) patch: 91 instead of 128 KB per channel block
+    h3_row<128, 8, 48, 4, 1, 3, false, 2, false>(67),      // 8x8 planes, two samples x 48 couts
+    h3_row<128, 4, 48, 4, 1, 3, false, 2, false>(68),      // 4x4 planes, eight samples x 48 couts
+};
+
+const ConvVariant* conv3h_variant(int id) {
+  for (const ConvVariant& v : kH3)
+    if (v.id == id) return &v;
+  return nullptr;
+}
+
+bool conv3h_supported(const ConvVariant& v, int dtype_size, const ConvP& p) {
+  if (v.family != CONV_HALO || !(dtype_size == 2 ? v.bf16 : v.f32)) return false;
+  const int kstep = 128 / dtype_size;
+  const int eo = 16 / dtype_size;
+  const int HW = p.H * p.W;
+  const int z = p.splitk > 0 ? p.splitk : 1;
+  const bool tile_ok = HW % v.bm == 0 || (v.bm % HW == 0 && (z > 1 || dtype_size == 2));    // several samples per tile: as split-K slabs, or (bf16) through the per-sample epilogue
+  const bool plane_ok = v.sub ? (p.W > v.w && p.W % v.w == 0 && p.H % (v.bm / v.w) == 0 && z == 1) : (p.W == v.w && p.H == p.W && tile_ok);
+  if (v.pers && !(z == 1 && HW % v.bm == 0 && p.C1 / kstep >= 2 && (!p.temb || p.temb_mod > 0))) return false;
+  return p.KS == 3 && p.C2 == 0 && plane_ok && p.M % v.bm == 0 && p.Cout % v.bn == 0 &&
+         p.C1 % kstep == 0 && (p.C1 / kstep) % z == 0 && p.out_mode == 0 && !p.y2 && p.y_ld % eo == 0 &&
+         (!p.residual || p.res_ld % eo == 0) && (!p.temb || (p.temb_stride % eo == 0 && p.temb_mod % eo == 0)) &&
+         (long long)p.M * p.C1 * dtype_size < (1ll << 31) && (long long)p.Cout * 9 * p.C1 * dtype_size < (1ll << 31) &&
+         p.Cout % 4 == 0 && aligned16(p.y) && aligned16(p.x1) && aligned16(p.w);
 }
 
 }  // namespace afldm

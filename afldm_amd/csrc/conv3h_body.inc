@@ -1,7 +1,7 @@
 // conv3h_body.inc - the tile body of the halo-patch 3x3 convolution, included TEXTUALLY (design notes: conv3h.hip):
 //   * by k_conv3h (conv3h.hip) with H3_BX / H3_NBX / H3_BZ = blockIdx.x / gridDim.x / blockIdx.z;
 //   * by the merged launches (actconv.hip) as the LAST phase of a workgroup that ran other work before it.
-// In scope at the point of inclusion: template parameters T, BM, W_, BN, WGM, WGN, NPROD, STAGES, MF, TPS, SUB; `ConvP p`;
+// In scope at the point of inclusion: template parameters T, BM, W_, BN, WGM, WGN, NPROD, TPS, SUB; `ConvP p`;
 // `char* smem` (the workgroup's dynamic LDS, LDS_TOTAL bytes, 16-byte aligned).  The early `return`s end the workgroup.
 // H3_PRODUCER_EXIT: what an LDS-DMA producer wave does when its K loop is over (`return;` - or, when the workgroup lives on
 // after the tile, the epilogue's barriers before it).
@@ -9,7 +9,7 @@
 // (Textual inclusion keeps k_conv3h's token stream - and so its register allocation - what it was before the split.)
   typedef Mma<T> MM;
   typedef typename MM::Chunk Chunk;
-  constexpr int NWC = WGM * WGN;
+  constexpr int NWC = WGM * WGN, MF = kH3MF, STAGES = kH3Stages;
   constexpr int EPC = MM::EPC, KSTEP = 8 * EPC, ESZ = (int)sizeof(T);
   constexpr int WMS = BM / WGM, WNS = BN / WGN, TM = WMS / MF, TN = WNS / MF;
   constexpr int ROWS = BM / W_, SEG = ROWS < W_ ? ROWS : W_, NSEG = ROWS / SEG;      // planes are square: H == W_
@@ -22,16 +22,15 @@
   constexpr int W_TAP = BN * 128, W_STAGE = TPS * W_TAP;
   constexpr int LDS_TOTAL = 2 * PATCH + STAGES * W_STAGE;
   constexpr unsigned OOB = 0x80000000u;
-  static_assert(MF == 16 || MF == 32, "MFMA flavour");
   static_assert(TPS == 1 || TPS == 3, "taps per step");
   static_assert(BM % W_ == 0 && ROWS % SEG == 0 && WI % NPROD == 0 && WMS % MF == 0 && WNS % MF == 0, "tile shape");
   static_assert((STAGES - 2) * WPW + PPW < 64, "vmcnt is a 6-bit counter");
-  static_assert(TPS == 1 || (STAGES == 3 && WIT % NPROD == 0), "three taps per step: a wave's first WPS instructions are the stage's first tap slot");
+  static_assert(STAGES == 3 && (TPS == 1 || WIT % NPROD == 0), "three-slot ring; three taps per step: a wave's first WPS instructions are the stage's first tap slot");
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave_all = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool is_producer = wave_all >= NWC;
-  const int li = lane & (MF - 1), lg = lane / MF;       // fragment row / lane group of the consumers
+  const int li = lane & 15, lg = lane >> 4;             // fragment row / lane group of the consumers
 
   // Tile order.  Default: each XCD (private L2) takes a contiguous run of tiles, n fastest - it reads 1/8 of the
   // pixels and ALL the weights.  p.xcd_gn > 0: the 8 XCDs form a (8 / gn) x gn grid over (m tiles, n tiles), so an
@@ -57,13 +56,11 @@
   const int ncb = Ct / KSTEP;
   const int ks = H3_BZ;
   const int cb_lo = (ncb * ks) / p.splitk, cb_hi = (ncb * (ks + 1)) / p.splitk;   // this slice's channel blocks
-  // folded 1x1 shortcut (conv3h_shortcut_ok): its nsc channel blocks follow the 3x3 ones as blocks cb_hi .. cb_end - 1 of ONE K
+  // folded 1x1 shortcut (h3_has_shortcut, conv3h_tile.hpp): its nsc channel blocks follow the 3x3 ones as blocks cb_hi .. cb_end - 1 of ONE K
   // step each - the centre tap of a patch whose halo is left zero (never read: no bytes fetched for it).  Three taps per step:
   // such a step fills the stage's first tap slot only; split-K slice ks takes the shortcut blocks [sc_lo, sc_lo + nsc) behind
   // its own 3x3 blocks (the shares may differ by one; the slabs then carry conv + shortcut partial sums).
-  // (not on the 256-pixel tiles of whole 16x16 samples, variants 44 / 49: the extra loop spills there; not on the 48-cout tiles,
-  //  variants 67 / 68: 92 -> 102 / 137 VGPRs with it; no shortcut site runs either - conv2's K is never long enough for them)
-  constexpr bool HAS_SC = !SUB && !(BM == 256 && W_ == 16) && !(TPS == 3 && BN == 48);
+  constexpr bool HAS_SC = h3_has_shortcut(BN, TPS, SUB);
   const int nsc_all = (HAS_SC && p.sc_x1) ? (p.sc_C1 + p.sc_C2) / KSTEP : 0;
   const int sc_lo = TPS == 3 ? (nsc_all * ks) / p.splitk : 0;
   const int nsc = TPS == 3 ? (nsc_all * (ks + 1)) / p.splitk - sc_lo : nsc_all;
@@ -104,7 +101,7 @@
       if (j > NPI - 1) j = NPI - 1;
       pj[i] = j;
       const int q = 8 * j + (lane >> 3);
-      const int c = h_chunk_at<MF>(lane & 7, h_sw_patch<MF, W_>(q));
+      const int c = h_chunk_at(lane & 7, h_sw_patch<W_>(q));
       const int pr = q / PW, pc = q - pr * PW;
       const int sg = pr / (SEG + 2), jj = pr - sg * (SEG + 2);            // segment (one sample's rows) and row inside it
       const int ih = oh0 + jj - 1;
@@ -129,7 +126,7 @@
     for (int i = 0; i < WPW; ++i) {
       const int j = wave + NPROD * i;                            // instruction inside the stage: (tap in step, row group)
       const int tis = j / WIT, r = 8 * (j - tis * WIT) + (lane >> 3);
-      const int c = h_chunk_at<MF>(lane & 7, h_sw_rows<MF>(r));
+      const int c = h_chunk_at(lane & 7, h_sw_rows(r));
       woff[i] = (((unsigned)(n0 + r) * 9u + (unsigned)tis) * (unsigned)Ct + (unsigned)(c * EPC)) * ESZ;
     }
     const int Csc = p.sc_C1 + p.sc_C2;
@@ -145,7 +142,7 @@
 #pragma unroll
         for (int i = 0; i < WPS; ++i) {
           const int r = 8 * (wave + NPROD * i) + (lane >> 3);
-          const unsigned wo = ((unsigned)(n0 + r) * (unsigned)Csc + (unsigned)(h_chunk_at<MF>(lane & 7, h_sw_rows<MF>(r)) * EPC)) * ESZ;
+          const unsigned wo = ((unsigned)(n0 + r) * (unsigned)Csc + (unsigned)(h_chunk_at(lane & 7, h_sw_rows(r)) * EPC)) * ESZ;
           lds_ptr_t dst = (lds_ptr_t)(sbase + (wave + NPROD * i) * 1024);
           if (p.w_nt) __builtin_amdgcn_raw_ptr_buffer_load_lds(rws, dst, 16, (int)wo, (int)so, 0, 2);
           else __builtin_amdgcn_raw_ptr_buffer_load_lds(rws, dst, 16, (int)wo, (int)so, 0, 0);
@@ -181,7 +178,7 @@
 #pragma unroll
         for (int i = 0; i < PPW; ++i) {
           const int q = 8 * pj[i] + (lane >> 3);
-          const int c = h_chunk_at<MF>(lane & 7, h_sw_patch<MF, W_>(q));
+          const int c = h_chunk_at(lane & 7, h_sw_patch<W_>(q));
           const int pr = q / PW, pc = q - pr * PW;
           const int sg = pr / (SEG + 2), jj = pr - sg * (SEG + 2);
           const bool in = q < NPQ && pc >= 1 && pc <= W_ && jj >= 1 && jj <= SEG;
@@ -209,7 +206,7 @@
       // after a patch issue - that patch (issued behind step g+STAGES-1's weights of its iteration).  A shortcut block is
       // one step long, so the next one's patch goes out IN FRONT of that step's weights and only those may stay in flight.
       if constexpr (TPS == 1) {
-        if (fresh) wait_vmcnt<(STAGES >= 3 ? WPW : 0)>();
+        if (fresh) wait_vmcnt<WPW>();
         else if (since <= STAGES - 1) wait_vmcnt<(STAGES - 2) * WPW + PPW>();
         else wait_vmcnt<(STAGES - 2) * WPW>();
       } else {
@@ -256,10 +253,7 @@
 
   // ------------------------------------------------------------------------------------------- consumers
   const int cw = wave_all, wm = cw / WGN, wn = cw - wm * WGN;
-  constexpr int NKK = MF == 16 ? 2 : 4;                          // fragment K steps inside a 128-byte row
-  constexpr int NACC = MF * MF / 64;                             // accumulator floats per lane and tile
-  constexpr int RQ = NACC / 4;                                   // cout quads per lane and tile
-  typedef __attribute__((ext_vector_type(NACC))) float AccT;
+  constexpr int NKK = 2;                                         // fragment K steps inside a 128-byte row
   int qb[TM];                                                    // patch pixel of (tile pixel, tap (0, 0))
 #pragma unroll
   for (int t = 0; t < TM; ++t) {
@@ -268,24 +262,22 @@
     const int sg = r / SEG, rr = r - sg * SEG;
     qb[t] = (sg * (SEG + 2) + rr) * PW + c;
   }
-  // fragment address of (row q, K step kk) = (q * 128 + (h_pos(chunk(0, lg), q) << 4)) ^ (kk << 5) in both flavours
-  auto frag_off = [&](int q) { return q * 128 + (h_pos<MF>(lg, h_sw_patch<MF, W_>(q)) << 4); };                      // patch rows
-  const int a_off0 = (wn * WNS + li) * 128 + (h_pos<MF>(lg, h_sw_rows<MF>(wn * WNS + li)) << 4);                    // + t * MF * 128 for weight tile t ((row >> 1) & 7 depends on li only)
+  // fragment address of (row q, K step kk) = (q * 128 + (h_pos(chunk(0, lg), q) << 4)) ^ (kk << 5)
+  auto frag_off = [&](int q) { return q * 128 + (h_pos(lg, h_sw_patch<W_>(q)) << 4); };                      // patch rows
+  const int a_off0 = (wn * WNS + li) * 128 + (h_pos(lg, h_sw_rows(wn * WNS + li)) << 4);                    // + t * MF * 128 for weight tile t ((row >> 1) & 7 depends on li only)
 
   // The residual enters through the ACCUMULATORS (fragment layout), a few tiles per K step during the first NRS
   // steps: requested at the top of step s, added at the top of step s + 1 - its latency runs under MFMA work instead
   // of in the epilogue (one dependent global load per copied row was most of the fixed cost of a residual
   // convolution) or in front of the first step.  residual + sum of products, fp32.
   // (split-K: the slabs carry plain partial sums, the reduction kernel adds the epilogue terms)
-  auto cout_of = [&](int tn, int rq) { return n0 + wn * WNS + tn * MF + (MF == 16 ? 4 * lg : 8 * rq + 4 * lg); };
-  AccT acc[TN][TM];
+  auto cout_of = [&](int tn) { return n0 + wn * WNS + tn * MF + 4 * lg; };      // a lane's accumulator: 4 consecutive couts of one pixel
+  f32x4 acc[TN][TM];
 #pragma unroll
   for (int a = 0; a < TN; ++a)
 #pragma unroll
-    for (int b = 0; b < TM; ++b)
-#pragma unroll
-      for (int e = 0; e < NACC; ++e) acc[a][b][e] = 0.f;
-  constexpr int NRT = TN * TM * RQ;                              // residual quads per lane
+    for (int b = 0; b < TM; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  constexpr int NRT = TN * TM;                                   // residual quads per lane
   constexpr int NRS = TPS == 1 ? 8 : 3;                          // steps they are spread over (G >= 9 / 3)
   constexpr int RCH = (NRT + NRS - 1) / NRS;
   typedef __attribute__((ext_vector_type(4))) T Quad;
@@ -299,13 +291,11 @@
 #pragma unroll
     for (int a = 0; a < TN; ++a)
 #pragma unroll
-      for (int b = 0; b < TM; ++b)
-#pragma unroll
-        for (int rq = 0; rq < RQ; ++rq) {
-          float r0, r1, r2, r3;
-          load4<T>(res + (size_t)gpix(wm * WMS + b * MF + li) * p.res_ld + cout_of(a, rq), r0, r1, r2, r3);
-          acc[a][b][4 * rq] = r0; acc[a][b][4 * rq + 1] = r1; acc[a][b][4 * rq + 2] = r2; acc[a][b][4 * rq + 3] = r3;
-        }
+      for (int b = 0; b < TM; ++b) {
+        float r0, r1, r2, r3;
+        load4<T>(res + (size_t)gpix(wm * WMS + b * MF + li) * p.res_ld + cout_of(a), r0, r1, r2, r3);
+        acc[a][b] = f32x4{r0, r1, r2, r3};
+      }
   }
   auto res_issue = [&](int chunk) {
     const T* res = (const T*)p.residual;
@@ -313,8 +303,8 @@
     for (int k = 0; k < RCH; ++k) {
       const int idx = chunk * RCH + k;
       if (idx < NRT) {
-        const int a = idx / (TM * RQ), b = (idx / RQ) % TM, rq = idx % RQ;
-        rv[k] = *reinterpret_cast<const Quad*>(res + (size_t)gpix(wm * WMS + b * MF + li) * p.res_ld + cout_of(a, rq));
+        const int a = idx / TM, b = idx % TM;
+        rv[k] = *reinterpret_cast<const Quad*>(res + (size_t)gpix(wm * WMS + b * MF + li) * p.res_ld + cout_of(a));
       }
     }
   };
@@ -323,9 +313,9 @@
     for (int k = 0; k < RCH; ++k) {
       const int idx = chunk * RCH + k;
       if (idx < NRT) {
-        const int a = idx / (TM * RQ), b = (idx / RQ) % TM, rq = idx % RQ;
+        const int a = idx / TM, b = idx % TM;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) acc[a][b][4 * rq + e] += to_f32(rv[k][e]);
+        for (int e = 0; e < 4; ++e) acc[a][b][e] += to_f32(rv[k][e]);
       }
     }
   };
@@ -377,10 +367,7 @@
 #pragma unroll
             for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
-              for (int tm = 0; tm < TM; ++tm) {
-                if constexpr (MF == 16) MM::mma(acc[tn][tm], a[tn], b[tm]);
-                else Mma32<T>::mma(acc[tn][tm], a[tn], b[tm]);
-              }
+              for (int tm = 0; tm < TM; ++tm) MM::mma(acc[tn][tm], a[tn], b[tm]);
             __builtin_amdgcn_sched_barrier(0);
           }
         }
@@ -444,8 +431,7 @@
             asm volatile("" ::"v"(af[i]), "v"(bf[i / TN][tm]));
             continue;
 #endif
-            if constexpr (MF == 16) MM::mma(acc[i % TN][tm], af[i], bf[i / TN][tm]);
-            else Mma32<T>::mma(acc[i % TN][tm], af[i], bf[i / TN][tm]);
+            MM::mma(acc[i % TN][tm], af[i], bf[i / TN][tm]);
           }
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -536,20 +522,18 @@
       }
       __syncthreads();
 #pragma unroll
-      for (int tn = 0; tn < TN; ++tn)
+      for (int tn = 0; tn < TN; ++tn) {
+        const int cl = cout_of(tn) - n0;
 #pragma unroll
-        for (int rq = 0; rq < RQ; ++rq) {
-          const int cl = cout_of(tn, rq) - n0;
+        for (int t = 0; t < TM; ++t) {
+          const int row = wm * WMS + t * MF + li;
+          const f32x4 b4 = *reinterpret_cast<const f32x4*>(sB + (NSEG == 1 ? 0 : row / HWT) * BN + cl);
+          Quad o;
 #pragma unroll
-          for (int t = 0; t < TM; ++t) {
-            const int row = wm * WMS + t * MF + li;
-            const f32x4 b4 = *reinterpret_cast<const f32x4*>(sB + (NSEG == 1 ? 0 : row / HWT) * BN + cl);
-            Quad o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = from_f32<T>(acc[tn][t][4 * rq + e] + b4[e]);
-            *reinterpret_cast<Quad*>(sO + row * OROW + cl) = o;
-          }
+          for (int e = 0; e < 4; ++e) o[e] = from_f32<T>(acc[tn][t][e] + b4[e]);
+          *reinterpret_cast<Quad*>(sO + row * OROW + cl) = o;
         }
+      }
       __syncthreads();
       if constexpr (NSEG > 1) {
         // row lanes are dealt per sample segment: a thread's rows (and its partial sums) belong to ONE sample
@@ -626,7 +610,7 @@
         constexpr int SR_NORM = ((SB_BYTES + BM * OROW * 2 + 15) / 16) * 16;
         // scratch behind the staged tile: sR [RPI][BN][2] + sCol [BN][2] + sG [BN / ncpg][2] (<= BN pairs: one channel per group)
         constexpr bool CAN_NORM = BM == W_ * W_ && SR_NORM + RPI * BN * 8 + BN * 8 + BN * 8 <= LDS_TOTAL;      // the tile is a whole sample
-        // the host promises this epilogue for the one-sample 8x8 tiles of 96 couts (norm_fusable in conv.hip: variants 51 / 53, bf16)
+        // the host promises this epilogue for the one-sample 8x8 tiles of 96 couts (norm_fusable in conv.hip: variant 51, bf16)
         static_assert(!(BM == 64 && W_ == 8 && BN == 96 && sizeof(T) == 2) || CAN_NORM, "y_norm epilogue: LDS budget no longer holds for the tiles norm_fusable() accepts");
         const bool do_norm = CAN_NORM && p.y_norm != nullptr;
         float* sR = reinterpret_cast<float*>(smem + (do_norm ? SR_NORM : 0));       // [RPI][BN][2]
@@ -735,11 +719,7 @@
 #pragma unroll
           for (int t = 0; t < TM; ++t) {
             const int row = wml * WMS + t * MF + li;
-#pragma unroll
-            for (int rq = 0; rq < RQ; ++rq) {
-              const f32x4 v = f32x4{acc[tn][t][4 * rq], acc[tn][t][4 * rq + 1], acc[tn][t][4 * rq + 2], acc[tn][t][4 * rq + 3]};
-              *reinterpret_cast<f32x4*>(sC + row * SROW + (cout_of(tn, rq) - n0)) = v;
-            }
+            *reinterpret_cast<f32x4*>(sC + row * SROW + (cout_of(tn) - n0)) = acc[tn][t];
             __builtin_amdgcn_sched_barrier(0);
           }
       }

@@ -67,13 +67,33 @@ __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// halo-patch 3x3 convolution (conv3h.hip): variant ids >= kConv3hFirst of the conv variant table
-constexpr int kConv3hFirst = 41;
-bool conv3h_supported(int variant, int dtype_size, const ConvP& p);      // p.splitk = the planned K slices
-bool conv3h_shortcut_ok(int variant);                                    // k_conv3h of this variant folds a 1x1 shortcut (ConvP.sc_*)
-int conv3h_taps_per_step(int variant);                                   // filter taps per K step of a k_conv3h variant (1 / 3; 0: no such variant)
-int conv3h_tile(int variant, int* bm, int* bn);
-void conv3h_launch(int variant, int dtype_size, const ConvP& p, hipStream_t st);
+// One row per convolution variant.  The id is what afldm_conv2d_tune / AFLDM_CONV_OVERRIDE take and afldm_conv2d_variant
+// returns; ids are sparse (retired tuning variants keep their numbers in profiles/ and DESIGN.md and are refused).  A row is
+// made by the helper that instantiates its launchers (conv_row_* in conv.hip, h3_row* in conv3h.hip), so its tile sizes are
+// the kernel's.
+enum ConvFamily {
+  CONV_IGEMM,       // k_igemm: register-staged implicit GEMM (any operand size)
+  CONV_IGEMM_DMA,   // k_igemm2: LDS-DMA implicit GEMM (operands addressed through buffer descriptors: < 2 GiB each)
+  CONV_HALO         // k_conv3h / k_conv3h_pers: halo-patch 3x3 convolution
+};
+typedef void (*ConvLaunch)(const ConvP&, hipStream_t);
+struct ConvVariant {
+  int id;
+  ConvFamily family;
+  int bm, bn;               // pixels x couts per tile
+  ConvLaunch f32, bf16;     // NULL: no instantiation for that type
+  bool producers;           // CONV_IGEMM_DMA: separate LDS-DMA producer waves, one workgroup per CU
+  // CONV_HALO only
+  int w;                    // plane width of a tile row (sub: width of the tile's block of a larger plane)
+  int tps;                  // filter taps per K step (1 / 3)
+  bool sub;                 // a tile is a (bm / w) x w block of a LARGER plane (p.W % w == 0, p.H % (bm / w) == 0)
+  bool pers;                // persistent workgroups (k_conv3h_pers): whole K per workgroup, bf16
+  bool may_split;           // the planner may split the channel blocks over K slices
+  bool folds_shortcut;      // the kernel runs a folded 1x1 shortcut (ConvP.sc_*) as extra centre-tap K steps
+};
+const ConvVariant* conv_variant(int id);               // conv.hip: the row of a live id, NULL for "no such variant"
+const ConvVariant* conv3h_variant(int id);             // conv3h.hip: its CONV_HALO rows
+bool conv3h_supported(const ConvVariant& v, int dtype_size, const ConvP& p);      // p.splitk = the planned K slices
 // conv.hip: true when afldm_conv2d(a) is ONE k_conv3h launch (whole K per workgroup, statistics from its epilogue); fills the
 // argument block of that launch and its variant id (the merged launches of actconv.hip run the tile as their last phase)
 bool conv3h_plan(const afldm_conv_args* a, ConvP* p, int* variant);

@@ -367,7 +367,10 @@ int afldm_conv2d_norm_ok(const afldm_conv_args* args);
  * defer_reduce (the slabs to afldm_af_act_slabs, which then takes bias = b2 + b_sc and no residual) or y_norm. */
 int afldm_conv2d_shortcut_ok(const afldm_conv_args* args);
 /* Tuning hook (benchmarks only): force tile/pipeline variant `variant` (>= 0) and/or a split-K
- * factor (>= 1) for subsequent afldm_conv2d calls; -1 restores the automatic choice. */
+ * factor (>= 1) for subsequent afldm_conv2d calls; -1 restores the automatic choice.  Variant ids are sparse: the
+ * live ones are 0, 1, 3 (register-staged GEMM), 29 - 33 (LDS-DMA GEMM) and 41, 43, 46, 51, 52, 54, 55, 58, 63,
+ * 65 - 68 (halo-patch 3x3); every other id (retired tuning variants) is refused with AFLDM_ESHAPE and
+ * leaves the forcing as it was.  A forced variant that cannot run a shape falls back to the automatic choice. */
 int afldm_conv2d_tune(int variant, int splitk);
 /* Enable (1) / disable (0, the default) the in-kernel split-K reduction for calls that pass `sync` words: measured
  * slower than the two-launch form on MI355X, kept as a tested option. */

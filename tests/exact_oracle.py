@@ -161,22 +161,20 @@ def _c(B, H, W, C1, C2, Cout, KS=3, **kw):
 # the ragged shape of test_conv2d_every_gemm_variant: M = 288 is no tile multiple, virtual concat, Cout = 200
 EVERY_VARIANT = _c(2, 12, 12, 128, 64, 200, residual=True)
 
-# H3_CASES of tests/test_gpu_ops.py (conv3h.hip variants 41 - 62), batches cut to what fills two tiles
+# H3_CASES of tests/test_gpu_ops.py (conv3h.hip variants), batches cut to what fills two tiles
 H3_EXACT = [
     # conv_case kwargs, variants
-    (_c(1, 32, 32, 192, 0, 192, temb=True), (41, 45, 46, 47, 50)),
-    (_c(1, 32, 32, 384, 0, 192, residual=True), (41, 45, 46, 47, 50)),
-    (_c(1, 32, 32, 64, 0, 384, temb=True, residual=True), (41, 45, 46, 47, 50)),
-    (_c(2, 16, 16, 384, 0, 384, temb=True, residual=True), (42, 43, 44, 48, 49)),
-    (_c(2, 16, 16, 128, 0, 192), (42, 43, 44, 48, 49)),
+    (_c(1, 32, 32, 192, 0, 192, temb=True), (41, 46)),
+    (_c(1, 32, 32, 384, 0, 192, residual=True), (41, 46)),
+    (_c(1, 32, 32, 64, 0, 384, temb=True, residual=True), (41, 46)),
+    (_c(2, 16, 16, 384, 0, 384, temb=True, residual=True), (43,)),
+    (_c(2, 16, 16, 128, 0, 192), (43,)),
     (_c(3, 8, 8, 384, 0, 384, temb=True, residual=True), (51,)),
     (_c(3, 8, 8, 768, 0, 96, residual=True), (51,)),
     (_c(8, 4, 4, 768, 0, 768, temb=True, residual=True), (52,)),
     (_c(4, 4, 4, 256, 0, 96), (52,)),
     (_c(2, 16, 16, 384, 0, 96, temb=True, residual=True), (54,)),
     (_c(1, 32, 32, 192, 0, 288, temb=True, residual=True), (55,)),
-    (_c(1, 32, 32, 192, 0, 192, temb=True, residual=True), (61,)),
-    (_c(2, 16, 16, 384, 0, 384, temb=True, residual=True), (62,)),
 ]
 
 # variant 58: 8 x 32 pixel blocks of planes larger than a tile (one non-square)
@@ -184,14 +182,6 @@ V58_EXACT = [
     _c(1, 64, 64, 128, 0, 128, temb=True, residual=True),
     _c(1, 72, 96, 64, 0, 256, residual=True),
     _c(1, 128, 128, 128, 0, 128),
-]
-
-# variant 40 (k_igemm3, persistent workgroups) against 29: the first case cut to B = 2, the other two as they are - a workgroup
-# walks more than one tile only where there are more tiles than workgroups (320 and 576 tiles)
-V40_EXACT = [
-    _c(2, 32, 32, 192, 0, 192, temb=True),
-    _c(80, 16, 16, 128, 64, 384, residual=True),
-    _c(72, 16, 16, 192, 0, 768, KS=1, temb=True, residual=True),
 ]
 
 # split-K: the 4^2, 8^2 and M = 48 shapes of test_conv2d_split_k_reduced_inside_the_launch with B <= 8
@@ -282,7 +272,7 @@ def static_cases():
     out = [("every_variant", lambda: conv_case(**EVERY_VARIANT))]
     for i, (kw, _) in enumerate(H3_EXACT):
         out.append((f"h3[{i}]", lambda kw=kw: conv_case(**kw)))
-    for name, table in (("v58", V58_EXACT), ("v40", V40_EXACT), ("splitk", SPLITK_EXACT), ("seam", SEAM_EXACT), ("model", MODEL_SHAPES)):
+    for name, table in (("v58", V58_EXACT), ("splitk", SPLITK_EXACT), ("seam", SEAM_EXACT), ("model", MODEL_SHAPES)):
         for i, kw in enumerate(table):
             out.append((f"{name}[{i}]", lambda kw=kw: conv_case(**kw)))
     for N, C1, C2, Cout, B in sorted({f[:5] for f in FOLD_CASES}):

@@ -233,13 +233,13 @@ def _variant(ops, x, w, bias, **kw):
     return (code, 1) if code < 0 else (code & 255, (code >> 8) & 255)
 
 
-# The halo-patch tiles that hold several whole planes (kH3[], conv3h.hip:420-457; BM pixels per tile, NSEG = BM / (N N)
-# planes, conv3h.hip:506):
+# The halo-patch tiles that hold several whole planes (the variant rows kH3[] of conv3h.hip; BM pixels per tile, NSEG = BM / (N N)
+# planes, launch_h3):
 #   variant 52: BM 64, 4x4 planes  -> g = 4      variant 68: BM 128, 4x4 planes -> g = 8      variant 67: BM 128, 8x8 -> g = 2
 # (51: one 8x8 plane per tile, g = 1 - its tiles cannot mix samples, it runs as the no-variant default below.)  A tile needs
-# M % BM == 0 (conv3h_supported, conv3h.hip:481): at B = g + 1 and 2 g + 1 the planner falls back to the GEMM tiles, which
+# M % BM == 0 (conv3h_supported, conv3h.hip): at B = g + 1 and 2 g + 1 the planner falls back to the GEMM tiles, which
 # run over rows of different samples too, so every form runs at g + 1, 2 g + 1 AND 2 g, 3 g; at the multiples the forced
-# variant must be the one that ran.  fp32 takes several samples per tile only as split-K slabs (conv3h.hip:477).
+# variant must be the one that ran.  fp32 takes several samples per tile only as split-K slabs (conv3h_supported).
 H3_MULTI = [
     # variant, N, Cin, Cout, K slices (0: the planner's), g
     (52, 4, 256, 192, 1, 4),          # no split: per-sample time embedding, residual, GroupNorm records from the epilogue
@@ -367,7 +367,7 @@ def test_conv3x3_on_2x2_plane_as_one_dense_layer(dtype, B):
     assert ("dense2x2", dtype, C1, C2) in conv.__dict__["_afldm_cache"]
 
 
-# linear_split (the fused q | k | v projection): GEMM tiles of 64 / 128 token rows (kVariants[], conv.hip:1546) run over the rows
+# linear_split (the fused q | k | v projection): GEMM tiles of 64 / 128 token rows (the variant rows of conv.hip) run over the rows
 # of several samples: T = 16 -> g = 4 .. 8, T = 64 -> g = 1 .. 2; from M = B T >= 4096 rows the weights-in-registers kernel (lin.hip,
 # persistent workgroups over 128-row blocks) takes over: B = 256 / 64 is that switch.
 @pytest.mark.parametrize("dtype", DTYPES, ids=_id)
@@ -380,7 +380,7 @@ def test_linear_split(dtype, T, B, g):
     relations(f"afldm_conv2d linear_split T={T}", lambda x: ops.linear_split(x, w, bias, 2 * C), x, g)
 
 
-# conv2d_slabs -> af_act_slabs: the split-K slabs come from GEMM tiles of 64 - 256 rows (kVariants[], conv.hip:1546: 16 - 64
+# conv2d_slabs -> af_act_slabs: the split-K slabs come from GEMM tiles of 64 - 256 rows (the variant rows of conv.hip: 16 - 64
 # planes of 2x2, 4 - 16 of 4x4); k_af_act_slabs itself takes one sample x `gpb` whole groups per workgroup (af.hip:1616-1619,
 # g = 1) and indexes slabs, time embedding and residual by sample  ->  the producer's g = 4 .. 32, one pair of batches per g.
 @pytest.mark.parametrize("dtype", DTYPES, ids=_id)

@@ -282,21 +282,27 @@ def test_model_sites_planner_choice(model, part, dtype):
 
 
 # ================================================================================================ b. every variant
+# the ids afldm_conv2d_tune accepts (sparse: retired tuning variants are refused), and the general GEMM tiles among them
+LIVE_CONV_VARIANTS = [0, 1, 3, 29, 30, 31, 32, 33, 41, 43, 46, 51, 52, 54, 55, 58, 63, 65, 66, 67, 68]
+GENERAL_GEMM_VARIANTS = [0, 1, 3, 29, 30, 31, 32, 33]
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_every_gemm_variant_exact(dtype):
     """The loop of test_conv2d_every_gemm_variant on its ragged shape (2 x 12 x 12, 128 | 64 -> 200, residual), split-K 1 and 3:
-    every variant afldm_conv2d_tune accepts.  The persistent and halo-patch variants (40 - 62) cannot take the shape and fall back
-    (as there; they have their own tests below); the general GEMM tiles (0 - 39, 56) must be the ones that ran."""
+    every variant afldm_conv2d_tune accepts among ids 0 ... 68 - exactly the live list.  The halo-patch variants (41 and up) cannot
+    take the shape and fall back (as there; they have their own tests below); the general GEMM tiles (0, 1, 3, 29 - 33) must be the
+    ones that ran."""
     ops, L = _ops(), _lib()
     c = conv_case(**xo.EVERY_VARIANT)
     o = operands(c, dtype)
     ws = torch.empty(4 * c.B * c.H * c.W * c.Cout, dtype=FP32, device="cuda")
-    fails, nvar, ran = Failures(), 0, set()
+    fails, accepted, ran = Failures(), [], set()
     try:
-        for v in range(64):
+        for v in range(69):
             if L.lib.afldm_conv2d_tune(v, 1) != 0:
-                break
-            nvar += 1
+                continue                  # a retired id: refused, the forcing stays as it was
+            accepted.append(v)
             for sk in (1, 3):
                 L.check(L.lib.afldm_conv2d_tune(v, sk), "tune")
 
@@ -310,9 +316,9 @@ def test_every_gemm_variant_exact(dtype):
     finally:
         L.lib.afldm_conv2d_tune(-1, -1)
     fails.check()
-    assert nvar >= 55
+    assert accepted == LIVE_CONV_VARIANTS
     print(f"[exact] variants that took the ragged shape ({dtype}): {sorted(ran)}")
-    want = {(v, z) for v in list(range(40)) + [56] for z in (1, 3)}      # every general GEMM tile takes any shape, with 1 and 3 slices
+    want = {(v, z) for v in GENERAL_GEMM_VARIANTS for z in (1, 3)}      # every general GEMM tile takes any shape, with 1 and 3 slices
     assert ran >= want, sorted(want - ran)
 
 
@@ -332,7 +338,7 @@ def _forced(c, dtype, v, sk=-1, stats=True):
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("i", range(len(xo.H3_EXACT)))
 def test_halo_patch_variants_exact(dtype, i):
-    """conv3h.hip variants 41 - 62 on the H3_CASES shapes (batches cut to what fills two tiles), forced and checked to have run."""
+    """conv3h.hip variants on the H3_CASES shapes (batches cut to what fills two tiles), forced and checked to have run."""
     kw, variants = xo.H3_EXACT[i]
     c = conv_case(**kw)
     fails = Failures()
@@ -346,16 +352,6 @@ def test_halo_patch_variants_exact(dtype, i):
 def test_halo_patch_on_blocks_of_large_planes_exact(dtype, i):
     """Variant 58: 8 x 32 pixel blocks of a plane larger than a tile, one of them non-square (72 x 96)."""
     _forced(conv_case(**xo.V58_EXACT[i]), dtype, 58)
-
-
-@pytest.mark.parametrize("i", range(len(xo.V40_EXACT)))
-def test_persistent_tile_variant_exact(i):
-    """Variant 40 (k_igemm3, bf16: persistent workgroups that walk several tiles) and variant 29 (one tile per workgroup) on the same
-    call: both equal the float64 reference, hence each other."""
-    c = conv_case(**xo.V40_EXACT[i])
-    y29, _ = _forced(c, BF16, 29, 1)
-    y40, _ = _forced(c, BF16, 40, 1)
-    assert torch.equal(y29, y40)
 
 
 # ================================================================================================ c. split-K

@@ -311,10 +311,15 @@ def test_conv2d(dtype, case):
     close(back(y), ref, dtype, f"conv {case}", bf16_rms=6e-3)
 
 
+# the variant ids afldm_conv2d_tune accepts (ids are sparse: retired tuning variants are refused)
+LIVE_CONV_VARIANTS = [0, 1, 3, 29, 30, 31, 32, 33, 41, 43, 46, 51, 52, 54, 55, 58, 63, 65, 66, 67, 68]
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_conv2d_every_gemm_variant(dtype):
-    """Force each implicit-GEMM tile / pipeline variant (afldm_conv2d_tune) on one ragged shape:
-    M = 2*12*12 = 288 (not a tile multiple), virtual concat, Cout = 200 (ragged N), split-K 1 and 3."""
+    """Force each variant afldm_conv2d_tune accepts (ids 0 ... 68; exactly the live list) on one ragged shape:
+    M = 2*12*12 = 288 (not a tile multiple), virtual concat, Cout = 200 (ragged N), split-K 1 and 3.  The halo-patch
+    variants cannot take the shape and fall back to the automatic choice."""
     from afldm_amd import _lib
     ops = _ops()
     B, H, W, C1, C2, Cout, KS = 2, 12, 12, 128, 64, 200, 3
@@ -326,58 +331,19 @@ def test_conv2d_every_gemm_variant(dtype):
     ref = F.conv2d(x, w, b, padding=1) + res
     x1, x2, wp, rp = nhwc(x[:, :C1], dtype), nhwc(x[:, C1:], dtype), ops.pack_weight(w.cuda(), dtype), nhwc(res, dtype)
     ws = torch.empty(4 * B * H * W * Cout, dtype=torch.float32, device="cuda")
-    nvar = 0
+    accepted = []
     try:
-        for v in range(64):
+        for v in range(69):
             if _lib.lib.afldm_conv2d_tune(v, 1) != 0:
-                break
-            nvar += 1
+                continue                  # a retired id: refused, the forcing stays as it was
+            accepted.append(v)
             for sk in (1, 3):
                 _lib.check(_lib.lib.afldm_conv2d_tune(v, sk), "tune")
                 y = ops.conv2d(x1, wp, b.cuda(), x2=x2, residual=rp, workspace=ws)
                 close(back(y), ref, dtype, f"conv variant {v} splitk {sk}", bf16_rms=6e-3)
     finally:
         _lib.lib.afldm_conv2d_tune(-1, -1)
-    assert nvar >= 55
-
-
-@pytest.mark.parametrize("case", [
-    # B, H, W, C1, C2, Cout, KS, temb, residual
-    (6, 32, 32, 192, 0, 192, 3, True, False),     # 48 tiles on <= 256 workgroups: 1 tile each
-    (80, 16, 16, 128, 64, 384, 3, False, True),   # 320 tiles: 64 workgroups walk 2 tiles, virtual concat, residual
-    (72, 16, 16, 192, 0, 768, 1, True, True),     # 576 tiles (3 rounds for some), 1x1, temb + residual, m-fast order
-])
-def test_conv2d_persistent_tile_variant_bit_identical(case):
-    """Variant 40 (k_igemm3: persistent workgroups, producers running ahead across tile boundaries, wave-private
-    epilogue) against variant 29 (one tile per workgroup) on the same call: outputs bit-identical, GroupNorm
-    partial sums equal after folding the splits, deterministic across repeats."""
-    from afldm_amd import _lib
-    ops = _ops()
-    dt = torch.bfloat16
-    B, H, W, C1, C2, Cout, KS, use_temb, use_res = case
-    g = torch.Generator().manual_seed(B + Cout)
-    x1 = torch.randn(B, H, W, C1, generator=g).to(dt).cuda()
-    x2 = torch.randn(B, H, W, C2, generator=g).to(dt).cuda() if C2 else None
-    w = (torch.randn(Cout, KS, KS, C1 + C2, generator=g) / (KS * (C1 + C2) ** 0.5)).to(dt).cuda()
-    bias = torch.randn(Cout, generator=g).cuda()
-    temb = torch.randn(B, Cout, generator=g).to(dt).cuda() if use_temb else None
-    res = torch.randn(B, H, W, Cout, generator=g).to(dt).cuda() if use_res else None
-    outs = {}
-    try:
-        for v in (29, 40, 40):
-            _lib.check(_lib.lib.afldm_conv2d_tune(v, 1), "tune")
-            y = ops.conv2d(x1, w, bias, x2=x2, temb=temb, temb_stride=Cout if use_temb else 0, residual=res, want_stats=True)
-            outs.setdefault(v, []).append((y, y.gn_partial))
-    finally:
-        _lib.lib.afldm_conv2d_tune(-1, -1)
-    y29, st29 = outs[29][0]
-    for y40, st40 in outs[40]:
-        assert torch.equal(y29, y40)
-        assert st40.shape[1] == (H * W // 128) * 4
-        yv = y40.float()
-        assert (st40.double().sum(1)[..., 0].cpu() - yv.double().sum((1, 2)).cpu()).abs().max() <= 1e-3 * (1 + yv.abs().sum((1, 2)).max().item())
-        torch.testing.assert_close(st40.sum(1), st29.sum(1), rtol=1e-4, atol=1e-2)
-    assert torch.equal(outs[40][0][1], outs[40][1][1])
+    assert accepted == LIVE_CONV_VARIANTS
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -447,19 +413,17 @@ def test_conv2d_split_k_reduced_inside_the_launch(dtype, case):
 
 H3_CASES = [
     # B, N (plane), Cin, Cout, temb, residual, variants (conv3h.hip ids)
-    (2, 32, 192, 192, True, False, (41, 45, 46, 47, 50)),
-    (3, 32, 384, 192, False, True, (41, 45, 46, 47, 50)),
-    (2, 32, 64, 384, True, True, (41, 45, 46, 47, 50)),
-    (3, 16, 384, 384, True, True, (42, 43, 44, 48, 49)),
-    (5, 16, 128, 192, False, False, (42, 43, 44, 48, 49)),
+    (2, 32, 192, 192, True, False, (41, 46)),
+    (3, 32, 384, 192, False, True, (41, 46)),
+    (2, 32, 64, 384, True, True, (41, 46)),
+    (3, 16, 384, 384, True, True, (43,)),
+    (5, 16, 128, 192, False, False, (43,)),
     (5, 8, 384, 384, True, True, (51,)),          # small-plane variants: one 8x8 sample per tile, 3 taps per step
     (3, 8, 768, 96, False, True, (51,)),
     (8, 4, 768, 768, True, True, (52,)),           # four 4x4 samples per tile, channel blocks split over 2-4 slices
     (4, 4, 256, 96, False, False, (52,)),
     (2, 16, 384, 96, True, True, (54,)),
     (2, 32, 192, 288, True, True, (55,)),
-    (3, 32, 192, 192, True, True, (61,)),          # 128 x 96 tiles sized for two workgroups per CU (round 3, A/B variants)
-    (5, 16, 384, 384, True, True, (62,)),
 ]
 
 
@@ -497,7 +461,7 @@ def test_conv3x3_halo_patch_variants(dtype, case):
             code = _lib.lib.afldm_conv2d_variant(ctypes.byref(probe))
             assert code & 255 == v, "the halo variant did not run this shape"
             split = (code >> 8) & 255
-            bm = 256 if v in (41, 44, 47, 49) else 64 if v in (51, 52, 53) else 128
+            bm = 256 if v == 41 else 64 if v in (51, 52) else 128
             if split == 1:    # (with K slices the statistics come from the reduction kernel)
                 assert ys[0].gn_partial.shape == (B, N * N // bm, Cout, 2), (v, ys[0].gn_partial.shape)     # the halo kernel ran
             close(back(ys[0]), ref, dtype, f"conv3h variant {v} {case}", bf16_rms=6e-3)

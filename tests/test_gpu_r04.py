@@ -385,8 +385,6 @@ def test_unet_forward_through_fused_attention_blocks(golden, cfg_name, monkeypat
     (63, 58, 40, 64, 64, 128, 128, True, True),      # 640 tiles: 2-3 per workgroup, producers run across tile boundaries
     (63, 58, 9, 128, 128, 128, 256, False, False),   # two n tiles, 1152 tiles: 4-5 per workgroup
     (63, 58, 3, 72, 96, 128, 256, False, True),      # non-square plane (9 x 3 blocks of 8 x 32 pixels)
-    (64, 46, 24, 32, 32, 192, 192, True, True),      # UNet 32^2 level: 4 rows per tile, 192 tiles
-    (64, 46, 66, 32, 32, 384, 192, False, True),     # 528 tiles: 2-3 per workgroup, ragged
 ])
 def test_conv3x3_halo_patch_persistent_tiles_bit_identical(case):
     """conv3h.hip k_conv3h_pers (round 4): persistent workgroups whose LDS-DMA producers run on across tile boundaries

@@ -11,8 +11,8 @@ from afldm_amd import _lib, ops
 from bench_kernels import timeit_graph
 
 
-# PAIRS=1: each case also on a sibling variant (e.g. 41 -> 47, the 32x32x16 MFMA form), outputs compared bit for bit
-SIB = {41: 47, 43: 48}
+# PAIRS=1: each case also on a sibling variant (the other tile of its plane size), outputs compared bit for bit
+SIB = {41: 46}
 CASES = (  # B, H, Cout, variant, input channel counts
     (64, 32, 192, 41, (64, 128, 192, 256, 384, 576)),
     (64, 16, 384, 43, (128, 256, 384, 512, 768)),

@@ -15,11 +15,9 @@ def short(n):
     if "k_conv3h" in n:
         m = re.search(r"Li(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E", n) or re.search(r"<\w+, (\d+), (\d+), (\d+), (\d+), (\d+)", n)
         return f"conv3h_{m.group(1)}x{m.group(3)}w{m.group(2)}c{int(m.group(4)) * int(m.group(5))}"
-    if "k_igemm3" in n:
-        return "igemm3_128x192p"
-    if "k_igemm" in n:
-        m = re.search(r"Li(\d+)ELi(\d+)ELi\d+ELi\d+ELi\d+E(?:Li(\d+)E)?", n) or re.search(r"<\w+, (\d+), (\d+), \d+, \d+, \d+(?:, (\d+))?", n)
-        return f"igemm{'2' if 'igemm2' in n else ''}_{m.group(1)}x{m.group(2)}" + (f"s{m.group(3)}" if m.group(3) else "")
+    if "k_igemm" in n:      # k_igemm<T, BM, BN, WGM, WGN, KCH> / k_igemm2<T, BM, BN, WGM, WGN, STAGES, NPROD, MINW>
+        m = re.search(r"Li(\d+)ELi(\d+)ELi\d+ELi\d+ELi(\d+)E", n) or re.search(r"<\w+, (\d+), (\d+), \d+, \d+, (\d+)", n)
+        return f"igemm2_{m.group(1)}x{m.group(2)}s{m.group(3)}" if "igemm2" in n else f"igemm_{m.group(1)}x{m.group(2)}"
     for k in ["k_attn_fused", "k_attn", "k_dense2_gn_act", "k_skinny", "k_af_act_plane", "k_af_act_p8", "k_af_act_slabs", "k_resample_small",
               "k_resample_plane", "k_conv_out_fused", "gn_partial", "gn_apply", "af_act_mfma", "af_act_kron", "af_act_small", "splitk", "axis_contract",
               "cin4", "small_cout", "silu", "ddim", "nchw", "timestep", "select", "advance"]:

@@ -15,22 +15,22 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # name: (M, Cout, KS, Ct), candidates "variant/splitk" (first = current policy)
 SHAPES = {
-    "S1 L32 3x3 192->192": ((65536, 192, 3, 192), ["29/1", "12/1", "26/1", "33/1"]),
-    "S1b L32 3x3 576->192": ((65536, 192, 3, 576), ["29/1", "26/1", "33/1"]),
-    "S1c L32 3x3 384->192": ((65536, 192, 3, 384), ["29/1", "26/1", "33/1"]),
-    "S1d L32 3x3 384->384": ((65536, 384, 3, 384), ["29/1", "26/1", "33/1"]),
-    "S2 L16 3x3 384->384": ((16384, 384, 3, 384), ["33/1", "29/1", "30/1", "22/1"]),
+    "S1 L32 3x3 192->192": ((65536, 192, 3, 192), ["29/1", "33/1"]),
+    "S1b L32 3x3 576->192": ((65536, 192, 3, 576), ["29/1", "33/1"]),
+    "S1c L32 3x3 384->192": ((65536, 192, 3, 384), ["29/1", "33/1"]),
+    "S1d L32 3x3 384->384": ((65536, 384, 3, 384), ["29/1", "33/1"]),
+    "S2 L16 3x3 384->384": ((16384, 384, 3, 384), ["33/1", "29/1", "30/1"]),
     "S2b L16 3x3 768->384": ((16384, 384, 3, 768), ["33/1", "29/1", "30/1"]),
-    "S3 L8 3x3 384->384": ((4096, 384, 3, 384), ["32/1", "33/4", "33/2", "31/2", "11/1"]),
-    "S4 L32 qkv 192->576": ((65536, 576, 1, 192), ["29/1", "31/1", "30/1", "12/1"]),
+    "S3 L8 3x3 384->384": ((4096, 384, 3, 384), ["32/1", "33/4", "33/2", "31/2"]),
+    "S4 L32 qkv 192->576": ((65536, 576, 1, 192), ["29/1", "31/1", "30/1"]),
     "S4b L16 qkv 384->1152": ((16384, 1152, 1, 384), ["31/1", "29/1", "30/1", "33/1"]),
-    "S5 L4 3x3 768->768": ((1024, 768, 3, 768), ["33/8", "33/4", "31/4", "31/8", "24/4"]),
-    "S6 L2 3x3 768->768": ((256, 768, 3, 768), ["32/4", "32/8", "11/4", "31/8"]),
-    "S7 L32 to_out 192->192": ((65536, 192, 1, 192), ["29/1", "31/1", "12/1"]),
+    "S5 L4 3x3 768->768": ((1024, 768, 3, 768), ["33/8", "33/4", "31/4", "31/8"]),
+    "S6 L2 3x3 768->768": ((256, 768, 3, 768), ["32/4", "32/8", "31/8"]),
+    "S7 L32 to_out 192->192": ((65536, 192, 1, 192), ["29/1", "31/1"]),
     "S9 L2 dense 3072->3072": ((64, 3072, 1, 3072), ["32/4", "32/8", "32/2", "32/12", "31/8", "33/8"]),
     "S9b L2 dense 6144->3072": ((64, 3072, 1, 6144), ["32/4", "32/8", "32/12", "31/8", "33/8"]),
     "T1 L4 qkv 768->2304": ((1024, 2304, 1, 768), ["32/1", "31/1", "30/1", "33/1", "32/2", "29/1"]),
-    "T2 L4 out 768->768": ((1024, 768, 1, 768), ["32/1", "31/1", "32/2", "11/1"]),
+    "T2 L4 out 768->768": ((1024, 768, 1, 768), ["32/1", "31/1", "32/2"]),
     "T3 L8 qkv 384->1152": ((4096, 1152, 1, 384), ["32/1", "31/1", "30/1", "29/1", "33/1"]),
     "T4 L8 out 384->384": ((4096, 384, 1, 384), ["32/1", "31/1", "30/1"]),
     "T5 L16 out 384->384": ((16384, 384, 1, 384), ["31/1", "30/1", "29/1", "32/1"]),
