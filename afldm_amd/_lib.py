@@ -24,6 +24,8 @@ ABI = _abi.read("afldm_hip.h")
 # the experiments' declarations (and their afldm_af_act_args) are read here too, so that they need no library: _exp.py binds
 # libafldm_exp.so from EXP_ABI on first use
 EXP_ABI = _abi.read("afldm_hip_experimental.h", ABI)
+# the slot sampler's extension (libafldm_slots.so): bound by _slots.py on first use
+SLOTS_ABI = _abi.read("afldm_hip_slots.h", ABI)
 ConvArgs, SepArgs, AfActArgs = ABI.structs["afldm_conv_args"], ABI.structs["afldm_sep_args"], EXP_ABI.structs["afldm_af_act_args"]
 F32, BF16 = ABI.constants["AFLDM_F32"], ABI.constants["AFLDM_BF16"]
 DTYPE_CODE = {torch.float32: F32, torch.bfloat16: BF16}

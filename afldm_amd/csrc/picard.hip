@@ -29,7 +29,7 @@ constexpr int PICARD_WINDOW_MAX = 256;      // rows of a window: the sweep keeps
 constexpr int PICARD_BLOCKS_MAX = 2048;     // blocks of a sweep per image (no grid stride: a thread owns ONE group of V elements)
 constexpr int STRIDE_THREADS = 1024;        // chunks of 16 bytes per pass of the gather (x 4 in flight per thread)
 
-// k_ddim_step's update, operation for operation, as slot_update in slots.hip spells it: x - c1 e is ONE fma, the division is
+// k_ddim_step's update, operation for operation, as slot_update in slot_common.hpp spells it: x - c1 e is ONE fma, the division is
 // correctly rounded, the last line two rounded products and a sum; contraction off, so that a swept row has afldm_ddim_step's bits.
 __device__ __forceinline__ float picard_update(float x, float e, float sa_t, float sb_t, float sa_p, float sb_p) {
 #pragma clang fp contract(off)

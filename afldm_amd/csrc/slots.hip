@@ -13,24 +13,15 @@
 // afldm_slot_exchange between replays: harvest a finished slot's latents and / or refill it, as a device command buffer says.
 // A block serves one slot (select: blockIdx.x, the other two: blockIdx.y): what it needs of the slot's state is uniform over the block.  HBM-bound; each
 // thread reads and writes its own indices only.  Every table index read from device memory is range-checked before use.
-#include "step_common.hpp"
+// (slot_update, the "ddim" update both translation units of the slot sampler apply, is in slot_common.hpp; the update for a table
+// of "ddim" AND "dpm" rows, afldm_slot_step_kinds, is slot_kinds.hip in libafldm_slots.so.)
+#include "slot_common.hpp"
 
 namespace afldm {
 
 namespace {
 
 constexpr int SELECT_THREADS = 256;      // chunks of 16 bytes per pass of a slot's row copy
-constexpr size_t SLOT_ELEMS_MAX = (size_t)1 << 30;      // elements of one slot: the kernels index a slot with int, grid stride included
-
-// k_ddim_step's update as the compiler builds it there: x - c1 e is ONE fma, the last line two rounded products and a sum.
-// Spelled out, with contraction off, because left to itself the compiler fuses the last line in the 4-wide form below and
-// not in k_ddim_step, and a slot must give afldm_ddim_step's bits (tests/test_gpu_slots.py compares them).
-__device__ __forceinline__ float slot_update(float x, float e, float sa_t, float sb_t, float sa_p, float sb_p) {
-#pragma clang fp contract(off)
-  const float x0 = __builtin_fmaf(-sb_t, e, x) / sa_t;
-  const float a = sa_p * x0, b = sb_p * e;
-  return a + b;
-}
 
 }  // namespace
 

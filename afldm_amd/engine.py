@@ -72,7 +72,8 @@ UNet batch is 2 B (conditional rows, then unconditional rows) and the step ends 
 SlotEngine has no schedule of its own: every batch row ("slot") walks its own stretch of one device row table with a cursor of
 its own, so "ddim" requests of different step counts share the graphs and a finished slot is harvested and refilled between replays
 (afldm_slot_select in place of afldm_select_step_row, afldm_slot_step in place of afldm_ddim_step, afldm_slot_exchange at the
-boundary); afldm_amd/serving.py drives it.
+boundary); afldm_amd/serving.py drives it.  Built with kinds=("ddim", "dpm") it takes "dpm" requests next to "ddim" ones: a
+history per slot and afldm_slot_step_kinds as the update, which reads each row's kind.
 
 PicardEngine (parallel-in-time sampling, ParaDiGMS) walks ONE "ddim" schedule, but a window of its rows at a time: every image keeps
 window + 1 states, the UNet evaluates the first `window` of them as one batch with a timestep per row, and the step ends in
@@ -981,19 +982,30 @@ class SlotTable:
     `schedule.key`, and the distinct timesteps they use in the order of the time-embedding table.  Plain Python - what the
     serving layer's host tests run against; SlotEngine uploads what `add` appends."""
 
-    def __init__(self, row_capacity, temb_capacity):
+    KIND_CODES = {"ddim": 0, "dpm": 1}                     # what afldm_slot_step_kinds reads in row_kind
+
+    def __init__(self, row_capacity, temb_capacity, kinds=("ddim",)):
         self.R, self.T = int(row_capacity), int(temb_capacity)
-        self.coef, self.t, self.temb = [], [], []          # per row: (c0, c1, c2, c3), the timestep, its time-embedding row
+        self.kinds = tuple(dict.fromkeys(kinds))
+        unknown = [k for k in self.kinds if k not in self.KIND_CODES]
+        if unknown or not self.kinds:
+            raise ValueError(f"SlotTable: kinds {tuple(kinds)!r}: slots know {tuple(self.KIND_CODES)} and need at least one")
+        self.coef, self.t, self.temb = [], [], []          # per row: the schedule's own row tuple, the timestep, its time-embedding row
+        self.kind = []                                     # per row: its kind's code
         self.timesteps, self._index = [], {}               # per time-embedding row: its timestep; timestep -> row
         self.spans = {}                                    # schedule.key -> (begin, end)
 
     def add(self, schedule):
         """(begin, end) of the schedule's rows, appended (with its unseen timesteps) on the first call for this key.  Raises
-        NotImplementedError for a kind other than "ddim" and RuntimeError when a table is full; a refused schedule leaves the
-        tables as they were."""
-        if schedule.kind != "ddim":
-            raise NotImplementedError(f"SlotEngine: update_kind {schedule.kind!r}: slots take 'ddim' schedules only (the other "
-                                      "kinds need a noise feed or a history per slot)")
+        NotImplementedError for a kind that is not among the table's `kinds` and RuntimeError when a table is full; a refused
+        schedule leaves the tables as they were."""
+        if schedule.kind not in self.kinds:
+            if self.kinds == ("ddim",):
+                raise NotImplementedError(f"SlotEngine: update_kind {schedule.kind!r}: slots take 'ddim' schedules only (the other "
+                                          "kinds need a noise feed or a history per slot; kinds=('ddim', 'dpm') adds the history)")
+            takes = " and ".join(repr(k) for k in sorted(self.kinds, key=lambda k: k == "ddim"))          # ('ddim' last)
+            raise NotImplementedError(f"SlotEngine: update_kind {schedule.kind!r}: slots take {takes} schedules only (the "
+                                      "other kinds need a noise feed or a second evaluation per slot)")
         if schedule.key in self.spans:
             return self.spans[schedule.key]
         unseen = [t for t in dict.fromkeys(schedule.timesteps) if t not in self._index]
@@ -1009,6 +1021,7 @@ class SlotTable:
             self.timesteps.append(t)
         for t, row in zip(schedule.timesteps, schedule.rows):
             self.coef.append(tuple(row))
+            self.kind.append(self.KIND_CODES[schedule.kind])
             self.t.append(float(t))
             self.temb.append(self._index[t])
         self.spans[schedule.key] = (begin, begin + n)
@@ -1024,15 +1037,18 @@ class SlotEngine(DenoiseEngine):
     finished or empty slot is frozen: evaluated, but not written).  So any grouping of steps into replays gives the same
     latents; grouping only affects utilisation, and is the serving layer's business (afldm_amd/serving.py).
 
-    add_schedule(schedule) -> (begin, end) stores a "ddim" schedule's rows once per `schedule.key`; the tables have fixed
-    capacities and fixed addresses, and are only appended to.  exchange(harvests, refills) is the boundary between replays:
-    one afldm_slot_exchange launch behind non-blocking uploads of the command buffer and the fresh latents from pinned
+    add_schedule(schedule) -> (begin, end) stores a schedule's rows once per `schedule.key`; the tables have fixed capacities and
+    fixed addresses, and are only appended to.  kinds: the schedule kinds the engine takes - ("ddim",) by default; with
+    ("ddim", "dpm") DPM-Solver++ requests share the batch with DDIM ones: the rows are 8 wide with a kind code each, every slot
+    has its own two history planes (`hist` [2, B, C, S, S], addressed by the slot like its latents, carried by _capture) and
+    the update is afldm_slot_step_kinds, which gives a "ddim" slot afldm_ddim_step's bits and a "dpm" slot afldm_dpm_step's.
+    exchange(harvests, refills) is the boundary between replays: one afldm_slot_exchange launch behind non-blocking uploads of the command buffer and the fresh latents from pinned
     staging, then one non-blocking device-to-host copy per harvested slot out of the output ring, each with its event.
     The engine has no schedule of its own: reset / run are the base class's and do not apply."""
     ONE_BRANCH = True           # one cursor table, one select launch: no parallel branches
 
     def __init__(self, unet, batch_size, use_graph=True, steps_per_graph=5, *, row_capacity=1024, temb_capacity=256,
-                 out_capacity=None):
+                 out_capacity=None, kinds=("ddim",)):
         if unet.device.type != "cuda":
             raise RuntimeError("SlotEngine needs the UNet on an MI355X ('cuda') device; there is no CPU path")
         refuse_class_conditional(unet, "SlotEngine")
@@ -1042,7 +1058,7 @@ class SlotEngine(DenoiseEngine):
         self.unet, self.scheduler, self.schedule = unet, None, None
         self.B, self.branches, self.use_graph = int(batch_size), 1, use_graph
         self.steps_per_graph = max(1, int(os.environ.get("AFLDM_STEPS_PER_GRAPH", steps_per_graph)))
-        self.table = SlotTable(row_capacity, temb_capacity)
+        self.table = SlotTable(row_capacity, temb_capacity, kinds)
         self.out_capacity = 2 * self.B if out_capacity is None else int(out_capacity)
         if self.out_capacity < 1:
             raise ValueError("SlotEngine: out_capacity must be at least 1")
@@ -1068,7 +1084,11 @@ class SlotEngine(DenoiseEngine):
         self.temb_table = torch.zeros(tb.T, width, dtype=unet.dtype, device=dev)
         self.temb_rows = torch.zeros(B, width, dtype=unet.dtype, device=dev)       # (zeros: a never-filled slot evaluates finite)
         self.temb_slices = unet.temb_slices(self.temb_rows, per_sample=True)
-        self.row_coef, self.row_t, self.row_temb = torch.zeros(tb.R, 4, **f32), torch.zeros(tb.R, **f32), torch.zeros(tb.R, **i32)
+        # one update per engine: a table of "ddim" rows alone keeps the 4-wide rows of afldm_slot_step; any other set of kinds takes
+        # 8-wide rows ("ddim" rows padded with zeros), a kind code per row and a history per slot (afldm_slot_step_kinds)
+        self._by_kind = tb.kinds != ("ddim",)
+        self.row_coef = torch.zeros(tb.R, 8 if self._by_kind else 4, **f32)
+        self.row_t, self.row_temb, self.row_kind = torch.zeros(tb.R, **f32), torch.zeros(tb.R, **i32), torch.zeros(tb.R, **i32)
         # the boundary's buffers: commands and fresh latents (two pinned stagings each, so the host can prepare one boundary
         # while the previous one's upload waits behind a replay), and the output ring with its pinned mirror
         self.cmd, self.fresh = torch.full((B, 4), -1, **i32), torch.zeros_like(self.lat)
@@ -1080,6 +1100,10 @@ class SlotEngine(DenoiseEngine):
         self._model_key = model_state_key(unet)
         self._side, self._sync = [], [ops.new_sync_buffer(dev)]
         self.hist = self.noise = self.known = self.mask = self.filter = self._static = None
+        if self._by_kind:
+            # h1, h2 per slot.  Never cleared at a refill: a request's first row has b1 = b2 = 0 and its second b2 = 0, and the
+            # update puts zeros in the place of a plane whose coefficient is 0, whatever the previous occupant left in it
+            self.hist = torch.zeros((2,) + tuple(self.lat.shape), **f32)
         self._busy.clear()
 
     def _upload(self, row0, temb0):
@@ -1087,7 +1111,10 @@ class SlotEngine(DenoiseEngine):
         tb = self.table
         if len(tb.t) > row0:
             dev = self.row_coef.device
-            self.row_coef[row0:len(tb.t)].copy_(torch.tensor(tb.coef[row0:], dtype=torch.float64).to(torch.float32).to(dev))
+            width = self.row_coef.shape[1]
+            rows = [tuple(row) + (0.0,) * (width - len(row)) for row in tb.coef[row0:]]
+            self.row_coef[row0:len(tb.t)].copy_(torch.tensor(rows, dtype=torch.float64).to(torch.float32).to(dev))
+            self.row_kind[row0:len(tb.t)].copy_(torch.tensor(tb.kind[row0:], dtype=torch.int32).to(dev))
             self.row_t[row0:len(tb.t)].copy_(torch.tensor(tb.t[row0:], dtype=torch.float32).to(dev))
             self.row_temb[row0:len(tb.t)].copy_(torch.tensor(tb.temb[row0:], dtype=torch.int32).to(dev))
         if len(tb.timesteps) > temb0:
@@ -1115,10 +1142,14 @@ class SlotEngine(DenoiseEngine):
         self._substep(self.lat, self.x_nhwc)
 
     def _apply(self, lat, eps, branch):
-        ops.slot_step(lat, eps, self.row_coef, self.pos, self.active)
+        if self._by_kind:
+            ops.slot_step_kinds(lat, eps, self.hist, self.row_coef, self.row_kind, self.pos, self.active)
+        else:
+            ops.slot_step(lat, eps, self.row_coef, self.pos, self.active)
 
     def _carried(self):
-        return [self.lat, self.pos, self.t_cur, self.temb_rows, self.active]
+        # (the history too: a capture happens with requests in their slots, and its warm-up step shifts their planes)
+        return [self.lat, self.pos, self.t_cur, self.temb_rows, self.active] + ([] if self.hist is None else [self.hist])
 
     def _rewind(self):
         pass                        # (the cursors are carried: _capture puts them back)

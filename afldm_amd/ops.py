@@ -2219,6 +2219,25 @@ def slot_step(x, eps_nhwc, row_coef, pos, active):
     return x
 
 
+def slot_step_kinds(x, eps_nhwc, hist, row_coef, row_kind, pos, active):
+    """afldm_slot_step_kinds (include/afldm_hip_slots.h, libafldm_slots.so), in place: slot b of x (NCHW fp32) with active[b] != 0 takes the update of its row's kind
+    (row_kind int32 [R]: 0 = ddim_step's with the first four floats of row_coef[pos[b]], 1 = dpm_step's with the row's first six
+    and the slot's own planes of hist fp32 [2, B, C, H, W]); row_coef fp32 [R, 8].  The other slots, and a "ddim" slot's history,
+    are not touched.  eps NHWC dtype."""
+    for name, t in (("x", x), ("eps", eps_nhwc), ("hist", hist), ("row_coef", row_coef), ("row_kind", row_kind)):
+        _dev(t, name)
+    B, C, H, W = x.shape
+    _slot_ints(B, pos=pos, active=active)
+    assert x.dtype == hist.dtype == row_coef.dtype == torch.float32 and row_coef.dim() == 2 and row_coef.shape[1] == 8
+    assert row_kind.dtype == torch.int32 and row_kind.numel() == row_coef.shape[0]
+    assert tuple(eps_nhwc.shape) == (B, H, W, C) and tuple(hist.shape) == (2, B, C, H, W)
+    from . import _slots              # (libafldm_slots.so, loaded on first use)
+    check(_slots.lib().afldm_slot_step_kinds(ptr(x), ptr(eps_nhwc), ptr(hist), ptr(row_coef), ptr(row_kind), ptr(pos),
+                                             ptr(active), B, row_coef.shape[0], C, H, W, _code(eps_nhwc), stream_ptr()),
+          "slot_step_kinds")
+    return x
+
+
 def slot_exchange(cmd, lat, out, fresh, pos, end):
     """afldm_slot_exchange: cmd int32 [B, 4] = {harvest, refill, begin, end} per slot - out[harvest] <- lat[b] where harvest >= 0,
     then lat[b] <- fresh[refill], pos[b] = begin - 1, end[b] = end where refill >= 0.  lat [B, ...], out [No, ...], fresh

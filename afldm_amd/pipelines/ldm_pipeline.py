@@ -80,12 +80,14 @@ class MyLDMPipeline(DiffusionPipeline):
     @torch.no_grad()
     def sample_mixed(self, num_inference_steps, generator=None, latents=None, output_type="pil", return_dict=True, slots=None,
                      steps_per_graph=5, engines=1):
-        """One DDIM sample (eta = 0) per entry of `num_inference_steps`, each with its own step count, in request order - through a
+        """One sample per entry of `num_inference_steps`, each with its own step count, in request order - DDIM (eta = 0), or
+        DPM-Solver(++) when `self.scheduler` is a DPMSolverMultistepScheduler (as __call__ chooses) - through a
         SamplingServer (afldm_amd/serving.py): the requests share the batch-`slots` graphs (default: one slot per request, 64 at
         the most, per engine) and a slot that finishes takes the next request.  generator: None, one torch.Generator (the start
         latents are drawn from it request by request) or one per request; latents: the start latents [n, C, S, S] instead.
         Request i is pipe(batch_size=1, num_inference_steps=num_inference_steps[i], generator=generator[i]) to the rounding of
-        the convolutions at another batch size.  output_type as __call__.  The server is kept for the next call."""
+        the convolutions at another batch size.  output_type as __call__.  The server is kept for the next call with the same
+        scheduler class: one built for DDIM takes no DPM requests, so swapping the scheduler builds another."""
         from ..serving import SamplingServer
         counts = [int(n) for n in num_inference_steps]
         if isinstance(generator, (list, tuple)) and len(generator) != len(counts):
@@ -93,9 +95,10 @@ class MyLDMPipeline(DiffusionPipeline):
         if latents is not None and latents.shape[0] != len(counts):
             raise ValueError(f"sample_mixed: {latents.shape[0]} start latents for {len(counts)} requests")
         slots = max(1, min(len(counts), 64)) if slots is None else int(slots)
-        key = (id(self.unet), slots, int(steps_per_graph), int(engines))
+        kinds = SamplingServer.default_kinds(self)
+        key = (id(self.unet), slots, int(steps_per_graph), int(engines), kinds)
         if key not in self.__dict__.get("_slot_servers", ()):
-            self.__dict__["_slot_servers"] = {key: SamplingServer(self, slots, steps_per_graph, engines)}
+            self.__dict__["_slot_servers"] = {key: SamplingServer(self, slots, steps_per_graph, engines, kinds=kinds)}
         server = self.__dict__["_slot_servers"][key]
         tickets = [server.submit(n, generator[i] if isinstance(generator, (list, tuple)) else generator,
                                  None if latents is None else latents[i:i + 1]) for i, n in enumerate(counts)]

@@ -19,10 +19,15 @@ The kernels freeze a finished slot, so every grouping gives the same latents; th
 runs ahead of the GPU: a turn only queues work.  Results leave the ring by non-blocking device-to-host copies with one event per
 ticket; a ring entry is free again once its ticket has been collected, and a turn that finds the ring full waits for the oldest.
 
+A pipeline whose scheduler is a DPMSolverMultistepScheduler gets engines built with kinds=("ddim", "dpm"): its requests are
+DPM-Solver++ ones by default, submit(..., solver="ddim" | "dpm") chooses per request, and both kinds share the batch - every
+slot carries its own solver history, and a 20-step DPM request next to 50-step DDIM ones leaves its slot after 20 evaluations.
+
 engines=2 builds two engines of `slots` slots each on two streams and deals the requests out alternately: two jobs in flight on
 one GPU, each filling the other's launch ramps and tails."""
 import collections
 import contextlib
+import inspect
 
 import torch
 
@@ -50,12 +55,16 @@ class Ticket:
 
 
 class SamplingServer:
-    def __init__(self, pipe, slots=64, steps_per_graph=5, engines=1, use_graph=True, engine_factory=None, **capacities):
-        """pipe: a MyLDMPipeline (its UNet and scheduler config); slots: per engine; capacities: SlotEngine's row_capacity,
-        temb_capacity, out_capacity.  engine_factory(i): builds engine i instead (the host tests pass a counting fake)."""
+    def __init__(self, pipe, slots=64, steps_per_graph=5, engines=1, use_graph=True, engine_factory=None, kinds=None,
+                 **capacities):
+        """pipe: a MyLDMPipeline (its UNet and scheduler config); slots: per engine; kinds: the schedule kinds the engines take
+        (SlotEngine's `kinds`; None: ("ddim", "dpm") when pipe.scheduler is a DPMSolverMultistepScheduler, else ("ddim",));
+        capacities: SlotEngine's row_capacity, temb_capacity, out_capacity.  engine_factory(i): builds engine i instead (the host
+        tests pass a counting fake)."""
         if slots < 1 or engines < 1 or steps_per_graph < 1:
             raise ValueError("SamplingServer: slots, engines and steps_per_graph must be at least 1")
         self.pipe, self.slots, self.steps_per_graph = pipe, int(slots), int(steps_per_graph)
+        self.kinds = self.default_kinds(pipe) if kinds is None else tuple(kinds)
         self._streams, self.engines = [], []
         for i in range(engines):
             # one stream per engine when there are several; a single engine works on the caller's current stream
@@ -65,7 +74,8 @@ class SamplingServer:
                     self.engines.append(engine_factory(i))
                 else:
                     from .engine import SlotEngine
-                    self.engines.append(SlotEngine(pipe.unet, self.slots, use_graph, self.steps_per_graph, **capacities))
+                    self.engines.append(SlotEngine(pipe.unet, self.slots, use_graph, self.steps_per_graph, kinds=self.kinds,
+                                                   **capacities))
         if any(s is not None for s in self._streams):
             torch.cuda.synchronize()
         self._queue = [collections.deque() for _ in self.engines]
@@ -81,19 +91,39 @@ class SamplingServer:
         return contextlib.nullcontext() if s is None else torch.cuda.stream(s)
 
     # ------------------------------------------------------------------------------------------------ requests
-    def _schedule(self, num_inference_steps):
+    @staticmethod
+    def default_kinds(pipe):
+        """What a server built for this pipeline takes: "dpm" schedules too when its scheduler is a DPM-Solver one."""
+        from .schedulers.dpmsolver import DPMSolverMultistepScheduler
+        return ("ddim", "dpm") if isinstance(pipe.scheduler, DPMSolverMultistepScheduler) else ("ddim",)
+
+    def _schedule(self, num_inference_steps, solver=None):
+        """The request's Schedule from a FRESH scheduler of the pipeline scheduler's config: solver None = the pipeline
+        scheduler's own class, "ddim" = DDIM (eta = 0), "dpm" = DPM-Solver(++) multistep."""
         from .schedulers.ddim import DDIMScheduler
         from .schedulers.dpmsolver import DPMSolverMultistepScheduler
         sched = self.pipe.scheduler
+        if solver is None:
+            solver = "dpm" if isinstance(sched, DPMSolverMultistepScheduler) else "ddim"
+        if solver not in ("ddim", "dpm"):
+            raise ValueError(f"SamplingServer: solver {solver!r}: 'ddim', 'dpm' or None (the pipeline scheduler's own)")
+        if solver == "dpm":
+            return DPMSolverMultistepScheduler.from_config(sched.config).schedule(int(num_inference_steps))
+        config = dict(sched.config)
         if isinstance(sched, DPMSolverMultistepScheduler):
-            raise NotImplementedError("SamplingServer needs a DDIMScheduler: slots take 'ddim' schedules only")
-        return DDIMScheduler.from_config(sched.config).schedule(int(num_inference_steps))
+            # a DPM config carries the noise schedule, the prediction type and the timestep spacing; what only DDIM has
+            # (set_alpha_to_one, ...) is DDIMScheduler's default, and the solver's own settings are not DDIM's to keep
+            named = inspect.signature(DDIMScheduler.__init__).parameters
+            config = {k: v for k, v in config.items() if k in named}
+        return DDIMScheduler.from_config(config).schedule(int(num_inference_steps))
 
-    def submit(self, num_inference_steps=50, generator=None, latents=None, schedule=None):
-        """Queue ONE sample of `num_inference_steps` DDIM steps (eta = 0), or of any "ddim"-kind Schedule given as `schedule`.
-        The start latents are drawn as pipe(batch_size=1, generator=...) draws them - randn_tensor([1, C, S, S]) with the
-        caller's generator - unless `latents` [1, C, S, S] is given, and scaled by the schedule's init_noise_sigma."""
-        sched = schedule if schedule is not None else self._schedule(num_inference_steps)
+    def submit(self, num_inference_steps=50, generator=None, latents=None, schedule=None, solver=None):
+        """Queue ONE sample of `num_inference_steps` steps of `solver` ("ddim": DDIM with eta = 0, "dpm": DPM-Solver(++) multistep,
+        None: the pipeline scheduler's own class), or of any Schedule of a kind the engines take given as `schedule`; a kind they
+        do not take raises the engine's NotImplementedError.  The start latents are drawn as pipe(batch_size=1, generator=...)
+        draws them - randn_tensor([1, C, S, S]) with the caller's generator - unless `latents` [1, C, S, S] is given, and scaled
+        by the schedule's init_noise_sigma."""
+        sched = schedule if schedule is not None else self._schedule(num_inference_steps, solver)
         e = self._count % len(self.engines)
         with self._on(e):
             span = self.engines[e].add_schedule(sched)
