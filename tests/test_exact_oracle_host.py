@@ -4,6 +4,7 @@ the three localised ones on Gaussian data - the gap that tests/test_gpu_exact_ge
 import pytest
 import torch
 
+import addressed_oracle as ado
 import exact_oracle as xo
 from test_gpu_ops import close
 
@@ -40,6 +41,62 @@ def test_helpers():
     bad[1, 3, 0, 5] += 1
     with pytest.raises(AssertionError, match=r"1 of 2048 values differ.*\(1, 3, 0, 5\)"):
         xo.assert_exact(bad, c.ref, "one value")
+
+
+# ------------------------------------------------------------------------------------------------ the fused UNet tail
+TAIL_CASES = [(C, Cout, G) for C in (64, 128, 192) for Cout, G in ado.tail_grid(C)]
+
+
+def test_silu_on_the_allowed_set():
+    """torch's fp32 SiLU rounded to bf16 returns v on {0, 8, 16, 24, 32} (silu moves v by a relative e^-v <= 3.4e-4, under the
+    2^-9 half-ulp) and zero on {-128, -256} (sigmoid underflows) - with an ulp of fp32 either way on v, too."""
+    v = torch.tensor(ado.TAIL_IDENTITY + ado.TAIL_ZERO, dtype=torch.float32)
+    want = ado.expected_silu_bf16(v.double())
+    for t in (v, torch.nextafter(v, v + 1), torch.nextafter(v, v - 1)):
+        got = torch.nn.functional.silu(t).to(torch.bfloat16).double()
+        ok = (got == want) | ((want == 0) & (got.abs() <= 1e-6))          # (an ulp beside 0 is not 0: silu(x) ~ x / 2 there)
+        assert bool(ok.all()), (t.tolist(), got.tolist())
+    assert torch.equal(torch.nn.functional.silu(v).to(torch.bfloat16).double(), want)
+
+
+@pytest.mark.parametrize("C,Cout,G", TAIL_CASES)
+def test_tail_cases_meet_the_caps(C, Cout, G):
+    """tail_case asserts the allowed set on the normalised values and integral y / 8 with |y / 8| <= 256 and sum((y / 8)^2) < 2^24
+    itself; the operands survive bf16, and the partials of every split count finish to (m, 1) (partials asserts it)."""
+    c = ado.tail_case(ado.TAIL_B, C, Cout, G)
+    assert c.max_abs <= xo.MAX_ABS and c.max_sumsq < xo.MAX_SUMSQ
+    for t in (c.x, c.w.double(), c.gamma, c.beta, c.ref):
+        assert ado.is_bf16(t)
+    assert torch.equal(c.bias, (c.bias / 8).round() * 8) and float(c.bias.abs().max()) <= 64
+    live = set(c.norm.unique().tolist())
+    assert live & set(ado.TAIL_ZERO) and live >= set(ado.TAIL_IDENTITY), f"the case does not reach both branches of silu: {sorted(live)}"
+    for S in ado.SPLITS:
+        ado.partials(c.m, C, c.N * c.N, S, c.seed)
+
+
+def test_tail_oracle_catches_planted_faults():
+    """A kernel that normalised and activated its zero padding (the shift beta - m gamma of sample 0 in every padded position), one
+    that took the statistics of the neighbouring sample, and one that lost the last input channel of one tap: each is caught by
+    assert_exact; the first differs on border pixels only."""
+    c = ado.tail_case(ado.TAIL_B, 192, 3, 32)
+    xo.assert_exact(ado.tail_reference(c.act, c.w, c.bias).to(torch.bfloat16), c.ref, "round trip")
+    cpg = c.C // c.G
+    pad = ado.expected_silu_bf16(c.beta)                                       # GroupNorm of a raw 0 with m = 0: beta
+    bad = ado.tail_reference(c.act, c.w, c.bias, activate_padding=pad)
+    diff = bad != c.ref
+    assert bool(diff.any()) and not bool(diff[:, 1:-1, 1:-1].any())
+    assert float((bad - c.ref).abs()[diff].min()) >= 8
+    with pytest.raises(AssertionError, match="differ from the float64 reference"):
+        xo.assert_exact(bad.to(torch.bfloat16), c.ref, "activated padding")
+    m_wrong = c.m.roll(1, 0).repeat_interleave(cpg, 1)[:, None, None, :]
+    act = torch.nn.functional.silu(c.gamma * (c.x - m_wrong) + c.beta).to(torch.bfloat16).double()     # (values off the allowed set)
+    with pytest.raises(AssertionError, match="differ from the float64 reference"):
+        xo.assert_exact(ado.tail_reference(act, c.w, c.bias).to(torch.bfloat16), c.ref, "another sample's statistics")
+    w = c.w.clone()
+    live = (w[:, 2, 2, :] != 0).any(0).nonzero()[-1]
+    w[:, 2, 2, int(live)] = 0
+    with pytest.raises(AssertionError, match="differ from the float64 reference"):
+        xo.assert_exact(ado.tail_reference(c.act, w, c.bias).to(torch.bfloat16), c.ref, "a dropped tap channel")
 
 
 # ------------------------------------------------------------------------------------------------ planted mutations

@@ -337,14 +337,16 @@ def _hot_token_block(T, C, heads, B=2, G=32, eps=1e-5, hot=5):
     return xb, gamma, beta, [w.to(BF16) for w in ws], bs
 
 
-def _bounded_loop_gaps(xb, gamma, beta, wb, bs, heads, G=32, eps=1e-5):
+def _bounded_loop_gaps(xb, gamma, beta, wb, bs, heads, G=32, eps=1e-5, h=None):
     """The kernel's own predicate from the bf16-rounded projections, per 32-query tile: max over the tile's queries of
     sqrt(|q|^2 max|k|^2) * 1.002 + 0.01 - m_run, q in log2 units (scale * log2 e folded in), m_run = the row maximum over the
-    first 32 keys, rounded to bf16.  A wave takes the bounded loop when this is <= 80 for all of its queries.  [B, heads, T / 32]"""
+    first 32 keys, rounded to bf16.  A wave takes the bounded loop when this is <= 80 for all of its queries.  [B, heads, T / 32]
+    h: the normalised tokens [B, T, C], where the caller dictates the statistics instead of taking them from the data."""
     import torch.nn.functional as F
     B, T, C = xb.shape
     d = C // heads
-    h = F.group_norm(xb.float().transpose(1, 2), G, gamma, beta, eps).transpose(1, 2)
+    if h is None:
+        h = F.group_norm(xb.float().transpose(1, 2), G, gamma, beta, eps).transpose(1, 2)
     q = ao.rnd(F.linear(h, wb[0].float(), bs[0]) * (d ** -0.5 * ao.LOG2E), BF16).view(B, T, heads, d).transpose(1, 2)
     k = ao.rnd(F.linear(h, wb[1].float(), bs[1]), BF16).view(B, T, heads, d).transpose(1, 2)
     kmax2 = k.pow(2).sum(-1).max(-1).values

@@ -3,14 +3,18 @@
 Operands are small integers (activations and weights in {-1, 0, +1}; bias, time embedding and residual in [-8, 8]), so every
 product and every partial sum is exact in fp32 in any order and the result is a bf16 value: the kernel must EQUAL the reference,
 whatever its tiling, slicing or summation order, and the GroupNorm partial sums must equal the sums of the stored output.  There is
-no tolerance anywhere in this file.  Out of scope (a GroupNorm-apply, SiLU, softmax or filter matrix inside the launch):
-act_conv_act, conv_out_fused, the trunk, af_* and the attention kernels.
+no tolerance anywhere in this file.  conv_out_fused (GroupNorm-apply and SiLU inside the launch) is covered on the inputs of
+addressed_oracle.tail_case: dictated statistics with rstd = 1 and normalised values on which bf16(silu(v)) is v or 0.  Out of
+scope (a GroupNorm-apply, SiLU, softmax or filter matrix inside the launch): act_conv_act, the trunk, af_* and the attention
+kernels (tests/test_gpu_attention_addressed.py holds the fused attention block to a derived per-element tolerance instead), and
+dense2.hip: its GroupNorm input is the convolution's own output, so its statistics cannot be dictated.
 """
 import ctypes
 
 import pytest
 import torch
 
+import addressed_oracle as ado
 import exact_oracle as xo
 from exact_oracle import assert_exact, assert_stats_exact, conv_case
 
@@ -757,3 +761,24 @@ def test_2x2_plane_as_dense_layer_exact(dtype, C1, C2, Cout, B):
         assert code == -16, f"the dense form of {c.what} {dtype} did not run on skinny.hip (code {code})"
     assert_exact(y, c.ref, c.what + " dense 2x2")
     assert_stats_exact(y.gn_partial, y, c.what + " dense 2x2")
+
+
+# ================================================================================================ g. the fused UNet tail
+@pytest.mark.parametrize("C", [64, 128, 192])
+def test_conv_out_fused_exact(C):
+    """afldm_conv_out_fused (GroupNorm-apply -> SiLU -> 3 x 3 convolution to <= 4 couts in one launch) bit for bit against the
+    float64 reference of addressed_oracle.tail_case: Cout 1 .. 4, G in {16, 32, 64}, B = 3, the fabricated partials in 1, 3 and 9
+    ragged splits (gn_channel_sums: its tail loop alone, and 8 + 1).  A kernel that activated its zero padding is off by at
+    least 8 on every border pixel; one that took another sample's or group's statistics is off on whole planes."""
+    ops = _ops()
+    fails = Failures()
+    for Cout, G in ado.tail_grid(C):
+        c = ado.tail_case(ado.TAIL_B, C, Cout, G)
+        x, w, bias = dev(c.x, BF16), dev(c.w, BF16), dev(c.bias, FP32)
+        gamma, beta = dev(c.gamma, FP32), dev(c.beta, FP32)
+        for S in ado.SPLITS:
+            x.gn_partial = ado.partials(c.m, C, c.N * c.N, S, c.seed).cuda()           # the op takes them from the tensor
+            y = ops.conv_out_fused(x, w, bias, gamma, beta, G, ado.EPS)
+            assert y is not None and y.shape == (c.B, c.N, c.N, Cout), "conv_out_fused refused the shape"
+            fails.run(f"{c.what} S={S}", lambda y=y, c=c, S=S: assert_exact(y, c.ref, f"{c.what} S={S}"))
+    fails.check()
