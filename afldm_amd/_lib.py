@@ -26,6 +26,8 @@ ABI = _abi.read("afldm_hip.h")
 EXP_ABI = _abi.read("afldm_hip_experimental.h", ABI)
 # the slot sampler's extension (libafldm_slots.so): bound by _slots.py on first use
 SLOTS_ABI = _abi.read("afldm_hip_slots.h", ABI)
+# counter-based device noise and the seeded samplers' updates (libafldm_noise.so): bound by _noise.py on first use
+NOISE_ABI = _abi.read("afldm_hip_noise.h", ABI)
 ConvArgs, SepArgs, AfActArgs = ABI.structs["afldm_conv_args"], ABI.structs["afldm_sep_args"], EXP_ABI.structs["afldm_af_act_args"]
 F32, BF16 = ABI.constants["AFLDM_F32"], ABI.constants["AFLDM_BF16"]
 DTYPE_CODE = {torch.float32: F32, torch.bfloat16: BF16}

@@ -15,44 +15,6 @@
 
 namespace afldm {
 
-namespace {
-
-// k_dpm_step's update as the compiler builds it there (gfx950 disassembly of its four instantiations; fp32 and bf16 eps agree,
-// the 16-byte and the scalar form do not).  V = 4: the packed fma pairs element 2j's p x with element 2j + 1's q e, so
-//   even elements  m = fma(p, x, rn(q e)),   odd elements  m = fma(q, e, rn(p x)),
-//   x' = fma(b2, h2, fma(b1, h1, fma(a, x, rn(b0 m))))
-// V = 1:  m = fma(p, x, rn(q e)),   x' = ((rn(a x) + rn(b0 m)) + rn(b1 h1)) + rn(b2 h2): four rounded products, three sums.
-// Spelled out with contraction off, as slot_update (slot_common.hpp): a slot must give afldm_dpm_step's bits (tests/test_gpu_slots_dpm.py).
-struct dpm_coef {
-  float p, q, a, b0, b1, b2;
-};
-
-template <int V>
-__device__ __forceinline__ float slot_dpm_m0(int k, float x, float e, const dpm_coef& c) {
-#pragma clang fp contract(off)
-  if (V == 4 && (k & 1)) {
-    const float t = c.p * x;
-    return __builtin_fmaf(c.q, e, t);
-  }
-  const float t = c.q * e;
-  return __builtin_fmaf(c.p, x, t);
-}
-
-template <int V>
-__device__ __forceinline__ float slot_dpm_out(float x, float m, float h1, float h2, const dpm_coef& c) {
-#pragma clang fp contract(off)
-  if (V == 4) {
-    const float t = c.b0 * m;
-    return __builtin_fmaf(c.b2, h2, __builtin_fmaf(c.b1, h1, __builtin_fmaf(c.a, x, t)));
-  }
-  const float ax = c.a * x, bm = c.b0 * m, t1 = c.b1 * h1, t2 = c.b2 * h2;
-  return ((ax + bm) + t1) + t2;
-}
-
-constexpr int KIND_DDIM = 0, KIND_DPM = 1;      // row_kind codes (SlotTable.KIND_CODES in afldm_amd/engine.py)
-
-}  // namespace
-
 // x NCHW fp32 [B, C, HW], in place; eps NHWC T; hist fp32 [2, B, C, HW] (h1, then h2; slot b's planes at b C HW in each half); row_coef [R, 8]: a "ddim" row's first
 // four floats, or the "dpm" row (p, q, a, b0, b1, b2, 0, 0).  V = 4 needs HW % 4 == 0 and 16-byte aligned x and hist.
 template <typename T, int V>

@@ -75,6 +75,10 @@ its own, so "ddim" requests of different step counts share the graphs and a fini
 boundary); afldm_amd/serving.py drives it.  Built with kinds=("ddim", "dpm") it takes "dpm" requests next to "ddim" ones: a
 history per slot and afldm_slot_step_kinds as the update, which reads each row's kind.
 
+SeededEngine (kind "seeded", DDIMScheduler.seeded_schedule) is stochastic DDIM without a noise buffer: afldm_seeded_step makes the
+noise in registers from a seed per sample, a device tensor the graphs read.  SeededSlotEngine takes such requests in slots, next to
+"ddim" and "dpm" ones: a seed per slot, an ordinal per row and afldm_slot_step_seeded as the update.
+
 PicardEngine (parallel-in-time sampling, ParaDiGMS) walks ONE "ddim" schedule, but a window of its rows at a time: every image keeps
 window + 1 states, the UNet evaluates the first `window` of them as one batch with a timestep per row, and the step ends in
 afldm_picard_sweep (the recurrence along the window, and how far each estimate moved), afldm_picard_stride (how many states to
@@ -544,6 +548,47 @@ class SDEditEngine(DenoiseEngine):
         self.known.copy_(orig)
         self.cmap.copy_(cmap)
         self.zfix.copy_(z)
+
+
+class SeededEngine(DenoiseEngine):
+    """Stochastic DDIM without a noise buffer: kind "seeded" (DDIMScheduler.seeded_schedule), whose update afldm_seeded_step makes
+    every element's noise in registers from (the sample's seed, the step's ordinal, the element) - Philox-4x32-10 and Box-Muller
+    (include/afldm_hip_noise.h).  run(latents, known=seeds): one integer seed per sample, 0 <= seed < 2^63, as a sequence or an
+    int64 tensor; they live in a device tensor the captured graphs read, so other seeds replay the same graphs.  Nothing is drawn
+    on the host and nothing is staged; a sample's result depends on its own seed and start latents only - not on its batch
+    position or on how the steps are grouped into replays.  The update is elementwise per sample, so parallel branches work:
+    each passes its slice of the seeds."""
+
+    def _seeded_state(self):
+        """The run's seeds, int64 [B]; every branch takes its batch slice."""
+        self.seeds = torch.zeros(self.B, dtype=torch.int64, device=self.lat.device)
+        return [self._slice(b, self.seeds) for b in range(self.branches)]
+
+    UPDATES = {"seeded": (ops.seeded_step, _seeded_state)}
+
+    def _check_known(self, known):
+        if known is None:
+            raise ValueError("SeededEngine: run(latents, known=seeds) needs one integer seed per sample")
+        return check_seeds(known, self.B, "SeededEngine"), None
+
+    def _set_known(self, seeds, extra):
+        self.seeds.copy_(seeds)
+
+
+def check_seeds(seeds, count, who):
+    """`seeds` (a sequence of ints or an integer tensor) as a host int64 tensor [count], every seed in [0, 2^63)."""
+    if isinstance(seeds, torch.Tensor):
+        if seeds.dtype not in (torch.int64, torch.int32) or seeds.numel() != count:
+            raise ValueError(f"{who}: seeds {tuple(seeds.shape)} {seeds.dtype}, want {count} integers")
+        host = seeds.detach().reshape(-1).to(device="cpu", dtype=torch.int64)
+    else:
+        seeds = list(seeds)
+        if len(seeds) != count or not all(isinstance(v, int) and not isinstance(v, bool) and 0 <= v < 2 ** 63 for v in seeds):
+            raise ValueError(f"{who}: seeds {seeds!r}, want {count} integers in [0, 2^63)")
+        host = torch.tensor(seeds, dtype=torch.int64)
+    if host.numel() and int(host.min()) < 0:
+        raise ValueError(f"{who}: a seed is negative; want integers in [0, 2^63)")
+    return host
 
 
 class ReversibleEngine(DenoiseEngine):
@@ -1046,6 +1091,7 @@ class SlotEngine(DenoiseEngine):
     staging, then one non-blocking device-to-host copy per harvested slot out of the output ring, each with its event.
     The engine has no schedule of its own: reset / run are the base class's and do not apply."""
     ONE_BRANCH = True           # one cursor table, one select launch: no parallel branches
+    TABLE = SlotTable           # the host's record of the row table (SeededSlotEngine: SeededSlotTable)
 
     def __init__(self, unet, batch_size, use_graph=True, steps_per_graph=5, *, row_capacity=1024, temb_capacity=256,
                  out_capacity=None, kinds=("ddim",)):
@@ -1058,7 +1104,7 @@ class SlotEngine(DenoiseEngine):
         self.unet, self.scheduler, self.schedule = unet, None, None
         self.B, self.branches, self.use_graph = int(batch_size), 1, use_graph
         self.steps_per_graph = max(1, int(os.environ.get("AFLDM_STEPS_PER_GRAPH", steps_per_graph)))
-        self.table = SlotTable(row_capacity, temb_capacity, kinds)
+        self.table = self.TABLE(row_capacity, temb_capacity, kinds)
         self.out_capacity = 2 * self.B if out_capacity is None else int(out_capacity)
         if self.out_capacity < 1:
             raise ValueError("SlotEngine: out_capacity must be at least 1")
@@ -1205,6 +1251,80 @@ class SlotEngine(DenoiseEngine):
     def take(self, idx):
         """out_host[idx] as a tensor of its own [1, C, H, W]; the caller has waited for the harvest's event."""
         return self.out_host[idx].clone().unsqueeze(0)
+
+
+class SeededSlotTable(SlotTable):
+    """SlotTable for engines that also take "seeded" schedules: a third kind code and, per row, its ordinal - the row's place in
+    its OWN schedule, 0 for the first evaluation, which is what the noise stream counts (not the row's index in the shared table)."""
+
+    KIND_CODES = {"ddim": 0, "dpm": 1, "seeded": 2}        # what afldm_slot_step_seeded reads in row_kind
+
+    def __init__(self, row_capacity, temb_capacity, kinds=("ddim", "seeded")):
+        super().__init__(row_capacity, temb_capacity, kinds)
+        self.ord = []                                      # per row: its ordinal
+
+    def add(self, schedule):
+        rows = len(self.t)
+        span = super().add(schedule)                       # (raises before it appends: a refused schedule changes nothing)
+        self.ord.extend(range(len(self.t) - rows))
+        return span
+
+
+class SeededSlotEngine(SlotEngine):
+    """SlotEngine that takes stochastic requests: kind "seeded" (DDIMScheduler.seeded_schedule) next to "ddim" and, if asked for,
+    "dpm".  The update is afldm_slot_step_seeded: afldm_slot_step_kinds plus the seeded update, whose noise is a function of the
+    slot's seed, its row's ordinal (`row_ord`) and the element - so a request's result does not depend on the slot it sits in,
+    on its neighbours or on the grouping into replays, and there is no noise feed.  exchange takes refills
+    {slot: (latents, begin, end, seed)}; the seeds of all slots are uploaded at a refill from pinned staging (two buffers, each
+    reused only after the event behind its previous upload, as the command buffer's)."""
+    TABLE = SeededSlotTable
+
+    def __init__(self, unet, batch_size, use_graph=True, steps_per_graph=5, *, row_capacity=1024, temb_capacity=256,
+                 out_capacity=None, kinds=("ddim", "seeded")):
+        super().__init__(unet, batch_size, use_graph, steps_per_graph, row_capacity=row_capacity, temb_capacity=temb_capacity,
+                         out_capacity=out_capacity, kinds=kinds)
+
+    def _allocate(self):
+        dev = self.unet.device
+        self.row_ord = torch.zeros(self.table.R, dtype=torch.int32, device=dev)      # (before the base class uploads the tables)
+        self.seeds = torch.zeros(self.B, dtype=torch.int64, device=dev)
+        self._seed_host = [0] * self.B                     # the host's mirror: every slot empty, as the base class leaves them
+        self._seed_staging = [(torch.zeros(self.B, dtype=torch.int64, pin_memory=True), torch.cuda.Event()) for _ in range(2)]
+        super()._allocate()
+
+    def _upload(self, row0, temb0):
+        super()._upload(row0, temb0)
+        tb = self.table
+        if len(tb.t) > row0:
+            self.row_ord[row0:len(tb.t)].copy_(torch.tensor(tb.ord[row0:], dtype=torch.int32).to(self.row_ord.device))
+
+    def _apply(self, lat, eps, branch):
+        if not self._by_kind:
+            return super()._apply(lat, eps, branch)
+        ops.slot_step_seeded(lat, eps, self.hist, self.row_coef, self.row_kind, self.row_ord, self.pos, self.active, self.seeds)
+
+    def exchange(self, harvests, refills):
+        """As SlotEngine.exchange, with refills {slot: (latents, begin, end, seed)}: seed an integer in [0, 2^63), read by the
+        slot's "seeded" rows only (a "ddim" or "dpm" request passes any, 0 say)."""
+        plain, seeds = {}, {}
+        for slot, refill in refills.items():
+            if len(refill) != 4:
+                raise ValueError("SeededSlotEngine: a refill is (latents, begin, end, seed)")
+            seed = refill[3]
+            if not (isinstance(seed, int) and not isinstance(seed, bool) and 0 <= seed < 2 ** 63):
+                raise ValueError(f"SeededSlotEngine: seed {seed!r}, want an integer in [0, 2^63)")
+            plain[slot], seeds[slot] = tuple(refill[:3]), seed
+        events = super().exchange(harvests, plain)
+        if seeds:
+            for slot, seed in seeds.items():
+                self._seed_host[slot] = seed
+            self._seed_staging.append(self._seed_staging.pop(0))
+            host, uploaded = self._seed_staging[-1]
+            uploaded.synchronize()                    # (its previous upload: two refills ago)
+            host.copy_(torch.tensor(self._seed_host, dtype=torch.int64))
+            self.seeds.copy_(host, non_blocking=True)
+            uploaded.record()
+        return events
 
 
 class PicardEngine(DenoiseEngine):

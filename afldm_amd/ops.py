@@ -2238,6 +2238,76 @@ def slot_step_kinds(x, eps_nhwc, hist, row_coef, row_kind, pos, active):
     return x
 
 
+# ----------------------------------------------------------------------------- counter-based device noise (libafldm_noise.so)
+def _seeds(seeds, B):
+    _dev(seeds, "seeds")
+    assert seeds.dtype == torch.int64 and seeds.is_contiguous() and seeds.numel() == B, f"seeds: int64 [{B}]"
+
+
+def philox_bits(seeds, groups, g0=0, ordinal=0, slot=0, c3=0, out=None):
+    """afldm_philox_bits (include/afldm_hip_noise.h): int32 [B, groups, 4] holding the raw Philox-4x32-10 words (as bit patterns)
+    of the counters (g0 + g, ordinal, slot, c3) - the low 32 bits of each - under the key of seeds[b] (int64 [B] on the device)."""
+    B = seeds.numel()
+    _seeds(seeds, B)
+    if out is None:
+        out = torch.empty((B, int(groups), 4), dtype=torch.int32, device=seeds.device)
+    assert out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (B, int(groups), 4)
+    from . import _noise              # (libafldm_noise.so, loaded on first use)
+    check(_noise.lib().afldm_philox_bits(ptr(out), ptr(seeds), int(g0), int(ordinal), int(slot), int(c3), B, int(groups),
+                                         stream_ptr()), "philox_bits")
+    return out
+
+
+def counter_noise(seeds, ordinals, shape, slot=0, out=None):
+    """afldm_counter_noise: the counter-based normal stream, fp32 NCHW `shape` = [B, C, H, W]; sample b from seeds[b] (int64 [B]) at
+    the step ordinal ordinals[b] (int32 [B]) and noise slot `slot`.  out: a contiguous fp32 tensor (or view) of that shape."""
+    B, C, H, W = (int(v) for v in shape)
+    _seeds(seeds, B)
+    _slot_ints(B, ordinals=ordinals)
+    if out is None:
+        out = torch.empty((B, C, H, W), dtype=torch.float32, device=seeds.device)
+    _dev(out, "out")
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, C, H, W)
+    from . import _noise
+    check(_noise.lib().afldm_counter_noise(ptr(out), ptr(seeds), ptr(ordinals), int(slot), B, C, H, W, stream_ptr()),
+          "counter_noise")
+    return out
+
+
+def seeded_step(x, eps_nhwc, seeds, coef, step_idx, advance=False, out=None):
+    """afldm_seeded_step: sde_step with the noise made in registers - sample b's from seeds[b] (int64 [B]) at the ordinal
+    *step_idx, noise slot 0.  x NCHW fp32 [B, C, H, W], eps NHWC dtype; coef float[8*nsteps] rows (p, q, lo, hi, a, b, d, c) and
+    step_idx int32[1] on device."""
+    _dev(x, "x"); _dev(eps_nhwc, "eps"); _dev(coef, "coef")
+    B, C, H, W = x.shape
+    _seeds(seeds, B)
+    assert x.dtype == torch.float32 and tuple(eps_nhwc.shape) == (B, H, W, C)
+    if out is None:
+        out = torch.empty_like(x)
+    from . import _noise
+    check(_noise.lib().afldm_seeded_step(ptr(x), ptr(eps_nhwc), ptr(seeds), ptr(out), ptr(coef), ptr(step_idx), int(advance),
+                                         B, C, H, W, _code(eps_nhwc), stream_ptr()), "seeded_step")
+    return out
+
+
+def slot_step_seeded(x, eps_nhwc, hist, row_coef, row_kind, row_ord, pos, active, seeds):
+    """afldm_slot_step_seeded, in place: slot_step_kinds plus kind code 2 - seeded_step's update with the row row_coef[pos[b]], the
+    ordinal row_ord[pos[b]] (int32 [R]) and the seed seeds[b] (int64 [B]); such a slot's history planes are not touched."""
+    for name, t in (("x", x), ("eps", eps_nhwc), ("hist", hist), ("row_coef", row_coef), ("row_kind", row_kind), ("row_ord", row_ord)):
+        _dev(t, name)
+    B, C, H, W = x.shape
+    _slot_ints(B, pos=pos, active=active)
+    _seeds(seeds, B)
+    assert x.dtype == hist.dtype == row_coef.dtype == torch.float32 and row_coef.dim() == 2 and row_coef.shape[1] == 8
+    assert row_kind.dtype == row_ord.dtype == torch.int32 and row_kind.numel() == row_ord.numel() == row_coef.shape[0]
+    assert tuple(eps_nhwc.shape) == (B, H, W, C) and tuple(hist.shape) == (2, B, C, H, W)
+    from . import _noise
+    check(_noise.lib().afldm_slot_step_seeded(ptr(x), ptr(eps_nhwc), ptr(hist), ptr(row_coef), ptr(row_kind), ptr(row_ord),
+                                              ptr(pos), ptr(active), ptr(seeds), B, row_coef.shape[0], C, H, W, _code(eps_nhwc),
+                                              stream_ptr()), "slot_step_seeded")
+    return x
+
+
 def slot_exchange(cmd, lat, out, fresh, pos, end):
     """afldm_slot_exchange: cmd int32 [B, 4] = {harvest, refill, begin, end} per slot - out[harvest] <- lat[b] where harvest >= 0,
     then lat[b] <- fresh[refill], pos[b] = begin - 1, end[b] = end where refill >= 0.  lat [B, ...], out [No, ...], fresh

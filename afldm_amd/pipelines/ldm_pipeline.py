@@ -79,7 +79,7 @@ class MyLDMPipeline(DiffusionPipeline):
 
     @torch.no_grad()
     def sample_mixed(self, num_inference_steps, generator=None, latents=None, output_type="pil", return_dict=True, slots=None,
-                     steps_per_graph=5, engines=1):
+                     steps_per_graph=5, engines=1, eta=None, seeds=None):
         """One sample per entry of `num_inference_steps`, each with its own step count, in request order - DDIM (eta = 0), or
         DPM-Solver(++) when `self.scheduler` is a DPMSolverMultistepScheduler (as __call__ chooses) - through a
         SamplingServer (afldm_amd/serving.py): the requests share the batch-`slots` graphs (default: one slot per request, 64 at
@@ -87,25 +87,84 @@ class MyLDMPipeline(DiffusionPipeline):
         latents are drawn from it request by request) or one per request; latents: the start latents [n, C, S, S] instead.
         Request i is pipe(batch_size=1, num_inference_steps=num_inference_steps[i], generator=generator[i]) to the rounding of
         the convolutions at another batch size.  output_type as __call__.  The server is kept for the next call with the same
-        scheduler class: one built for DDIM takes no DPM requests, so swapping the scheduler builds another."""
+        scheduler class: one built for DDIM takes no DPM requests, so swapping the scheduler builds another.
+        eta, seeds: a float (or one per request) and one integer seed per request - request i with eta != 0 is a stochastic DDIM
+        sample whose noise is a function of seeds[i] (SamplingServer.submit(eta=, seed=)); the server then also takes "seeded"
+        schedules.  With seeds and neither generator nor latents, request i starts from manual_seed(seeds[i])."""
         from ..serving import SamplingServer
         counts = [int(n) for n in num_inference_steps]
+        etas = [0.0] * len(counts) if eta is None else [float(v) for v in eta] if isinstance(eta, (list, tuple)) else [float(eta)] * len(counts)
+        if len(etas) != len(counts) or (seeds is not None and len(seeds) != len(counts)):
+            raise ValueError(f"sample_mixed: {len(etas)} eta values and {None if seeds is None else len(seeds)} seeds for "
+                             f"{len(counts)} requests")
         if isinstance(generator, (list, tuple)) and len(generator) != len(counts):
             raise ValueError(f"sample_mixed: {len(generator)} generators for {len(counts)} requests")
         if latents is not None and latents.shape[0] != len(counts):
             raise ValueError(f"sample_mixed: {latents.shape[0]} start latents for {len(counts)} requests")
         slots = max(1, min(len(counts), 64)) if slots is None else int(slots)
-        kinds = SamplingServer.default_kinds(self)
+        kinds = SamplingServer.default_kinds(self) + (("seeded",) if any(etas) or seeds is not None else ())
         key = (id(self.unet), slots, int(steps_per_graph), int(engines), kinds)
         if key not in self.__dict__.get("_slot_servers", ()):
             self.__dict__["_slot_servers"] = {key: SamplingServer(self, slots, steps_per_graph, engines, kinds=kinds)}
         server = self.__dict__["_slot_servers"][key]
         tickets = [server.submit(n, generator[i] if isinstance(generator, (list, tuple)) else generator,
-                                 None if latents is None else latents[i:i + 1]) for i, n in enumerate(counts)]
+                                 None if latents is None else latents[i:i + 1], eta=etas[i],
+                                 seed=None if seeds is None else seeds[i]) for i, n in enumerate(counts)]
         server.run()
         if not tickets:
             raise ValueError("sample_mixed: no requests")
         return server.decode(tickets, output_type, return_dict)
+
+    # ------------------------------------------------------------------------------------------------ seeded stochastic sampling
+    @torch.no_grad()
+    def sample_seeded_latents(self, seeds, eta=1.0, num_inference_steps=50, latents=None, use_graph=True):
+        """Stochastic DDIM, one sample per entry of `seeds` (integers in [0, 2^63)), with counter-based device noise: the noise
+        of sample i at step k is a function of (seeds[i], k, element) that the update kernel computes in registers
+        (include/afldm_hip_noise.h) - no noise buffer and no host draw, and the sample does not depend on its batch position or
+        its neighbours.  The start latents of sample i are randn_tensor(generator=manual_seed(seeds[i])) unless `latents`
+        [n, C, S, S] is given.  use_graph: SeededEngine on replayed HIP graphs; otherwise the eager loop - afldm_counter_noise
+        materialises the step's noise and afldm_sde_step applies it, which differs from the graph path by float rounding only.
+        eta = 0 is the plain "ddim" schedule: pipe(generator=[manual_seed(s) for s in seeds]) exactly.  A DPM scheduler raises.
+        Returns fp32 latents.  The stream is this project's own: it does not match torch's generators."""
+        from .. import ops
+        from ..engine import SeededEngine, check_seeds
+        self._refuse_dpm("sample_seeded_latents")
+        host = check_seeds(seeds, len(seeds), "sample_seeded_latents")
+        c, s = self.unet.config.in_channels, self.unet.config.sample_size
+        shape = (len(seeds), c, s, s)
+        if latents is None:
+            latents = randn_tensor(shape, generator=[torch.Generator().manual_seed(int(v)) for v in host.tolist()])
+        elif tuple(latents.shape) != shape:
+            raise ValueError(f"sample_seeded_latents: latents {tuple(latents.shape)}, want {shape}")
+        self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
+        if float(eta) == 0.0:
+            eng = cached_engine(self, "_engines", self.scheduler.schedule(num_inference_steps), shape[0], use_graph, self.unet)
+            eng.scheduler = self.scheduler
+            return eng.run(latents)
+        sched = self.scheduler.seeded_schedule(num_inference_steps, eta)
+        if use_graph:
+            eng = cached_engine(self, "_seeded_engines", sched, shape[0], True, self.unet, SeededEngine)
+            eng.scheduler = self.scheduler
+            return eng.run(latents, known=host)
+        dev = self.unet.device
+        if dev.type != "cuda":
+            raise RuntimeError("sample_seeded_latents needs the UNet on an MI355X ('cuda') device; there is no CPU path")
+        x = (latents.to(device=dev, dtype=torch.float32) * sched.init_noise_sigma).contiguous()
+        seeds_dev, rows = host.to(dev), sched.table(dev)
+        first = torch.zeros(1, dtype=torch.int32, device=dev)          # (every launch gets its step's row alone)
+        for k, t in enumerate(self.progress_bar(list(sched.timesteps))):
+            eps = self.unet.forward_nhwc(ops.to_nhwc(x, self.unet.dtype), t)
+            z = ops.counter_noise(seeds_dev, torch.full((shape[0],), k, dtype=torch.int32, device=dev), shape)
+            x = ops.sde_step(x, eps, z.unsqueeze(0), rows[k].contiguous(), first)
+        return x
+
+    @torch.no_grad()
+    def sample_seeded(self, seeds, eta=1.0, num_inference_steps=50, latents=None, use_graph=True, output_type="pil",
+                      return_dict=True):
+        """Sample images with seeded stochastic DDIM: sample_seeded_latents, then decode.  output_type as __call__; 'latent'
+        returns the latents in the UNet's dtype."""
+        out = self.sample_seeded_latents(seeds, eta, num_inference_steps, latents, use_graph)
+        return self._deliver(out.to(self.unet.dtype), output_type, return_dict)
 
     # ------------------------------------------------------------------------------------------------ parallel-in-time sampling
     @torch.no_grad()

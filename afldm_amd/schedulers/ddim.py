@@ -137,6 +137,13 @@ class DDIMScheduler:
         return Schedule.of(self, "sde", ts, lambda t: self.sde_coefficients(t, eta), [True] * len(ts),
                            _ddim_steps=int(num_inference_steps), _ddim_eta=float(eta))
 
+    def seeded_schedule(self, num_inference_steps, eta):
+        """stochastic_schedule(num_inference_steps, eta) for the seeded samplers (SeededEngine, SeededSlotEngine): the same rows,
+        float for float, as kind "seeded" - afldm_seeded_step makes every step's noise in registers from the sample's seed and
+        the step's ordinal, so nothing is drawn - under a key of its own."""
+        sde = self.stochastic_schedule(num_inference_steps, eta)
+        return Schedule.of(self, "seeded", sde.timesteps, sde.rows, _seeded_steps=int(num_inference_steps), _seeded_eta=float(eta))
+
     def panorama_schedule(self, num_inference_steps, eta=0.0):
         """MultiDiffusion sampling of a canvas larger than the model's window (Bar-Tal et al., ICML 2023) over this scheduler's
         `num_inference_steps` timesteps, as the Schedule PanoramaEngine replays with afldm_pano_step: the rows are

@@ -4,6 +4,9 @@ UNet evaluation, fixed when it is made.  `kind` names the update kernel that rea
     "ddim"  (c0, c1, c2, c3):            x0 = (x - c1 eps) / c0;  x_out = c2 x0 + c3 eps                  afldm_ddim_step
     "dpm"   (p, q, a, b0, b1, b2, 0, 0): m0 = p x + q eps;  x_out = a x + b0 m0 + b1 m1 + b2 m2           afldm_dpm_step
     "sde"   (p, q, lo, hi, a, b, d, c):  x0 = clamp(p x + q eps, lo, hi);  x_out = a x + b x0 + d eps + c z   afldm_sde_step
+    "seeded" the "sde" row, float for float, with z made in the update's registers from (the sample's seed, the step ordinal,
+            the element) by a counter-based generator - no draws, no noise buffer:
+            t = rn(p x) + rn(q eps);  x0 = clamp(t, lo, hi);  x_out = ((rn(a x) + rn(b x0)) + rn(d eps)) + rn(c z)   afldm_seeded_step
     "repaint" (p, q, lo, hi, a, b, c, k0, k1, u0, u1, 0):  x0 = clamp(p x + q eps, lo, hi);  unknown = a x0 + b eps + c z_u;
             y = m (k0 known + k1 z_k) + (1 - m) unknown;  x_out = u0 y + u1 z_b                           afldm_repaint_step
     "ilvr"  (p, q, lo, hi, a, b, c, k0, k1, w, 0, 0):  x0 = clamp(p x + q eps, lo, hi);  xp = a x0 + b eps + c z_u;
@@ -33,7 +36,7 @@ UNet evaluation, fixed when it is made.  `kind` names the update kernel that rea
             latents on the grid 2^-32:  f = boot ? near : far;  x = rn_f32(near) 2^-32;  q = rn_i64(fl32(fl32(cx x) + fl32(ce eps)) 2^32);
             far <- near;  near <- f + sign q - integer arithmetic, so the same row with the other sign undoes it    afldm_rev_step
 
-The rows come from the scheduler that owns the update (DDIMScheduler.schedule / stochastic_schedule,
+The rows come from the scheduler that owns the update (DDIMScheduler.schedule / stochastic_schedule / seeded_schedule,
 DDIMScheduler.repaint_schedule / ilvr_schedule / panorama_schedule / pag_schedule / sag_schedule / outpaint_schedule / hires_schedule / sdedit_schedule / reversible_schedule, DPMSolverMultistepScheduler.schedule, I2SBScheduler.ode_schedule / bridge_schedule,
 MyLDMPipeline.inversion_schedule) as Python floats and are rounded once to fp32 by `table`.  An "sde" schedule also states which
 steps draw noise and how: exactly the randn_tensor calls, in the same order, that the scheduler's eager `step()` makes, so that
@@ -53,7 +56,7 @@ from ..utils import randn_tensor
 # kind -> (row width, noise slots per step, may a step draw): the one place that states them.  Several slots: `draws` is per slot
 KINDS = {"ddim": (4, 1, False), "dpm": (8, 1, False), "sde": (8, 1, True), "repaint": (12, 3, True), "ilvr": (12, 2, True),
          "pano": (8, 1, True), "pag": (12, 1, True), "sag": (12, 1, True), "outpaint": (12, 3, True),
-         "hires": (12, 1, True), "sdedit": (12, 1, True), "rev": (4, 1, False), "cfg": (12, 1, True)}
+         "hires": (12, 1, True), "sdedit": (12, 1, True), "rev": (4, 1, False), "cfg": (12, 1, True), "seeded": (8, 1, False)}
 ROW_WIDTH, NOISE_SLOTS = {k: v[0] for k, v in KINDS.items()}, {k: v[1] for k, v in KINDS.items() if v[2]}      # derived views
 _MADE = {}          # key -> Schedule: the rows are ~0.1 ms of scalar tensor arithmetic each, and a sampler asks per call
 

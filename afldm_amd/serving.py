@@ -23,6 +23,10 @@ A pipeline whose scheduler is a DPMSolverMultistepScheduler gets engines built w
 DPM-Solver++ ones by default, submit(..., solver="ddim" | "dpm") chooses per request, and both kinds share the batch - every
 slot carries its own solver history, and a 20-step DPM request next to 50-step DDIM ones leaves its slot after 20 evaluations.
 
+A server built with kinds that hold "seeded" - kinds=("ddim", "seeded"), or ("ddim", "dpm", "seeded") - builds SeededSlotEngines and
+also takes stochastic DDIM requests: submit(n, eta=0.7, seed=s).  Such a request's noise is a function of its seed, the step and
+the element (include/afldm_hip_noise.h), so its result is the same in any slot, next to any neighbours, under any grouping.
+
 engines=2 builds two engines of `slots` slots each on two streams and deals the requests out alternately: two jobs in flight on
 one GPU, each filling the other's launch ramps and tails."""
 import collections
@@ -38,8 +42,8 @@ class Ticket:
     """One submitted sample.  done(): its latents have arrived on the host; result(): the fp32 latents [1, C, H, W] (waits for the
     copy if the sample has been harvested, raises if it has not: drive the server with run() or poll())."""
 
-    def __init__(self, server, index, engine, steps, span, latents):
-        self.server, self.index, self.engine, self.steps = server, index, engine, steps
+    def __init__(self, server, index, engine, steps, span, latents, seed=0):
+        self.server, self.index, self.engine, self.steps, self.seed = server, index, engine, steps, seed
         self._span, self._start, self._ring, self._event, self._latents = span, latents, None, None, None
 
     def done(self):
@@ -58,13 +62,15 @@ class SamplingServer:
     def __init__(self, pipe, slots=64, steps_per_graph=5, engines=1, use_graph=True, engine_factory=None, kinds=None,
                  **capacities):
         """pipe: a MyLDMPipeline (its UNet and scheduler config); slots: per engine; kinds: the schedule kinds the engines take
-        (SlotEngine's `kinds`; None: ("ddim", "dpm") when pipe.scheduler is a DPMSolverMultistepScheduler, else ("ddim",));
+        (SlotEngine's `kinds`; None: ("ddim", "dpm") when pipe.scheduler is a DPMSolverMultistepScheduler, else ("ddim",); kinds
+        that hold "seeded" build SeededSlotEngines, which take stochastic requests: submit(n, eta=..., seed=...));
         capacities: SlotEngine's row_capacity, temb_capacity, out_capacity.  engine_factory(i): builds engine i instead (the host
         tests pass a counting fake)."""
         if slots < 1 or engines < 1 or steps_per_graph < 1:
             raise ValueError("SamplingServer: slots, engines and steps_per_graph must be at least 1")
         self.pipe, self.slots, self.steps_per_graph = pipe, int(slots), int(steps_per_graph)
         self.kinds = self.default_kinds(pipe) if kinds is None else tuple(kinds)
+        self._seeded = "seeded" in self.kinds                          # refills then carry the request's seed
         self._streams, self.engines = [], []
         for i in range(engines):
             # one stream per engine when there are several; a single engine works on the caller's current stream
@@ -73,9 +79,9 @@ class SamplingServer:
                 if engine_factory is not None:
                     self.engines.append(engine_factory(i))
                 else:
-                    from .engine import SlotEngine
-                    self.engines.append(SlotEngine(pipe.unet, self.slots, use_graph, self.steps_per_graph, kinds=self.kinds,
-                                                   **capacities))
+                    from .engine import SeededSlotEngine, SlotEngine
+                    cls = SeededSlotEngine if self._seeded else SlotEngine
+                    self.engines.append(cls(pipe.unet, self.slots, use_graph, self.steps_per_graph, kinds=self.kinds, **capacities))
         if any(s is not None for s in self._streams):
             torch.cuda.synchronize()
         self._queue = [collections.deque() for _ in self.engines]
@@ -97,14 +103,14 @@ class SamplingServer:
         from .schedulers.dpmsolver import DPMSolverMultistepScheduler
         return ("ddim", "dpm") if isinstance(pipe.scheduler, DPMSolverMultistepScheduler) else ("ddim",)
 
-    def _schedule(self, num_inference_steps, solver=None):
+    def _schedule(self, num_inference_steps, solver=None, eta=0.0):
         """The request's Schedule from a FRESH scheduler of the pipeline scheduler's config: solver None = the pipeline
-        scheduler's own class, "ddim" = DDIM (eta = 0), "dpm" = DPM-Solver(++) multistep."""
+        scheduler's own class, "ddim" = DDIM (eta = 0), "dpm" = DPM-Solver(++) multistep; eta != 0: DDIM's "seeded" schedule."""
         from .schedulers.ddim import DDIMScheduler
         from .schedulers.dpmsolver import DPMSolverMultistepScheduler
         sched = self.pipe.scheduler
         if solver is None:
-            solver = "dpm" if isinstance(sched, DPMSolverMultistepScheduler) else "ddim"
+            solver = "dpm" if isinstance(sched, DPMSolverMultistepScheduler) and eta == 0.0 else "ddim"
         if solver not in ("ddim", "dpm"):
             raise ValueError(f"SamplingServer: solver {solver!r}: 'ddim', 'dpm' or None (the pipeline scheduler's own)")
         if solver == "dpm":
@@ -115,26 +121,42 @@ class SamplingServer:
             # (set_alpha_to_one, ...) is DDIMScheduler's default, and the solver's own settings are not DDIM's to keep
             named = inspect.signature(DDIMScheduler.__init__).parameters
             config = {k: v for k, v in config.items() if k in named}
-        return DDIMScheduler.from_config(config).schedule(int(num_inference_steps))
+        ddim = DDIMScheduler.from_config(config)
+        if eta != 0.0:
+            return ddim.seeded_schedule(int(num_inference_steps), eta)
+        return ddim.schedule(int(num_inference_steps))
 
-    def submit(self, num_inference_steps=50, generator=None, latents=None, schedule=None, solver=None):
+    def submit(self, num_inference_steps=50, generator=None, latents=None, schedule=None, solver=None, eta=0.0, seed=None):
         """Queue ONE sample of `num_inference_steps` steps of `solver` ("ddim": DDIM with eta = 0, "dpm": DPM-Solver(++) multistep,
         None: the pipeline scheduler's own class), or of any Schedule of a kind the engines take given as `schedule`; a kind they
         do not take raises the engine's NotImplementedError.  The start latents are drawn as pipe(batch_size=1, generator=...)
         draws them - randn_tensor([1, C, S, S]) with the caller's generator - unless `latents` [1, C, S, S] is given, and scaled
-        by the schedule's init_noise_sigma."""
-        sched = schedule if schedule is not None else self._schedule(num_inference_steps, solver)
+        by the schedule's init_noise_sigma.
+        eta != 0 queues a stochastic DDIM sample (a "seeded" schedule): it needs `seed`, an integer in [0, 2^63) that fixes the
+        noise of every step, and a server whose kinds hold "seeded" (otherwise the engine's NotImplementedError); solver must be
+        None or "ddim".  With a seed and neither `latents` nor `generator`, the start latents are
+        randn_tensor(shape, generator=torch.Generator().manual_seed(seed)).  A "seeded" Schedule given as `schedule` needs a seed too."""
+        eta = float(eta)
+        if seed is not None and not (isinstance(seed, int) and not isinstance(seed, bool) and 0 <= seed < 2 ** 63):
+            raise ValueError(f"SamplingServer.submit: seed {seed!r}, want an integer in [0, 2^63)")
+        if eta != 0.0 and solver not in (None, "ddim"):
+            raise ValueError(f"SamplingServer.submit: eta = {eta} goes with DDIM, not with solver {solver!r}")
+        sched = schedule if schedule is not None else self._schedule(num_inference_steps, solver, eta)
+        if sched.kind == "seeded" and seed is None:
+            raise ValueError("SamplingServer.submit: a stochastic request (eta != 0) needs seed=: its noise is a function of the seed")
         e = self._count % len(self.engines)
         with self._on(e):
             span = self.engines[e].add_schedule(sched)
         cfg = self.pipe.unet.config
         shape = (1, cfg.in_channels, cfg.sample_size, cfg.sample_size)
         if latents is None:
+            if generator is None and seed is not None:
+                generator = torch.Generator().manual_seed(seed)
             latents = randn_tensor(shape, generator=generator)
         elif tuple(latents.shape) != shape:
             raise ValueError(f"SamplingServer.submit: latents {tuple(latents.shape)}, want {shape}")
         start = latents.to(torch.float32) * sched.init_noise_sigma
-        ticket = Ticket(self, self._count, e, span[1] - span[0], span, start)
+        ticket = Ticket(self, self._count, e, span[1] - span[0], span, start, 0 if seed is None else seed)
         self._count += 1
         if ticket.steps == 0:
             ticket._latents, ticket._start = start.cpu(), None
@@ -169,7 +191,7 @@ class SamplingServer:
         for b in range(len(slots)):
             if slots[b] is None and queue:
                 ticket = queue.popleft()
-                refills[b] = (ticket._start, *ticket._span)
+                refills[b] = (ticket._start, *ticket._span) + ((ticket.seed,) if self._seeded else ())
                 slots[b] = [ticket, ticket.steps]
                 ticket._start = None
         with self._on(e):
