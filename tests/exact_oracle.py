@@ -8,6 +8,8 @@ must then equal a float64 evaluation bit for bit, whatever its tiling, slicing o
 conv_case() builds the operands of one ops.conv2d-style problem with its float64 reference and asserts the two conditions on the
 reference itself: (a) max|y| <= 256, (b) for every sample and channel sum(y^2) < 2^24 (the GroupNorm partial sums are then exact
 integers as well).  They are conditions, not measurements: a case that breaks one gets another seed or a lower density.
+The launches that normalise such an output themselves (dense2.hip, afldm_af_act_slabs, the y_norm epilogue) are held to a
+per-element tolerance on the same kind of operands by tests/fusednorm_oracle.py, which builds its chain cases with conv_case.
 """
 import types
 

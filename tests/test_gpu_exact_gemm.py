@@ -5,17 +5,21 @@ product and every partial sum is exact in fp32 in any order and the result is a 
 whatever its tiling, slicing or summation order, and the GroupNorm partial sums must equal the sums of the stored output.  There is
 no tolerance anywhere in this file.  conv_out_fused (GroupNorm-apply and SiLU inside the launch) is covered on the inputs of
 addressed_oracle.tail_case: dictated statistics with rstd = 1 and normalised values on which bf16(silu(v)) is v or 0.  Out of
-scope (a GroupNorm-apply, SiLU, softmax or filter matrix inside the launch): act_conv_act, the trunk, af_* and the attention
-kernels (tests/test_gpu_attention_addressed.py holds the fused attention block to a derived per-element tolerance instead), and
-dense2.hip: its GroupNorm input is the convolution's own output, so its statistics cannot be dictated.
+scope (a GroupNorm-apply, SiLU, softmax or filter matrix inside the launch): act_conv_act, the trunk, the stand-alone af_* launches
+and the attention kernels (tests/test_gpu_attention_addressed.py holds the fused attention block to a derived per-element tolerance
+instead).  dense2.hip, afldm_af_act_slabs and the y_norm epilogue normalise the convolution's own output: on integer operands that
+output and its statistics are exact, and tests/test_gpu_fused_norm_exact.py holds what follows to a half-ulp tolerance per element
+(y_norm here too: test_norm_out_*).
 """
 import ctypes
+import functools
 
 import pytest
 import torch
 
 import addressed_oracle as ado
 import exact_oracle as xo
+import fusednorm_oracle as fo
 from exact_oracle import assert_exact, assert_stats_exact, conv_case
 
 pytestmark = pytest.mark.gpu
@@ -645,25 +649,63 @@ def test_c8_layout_exact(N, C, Cout, B, tile):
     assert_stats_exact(y2.gn_partial, y2, c2.what + " c8 -> NHWC")
 
 
-@pytest.mark.parametrize("B", [3, 64])
-@pytest.mark.parametrize("C,Cout,sc,applied", [(384, 384, None, True), (768, 384, None, False), (384, 384, (384, 384), True)])
-def test_norm_out_leaves_output_and_statistics_exact(B, C, Cout, sc, applied):
-    """norm_out set (8^2 planes, bf16: the epilogue also applies the GroupNorm that follows): the plain output y and its statistics
-    are still exact.  y_norm is not checked here (it is not an exact quantity).  applied: at batch 64 the one-sample tile with the
-    whole K per workgroup normalises in its epilogue (768 -> 384 splits K there: the wrapper then attaches nothing).  With a
-    shortcut the call is the three-tap fold at both batches (afldm_conv2d_shortcut_ok == 2)."""
+@functools.lru_cache(None)
+def _norm_out_case(B, C, Cout, sc):
+    return conv_case(B, 8, 8, C, 0, Cout, 3, temb=sc is None, shortcut=sc)
+
+
+def _norm_out(B, C, Cout, G, sc, applied):
+    """conv2d with norm_out = per-channel (gamma in [0.5, 1.5], beta ~ 0.3 N(0, 1)), G groups: y and its statistics exact; where the
+    epilogue normalised (`applied`), y.norm_applied within fusednorm_oracle.check_elements of float64 GroupNorm of the exact y."""
     ops = _ops()
-    c = conv_case(B, 8, 8, C, 0, Cout, 3, temb=sc is None, shortcut=sc)
+    c = _norm_out_case(B, C, Cout, sc)
     o = operands(c, BF16)
     kw = conv_kwargs(c, o)
     if sc is not None:
         assert ops.conv2d_shortcut_ok(o["x1"], o["w"], o["bias"], o["shortcut"]) == 2
-    gamma, beta = torch.ones(Cout, device="cuda"), torch.zeros(Cout, device="cuda")
-    y = ops.conv2d(o["x1"], o["w"], o["bias"], want_stats=True, norm_out=(gamma, beta, 32, 1e-5), **kw)
-    if B == 64 and applied:
-        assert getattr(y, "norm_applied", None) is not None, "the one-sample 8x8 tile normalises in its epilogue"
+    gen = torch.Generator().manual_seed(Cout + G)
+    gamma, beta = (torch.rand(Cout, generator=gen) + 0.5).float(), (torch.randn(Cout, generator=gen) * 0.3).float()
+    y = ops.conv2d(o["x1"], o["w"], o["bias"], want_stats=True, norm_out=(gamma.cuda(), beta.cuda(), G, fo.EPS), **kw)
+    hn = getattr(y, "norm_applied", None)
+    if applied:
+        assert hn is not None, "the one-sample 8x8 tile normalises in its epilogue"
     assert_exact(y, c.ref, c.what + " norm_out")
     assert_stats_exact(y.gn_partial, y, c.what + " norm_out")
+    if hn is not None:
+        y3 = c.ref.reshape(B, 64, Cout)
+        _, _, var = fo.group_norm64(y3, gamma, beta, G)
+        assert float(var.min()) >= fo.MIN_VAR, c.what
+        hn64, _, _ = fo.group_norm64(y3, gamma, beta, G)
+        worst = fo.check_elements(hn, hn64, hn64, BF16, f"{c.what} G{G} y_norm")
+        print(f"[exact] y_norm {c.what} G{G}: error / tolerance {worst:.3f}")
+
+
+@pytest.mark.parametrize("B", [3, 64])
+@pytest.mark.parametrize("C,Cout,sc,applied", [(384, 384, None, True), (768, 384, None, False), (384, 384, (384, 384), True)])
+def test_norm_out_leaves_output_and_statistics_exact(B, C, Cout, sc, applied):
+    """norm_out set (8^2 planes, bf16: the epilogue also applies the GroupNorm that follows): the plain output y and its statistics
+    are still exact, and where `norm_applied` is attached it is held element by element to the float64 GroupNorm of that exact y
+    (per-channel gamma / beta; tests/fusednorm_oracle.py: 2^-8 |ref| + 2^-16 max|hn|).  applied: at batch 64 the one-sample tile with
+    the whole K per workgroup normalises in its epilogue (768 -> 384 splits K there: the wrapper then attaches nothing).  With a
+    shortcut the call is the three-tap fold at both batches (afldm_conv2d_shortcut_ok == 2).  These cases keep the weight density of
+    the exact file (sigma of a group ~ 30, outside the oracle's sigma <= 12 window, which is a matter of sensitivity, not of the
+    tolerance's validity); the cases inside the window are those of tests/test_gpu_fused_norm_exact.py."""
+    _norm_out(B, C, Cout, 32, sc, B == 64 and applied)
+
+
+# afldm_conv2d_norm_ok among Cin = Cout in {96, 192, 384, 768} and G in {8, 32} (bf16, 8^2): 192 from batch 54, 384 from batch 41,
+# 768 from batch 21 but not at 64 (another tile takes it there), 96 never, whatever G is (fusednorm_oracle.NORM_OK_FROM; the host file
+# asserts this list).  Each accepted pair at the first batch that reports 1 and, where 64 does too, at 64.
+NORM_OUT_MORE = [(54, 192, 8), (64, 192, 8), (54, 192, 32), (64, 192, 32), (41, 384, 8), (64, 384, 8), (41, 384, 32),
+                 (21, 768, 8), (21, 768, 32)]
+
+
+@pytest.mark.parametrize("B,C,G", NORM_OUT_MORE)
+def test_norm_out_other_groups_and_first_batches(B, C, G):
+    """The other (Cout, G) afldm_conv2d_norm_ok accepts (NORM_OUT_MORE), at the smallest batch at which it reports 1 beside 64:
+    6 / 12 / 24 / 48 / 96 channels per group."""
+    assert B in (fo.NORM_OK_FROM[C], 64)
+    _norm_out(B, C, C, G, None, True)
 
 
 def _resample_exact(c, dtype, want_stats=True):
