@@ -80,10 +80,20 @@ __global__ void k_timestep_embedding(const float* __restrict__ t, T* __restrict_
   }
 }
 
+// silu_f's hardware reciprocal returns 0 for a denormal result: from x = -87.35 down 1 + exp(-x) is above 2^126 and
+// silu_f gives -0, where x / (1 + exp(-x)) stays a normal number down to x = -91.9 (1.0e-36 at -87.35).  Below -87
+// 1 + exp(-x) is exp(-x) in fp32, so the value is x exp(x): the exponential is taken 2^32 too large, which keeps it and
+// the product normal, and the last product scales back (it may round to a denormal).  NaN takes the silu_f side, -inf
+// gives -inf * 0 = NaN as the formula does.  Only this launch does so: the fused kernels call silu_f as it is.
+__device__ __forceinline__ float silu_full_range(float x) {
+  if (x < -87.0f) return (x * __builtin_amdgcn_exp2f(fmaf(x, 1.4426950408889634f, 32.0f))) * 0x1p-32f;
+  return silu_f(x);
+}
+
 template <typename T>
 __global__ void k_silu(const T* __restrict__ x, T* __restrict__ y, size_t n) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    y[i] = from_f32<T>(silu_f(to_f32(x[i])));
+    y[i] = from_f32<T>(silu_full_range(to_f32(x[i])));
 }
 
 // ----------------------------------------------------------------------------- DDIM
