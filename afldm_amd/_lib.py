@@ -28,6 +28,8 @@ EXP_ABI = _abi.read("afldm_hip_experimental.h", ABI)
 SLOTS_ABI = _abi.read("afldm_hip_slots.h", ABI)
 # counter-based device noise and the seeded samplers' updates (libafldm_noise.so): bound by _noise.py on first use
 NOISE_ABI = _abi.read("afldm_hip_noise.h", ABI)
+# the slot sampler's update for image-conditioned requests (libafldm_edit.so): bound by _edit.py on first use
+EDIT_ABI = _abi.read("afldm_hip_edit.h", ABI)
 ConvArgs, SepArgs, AfActArgs = ABI.structs["afldm_conv_args"], ABI.structs["afldm_sep_args"], EXP_ABI.structs["afldm_af_act_args"]
 F32, BF16 = ABI.constants["AFLDM_F32"], ABI.constants["AFLDM_BF16"]
 DTYPE_CODE = {torch.float32: F32, torch.bfloat16: BF16}

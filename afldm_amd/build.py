@@ -25,6 +25,10 @@ SLOTS_SOURCES = ["slot_kinds.hip"]
 # the product library, loaded by the seeded engines on first use (afldm_amd/_noise.py)
 NOISE_LIB = os.path.join(OUT_DIR, "libafldm_noise.so")
 NOISE_SOURCES = ["noise.hip"]
+# The slot sampler's update for image-conditioned requests (include/afldm_hip_edit.h): a library of its own that links against the
+# product library, loaded by an EditSlotEngine on first use (afldm_amd/_edit.py)
+EDIT_LIB = os.path.join(OUT_DIR, "libafldm_edit.so")
+EDIT_SOURCES = ["edit.hip"]
 ARCH = "gfx950"
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # Kernels whose MFMA accumulators are post-processed by VALU code (softmax, SiLU, GroupNorm affine):
@@ -70,21 +74,24 @@ def build(force=False, verbose=True):
                                                "af_plane.hpp", "af_plane_passes.inc")] + [os.path.join(HERE, "..", "include", "afldm_hip.h")]
     exp_headers = headers + [os.path.join(HERE, "..", "include", "afldm_hip_experimental.h")]
     slots_headers = headers + [os.path.join(HERE, "..", "include", "afldm_hip_slots.h")]
-    noise_headers = headers + [os.path.join(CSRC, "philox.hpp"), os.path.join(HERE, "..", "include", "afldm_hip_noise.h")]
+    seeded_headers = headers + [os.path.join(CSRC, "philox.hpp"), os.path.join(CSRC, "seeded_common.hpp")]
+    noise_headers = seeded_headers + [os.path.join(HERE, "..", "include", "afldm_hip_noise.h")]
+    edit_headers = seeded_headers + [os.path.join(HERE, "..", "include", "afldm_hip_edit.h")]
     def command(src, obj):
         mode = os.environ.get("AFLDM_VGPR_FORM", "")
         vg = mode == "all" or (mode != "none" and os.path.basename(src) in VGPR_FORM)
         wt = ["-DAFLDM_WT=1"] if os.path.basename(src) in WRITE_THROUGH and os.environ.get("AFLDM_NO_WT") is None else []
         return [hipcc] + FLAGS + (VGPR_FORM_FLAGS if vg else []) + wt + ["-c", src, "-o", obj]
 
-    objs, exp_objs, slots_objs, noise_objs, jobs = [], [], [], [], []
-    for s in SOURCES + EXP_SOURCES + SLOTS_SOURCES + NOISE_SOURCES:
+    objs, exp_objs, slots_objs, noise_objs, edit_objs, jobs = [], [], [], [], [], []
+    for s in SOURCES + EXP_SOURCES + SLOTS_SOURCES + NOISE_SOURCES + EDIT_SOURCES:
         src = os.path.join(CSRC, s)
         obj = os.path.join(OUT_DIR, s.replace(".hip", ".o"))
-        (exp_objs if s in EXP_SOURCES else slots_objs if s in SLOTS_SOURCES else noise_objs if s in NOISE_SOURCES else objs).append(obj)
+        (exp_objs if s in EXP_SOURCES else slots_objs if s in SLOTS_SOURCES else noise_objs if s in NOISE_SOURCES else
+         edit_objs if s in EDIT_SOURCES else objs).append(obj)
         fp = _fingerprint([os.path.basename(c) if os.sep in c else c for c in command(src, obj)],
                           [src] + (exp_headers if s in EXP_SOURCES else slots_headers if s in SLOTS_SOURCES else
-                                   noise_headers if s in NOISE_SOURCES else headers))
+                                   noise_headers if s in NOISE_SOURCES else edit_headers if s in EDIT_SOURCES else headers))
         stamp = obj + ".sha256"
         same = os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read().strip() == fp
         if force or not same:
@@ -142,6 +149,13 @@ def build(force=False, verbose=True):
             raise RuntimeError(f"link of libafldm_noise.so failed:\n{r.stdout}\n{r.stderr}")
         if verbose:
             print("[afldm_amd.build] linked", NOISE_LIB, flush=True)
+    if force or _stale(EDIT_LIB, edit_objs + [LIB]):
+        cmd = [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", EDIT_LIB] + edit_objs + [f"-L{OUT_DIR}", "-lafldm_hip", "-Wl,-rpath,$ORIGIN"]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"link of libafldm_edit.so failed:\n{r.stdout}\n{r.stderr}")
+        if verbose:
+            print("[afldm_amd.build] linked", EDIT_LIB, flush=True)
     try:
         build_aql(force, verbose)
     except Exception as e:          # a diagnostic library (AQL packet view): the product never loads it

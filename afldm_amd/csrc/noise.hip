@@ -5,8 +5,8 @@
 //   afldm_counter_noise     the stream materialised, fp32 NCHW (the eager path and the tests)
 //   afldm_seeded_step       afldm_sde_step with z made in registers: ordinal *step_idx, one seed per sample
 //   afldm_slot_step_seeded  afldm_slot_step_kinds plus kind code 2: that update with ordinal row_ord[pos[b]] and seed seeds[b]
-// The update is seeded_update below, written once with contraction off and no fma, so a float32 restatement in the stated order
-// gives its bits (tests/noise_oracle.py).  A row whose c is 0 generates nothing: z = 0.
+// The update is seeded_update (seeded_common.hpp, shared with edit.hip), written once with contraction off and no fma, so a
+// float32 restatement in the stated order gives its bits (tests/noise_oracle.py).  A row whose c is 0 generates nothing: z = 0.
 // Layout as sde.hip / slot_kinds.hip: a thread owns 4 consecutive elements of one (b, c) plane (one Philox call, 16-byte loads
 // and stores) or, in the scalar form, one element (the call of its group, lane i & 3: the values do not depend on the form);
 // grid capped at 2048 blocks and grid-stride beyond.  Each thread reads and writes its own indices only, so x and x_out may
@@ -15,8 +15,7 @@
 // Resources (gfx950, -O3, the compiler's resource report; no scratch, no LDS, no AGPRs in any of them):
 //   k_philox_bits 20 VGPRs;  k_counter_noise 32 in the 16-byte form, 22 in the scalar form;  k_seeded_step 45 (fp32 eps) / 49 (bf16
 //   eps) and 30;  k_slot_step_seeded 40 / 44 and 24;  8 waves per SIMD everywhere
-#include "philox.hpp"
-#include "slot_common.hpp"
+#include "seeded_common.hpp"
 
 #include "../../include/afldm_hip_noise.h"
 
@@ -25,41 +24,6 @@ namespace afldm {
 namespace {
 
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
-struct sde_row {
-  float p, q, lo, hi, a, b, d, c;
-};
-
-// The "seeded" update, the "sde" row (p, q, lo, hi, a, b, d, c) in this order of float operations - products rounded one by one,
-// sums left to right, no fma:
-//   t = rn(p x) + rn(q e);  x0 = clamp_nan(t, lo, hi);  out = ((rn(a x) + rn(b x0)) + rn(d e)) + rn(c z)
-__device__ __forceinline__ float seeded_update(float x, float e, float z, const sde_row& r) {
-#pragma clang fp contract(off)
-  const float px = r.p * x, qe = r.q * e;
-  const float t = px + qe;
-  const float x0 = clamp_nan(t, r.lo, r.hi);
-  const float ax = r.a * x, bx = r.b * x0, de = r.d * e, cz = r.c * z;
-  return ((ax + bx) + de) + cz;
-}
-
-// V elements of one sample from element i (i % V == 0) of its flat [C, H, W] order; zeros when the row generates nothing
-template <int V>
-__device__ __forceinline__ vecf<V> seeded_z(bool on, long long seed, uint32_t i, uint32_t ordinal, uint32_t slot) {
-  vecf<V> z;
-  if (!on) {
-#pragma unroll
-    for (int k = 0; k < V; ++k) z.v[k] = 0.0f;
-  } else if constexpr (V == 4) {
-    const philox_normals n = philox_normal4(seed, i >> 2, ordinal, slot);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) z.v[k] = n.z[k];
-  } else {
-    z.v[0] = philox_normal1(seed, i, ordinal, slot);
-  }
-  return z;
-}
-
-constexpr int KIND_SEEDED = 2;                 // row_kind code (SeededSlotTable.KIND_CODES in afldm_amd/engine.py)
 
 }  // namespace
 

@@ -1,8 +1,8 @@
-// philox.hpp — the counter-based noise stream of the seeded samplers (noise.hip, slot_seeded.hip).
+// philox.hpp — the counter-based noise stream of the seeded samplers (noise.hip, edit.hip).
 // Philox-4x32-10 as in Random123 (Salmon et al., SC'11), then Box-Muller.  The noise of a request is a pure function of
 //   key      (seed & 0xffffffff, seed >> 32)                                  the request's seed, 0 <= seed < 2^63
 //   counter  (g, ordinal, slot, 0)    g = i >> 2 of element i in the sample's own flat [C, H, W] order, ordinal = the step
-//                                     within the request's own schedule, slot = the noise slot (0; 1, 2 reserved)
+//                                     within the request's own schedule, slot = the noise slot (0; 1, 2: edit.hip)
 //   uniforms u_j = ((r_j >> 9) + 0.5) 2^-23: exact in fp32, in [2^-24, 1 - 2^-24]
 //   normals  (z0, z1) = sqrt(-2 ln u0) (cos 2 pi u1, sin 2 pi u1), (z2, z3) likewise from (u2, u3); element 4 g + k gets z_k
 // so it needs no buffer and no host draw, and does not depend on the batch position, the neighbours or the vector width.

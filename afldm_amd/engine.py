@@ -1092,6 +1092,7 @@ class SlotEngine(DenoiseEngine):
     The engine has no schedule of its own: reset / run are the base class's and do not apply."""
     ONE_BRANCH = True           # one cursor table, one select launch: no parallel branches
     TABLE = SlotTable           # the host's record of the row table (SeededSlotEngine: SeededSlotTable)
+    ROW_WIDTH = 8               # floats per row once the table holds more than "ddim" rows (EditSlotEngine: 12)
 
     def __init__(self, unet, batch_size, use_graph=True, steps_per_graph=5, *, row_capacity=1024, temb_capacity=256,
                  out_capacity=None, kinds=("ddim",)):
@@ -1133,7 +1134,7 @@ class SlotEngine(DenoiseEngine):
         # one update per engine: a table of "ddim" rows alone keeps the 4-wide rows of afldm_slot_step; any other set of kinds takes
         # 8-wide rows ("ddim" rows padded with zeros), a kind code per row and a history per slot (afldm_slot_step_kinds)
         self._by_kind = tb.kinds != ("ddim",)
-        self.row_coef = torch.zeros(tb.R, 8 if self._by_kind else 4, **f32)
+        self.row_coef = torch.zeros(tb.R, self.ROW_WIDTH if self._by_kind else 4, **f32)
         self.row_t, self.row_temb, self.row_kind = torch.zeros(tb.R, **f32), torch.zeros(tb.R, **i32), torch.zeros(tb.R, **i32)
         # the boundary's buffers: commands and fresh latents (two pinned stagings each, so the host can prepare one boundary
         # while the previous one's upload waits behind a replay), and the output ring with its pinned mirror
@@ -1324,6 +1325,97 @@ class SeededSlotEngine(SlotEngine):
             host.copy_(torch.tensor(self._seed_host, dtype=torch.int64))
             self.seeds.copy_(host, non_blocking=True)
             uploaded.record()
+        return events
+
+
+class EditSlotTable(SeededSlotTable):
+    """SeededSlotTable for engines that also take the image-conditioned kinds: "seeded_sdedit" (img2img with a change map,
+    DDIMScheduler.seeded_sdedit_schedule) and "seeded_repaint" (RePaint inpainting, DDIMScheduler.seeded_repaint_schedule).  A row's
+    ordinal is its place in its own schedule, as in the parent - RePaint's schedule visits a timestep several times, and every
+    visit has an ordinal, and so a noise, of its own."""
+
+    KIND_CODES = {"ddim": 0, "dpm": 1, "seeded": 2, "seeded_sdedit": 3, "seeded_repaint": 4}      # what afldm_slot_step_edit reads
+
+    def __init__(self, row_capacity, temb_capacity, kinds=("ddim", "seeded", "seeded_sdedit", "seeded_repaint")):
+        super().__init__(row_capacity, temb_capacity, kinds)
+
+
+class EditSlotEngine(SeededSlotEngine):
+    """SeededSlotEngine that takes image-conditioned requests: kinds "seeded_sdedit" and "seeded_repaint" next to "ddim", "seeded"
+    and, if asked for, "dpm".  The rows are 12 wide and the update is afldm_slot_step_edit: afldm_slot_step_seeded plus the two
+    kinds, which read the slot's own conditioning planes - `cond` [B, C, S, S], its original or known latents, and `cmask`
+    [B, 1, S, S], its change map or keep mask - and make all of their noise from the slot's seed and the row's ordinal.  So such a
+    request's result, too, depends on nothing but the request.  exchange takes refills {slot: (latents, begin, end, seed, cond,
+    cmask)}, cond and cmask None for the other kinds; the planes of a refilled slot are written on the engine's stream at the
+    boundary - host tensors through pinned staging (two buffers, each reused only behind the event of its previous upload, as
+    the fresh latents' and the seeds'), device tensors directly.  A slot's planes are only read by rows of the two kinds, so a
+    request of another kind leaves whatever its predecessor put there."""
+    TABLE = EditSlotTable
+    ROW_WIDTH = 12
+    PLANE_CODES = (EditSlotTable.KIND_CODES["seeded_sdedit"], EditSlotTable.KIND_CODES["seeded_repaint"])     # the kinds that read planes
+
+    def __init__(self, unet, batch_size, use_graph=True, steps_per_graph=5, *, row_capacity=1024, temb_capacity=256,
+                 out_capacity=None, kinds=("ddim", "seeded", "seeded_sdedit", "seeded_repaint")):
+        super().__init__(unet, batch_size, use_graph, steps_per_graph, row_capacity=row_capacity, temb_capacity=temb_capacity,
+                         out_capacity=out_capacity, kinds=kinds)
+
+    def _allocate(self):
+        unet, dev, B = self.unet, self.unet.device, self.B
+        c, s = unet.config.in_channels, unet.config.sample_size
+        self.cond = torch.zeros(B, c, s, s, dtype=torch.float32, device=dev)
+        self.cmask = torch.zeros(B, 1, s, s, dtype=torch.float32, device=dev)
+        self._plane_staging = [(torch.zeros(B, c, s, s, dtype=torch.float32, pin_memory=True),
+                                torch.zeros(B, 1, s, s, dtype=torch.float32, pin_memory=True), torch.cuda.Event()) for _ in range(2)]
+        super()._allocate()
+
+    def _apply(self, lat, eps, branch):
+        if not self._by_kind:
+            return super()._apply(lat, eps, branch)
+        ops.slot_step_edit(lat, eps, self.hist, self.cond, self.cmask, self.row_coef, self.row_kind, self.row_ord, self.pos,
+                           self.active, self.seeds)
+
+    def exchange(self, harvests, refills):
+        """As SeededSlotEngine.exchange, with refills {slot: (latents, begin, end, seed, cond, cmask)}: cond [C, S, S] or
+        [1, C, S, S] and cmask [S, S], [1, S, S] or [1, 1, S, S] for a request of an image-conditioned kind, (None, None) for any
+        other; a span of such a kind without planes, and planes with any other span, raise.  A refill that is refused leaves the
+        engine as it was."""
+        seeded, planes = {}, {}
+        for slot, refill in refills.items():
+            if len(refill) != 6:
+                raise ValueError("EditSlotEngine: a refill is (latents, begin, end, seed, cond, cmask)")
+            cond, cmask = refill[4], refill[5]
+            if (cond is None) != (cmask is None):
+                raise ValueError("EditSlotEngine: a refill carries both planes, cond and cmask, or neither")
+            begin, end = refill[1], refill[2]
+            if 0 <= begin < end <= len(self.table.t):          # (any other span is the base class's to refuse)
+                wants = self.table.kind[begin] in self.PLANE_CODES
+                if wants != (cond is not None):
+                    raise ValueError(f"EditSlotEngine: rows {begin} .. {end} are " + ("of an image-conditioned kind and need cond "
+                                     "and cmask" if wants else "of a kind that reads no planes: pass None, None"))
+            if cond is not None:
+                if cond.numel() != self.cond[0].numel() or tuple(cond.shape[-3:]) != tuple(self.cond.shape[1:]):
+                    raise ValueError(f"EditSlotEngine: cond {tuple(cond.shape)}, want {tuple(self.cond.shape[1:])}")
+                if cmask.numel() != self.cmask[0].numel() or tuple(cmask.shape[-2:]) != tuple(self.cmask.shape[2:]):
+                    raise ValueError(f"EditSlotEngine: cmask {tuple(cmask.shape)}, want {tuple(self.cmask.shape[1:])}")
+                planes[slot] = (cond, cmask)
+            seeded[slot] = tuple(refill[:4])
+        events = super().exchange(harvests, seeded)
+        if planes:
+            cond_host = cmask_host = uploaded = None
+            if any(t.device.type == "cpu" for pair in planes.values() for t in pair):
+                self._plane_staging.append(self._plane_staging.pop(0))
+                cond_host, cmask_host, uploaded = self._plane_staging[-1]
+                uploaded.synchronize()                # (its previous upload: two such boundaries ago)
+            for i, (slot, pair) in enumerate(planes.items()):
+                for dst, host, t in ((self.cond[slot], cond_host, pair[0]), (self.cmask[slot], cmask_host, pair[1])):
+                    t = t.reshape(dst.shape)
+                    if t.device.type == "cpu":
+                        host[i].copy_(t)
+                        dst.copy_(host[i], non_blocking=True)
+                    else:
+                        dst.copy_(t)
+            if uploaded is not None:
+                uploaded.record()
         return events
 
 

@@ -2308,6 +2308,30 @@ def slot_step_seeded(x, eps_nhwc, hist, row_coef, row_kind, row_ord, pos, active
     return x
 
 
+def slot_step_edit(x, eps_nhwc, hist, cond, cmask, row_coef, row_kind, row_ord, pos, active, seeds):
+    """afldm_slot_step_edit (include/afldm_hip_edit.h, libafldm_edit.so), in place: slot_step_seeded on 12-wide rows plus the kind
+    codes 3 - "seeded_sdedit": img2img's select between the slot's original cond[b], noised by the run's one noise, and the reverse
+    step, by its change map cmask[b] - and 4 - "seeded_repaint": RePaint's blend of the slot's known latents cond[b] and the reverse
+    step by its mask cmask[b], and the jump.  cond fp32 [B, C, H, W], cmask fp32 [B, 1, H, W]; every noise is the counter stream of
+    seeds[b] at the ordinal row_ord[pos[b]].  Such a slot's history planes are not touched."""
+    for name, t in (("x", x), ("eps", eps_nhwc), ("hist", hist), ("cond", cond), ("cmask", cmask), ("row_coef", row_coef),
+                    ("row_kind", row_kind), ("row_ord", row_ord)):
+        _dev(t, name)
+    B, C, H, W = x.shape
+    _slot_ints(B, pos=pos, active=active)
+    _seeds(seeds, B)
+    assert x.dtype == hist.dtype == cond.dtype == cmask.dtype == row_coef.dtype == torch.float32
+    assert row_coef.dim() == 2 and row_coef.shape[1] == 12
+    assert row_kind.dtype == row_ord.dtype == torch.int32 and row_kind.numel() == row_ord.numel() == row_coef.shape[0]
+    assert tuple(eps_nhwc.shape) == (B, H, W, C) and tuple(hist.shape) == (2, B, C, H, W)
+    assert tuple(cond.shape) == (B, C, H, W) and tuple(cmask.shape) == (B, 1, H, W)
+    from . import _edit               # (libafldm_edit.so, loaded on first use)
+    check(_edit.lib().afldm_slot_step_edit(ptr(x), ptr(eps_nhwc), ptr(hist), ptr(cond), ptr(cmask), ptr(row_coef), ptr(row_kind),
+                                           ptr(row_ord), ptr(pos), ptr(active), ptr(seeds), B, row_coef.shape[0], C, H, W,
+                                           _code(eps_nhwc), stream_ptr()), "slot_step_edit")
+    return x
+
+
 def slot_exchange(cmd, lat, out, fresh, pos, end):
     """afldm_slot_exchange: cmd int32 [B, 4] = {harvest, refill, begin, end} per slot - out[harvest] <- lat[b] where harvest >= 0,
     then lat[b] <- fresh[refill], pos[b] = begin - 1, end[b] = end where refill >= 0.  lat [B, ...], out [No, ...], fresh

@@ -262,8 +262,11 @@ class MyLDMPipeline(DiffusionPipeline):
             return latents
         if self.vae is None:
             raise NotImplementedError("this pipeline was built without a VAE: use output_type='latent'")
-        decoded = self.vae.decode(latents.to(self.vae.dtype) / self.vae.config.scaling_factor).sample
-        return self._images(decoded, output_type, return_dict)
+        return self._images(self._decode(latents), output_type, return_dict)
+
+    def _decode(self, latents):
+        """The VAE's decoding of scaled latents, in [-1, 1] and the VAE's dtype (_deliver; SamplingServer.decode)."""
+        return self.vae.decode(latents.to(self.vae.dtype) / self.vae.config.scaling_factor).sample
 
     def _images(self, decoded, output_type, return_dict):
         """A decoded tensor in [-1, 1] as `output_type` 'pt', 'np' or 'pil' (_deliver)."""
@@ -391,31 +394,42 @@ class MyLDMPipeline(DiffusionPipeline):
         'mean': the kept fraction as a soft mask), the latents sampled by inpaint_latents and decoded.  composite: the result is
         m image + (1 - m) decoded in pixel space, in fp32, so that kept pixels are the input's exactly.  output_type as
         __call__; 'latent' returns the sampled latents."""
-        from .. import ops
-        self._refuse_dpm("inpaint")
-        if self.vae is None:
-            raise NotImplementedError("this pipeline was built without a VAE: use inpaint_latents")
-        if mask_mode not in ("min", "mean"):
-            raise ValueError(f"inpaint: mask_mode {mask_mode!r} (want 'min' or 'mean')")
-        r = self._vae_ratio()
-        s = self.unet.config.sample_size
-        if image.dim() != 4 or tuple(image.shape[1:]) != (3, s * r, s * r):
-            raise ValueError(f"inpaint: image {tuple(image.shape)}, want [B, 3, {s * r}, {s * r}]")
-        if mask.dim() != 4 or tuple(mask.shape[1:]) != (1, s * r, s * r) or mask.shape[0] not in (1, image.shape[0]):
-            raise ValueError(f"inpaint: mask {tuple(mask.shape)}, want [{image.shape[0]} or 1, 1, {s * r}, {s * r}]")
-        dev = self.unet.device
-        image = image.to(device=dev, dtype=torch.float32)
-        mask = mask.to(device=dev, dtype=torch.float32).contiguous()
-        known = self._encode_mode(image)
-        latent_mask = ops.mask_pool(mask, r, ops.MASK_MIN if mask_mode == "min" else ops.MASK_MEAN)
+        image, mask, known, latent_mask = self._inpaint_inputs(image, mask, mask_mode)
         out = self.inpaint_latents(known, latent_mask, num_inference_steps, eta, jump_length, jump_n_sample, generator, latents,
                                    use_graph)
         if output_type == "latent":
             return out
         decoded = self.vae.decode(out.to(self.vae.dtype) / self.vae.config.scaling_factor).sample
         if composite:
-            decoded = mask * image + (1 - mask) * decoded.float()
+            decoded = self._inpaint_composite(decoded, image, mask)
         return self._images(decoded, output_type, return_dict)
+
+    def _inpaint_inputs(self, image, mask, mask_mode="min", who="inpaint"):
+        """What `inpaint` samples from (and SamplingServer.submit_inpaint): (image, mask) as fp32 on the device, the image's
+        latents and the mask pooled to the latent grid.  Raises what `inpaint` raises."""
+        from .. import ops
+        self._refuse_dpm(who)
+        if self.vae is None:
+            raise NotImplementedError(f"this pipeline was built without a VAE: use {who}_latents")
+        if mask_mode not in ("min", "mean"):
+            raise ValueError(f"{who}: mask_mode {mask_mode!r} (want 'min' or 'mean')")
+        r = self._vae_ratio()
+        s = self.unet.config.sample_size
+        if image.dim() != 4 or tuple(image.shape[1:]) != (3, s * r, s * r):
+            raise ValueError(f"{who}: image {tuple(image.shape)}, want [B, 3, {s * r}, {s * r}]")
+        if mask.dim() != 4 or tuple(mask.shape[1:]) != (1, s * r, s * r) or mask.shape[0] not in (1, image.shape[0]):
+            raise ValueError(f"{who}: mask {tuple(mask.shape)}, want [{image.shape[0]} or 1, 1, {s * r}, {s * r}]")
+        dev = self.unet.device
+        image = image.to(device=dev, dtype=torch.float32)
+        mask = mask.to(device=dev, dtype=torch.float32).contiguous()
+        known = self._encode_mode(image)
+        latent_mask = ops.mask_pool(mask, r, ops.MASK_MIN if mask_mode == "min" else ops.MASK_MEAN)
+        return image, mask, known, latent_mask
+
+    @staticmethod
+    def _inpaint_composite(decoded, image, mask):
+        """m image + (1 - m) decoded in pixel space, in fp32: kept pixels are the input's exactly."""
+        return mask * image + (1 - mask) * decoded.float()
 
     # ------------------------------------------------------------------------------------------------ image-to-image (SDEdit)
     @torch.no_grad()
@@ -474,33 +488,43 @@ class MyLDMPipeline(DiffusionPipeline):
         (harness.vae_encode_mode), the map pooled to the latent grid by its mean over the VAE's down-sampling blocks
         (afldm_mask_pool), the latents sampled by img2img_latents and decoded.  composite: pixels whose change value is exactly 0
         are the input's, in fp32; nothing is blended elsewhere.  output_type as __call__; 'latent' returns the sampled latents."""
+        image, change_map, orig, latent_map = self._img2img_inputs(image, strength, change_map)
+        out = self.img2img_latents(orig, strength, latent_map, num_inference_steps, eta, generator, noise, use_graph)
+        if output_type == "latent":
+            return out
+        decoded = self.vae.decode(out.to(self.vae.dtype) / self.vae.config.scaling_factor).sample
+        if composite and change_map is not None:
+            decoded = self._img2img_composite(decoded, image, change_map)
+        return self._images(decoded, output_type, return_dict)
+
+    def _img2img_inputs(self, image, strength, change_map, who="img2img"):
+        """What `img2img` samples from (and SamplingServer.submit_img2img): (image, change_map) as fp32 on the device (the map may
+        be None), the image's latents and the map pooled to the latent grid (None for None).  Raises what `img2img` raises."""
         from .. import ops
-        self._refuse_dpm("img2img")
+        self._refuse_dpm(who)
         if self.vae is None:
-            raise NotImplementedError("this pipeline was built without a VAE: use img2img_latents")
+            raise NotImplementedError(f"this pipeline was built without a VAE: use {who}_latents")
         r = self._vae_ratio()
         s = self.unet.config.sample_size
         if image.dim() != 4 or tuple(image.shape[1:]) != (3, s * r, s * r):
-            raise ValueError(f"img2img: image {tuple(image.shape)}, want [B, 3, {s * r}, {s * r}]")
+            raise ValueError(f"{who}: image {tuple(image.shape)}, want [B, 3, {s * r}, {s * r}]")
         if change_map is not None and (change_map.dim() != 4 or tuple(change_map.shape[1:]) != (1, s * r, s * r)
                                        or change_map.shape[0] not in (1, image.shape[0])):
-            raise ValueError(f"img2img: change_map {tuple(change_map.shape)}, want [{image.shape[0]} or 1, 1, {s * r}, {s * r}]")
+            raise ValueError(f"{who}: change_map {tuple(change_map.shape)}, want [{image.shape[0]} or 1, 1, {s * r}, {s * r}]")
         if not 0.0 <= float(strength) <= 1.0:
-            raise ValueError(f"img2img: strength = {strength} must be in [0, 1]")
+            raise ValueError(f"{who}: strength = {strength} must be in [0, 1]")
         dev = self.unet.device
         image = image.to(device=dev, dtype=torch.float32)
         latent_map = None
         if change_map is not None:
             change_map = change_map.to(device=dev, dtype=torch.float32).contiguous()
             latent_map = ops.mask_pool(change_map, r, ops.MASK_MEAN)
-        out = self.img2img_latents(self._encode_mode(image), strength, latent_map, num_inference_steps, eta, generator, noise,
-                                   use_graph)
-        if output_type == "latent":
-            return out
-        decoded = self.vae.decode(out.to(self.vae.dtype) / self.vae.config.scaling_factor).sample
-        if composite and change_map is not None:
-            decoded = torch.where(change_map == 0, image, decoded.float())
-        return self._images(decoded, output_type, return_dict)
+        return image, change_map, self._encode_mode(image), latent_map
+
+    @staticmethod
+    def _img2img_composite(decoded, image, change_map):
+        """Pixels whose change value is exactly 0 are the input's, in fp32; nothing is blended elsewhere."""
+        return torch.where(change_map == 0, image, decoded.float())
 
     # ------------------------------------------------------------------------------------------------ bit-reversible sampling
     @staticmethod

@@ -379,6 +379,23 @@ class DDIMScheduler:
         ab = float(self.alphas_cumprod[self._sdedit_timesteps(num_inference_steps, strength)[0]])
         return math.sqrt(ab), math.sqrt(1 - ab)
 
+    def seeded_sdedit_schedule(self, num_inference_steps, strength, eta=0.0):
+        """sdedit_schedule(num_inference_steps, strength, eta) for the slot sampler (EditSlotEngine): the same timesteps and rows,
+        float for float, as kind "seeded_sdedit" - afldm_slot_step_edit makes z_u and the run's fixed noise z in registers from
+        the request's seed, so nothing is drawn - under a key of its own.  sdedit_start gives the level the run starts from."""
+        sd = self.sdedit_schedule(num_inference_steps, strength, eta)
+        return Schedule.of(self, "seeded_sdedit", sd.timesteps, sd.rows, _seeded_sdedit_steps=int(num_inference_steps),
+                           _seeded_sdedit_evaluations=len(sd.rows), _seeded_sdedit_eta=float(eta))
+
+    def seeded_repaint_schedule(self, num_inference_steps, eta=0.0, jump_length=10, jump_n_sample=10):
+        """repaint_schedule(num_inference_steps, eta, jump_length, jump_n_sample) for the slot sampler (EditSlotEngine): the same
+        timesteps and rows, float for float, as kind "seeded_repaint" - afldm_slot_step_edit makes z_k, z_u and z_b in registers
+        from the request's seed and the evaluation's ordinal, so nothing is drawn - under a key of its own."""
+        rp = self.repaint_schedule(num_inference_steps, eta, jump_length, jump_n_sample)
+        return Schedule.of(self, "seeded_repaint", rp.timesteps, rp.rows, _seeded_repaint_steps=int(num_inference_steps),
+                           _seeded_repaint_eta=float(eta), _seeded_repaint_jump_length=int(jump_length),
+                           _seeded_repaint_jump_n_sample=int(jump_n_sample))
+
     def reversible_levels(self, num_inference_steps, strength=None):
         """(tau, ab) of the bit-reversible sampler: tau[1] < ... < tau[N] this scheduler's timesteps in ascending order (with
         `strength`, those of _sdedit_timesteps), tau[0] = None, and ab[0] = final_alpha_cumprod, ab[k] = alphas_cumprod[tau[k]],

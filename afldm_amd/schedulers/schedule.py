@@ -32,12 +32,20 @@ UNet evaluation, fixed when it is made.  `kind` names the update kernel that rea
     "sdedit" (p, q, lo, hi, a, b, c, k0, k1, thr, 0, 0):  image-to-image sampling (SDEdit) with a per-element change map
             (Differential Diffusion):  x0 = clamp(p x + q eps, lo, hi);  xp = a x0 + b eps + c z_u;  held = k0 orig + k1 z, z the
             run's ONE fixed noise;  x_out = (cmap <= thr) ? held : xp - a select, not a blend         afldm_sdedit_step
+    "seeded_sdedit"  the "sdedit" row, float for float, for the slot sampler (EditSlotEngine): both of its noises are made in the
+            update's registers from the request's seed - z_u is noise slot 0 at the row's ordinal, the run's one fixed noise z is
+            slot 1 at ordinal 0 - and the original and the change map are the slot's own planes; no draws:
+            t = rn(p x) + rn(q eps);  x0 = clamp(t, lo, hi);  xp = (rn(a x0) + rn(b eps)) + rn(c z_u);  held = rn(k0 orig) + rn(k1 z);
+            x_out = (cmap <= thr) ? held : xp                                                              afldm_slot_step_edit
+    "seeded_repaint"  the "repaint" row, float for float, likewise: z_k, z_u, z_b are the noise slots 0, 1, 2 at the row's ordinal,
+            the known latents and the mask the slot's own planes; no draws:  x0 as above;  unknown = (rn(a x0) + rn(b eps)) + rn(c z_u);
+            knownp = rn(k0 known) + rn(k1 z_k);  y = rn(m knownp) + rn(rn(1 - m) unknown);  x_out = rn(u0 y) + rn(u1 z_b)   afldm_slot_step_edit
     "rev"   (cx, ce, sign, boot):  the bit-reversible sampler (two-step DDIM after BDIA, gamma = 1) on a pair (far, near) of int64
             latents on the grid 2^-32:  f = boot ? near : far;  x = rn_f32(near) 2^-32;  q = rn_i64(fl32(fl32(cx x) + fl32(ce eps)) 2^32);
             far <- near;  near <- f + sign q - integer arithmetic, so the same row with the other sign undoes it    afldm_rev_step
 
 The rows come from the scheduler that owns the update (DDIMScheduler.schedule / stochastic_schedule / seeded_schedule,
-DDIMScheduler.repaint_schedule / ilvr_schedule / panorama_schedule / pag_schedule / sag_schedule / outpaint_schedule / hires_schedule / sdedit_schedule / reversible_schedule, DPMSolverMultistepScheduler.schedule, I2SBScheduler.ode_schedule / bridge_schedule,
+DDIMScheduler.seeded_sdedit_schedule / seeded_repaint_schedule / repaint_schedule / ilvr_schedule / panorama_schedule / pag_schedule / sag_schedule / outpaint_schedule / hires_schedule / sdedit_schedule / reversible_schedule, DPMSolverMultistepScheduler.schedule, I2SBScheduler.ode_schedule / bridge_schedule,
 MyLDMPipeline.inversion_schedule) as Python floats and are rounded once to fp32 by `table`.  An "sde" schedule also states which
 steps draw noise and how: exactly the randn_tensor calls, in the same order, that the scheduler's eager `step()` makes, so that
 the engine can draw them from the caller's generator before the captured graphs need them.  A "repaint" schedule has up to
@@ -56,7 +64,8 @@ from ..utils import randn_tensor
 # kind -> (row width, noise slots per step, may a step draw): the one place that states them.  Several slots: `draws` is per slot
 KINDS = {"ddim": (4, 1, False), "dpm": (8, 1, False), "sde": (8, 1, True), "repaint": (12, 3, True), "ilvr": (12, 2, True),
          "pano": (8, 1, True), "pag": (12, 1, True), "sag": (12, 1, True), "outpaint": (12, 3, True),
-         "hires": (12, 1, True), "sdedit": (12, 1, True), "rev": (4, 1, False), "cfg": (12, 1, True), "seeded": (8, 1, False)}
+         "hires": (12, 1, True), "sdedit": (12, 1, True), "rev": (4, 1, False), "cfg": (12, 1, True), "seeded": (8, 1, False),
+         "seeded_sdedit": (12, 2, False), "seeded_repaint": (12, 3, False)}
 ROW_WIDTH, NOISE_SLOTS = {k: v[0] for k, v in KINDS.items()}, {k: v[1] for k, v in KINDS.items() if v[2]}      # derived views
 _MADE = {}          # key -> Schedule: the rows are ~0.1 ms of scalar tensor arithmetic each, and a sampler asks per call
 
@@ -88,11 +97,12 @@ class Schedule:
         rows = tuple(tuple(float(v) for v in r) for r in rows)
         width, nslots, may_draw = KINDS[kind]
         if nslots > 1:
-            draws = tuple(tuple(bool(v) for v in d) for d in draws)
+            draws = tuple(tuple(bool(v) for v in d) for d in draws) if draws is not None else ((False,) * nslots,) * len(rows)
             assert all(len(d) == nslots for d in draws)
         else:
             draws = tuple(bool(d) for d in draws) if draws is not None else (False,) * len(rows)
-        assert len(timesteps) == len(rows) == len(draws) and all(len(r) == width for r in rows) and (may_draw or not any(draws))
+        drawn = any(any(d) if isinstance(d, tuple) else d for d in draws)
+        assert len(timesteps) == len(rows) == len(draws) and all(len(r) == width for r in rows) and (may_draw or not drawn)
         while len(_MADE) >= 64:
             del _MADE[next(iter(_MADE))]          # the oldest: a schedule just made outlives the next 63, whoever makes them
         made = _MADE[key] = cls(kind, timesteps, rows, draws, noise_dtype, float(owner.init_noise_sigma), config, key)

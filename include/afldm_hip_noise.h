@@ -8,7 +8,7 @@
  * 0xBB67AE85, ten rounds), then Box-Muller:
  *   key      (seed & 0xffffffff, seed >> 32) of the sample's seed, 0 <= seed < 2^63
  *   counter  (g, ordinal, slot, 0): g = i >> 2 of element i in the sample's own flat [C][H][W] order, ordinal the step within
- *            the sample's own schedule (0 for its first evaluation), slot the noise slot (0; 1 and 2 are reserved)
+ *            the sample's own schedule (0 for its first evaluation), slot the noise slot (0 here; afldm_hip_edit.h uses 1 and 2)
  *   uniforms u_j = ((r_j >> 9) + 0.5) 2^-23, exact in fp32 and in [2^-24, 1 - 2^-24]
  *   normals  (z0, z1) = sqrt(-2 ln u0) (cos 2 pi u1, sin 2 pi u1), (z2, z3) likewise from (u2, u3); element 4 g + k gets z_k;
  *            |z| <= 5.77
